@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — GCUPS of the all-pairs bit-parallel alignment hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over the whole workload: every query against every subject of the job's bucket
 (BASELINE.json configs[1] by default: Myers unit-cost global, 10k queries x 1M subjects, 150 bp).  Inputs (mapped queries, Peq
@@ -12,19 +12,22 @@ blocks) are resident in HBM before the timed region.  The job is the SAME at eve
     backend's dispatch_task, BGSA_KNC/global.c:374-431), the query set is broadcast from rank 0 once, and a step is, per block of
     gather_block_rows(nq) queries (1,000 for the 10k-query configs), the kernel on the rank's slice + its tile handed to the streamed gather (ScoreGatherStream: a side
     stream sends it to rank 0 while the next block is scored; cal_mic.c:121-147, 535-536), then drain() — the gather is INSIDE the
-    timed region, so `value` is what the node delivers to rank 0, not what its kernels could.  Beside it: `kernel_only` (one launch
-    per pass, no transfer: the reference's "cal"), `gather_blocks_of_100` (the same mechanism in the reference's block size),
-    `weak` (rounds 1-4's headline: a full bucket per rank, kernels only — linear in N by construction) and `config5_sharded`
-    (BASELINE configs[4]: 1k x 1M x 1000 bp cut the same way, kernel-only and with the streamed gather).
+    timed region, so `value` is what the node delivers to rank 0, not what its kernels could.  With --full, beside it:
+    `kernel_only` (one launch per pass, no transfer: the reference's "cal"), `gather_blocks_of_100` (the same mechanism in the
+    reference's block size), `weak` (rounds 1-4's headline: a full bucket per rank, kernels only — linear in N by construction)
+    and `config5_sharded` (BASELINE configs[4]: 1k x 1M x 1000 bp cut the same way, kernel-only and with the streamed gather).
 
-`value` is the reference's formula over the max-over-ranks wall time of the timed steps (cal_cpu.c:472); beside it the line
-carries `total_gcups` (N = 1: raw rows on the host -> scores on the host, the whole job in reference-sized blocks: H2D + GPU
-preprocess + kernel + D2H, the reference's "Total GCUPS", cal_cpu.c:473-474).
+`value` is the reference's formula over the max-over-ranks wall time of the timed steps (cal_cpu.c:472), `ms_per_step` the same
+wall time per timed step.  A plain run does only that: set-up, W warm-up steps, the K timed steps, --dump-outputs if given
+(a fixed sample of what the last step computed, dump_outputs), the line.
 
-The default invocation at N = 1 also carries the other BASELINE GPU configs — `other_configs`: configs 3 (planted mix), 4 and 5, one
-warm-up + two passes each after the timed region, each with the reference's CPU path for that config timed on this node's host
-cores (`cpu_baseline`, 64 threads) — and the utilisation figures as scalars (`roofline.issued_frac`, `.issued_frac_sustained`,
-`.valu_per_wave_row`, `.cfg<N>_*`; `cpu_baseline.cfg<N>_value`).
+--full adds everything else this file measures or checks, after the timed region unless said otherwise: the sustained clock
+(probe waves beside the timed kernels) and the card's power, the output checksum, `total_gcups` (N = 1: raw rows on the host ->
+scores on the host, the whole job in reference-sized blocks: H2D + GPU preprocess + kernel + D2H, the reference's "Total GCUPS",
+cal_cpu.c:473-474), for config 3 the other subject mixes, and for config 2 at N = 1 the other BASELINE GPU configs —
+`other_configs`: configs 3 (planted mix), 4 and 5, one warm-up + two passes each, each with the reference's CPU path for that
+config timed on this node's host cores (`cpu_baseline`, 64 threads) — and the utilisation figures as scalars
+(`roofline.issued_frac`, `.issued_frac_sustained`, `.valu_per_wave_row`, `.cfg<N>_*`; `cpu_baseline.cfg<N>_value`).
 
 The whole run sits under a watchdog that is armed BEFORE init_process_group: a hang (RCCL init, a collective, a
 kernel) ends with rank 0 printing what it has, `"rccl_ok": false`, and every rank leaving with status 3.
@@ -514,6 +517,56 @@ def checksum_int64(out, ns, rows_per_block: int = 256) -> int:
     return total
 
 
+DUMP_QUERIES, DUMP_SUBJECTS = 512, 8192      # scores.npy: 4M float32 = 16 MB
+DUMP_SURVIVORS_MAX = 1 << 20                 # survivors.npy: at most 24 MB of float64
+
+
+def dump_outputs(path, out, algo, nq, ns_total, shard_start, shard_count, rank, dist):
+    """--dump-outputs: what the timed path computed in its last step, so that two builds can be compared output for output on
+    the same seeded inputs.  The score matrix is nq x ns_total (10^10 scores at the BASELINE sizes), so what is written is a
+    fixed sample of it: scores.npy [query_index.npy x subject_index.npy], the rows and columns drawn by a fixed seed.  For the
+    banded filter, whose sample would hold almost no pair it lets through, also survivors.npy: (query, subject, score) of every
+    pair not rejected (score != 127), in row-major order, at most DUMP_SURVIVORS_MAX.  At N > 1 every rank contributes the
+    columns of its slice and rank 0 writes the files."""
+    rng = np.random.default_rng(0xB65A0D)
+    rows = np.sort(rng.choice(nq, min(nq, DUMP_QUERIES), replace=False))
+    cols = np.sort(rng.choice(ns_total, min(ns_total, DUMP_SUBJECTS), replace=False))
+    mine = cols[(cols >= shard_start) & (cols < shard_start + shard_count)] - shard_start
+    dev = out.device
+    part = out.index_select(1, torch.as_tensor(mine, device=dev)).index_select(0, torch.as_tensor(rows, device=dev))
+    part = part.float().cpu().numpy()
+    surv = None
+    if algo == B.ALGO_BANDED:
+        found, n = [], 0
+        step = max(1, (1 << 26) // max(shard_count, 1))        # at most 64M pairs per block: the index list stays under 1 GB
+        for lo in range(0, nq, step):
+            blk = out[lo:lo + step, :shard_count]
+            idx = torch.nonzero(blk != 127)
+            if idx.numel():
+                val = blk[idx[:, 0], idx[:, 1]].double()
+                found.append(torch.stack([idx[:, 0].double() + lo, idx[:, 1].double() + shard_start, val], 1).cpu().numpy())
+                n += found[-1].shape[0]
+            if n >= DUMP_SURVIVORS_MAX:
+                break
+        surv = np.concatenate(found)[:DUMP_SURVIVORS_MAX] if found else np.zeros((0, 3))
+    if dist is not None:
+        got = [None] * dist.get_world_size()
+        dist.all_gather_object(got, (part, surv))      # rank order = subject order (plan_shards' slices are contiguous)
+        part = np.concatenate([g[0] for g in got], axis=1)
+        if surv is not None:
+            surv = np.concatenate([g[1] for g in got])
+            surv = surv[np.lexsort((surv[:, 1], surv[:, 0]))][:DUMP_SURVIVORS_MAX]
+    if rank != 0:
+        return
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "scores.npy", part.astype(np.float32))
+    np.save(d / "query_index.npy", rows.astype(np.float64))
+    np.save(d / "subject_index.npy", cols.astype(np.float64))
+    if surv is not None:
+        np.save(d / "survivors.npy", surv.astype(np.float64))
+
+
 def preflight(dist, dev, rank, world, local_rank):
     """Cheap evidence about the node before anything is timed: which peers this rank's device can address
     directly (hipDeviceCanAccessPeer), and one all_gather of BGSA_BENCH_PREFLIGHT_MB (64) per rank."""
@@ -659,6 +712,13 @@ def main() -> int:
     ap.add_argument("--no-clock-probe", action="store_true",
                     help="do not run the sustained-clock probe waves beside the timed kernels (set it under rocprofv3 --pmc, "
                          "which may serialise kernels: the probes then delay the launch they are meant to observe)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: clock probes and power, the output checksum, the "
+                         "pre-flight all_gather, the other banded mixes, Total GCUPS, the other BASELINE configs, the CPU baseline and, "
+                         "at N > 1, the kernels-only, reference-block, weak and config-5 legs (the --no-* options above apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, a fixed "
+                         "seeded sample of the score matrix; see dump_outputs)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -693,7 +753,7 @@ def main() -> int:
         wd.stage = "first barrier"
         dist.barrier()
     wd.stage = "preflight"
-    pre = preflight(dist, dev, rank, world, local_rank)
+    pre = preflight(dist, dev, rank, world, local_rank) if args.full else {}
 
     algo, cfg_name, nq, ns_total, length, k, scaling = CONFIGS[args.config]
     scores = tuple(int(x) for x in args.scores.split(",")) if args.scores else None
@@ -731,9 +791,9 @@ def main() -> int:
         torch.cuda.synchronize()
 
     # The sustained shader clock of the timed region (probe.hip): eight sleeping one-wave workgroups, one per XCD, read
-    # the shader-clock and the reference-clock counters beside the timed kernels.  Off under a profiler.
+    # the shader-clock and the reference-clock counters beside the timed kernels.  With --full only; off under a profiler.
     profiled = any(name.startswith(("ROCPROF", "ROCP_")) for name in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    use_probe = not args.no_clock_probe and not profiled
+    use_probe = args.full and not args.no_clock_probe and not profiled
     probe_note = None
     if use_probe and algo == B.ALGO_MYERS and aligner.wn >= 25 and aligner.wn <= 32:
         # these kernels hold 253-255 VGPRs at two waves per SIMD: a probe wave finds no register granule beside them and displaces a
@@ -796,6 +856,7 @@ def main() -> int:
     power = None
     one_launch = lambda: aligner.score(0, nq, out=out)     # noqa: E731  every query against the rank's resident subjects
     kernel_only = None
+    q_tile_used = None
     gs = None
     GATHER_BLOCK_ROWS = gather_block_rows(nq)
     n_blocks_step = -(-nq // GATHER_BLOCK_ROWS)
@@ -805,15 +866,16 @@ def main() -> int:
         # block on the host device, rank 0.  So the timed step is: per block of GATHER_BLOCK_ROWS queries the kernel on the
         # rank's slice, its tile handed to the streamed gather (ScoreGatherStream.submit: a side stream sends it to rank 0
         # while the next block is scored), and drain() at the end — the gather is INSIDE the timed region.
-        # First, kernels only (the reference's `cal`: one launch over all queries, nothing moved): the side key `kernel_only`.
-        wd.stage = "kernel-only leg"
-        ko_elapsed, kernel_s = timed(one_launch, 2, 1)
-        aligner.check_faults()
-        kernel_only = {"what": "one launch per pass over all queries on every rank's slice, no transfer (the reference's cal timer); max over ranks",
-                       "passes": 2, "ms_per_pass": round(ko_elapsed / 2 * 1e3, 3),
-                       "gcups": round(float(nq) * ns_total * length * length * 2 / ko_elapsed / 1e9, 2)}
-        wd.extra["kernel_only"] = kernel_only          # a watchdog that fires in the gathered region still prints this
-        q_tile_used = int(L.bgsa_hip_last_query_tile())
+        # First (--full), kernels only (the reference's `cal`: one launch over all queries, nothing moved): the side key `kernel_only`.
+        if args.full:
+            wd.stage = "kernel-only leg"
+            ko_elapsed, kernel_s = timed(one_launch, 2, 1)
+            aligner.check_faults()
+            kernel_only = {"what": "one launch per pass over all queries on every rank's slice, no transfer (the reference's cal timer); max over ranks",
+                           "passes": 2, "ms_per_pass": round(ko_elapsed / 2 * 1e3, 3),
+                           "gcups": round(float(nq) * ns_total * length * length * 2 / ko_elapsed / 1e9, 2)}
+            wd.extra["kernel_only"] = kernel_only          # a watchdog that fires in the gathered region still prints this
+            q_tile_used = int(L.bgsa_hip_last_query_tile())
         wd.stage = "gather set-up"
         setup_error = None
         try:
@@ -834,10 +896,16 @@ def main() -> int:
             wd.cancel()
             return 4
 
+        # HIP events around every block's launch on the launch stream: the rank's kernel time of a step where no kernels-only
+        # leg ran (a plain run); the events of the last step are read after the closing fence
+        block_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_blocks_step)]
+
         def gathered_step():
-            for lo in range(0, nq, GATHER_BLOCK_ROWS):
+            for b, lo in enumerate(range(0, nq, GATHER_BLOCK_ROWS)):
                 hi = min(nq, lo + GATHER_BLOCK_ROWS)
+                block_ev[b][0].record()
                 aligner.score(lo, hi, out=out[lo:hi])
+                block_ev[b][1].record()
                 gs.submit(out[lo:hi, :ns])
             gs.drain()
 
@@ -856,9 +924,11 @@ def main() -> int:
         elapsed, step_s = timed(gathered_step, args.steps, args.warmup, probe=True)
         gather_timer.cancel()
         clock = clock_box[0]
+        if kernel_only is None:
+            kernel_s = sum(e0.elapsed_time(e1) for e0, e1 in block_ev) / 1e3
     else:
         wd.stage = "timed region"
-        sampler = PowerSampler().start() if (rank == 0 and os.environ.get("BGSA_BENCH_POWER", "1") != "0") else None
+        sampler = PowerSampler().start() if (args.full and rank == 0 and os.environ.get("BGSA_BENCH_POWER", "1") != "0") else None
         elapsed, kernel_s = timed(one_launch, args.steps, args.warmup, probe=True)
         power = sampler.stop() if sampler else None
         clock = clock_box[0]
@@ -877,14 +947,18 @@ def main() -> int:
                 use_probe = False
                 elapsed, kernel_s = timed(one_launch, args.steps, 0, probe=False)
                 clock = None
+    if q_tile_used is None:
         q_tile_used = int(L.bgsa_hip_last_query_tile())
     aligner.check_faults()
     wd.stage = "after the timed region"
+    if args.dump_outputs:
+        wd.stage = "dump outputs"
+        dump_outputs(args.dump_outputs, out, algo, nq, ns_total, shards[rank].start, ns, rank, dist)
 
-    # ---- N > 1: did the blocks arrive?  One more block after the timed region, checked end to end: every rank sums the tile it
-    # sent, rank 0 sums the segment that arrived in its block buffer (the reference's per-device block layout).
+    # ---- N > 1 (--full): did the blocks arrive?  One more block after the timed region, checked end to end: every rank sums the
+    # tile it sent, rank 0 sums the segment that arrived in its block buffer (the reference's per-device block layout).
     gather_check = None
-    if gs is not None:
+    if gs is not None and args.full:
         wd.stage = "gather content check"
         hi = min(nq, GATHER_BLOCK_ROWS)
         aligner.score(0, hi, out=out[:hi])
@@ -907,11 +981,17 @@ def main() -> int:
     # blocks once, every score is written once, every stream read once per subject workgroup column (L2-resident: not
     # counted).  Where a PMC pass exists (N = 1) the counters check the model; per rank at N > 1 the model is what
     # there is (config 5: does the ratio grow when eight GPUs' slices shrink? — it depends on the tile, not the slice).
+    # Which launches the kernel time and the query tile come from: one over all queries (N = 1, and the kernels-only leg at
+    # N > 1), else the gathered step's per-block launches (a plain run at N > 1; the tile is that of the last block's launch).
+    rows_per_launch = nq if (world == 1 or kernel_only is not None) else GATHER_BLOCK_ROWS
+    kernel_launch = "one launch over all queries" if rows_per_launch >= nq else \
+        f"sum over the step's launches of {rows_per_launch} queries each (the gathered step's blocks)"
     traffic_model = None
     if q_tile_used > 0 and "blocked" not in aligner.kernel_name():
         peq_bytes = B.group_words(algo, aligner.wn, k) * 4 * (ns_pad // 64)
-        model_bytes = -(-nq // q_tile_used) * peq_bytes + float(nq) * ns_pad * out.element_size()
-        traffic_model = {"query_tile": q_tile_used, "bytes": round(model_bytes),
+        tiles = sum(-(-min(rows_per_launch, nq - lo) // q_tile_used) for lo in range(0, nq, rows_per_launch))
+        model_bytes = tiles * peq_bytes + float(nq) * ns_pad * out.element_size()
+        traffic_model = {"query_tile": q_tile_used, "launches": kernel_launch, "bytes": round(model_bytes),
                          "ratio_to_algorithmic": round(model_bytes / (float(nq) * ns_pad * algorithmic_bytes_per_pair(algo, length, aligner.wn)), 2)}
 
     # ---- evidence that N ranks on N devices ran: gathered through the process group itself ----------------------
@@ -926,9 +1006,9 @@ def main() -> int:
         ranks_info = [None] * world
         dist.all_gather_object(ranks_info, me)
 
-    # size-independent sanity on the full-size output
-    checksum = checksum_int64(out, ns) if rank == 0 else 0
-    survivors = int((out[:, :ns] != 127).sum().item()) if (rank == 0 and algo == B.ALGO_BANDED) else None
+    # size-independent sanity on the full-size output (--full)
+    checksum = checksum_int64(out, ns) if (rank == 0 and args.full) else None
+    survivors = int((out[:, :ns] != 127).sum().item()) if (rank == 0 and args.full and algo == B.ALGO_BANDED) else None
 
     n_subjects_job = ns_total
     cells_per_step_rank = float(nq) * ns * length * length
@@ -1029,6 +1109,7 @@ def main() -> int:
                 "traffic_ratio": round(traffic / algorithmic_bytes, 2) if traffic else None,
                 "traffic_model": traffic_model,
                 "kernel_ms": round(kernel_s * 1e3, 3),
+                "kernel_launch": kernel_launch,
                 "kernel_gcups": round(kernel_gcups, 1),
                 "note": "peak = 256 CU x 4 SIMD x 32 lanes x 2.4 GHz; kernel time from HIP events on the launch stream; "
                         "traffic_ratio = counter bytes / SURVEY's algorithmic bytes (its model: one Peq block per 100 queries; the counter launches tile up to 128)",
@@ -1037,15 +1118,16 @@ def main() -> int:
                         "bytes_per_pair": round(bpp, 3),
                         "measured_gbps": round(traffic / kernel_s / 1e9, 2) if traffic else None},
             },
-            "checksum": checksum,
         }
+        if args.full:
+            result["checksum"] = checksum
         if issued and frac > 1:
             per_cell = issued["achieved"] * 1e12 / (kernel_gcups * 1e9)
             result["roofline"]["ops_note"] = (f"frac > 1 is not skipped work: the kernel issues {per_cell:.3f} lane-ops per cell where the "
                                               f"reference counts {ops_cell:.3f} (v_bitop3 + VCC carry chains + 32 data bits per word)")
         if algo == B.ALGO_BANDED:
-            result["config"]["banded_mix"] = {"name": mix, "what": BANDED_MIXES[mix],
-                                              "pairs_not_rejected": survivors, "fraction": survivors / (float(nq) * ns)}
+            result["config"]["banded_mix"] = {"name": mix, "what": BANDED_MIXES[mix], "pairs_not_rejected": survivors,
+                                              "fraction": survivors / (float(nq) * ns) if survivors is not None else None}
 
     # ---- N > 1: the same steps with the score gather of SURVEY §2a C3 streamed beside them -------------------
     gather_info = None
@@ -1063,9 +1145,9 @@ def main() -> int:
                            "bytes_to_root_per_block": int(sum(sh.count for sh in shards[1:]) * min(nq, GATHER_BLOCK_ROWS) * out.element_size()),
                            "bytes_to_root_per_step": int(sum(sh.count for sh in shards[1:]) * nq * out.element_size()),
                            "root_blocks_received": gs.n_submitted,
-                           "gcups_with_gather": round(gcups, 2), "gcups_kernels_only": kernel_only["gcups"],
+                           "gcups_with_gather": round(gcups, 2), "gcups_kernels_only": kernel_only["gcups"] if kernel_only else None,
                            "content_check": gather_check}
-        small_wanted = os.environ.get("BGSA_BENCH_GATHER", "1") != "0" and GATHER_BLOCK_ROWS != REF_BUCKET_COUNT
+        small_wanted = args.full and os.environ.get("BGSA_BENCH_GATHER", "1") != "0" and GATHER_BLOCK_ROWS != REF_BUCKET_COUNT
         small_info = None
         if small_wanted:
             # The reference moves REF_BUCKET_COUNT = 100 query rows per block: ten such blocks, with and without the gather (an
@@ -1103,14 +1185,14 @@ def main() -> int:
         if rank == 0:
             with print_lock:
                 result["gather"] = gather_info
-                result["gather_ok"] = bool(gather_check and gather_check["segments_ok"])
+                result["gather_ok"] = bool(gather_check["segments_ok"]) if gather_check else None    # checked with --full
                 if small_info is not None:
                     result["gather_blocks_of_100"] = small_info
 
     # ---- N > 1, the default invocation: the weak-scaling figure of rounds 1-4 as a side key — every rank a full bucket of its
     # own (config 2: 1M subjects per rank, job = N x 1M), kernels only.  It is linear in N by construction; it says what the
     # ranks do when nothing is shared, nothing about the gather.
-    if dist is not None and world > 1 and args.config == 2 and not args.no_weak and args.length is None:
+    if args.full and dist is not None and world > 1 and args.config == 2 and not args.no_weak and args.length is None:
         wd.stage = "weak leg (a full bucket per rank)"
         weak, err = None, None
         weak_limit = float(os.environ.get("BGSA_BENCH_WEAK_TIMEOUT", "180"))
@@ -1141,7 +1223,7 @@ def main() -> int:
     # ---- N > 1, the default invocation: BASELINE configs[4] — ONE 1M-subject bucket of 1000 bp reads cut by plan_shards
     # over the ranks (dispatch_task, BGSA_KNC/global.c:374-431; per-device offload + result download, cal_mic.c:121-147) —
     # kernel-only and with the streamed per-block gather, so that a SCALE run times the north star's sharded config too.
-    if dist is not None and world > 1 and args.config == 2 and not args.no_strong and args.length is None:
+    if args.full and dist is not None and world > 1 and args.config == 2 and not args.no_strong and args.length is None:
         wd.stage = "config 5 sharded"
         strong, err = None, None
         strong_limit = float(os.environ.get("BGSA_BENCH_STRONG_TIMEOUT", "300"))
@@ -1200,7 +1282,7 @@ def main() -> int:
                 result["config5_sharded"] = strong if strong is not None else {"error": err}
 
     # ---- config 3, one GPU: the other subject mixes (same kernel, same sizes) ---------------------------------
-    if algo == B.ALGO_BANDED and world == 1 and args.banded_variants and not overridden:
+    if args.full and algo == B.ALGO_BANDED and world == 1 and args.banded_variants and not overridden:
         variants = {}
         for name in [v for v in args.banded_variants.split(",") if v and v != mix]:
             del s_rows
@@ -1227,12 +1309,12 @@ def main() -> int:
         q_rows, s_rows, _ = make_workload(args.config, algo, nq, ns, length, k, mix, rank, dev, None)
         q_host = q_rows.cpu().numpy()
 
-    if rank == 0 and world > 1:
+    if rank == 0 and world > 1 and args.full:
         result["total_gcups"] = {"skipped": "measured by rank 0 at N = 1 only"}
         result["cpu_baseline"] = {"skipped": "measured by rank 0 at N = 1 only"}
         result["other_configs"] = {"skipped": "N = 1 only; at N > 1 the line carries `config5_sharded`"}
     if rank == 0:
-        if not args.no_total and world == 1:
+        if args.full and not args.no_total and world == 1:
             wd.stage = "total_gcups leg"
             try:
                 del out
@@ -1245,7 +1327,7 @@ def main() -> int:
                 result["total_gcups"]["runs_wall_ms"] = [r["wall_ms"] for r in runs]
             except Exception as e:
                 result["total_gcups"] = {"error": repr(e)}
-        if world == 1 and args.config == 2 and not args.no_other_configs and args.length is None and args.k is None:
+        if args.full and world == 1 and args.config == 2 and not args.no_other_configs and args.length is None and args.k is None:
             # ---- the other BASELINE GPU configs in the line the driver runs: 3 (planted mix), 4, 5 -----------------
             wd.stage = "other_configs leg"
             try:
@@ -1277,7 +1359,7 @@ def main() -> int:
                 result["roofline"][f"cfg{cid}_issued_frac_sustained"] = e["issued_frac_sustained"]
                 result["roofline"][f"cfg{cid}_valu_per_wave_row"] = e["valu_per_wave_row"]
                 result["roofline"][f"cfg{cid}_watts_mean"] = e["watts_mean"]
-        if not args.no_cpu_baseline and world == 1 and not custom_scores:  # the reference commits 2/-3/-5 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not custom_scores:  # the reference commits 2/-3/-5 only
             wd.stage = "cpu_baseline leg"
             cq, cs = (int(x) for x in args.cpu_sample.split("x"))
             cq, cs = min(cq, nq), min(cs, ns) // 8 * 8

@@ -31,7 +31,11 @@ def build(ref: bool | None = None) -> None:
     """Compile the restatement (always) and the real reference (when /root/reference exists)."""
     subprocess.run(["make", "-C", str(HERE), "all"], check=True, stdout=subprocess.DEVNULL)
     if ref is None:
-        ref = Path(os.environ.get("BGSA_REFERENCE", "/root/reference")).is_dir()
+        # where `make ref` reads the reference: $BGSA_REFERENCE, else the Makefile's REFERENCE.  os.path.isdir, not
+        # Path.is_dir: a directory this user may not enter counts as absent, not as an error.
+        where = os.environ.get("BGSA_REFERENCE") or subprocess.run(
+            ["make", "-s", "-C", str(HERE), "print-reference"], check=True, capture_output=True, text=True).stdout.strip()
+        ref = os.path.isdir(where)
     if ref:
         subprocess.run(["make", "-C", str(HERE), "ref"], check=True, stdout=subprocess.DEVNULL)
 

@@ -23,10 +23,10 @@ if has tests; then
 fi
 if has bench; then
   cfg() { case " $CONFIGS " in *" $1 "*) return 0;; *) return 1;; esac; }
-  cfg 2 && step cfg2 500 python bench.py --config 2 > $out/bench_cfg2.json 2> $out/bench_cfg2.err
-  cfg 3 && step cfg3 500 python bench.py --config 3 --cpu-sample 1000x100000 > $out/bench_cfg3.json 2> $out/bench_cfg3.err
-  cfg 4 && step cfg4 600 python bench.py --config 4 --cpu-sample 1000x50000 > $out/bench_cfg4.json 2> $out/bench_cfg4.err
-  cfg 5 && step cfg5 600 python bench.py --config 5 --steps 2 --cpu-sample 200x20000 > $out/bench_cfg5.json 2> $out/bench_cfg5.err
+  cfg 2 && step cfg2 500 python bench.py --full --config 2 > $out/bench_cfg2.json 2> $out/bench_cfg2.err
+  cfg 3 && step cfg3 500 python bench.py --full --config 3 --cpu-sample 1000x100000 > $out/bench_cfg3.json 2> $out/bench_cfg3.err
+  cfg 4 && step cfg4 600 python bench.py --full --config 4 --cpu-sample 1000x50000 > $out/bench_cfg4.json 2> $out/bench_cfg4.err
+  cfg 5 && step cfg5 600 python bench.py --full --config 5 --steps 2 --cpu-sample 200x20000 > $out/bench_cfg5.json 2> $out/bench_cfg5.err
 fi
 if has prof; then
   for c in $CONFIGS; do
@@ -52,7 +52,7 @@ if has banded; then
   done
 fi
 if has k31; then   # the reference's DEFAULT banded threshold (banded/BGSA_CPU/main.c:43), every pair surviving: time + the three PMC passes
-  step "bench cfg3 k31" 300 python bench.py --config 3 --k 31 --banded-mix survivors --banded-variants '' --steps 3 --no-cpu-baseline --no-total > $out/bench_cfg3_k31.json 2> $out/bench_cfg3_k31.err
+  step "bench cfg3 k31" 300 python bench.py --full --config 3 --k 31 --banded-mix survivors --banded-variants '' --steps 3 --no-cpu-baseline --no-total > $out/bench_cfg3_k31.json 2> $out/bench_cfg3_k31.err
   for grp in FETCH_SIZE WRITE_SIZE SQ; do
     ctrs=$grp; [ $grp = SQ ] && ctrs=$SQ
     step "pmc cfg3 k31 $grp" 300 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $out/pmc_cfg3_k31_$grp -- python3 bench.py --config 3 --k 31 --banded-mix survivors --banded-variants '' --steps 1 --warmup 1 --no-cpu-baseline --no-total --no-clock-probe > $out/pmc_cfg3_k31_$grp.log 2>&1

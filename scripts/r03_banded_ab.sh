@@ -6,7 +6,7 @@ out=gpurun_out/${1:-r03}; mkdir -p $out; shift
 variants=${@:-"funnel cut_g1 cut_g2"}
 run() { # run <tag> <env...>
   local tag=$1; shift
-  env "$@" timeout -k 10 280 python bench.py --config 3 --steps 5 --warmup 2 --no-cpu-baseline --no-total > $out/banded_ab_$tag.json 2> $out/banded_ab_$tag.err
+  env "$@" timeout -k 10 280 python bench.py --full --config 3 --steps 5 --warmup 2 --no-cpu-baseline --no-total > $out/banded_ab_$tag.json 2> $out/banded_ab_$tag.err
   echo "$tag rc=$?" | tee -a $out/banded_ab_summary.txt
   python - $out/banded_ab_$tag.json <<'PY' | tee -a $out/banded_ab_summary.txt
 import json, sys

@@ -5,7 +5,7 @@
 out=gpurun_out/${1:-r03}; mkdir -p $out
 one() { # one <label> <env> <bench args...>
   local label=$1 e=$2; shift 2
-  r=$(env $e timeout -k 10 300 python bench.py "$@" --no-cpu-baseline --no-total --no-clock-probe --banded-variants '' 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['roofline']['kernel_ms'], r['value'], r['config']['kernel'], r['checksum'])" 2>/dev/null)
+  r=$(env $e timeout -k 10 300 python bench.py --full "$@" --no-cpu-baseline --no-total --no-clock-probe --banded-variants '' 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['roofline']['kernel_ms'], r['value'], r['config']['kernel'], r['checksum'])" 2>/dev/null)
   echo "$label: ${r:-fail}" | tee -a $out/seam_ab.txt
 }
 for nq in 12 25 100 200 400 1000; do

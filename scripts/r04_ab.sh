@@ -8,7 +8,7 @@ PREV=$PWD/bgsa_amd/_prev/libbgsa_hip_prev.so
 one() { # one <label> <env...>
   local label=$1; shift
   local r
-  r=$(env "$@" timeout -k 10 400 python bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-total --no-other-configs --banded-variants '' $EXTRA 2>/dev/null |
+  r=$(env "$@" timeout -k 10 400 python bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-total --no-other-configs --banded-variants '' $EXTRA 2>/dev/null |
       python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['roofline']['kernel_ms'], r['value'], r['config']['kernel'], r['checksum'], (r.get('clock') or {}).get('sustained_mhz'))" 2>/dev/null)
   echo "cfg$cfg $EXTRA $label: $r" | tee -a $out
 }

@@ -7,7 +7,7 @@
 out=${1:-gpurun_out/r04/banded_collector_ab.txt}; mkdir -p $(dirname $out)
 PREV=$PWD/bgsa_amd/_prev/libbgsa_hip_prev.so
 one() { local label=$1 k=$2 mix=$3; shift 3
-  r=$(env "$@" timeout -k 10 300 python bench.py --config 3 --k $k --banded-mix $mix --banded-variants '' --steps 3 --warmup 1 --no-cpu-baseline --no-total --no-clock-probe --no-other-configs 2>/dev/null |
+  r=$(env "$@" timeout -k 10 300 python bench.py --full --config 3 --k $k --banded-mix $mix --banded-variants '' --steps 3 --warmup 1 --no-cpu-baseline --no-total --no-clock-probe --no-other-configs 2>/dev/null |
       python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['roofline']['kernel_ms'], r['config']['kernel'], r['checksum'])" 2>/dev/null)
   echo "k=$k $mix $label: $r" | tee -a $out; }
 for k in ${KS:-13 15 16 24 31}; do

@@ -5,7 +5,7 @@
 out=${1:-gpurun_out/r04d/bitpal_ab.txt}
 P=$PWD/bgsa_amd/_prev
 one() { local label=$1; shift
-  r=$(env "$@" timeout -k 10 400 python bench.py --config 4 --steps 3 --warmup 1 --no-cpu-baseline --no-total 2>/dev/null |
+  r=$(env "$@" timeout -k 10 400 python bench.py --full --config 4 --steps 3 --warmup 1 --no-cpu-baseline --no-total 2>/dev/null |
       python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['roofline']['kernel_ms'], r['value'], r['checksum'], (r.get('clock') or {}).get('sustained_mhz'), r['roofline']['issued']['generator_count']['valu_per_row'])" 2>/dev/null)
   echo "$label: $r" | tee -a $out; }
 for rep in 1 2; do

@@ -4,7 +4,7 @@
 # Same box, kernel ms from bench.py's HIP events, checksums compared.
 out=${1:-gpurun_out/r04/dyn_ab.txt}
 one() { local label=$1 cfg=$2; shift 2
-  r=$(env "$@" timeout -k 10 400 python bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-total $EXTRA 2>/dev/null |
+  r=$(env "$@" timeout -k 10 400 python bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-total $EXTRA 2>/dev/null |
       python -c "
 import sys,json
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -30,7 +30,7 @@ for length in (150, 1000, 1024):
 sys.exit(1 if bad or B.lib().bgsa_hip_stream_faults(1) else 0)
 P
 }
-run() { python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-total --no-other-configs "$@" 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-total --no-other-configs "$@" 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); print('  ', r['config']['kernel'], '|', r['roofline']['kernel_ms'], 'ms |', r['value'], 'GCUPS | MHz', (r.get('clock') or {}).get('sustained_mhz'), '| checksum', r['checksum'])"; }
 lib() { echo $PWD/bgsa_amd/_ab/libbgsa_hip_$1.so; }

@@ -9,5 +9,5 @@ cd "$(dirname "$0")/.."
 ranks=${1:-4}
 export BGSA_BENCH_SAME_GPU=1 BGSA_BENCH_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 BGSA_BENCH_TIMEOUT=1100 BGSA_BENCH_GATHER_TIMEOUT=600 \
        BGSA_BENCH_STRONG_TIMEOUT=400 BGSA_BENCH_WEAK_TIMEOUT=300
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $ranks --master-addr 127.0.0.1 --master-port 29577 bench.py --gpus $ranks \
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $ranks --master-addr 127.0.0.1 --master-port 29577 bench.py --full --gpus $ranks \
     --steps 2 --warmup 1 2> gpurun_out/r05_scale_rehearsal.err | grep '^{'

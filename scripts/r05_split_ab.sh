@@ -30,7 +30,7 @@ for length in (1000, 1024, 930):
 sys.exit(1 if bad or B.lib().bgsa_hip_stream_faults(1) else 0)
 P
 }
-run() { python3 bench.py --config 5 --steps 2 --warmup 1 --no-cpu-baseline --no-total "$@" 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --config 5 --steps 2 --warmup 1 --no-cpu-baseline --no-total "$@" 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); print('  ', r['config']['kernel'], '|', r['roofline']['kernel_ms'], 'ms |', r['value'], 'GCUPS | tile', (r['roofline']['traffic_model'] or {}).get('query_tile'), '| MHz', (r.get('clock') or {}).get('sustained_mhz'), '| checksum', r['checksum'])"; }
 echo "== parity, resident Peq planes at 30/32 words (BGSA_MYERS_PEQ_MAX_WORDS=32), counter and static grids"

@@ -3,7 +3,7 @@
 # bodies (schedule_ilp 2,24), static grids for all (the counter instantiation only fits 256 VGPRs up to K = 8), config 5.
 set -e
 cd "$(dirname "$0")/.."
-run() { python3 bench.py --config 5 --steps 2 --warmup 1 --no-cpu-baseline --no-total "$@" 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --config 5 --steps 2 --warmup 1 --no-cpu-baseline --no-total "$@" 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); print('  ', r['config']['kernel'], '|', r['roofline']['kernel_ms'], 'ms |', r['value'], 'GCUPS | MHz', (r.get('clock') or {}).get('sustained_mhz'), '| checksum', r['checksum'])"; }
 lib() { echo $PWD/bgsa_amd/_ab/libbgsa_hip_$1.so; }

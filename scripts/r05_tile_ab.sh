@@ -4,7 +4,7 @@
 #     scripts/r05_tile_ab.sh > gpurun_out/r05_tile_ab.txt
 set -e
 cd "$(dirname "$0")/.."
-run() { python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-total --no-other-configs "$@" 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-total --no-other-configs "$@" 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); print('  ', r['config']['kernel'], '|', r['roofline']['kernel_ms'], 'ms |', r['value'], 'GCUPS | tile', (r['roofline']['traffic_model'] or {}).get('query_tile'), '| model bytes / algorithmic', (r['roofline']['traffic_model'] or {}).get('ratio_to_algorithmic'), '| checksum', r['checksum'])"; }
 for i in 1 2; do

@@ -146,3 +146,27 @@ def test_every_config_is_one_job_at_every_n():
     # never below the reference's block
     assert bench.gather_block_rows(10_000) == 1000 and bench.gather_block_rows(1_000) == 100 and bench.gather_block_rows(300) == 100
     assert bench.gather_block_rows(50_000) == 1000 and bench.REF_BUCKET_COUNT == 100
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_last_step(tmp_path):
+    """--dump-outputs: the same seeded rows x columns of the score matrix every time, as float32 next to their indices; for the
+    banded filter also every pair it did not reject, in row-major order."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    out = torch.randint(-150, 1, (700, 9000 + 64), dtype=torch.int16)
+    bench.dump_outputs(tmp_path / "a", out, bench.B.ALGO_MYERS, 700, 9000, 0, 9000, 0, None)
+    bench.dump_outputs(tmp_path / "b", out.clone(), bench.B.ALGO_MYERS, 700, 9000, 0, 9000, 0, None)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["query_index.npy", "scores.npy", "subject_index.npy"]
+    rows, cols = np.load(tmp_path / "a" / "query_index.npy"), np.load(tmp_path / "a" / "subject_index.npy")
+    got = np.load(tmp_path / "a" / "scores.npy")
+    assert got.dtype == np.float32 and rows.dtype == cols.dtype == np.float64
+    assert got.shape == (bench.DUMP_QUERIES, bench.DUMP_SUBJECTS) and cols.max() < 9000 and len(set(rows)) == len(rows)
+    assert np.array_equal(got, out.numpy()[rows.astype(int)][:, cols.astype(int)])
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in files)
+    band = torch.full((100, 200), 127, dtype=torch.int8)
+    band[3, 7], band[50, 0], band[99, 150] = 2, 0, 5
+    bench.dump_outputs(tmp_path / "c", band, bench.B.ALGO_BANDED, 100, 150, 0, 150, 0, None)
+    assert np.load(tmp_path / "c" / "scores.npy").shape == (100, 150)
+    assert np.load(tmp_path / "c" / "survivors.npy").tolist() == [[3, 7, 2], [50, 0, 0]]   # column 150 is padding

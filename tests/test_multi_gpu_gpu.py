@@ -65,8 +65,8 @@ def test_two_ranks_hip_compute_and_streamed_gather(tmp_path, oracle, algo, layou
     assert np.array_equal(got, np.concatenate(parts))
 
 
-def _bench_two_ranks(extra_env, extra_args=(), want_rc=0, ranks=2):
-    """bench.py exactly as the driver starts it for N = 2, except that both ranks share this box's one card and the
+def _bench_two_ranks(extra_env, extra_args=(), want_rc=0, ranks=2, full=True):
+    """bench.py (--full by default) exactly as the driver starts it for N = 2, except that both ranks share this box's one card and the
     collectives go through gloo (BGSA_BENCH_SAME_GPU / BGSA_BENCH_BACKEND: a rehearsal of the code path, not a
     measurement)."""
     import json
@@ -74,7 +74,7 @@ def _bench_two_ranks(extra_env, extra_args=(), want_rc=0, ranks=2):
     env = dict(os.environ, BGSA_BENCH_SAME_GPU="1", BGSA_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
-           "--nq", "300", "--ns", "64000", *extra_args]
+           "--nq", "300", "--ns", "64000", *(("--full",) if full else ()), *extra_args]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert (p.returncode == 0) if want_rc == 0 else (p.returncode != 0), p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -125,6 +125,35 @@ def test_bench_line_for_two_ranks(config):
     assert all(name in r["roofline"] for name in ("issued_frac", "issued_frac_sustained", "valu_per_wave_row"))
 
 
+def test_plain_bench_line_for_two_ranks_and_its_dumped_outputs(tmp_path, oracle):
+    """A plain run at N = 2 (no --full): the gathered timed region alone, its kernel time from HIP events around the step's
+    per-block launches, no side leg; --dump-outputs gathers each rank's columns of the sample to rank 0, and the sample is what
+    the oracle scores for those pairs (each rank's subjects rebuilt here from its own seed)."""
+    import importlib.util
+    import torch
+    r = _bench_two_ranks({}, ("--config", "2", "--dump-outputs", str(tmp_path / "d")), full=False)
+    assert r["n_gpus"] == 2 and r["value"] > 0 and r["ms_per_step"] > 0 and r["steps"] == 2 and r["scaling"] == "strong"
+    assert r["kernel_only"] is None and r["gather_ok"] is None and r["gather"]["content_check"] is None
+    assert r["gather"]["blocks_per_step"] == 3 and r["gather"]["root_blocks_received"] == 3 * 3     # warm-up + two steps
+    assert not {"weak", "config5_sharded", "gather_blocks_of_100", "cpu_baseline", "total_gcups", "other_configs", "checksum"} & set(r)
+    assert all(x["kernel_ms"] > 0 for x in r["ranks"]) and r["ranks_seen"] == 2
+    ro = r["roofline"]
+    assert ro["kernel_ms"] > 0 and "100 queries each" in ro["kernel_launch"] and ro["traffic_model"]["launches"] == ro["kernel_launch"]
+    assert r["ms_per_step"] >= 0.9 * ro["kernel_ms"]       # a step holds this rank's kernels (both ranks share the one card here)
+    spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    dev = torch.device("cuda:0")
+    q_rows, s0, _ = bench.make_workload(2, bench.B.ALGO_MYERS, 300, 32000, 150, 0, None, 0, dev, None)
+    _, s1, _ = bench.make_workload(2, bench.B.ALGO_MYERS, 300, 32000, 150, 0, None, 1, dev, None)
+    subjects = np.concatenate([s0[:32000, :150].cpu().numpy(), s1[:32000, :150].cpu().numpy()])
+    rows = np.load(tmp_path / "d" / "query_index.npy").astype(int)
+    cols = np.load(tmp_path / "d" / "subject_index.npy").astype(int)
+    got = np.load(tmp_path / "d" / "scores.npy")
+    assert got.shape == (300, 8192) and (cols < 32000).any() and (cols >= 32000).any()
+    assert np.array_equal(got, oracle.myers64(q_rows.cpu().numpy()[rows], subjects[cols]).astype(np.float32))
+
+
 def test_bench_line_for_four_ranks_one_bucket_in_four_slices():
     """Four ranks on the one card (the most this box allows beside the test process): ONE 64,000-subject bucket cut by
     plan_shards into four slices, three peers streaming their tiles to rank 0 inside the timed region, several blocks per step
@@ -166,7 +195,7 @@ def test_bench_line_under_torchrun_with_one_rank_goes_through_rccl():
     env.pop("BGSA_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--nq", "300", "--ns", "64000", "--no-cpu-baseline", "--no-total", "--no-other-configs"]
+           "--nq", "300", "--ns", "64000", "--full", "--no-cpu-baseline", "--no-total", "--no-other-configs"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -193,7 +222,7 @@ def test_bench_line_carries_the_other_baseline_configs():
     import json
     import subprocess
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--nq", "300", "--ns", "64000",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--nq", "300", "--ns", "64000", "--full",
            "--no-cpu-baseline", "--no-total"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
@@ -222,7 +251,7 @@ def test_bench_line_carries_the_sustained_clock_without_paying_for_it():
     import json
     import subprocess
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "1", "--nq", "2000", "--ns", "256000",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "1", "--nq", "2000", "--ns", "256000", "--full",
            "--no-cpu-baseline", "--no-total", "--no-other-configs"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
@@ -248,7 +277,7 @@ def test_no_clock_probes_beside_a_kernel_that_fills_the_register_file():
     import subprocess
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, str(ROOT / "bench.py"), "--config", "5", "--steps", "2", "--warmup", "1", "--nq", "64", "--ns", "65536",
-           "--no-cpu-baseline", "--no-total"]
+           "--full", "--no-cpu-baseline", "--no-total"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -305,3 +334,45 @@ def test_config5_eight_shards_one_after_another_equal_the_whole_bucket():
         del a, got
     assert B.lib().bgsa_hip_stream_faults(1) == 0
     print("query tile: whole bucket", tile_whole, "shards", tiles)
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path, oracle):
+    """A plain run (no --full) times exactly --steps steps and prints the headline without the side legs; --dump-outputs writes
+    the same seeded sample of the last step's scores in two runs, and the sample is what the oracle scores for those pairs."""
+    import importlib.util
+    import json
+    import subprocess
+    import torch
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import time
+    lines, walls = [], []
+    for run in ("a", "b"):
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--nq", "300", "--ns", "64000",
+               "--dump-outputs", str(tmp_path / run)]
+        t0 = time.perf_counter()
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
+        walls.append(time.perf_counter() - t0)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+        lines.append(json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1]))
+    r = lines[0]
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["value"] > 0 and r["ms_per_step"] > 0 and r["unit"] == "GCUPS"
+    assert r["higher_is_better"] is True and r["dtype"] == "u32" and r["metric"].startswith("GCUPS")
+    assert not {"other_configs", "cpu_baseline", "total_gcups", "checksum", "banded_variants"} & set(r)
+    assert r["clock"] is None and r["power"] is None
+    # --steps sets the number of timed steps: ms_per_step = wall time of the timed region / steps is one step's kernel time (HIP
+    # events, mean per step) plus launch overhead, and the whole run holds at least warm-up + steps of it
+    assert 0.9 * r["roofline"]["kernel_ms"] <= r["ms_per_step"] <= 1.15 * r["roofline"]["kernel_ms"] + 2.0, r
+    assert walls[0] * 1e3 >= (3 + 1) * r["ms_per_step"]
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == ["query_index.npy", "scores.npy", "subject_index.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in files)
+    # the same inputs rebuilt here (bench.make_workload, same seeds): the sampled scores are the oracle's
+    spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    q_rows, s_rows, _ = bench.make_workload(2, bench.B.ALGO_MYERS, 300, 64000, 150, 0, None, 0, torch.device("cuda:0"), None)
+    rows = np.load(tmp_path / "a" / "query_index.npy").astype(int)
+    cols = np.load(tmp_path / "a" / "subject_index.npy").astype(int)
+    want = oracle.myers64(q_rows.cpu().numpy()[rows], s_rows[:, :150].cpu().numpy()[cols])
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), want.astype(np.float32))
