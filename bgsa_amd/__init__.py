@@ -106,6 +106,9 @@ def lib() -> ctypes.CDLL:
     L.bgsa_hip_event_elapsed_ms.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.bgsa_hip_stream_wait_event.argtypes = [vp, vp]
     L.bgsa_hip_query_stream.argtypes = [i32, vp, i32, i32, vp, i32]
+    L.bgsa_hip_myers_band_stream.argtypes = [vp, i32, i32, vp, i32]
+    L.bgsa_hip_myers_band_half.argtypes = [i32, i32]
+    L.bgsa_hip_myers_band_stats.argtypes = [vp, i32]
     L.bgsa_hip_kernel_name.argtypes = [i32, i32]
     L.bgsa_hip_kernel_name.restype = ctypes.c_char_p
     L.bgsa_hip_malloc.argtypes = [ctypes.POINTER(vp), sz]

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "bgsa_common.h"
+#include "myers_band.h"
 
 namespace bgsa {
 
@@ -230,7 +231,9 @@ static size_t plan_workspace_bytes(const Plan &plan, int ref_len, int read_len, 
     }
     if (algo == BGSA_ALGO_BANDED)  // the stream length depends on k: sized for the worst k
         return banded_stream_bound(ref_len) * n_queries + kTaskCounterBytes;
-    return stream_stride(ref_len) * static_cast<size_t>(n_queries) + kTaskCounterBytes;   // bgsa_common.h "dynamic task handout"
+    // the longer of the plain stream and the Myers band stream (myers_band.h), whichever kernel the plan picks: one size for
+    // every plain plan, as the score sets that reduce to edit distance run the Myers kernels
+    return band_stream_stride(ref_len) * static_cast<size_t>(n_queries) + kTaskCounterBytes;   // bgsa_common.h "dynamic task handout"
 }
 
 int ab_knob_refused(const char *what)
@@ -575,6 +578,46 @@ int bgsa_hip_stream_faults(int clear)
         set_error_text(msg);
     }
     return static_cast<int>(value);
+}
+
+int bgsa_hip_myers_band_half(int ref_len, int read_len)
+{
+    if (ref_len <= 0 || read_len <= 0) return BGSA_HIP_EINVAL;
+    BandSchedule s;
+    const int h = band_half(ref_len, read_len);
+    return band_schedule(ref_len, read_len, h, (read_len + 31) / 32, &s) ? h : 0;
+}
+
+int bgsa_hip_myers_band_stream(const char *mapped_row, int ref_len, int read_len, unsigned char *dst, int cap)
+{
+    if (!mapped_row || ref_len <= 0 || read_len <= 0) return BGSA_HIP_EINVAL;
+    BandSchedule s;
+    if (!band_schedule(ref_len, read_len, band_half(ref_len, read_len), (read_len + 31) / 32, &s)) return 0;
+    const int n = band_stream_layout(ref_len, s, mapped_row, nullptr);
+    if (dst && cap >= n)   // window by window, as pack_band_kernel writes it
+        for (int i = 0; 8 * i < n; i++) {
+            memset(dst + 8 * i, kCodeEnd, 8);
+            band_stream_layout(ref_len, s, mapped_row, dst + 8 * i, 8 * i, 8);
+        }
+    return n;
+}
+
+int bgsa_hip_myers_band_stats(unsigned long long *out, int clear)
+{
+    if (!out) return BGSA_HIP_EINVAL;
+    out[0] = out[1] = 0;
+    int dev = 0;
+    BGSA_HIP_TRY(hipGetDevice(&dev));
+    unsigned *word = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_fault_mu);
+        auto it = g_fault_words.find(dev);
+        if (it == g_fault_words.end()) return BGSA_HIP_OK;  // nothing was ever launched on this device
+        word = it->second;
+    }
+    BGSA_HIP_TRY(hipMemcpy(out, band_stats_words(word), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (clear) BGSA_HIP_TRY(hipMemset(band_stats_words(word), 0, 2 * sizeof(unsigned long long)));
+    return BGSA_HIP_OK;
 }
 
 int bgsa_hip_debug_inject_stream_fault(int kind)

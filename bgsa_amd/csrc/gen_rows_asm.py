@@ -65,6 +65,7 @@ def ilp_planes(body: R.Body) -> R.Body:      # BGSA_GEN_MYERS_ILP_PLANES=1: the 
 
 MYERS_PLANES_SPLIT = int(os.environ.get("BGSA_GEN_MYERS_PLANES_SPLIT", "0"))   # A/B: the code-plane rows of 30 / 32 words with the chains in turns
 MYERS_PEQ_BLOCK_NW = [12, 14, 16, 18, 20]  # column blocks with resident Peq planes (20 words: 238 VGPRs; 22 would need 256)
+MYERS_BAND_NW = list(range(3, R.MYERS_BAND_MAX_WORDS + 1))   # windowed rows of the certified band (gen_band_function): 65..256 bp
 MYERS_PAIR_NW = [1, 2]  # two rows per stream token: the 10-20 VALU row cannot hide the scalar dispatch
 MYERS_PLANES_NW = [10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32]  # at most one padding word
 MYERS_SEMI_PLANES_NW = [26, 28, 30, 32]  # semi-global beyond the resident Peq planes (24 words), up to 1024 bp
@@ -222,6 +223,132 @@ __device__ __forceinline__ int {fn_name}<{template_args}>(uint32_t (&state)[{n_s
                                                    const int n_windows)
 {{
     uint32_t tmp[{max(n_slots, 1)}];
+    int left;
+    asm volatile(
+{text}
+        : {", ".join(outs)}
+        : {", ".join(ins)}
+        : {clob});
+    return left;
+}}
+"""
+
+
+def gen_band_function(nw: int) -> str:
+    """Row loop of the certified band (rows_ir.py: myers_window_body): one slot group per window [a, b] of
+    the nw words, in the order of rows_ir.myers_window_index.  A group is the plain loop's eight slots — five row bodies of
+    that window, END, REFILL — and SETWIN (code 7) in place of the fail slot: it reads the window byte that follows and moves
+    the dispatch base to that window's group.  Every slot has the stride of the full window's slot (the shorter bodies are
+    padded, never executed), so the dispatch is the plain loop's.  %[band] = 0 makes every SETWIN pick the full window: the
+    same stream then runs full rows (the certificate's fallback).  A window byte past the last group leaves with S_LEFT = -2."""
+    windows = [(a, b) for a in range(nw) for b in range(a, nw)]
+    assert all(R.myers_window_index(nw, a, b) == k for k, (a, b) in enumerate(windows))
+    k_full = R.myers_window_index(nw, 0, nw - 1)
+    full = ilp(R.myers_body(nw, 1, balanced=MYERS_BALANCED))
+    slot_of, n_slots = full.allocate_temps()
+    stride = f"(L_g{k_full}s1_%= - L_g{k_full}s0_%=)"
+
+    def reg_for(c: int, slots: dict):
+        def reg(name: str) -> str:
+            if name.startswith("S"):
+                return f"%[s{name[1:]}]"
+            if name.startswith("E"):
+                return f"%[e{c}_{name[1:]}]"
+            return f"%[t{slots[name]}]"
+        return reg
+
+    def disp() -> list[str]:
+        return [
+            f"s_and_b32 {S_C}, {S_WIN_LO}, 7",
+            f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
+            f"s_mul_i32 {S_C}, {S_C}, {stride}",
+            f"s_add_u32 {S_PC_LO}, {S_BASE_LO}, {S_C}",
+            f"s_addc_u32 {S_PC_HI}, {S_BASE_HI}, 0",
+            f"s_setpc_b64 {S_PC}",
+        ]
+
+    def pad(k: int, s: int) -> str:   # fill slot s of group k up to the stride (the full group's bodies define it)
+        return f".fill ({stride} - (L_g{k}e{s}_%= - L_g{k}s{s}_%=)) / 4, 4, 0xbf800000"
+
+    asm: list[str] = [
+        f"s_mov_b64 {S_PTR}, %[qp]",
+        f"s_mov_b32 {S_LEFT}, %[nwin]",
+        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
+        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
+        f"s_getpc_b64 {S_PC}",
+        "L_anchor_%=:",
+        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, (L_g{k_full}s0_%= - L_anchor_%=)",   # the stream's first SETWIN picks the window
+        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
+        "s_waitcnt lgkmcnt(0)",
+    ]
+    asm += disp()
+    for k, (a, b) in enumerate(windows):
+        body = full if (a, b) == (0, nw - 1) else ilp(R.myers_window_body(nw, a, b, balanced=MYERS_BALANCED))
+        slots, n = (slot_of, n_slots) if body is full else body.allocate_temps()
+        assert n <= n_slots
+        for c in range(5):
+            asm.append(f"L_g{k}s{c}_%=:")
+            asm += body.emit_asm(reg_for(c, slots), c)
+            asm += disp()
+            if body is not full:
+                asm.append(f"L_g{k}e{c}_%=:")
+                asm.append(pad(k, c))
+        asm.append(f"L_g{k}s5_%=:")     # END
+        asm.append("s_branch L_done_%=")
+        asm.append(f"L_g{k}e5_%=:")
+        asm.append(pad(k, 5))
+        asm.append(f"L_g{k}s6_%=:")     # REFILL
+        asm += [
+            f"s_sub_u32 {S_LEFT}, {S_LEFT}, 1",
+            "s_cbranch_scc1 L_done_%=",
+            "s_waitcnt lgkmcnt(0)",
+            f"s_mov_b64 {S_WIN}, {S_NXT}",
+            f"s_add_u32 {S_PTR_LO}, {S_PTR_LO}, 8",
+            f"s_addc_u32 {S_PTR_HI}, {S_PTR_HI}, 0",
+            f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
+        ]
+        asm += disp()
+        asm.append(f"L_g{k}e6_%=:")
+        asm.append(pad(k, 6))
+        asm.append(f"L_g{k}s7_%=:")     # SETWIN <window byte>
+        asm += [
+            f"s_and_b32 {S_C}, {S_WIN_LO}, 0xff",
+            f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
+            f"s_cmp_ge_u32 {S_C}, {len(windows)}",
+            "s_cbranch_scc1 L_fail_%=",
+            f"s_cmp_eq_u32 %[band], 0",
+            f"s_cselect_b32 {S_C}, {k_full}, {S_C}",
+            f"s_mul_i32 {S_C}, {S_C}, 8 * {stride}",
+            f"s_getpc_b64 {S_PC}",            # group 0 = this slot's address - its distance from group 0
+            f"L_g{k}a_%=:",
+            f"s_sub_u32 {S_PC_LO}, {S_PC_LO}, (L_g{k}a_%= - L_g0s0_%=)",
+            f"s_subb_u32 {S_PC_HI}, {S_PC_HI}, 0",
+            f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, {S_C}",
+            f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
+        ]
+        asm += disp()
+        asm.append(f"L_g{k}e7_%=:")
+        asm.append(pad(k, 7))
+    asm.append("L_fail_%=:")
+    asm += fail_slot()
+    asm += done()
+
+    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
+    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(2 * nw)]
+    outs += ['[left] "=s"(left)']
+    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
+    ins = [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(nw)]
+    ins += ['[qp] "s"(stream)', '[nwin] "s"(n_windows)', '[band] "s"(band)']
+    clob = ", ".join(f'"{c}"' for c in CLOBBERS)
+    return f"""
+// {len(windows)} windows; full rows {full.valu_count()} VALU, {n_slots} temporaries
+template <>
+__device__ __forceinline__ int myers_band_rows_asm<{nw}>(uint32_t (&state)[{2 * nw}],
+                                                  const uint32_t (&P)[5][{nw}],
+                                                  const unsigned long long stream,
+                                                  const int n_windows, const int band)
+{{
+    uint32_t tmp[{n_slots}];
     int left;
     asm volatile(
 {text}
@@ -1475,7 +1602,25 @@ def bitpal_inc_text(sc: R.BitpalScores) -> str:
     return "".join(parts)
 
 
+def band_inc_text() -> str:
+    """The certified band's row loops (gen_band_function): one slot group per window, 1.2 MB of text for 3..8 words, so
+    this header is written at build time (Makefile: _gen/myers_band_rows_gen.inc) instead of being committed."""
+    parts = ["// GENERATED by gen_rows_asm.py --band from rows_ir.py at build time — do not edit.\n",
+             "// Certified band (DESIGN §4.2): the rows of one query on the band stream (myers_band.h), each row on the words of its\n"
+             "// window only; band = 0: every row on all NW words (the fallback of a wave whose certificate failed).\n"
+             "template <int NW>\n"
+             "__device__ __forceinline__ int myers_band_rows_asm(uint32_t (&state)[2 * NW],\n"
+             "                                                    const uint32_t (&P)[5][NW],\n"
+             "                                                    const unsigned long long stream, const int n_windows,\n"
+             "                                                    const int band);\n"]
+    parts += [gen_band_function(nw) for nw in MYERS_BAND_NW]
+    return "".join(parts)
+
+
 def main() -> int:
+    if "--band" in sys.argv:   # `--band FILE`: the band header only (built, not committed)
+        Path(sys.argv[sys.argv.index("--band") + 1]).write_text(band_inc_text())
+        return 0
     # `--out DIR`: write the three headers there instead of beside this script (tests/test_generated_inc_cpu.py compares them
     # with the committed ones)
     here = Path(sys.argv[sys.argv.index("--out") + 1]) if "--out" in sys.argv else Path(__file__).resolve().parent

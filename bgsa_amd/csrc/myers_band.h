@@ -1,0 +1,150 @@
+// myers_band.h — the certified diagonal band of the Myers global kernels.
+//
+// A path through cell (i, j) of the m x n matrix (query rows, subject columns) holds at least |d| + |d - (n - m)| indels,
+// d = j - i.  If a pair's distance is <= B = 2h + 1, its optimal paths stay inside the band |d| + |d - (n - m)| <= B, and a
+// row needs only the words that hold the band's columns: its WINDOW [a, b].  Words left of the window keep their last
+// deltas (the lowest active word gets the row-edge carry-ins, a vertical step), words right of it keep their initial
+// state (a horizontal path), so every column still holds the cost of a real path: the score D' >= D, and D' <= B
+// certifies D' = D.  A wave with a lane above B runs the query again with full rows (myers_global_asm_kernel<NW, 1, *, true>).
+//
+// Band stream (one per query, 8-byte windows, `band_stream_stride` bytes): the plain stream's codes — 0..4 rows, 5 END,
+// 6 REFILL — plus 7 = SETWIN followed by one byte, the slot group (band_window_index) of the rows that follow.  A SETWIN
+// and its byte always share a window: where only byte 6 is left, a REFILL there ends the window early.  The packer pads
+// with END up to the stride; the last window is all END.  rows_ir.py: myers_band_stream restates it.
+#pragma once
+
+#include <stdlib.h>
+
+#include "bgsa_common.h"
+
+namespace bgsa {
+
+constexpr int kBandMaxWords = 8;                        // widths with windowed bodies (gen_rows_asm.py: MYERS_BAND_NW): 65..256 bp
+constexpr int kBandMinWords = 3;
+constexpr int kBandMaxSwitches = 2 * kBandMaxWords;     // a query's window changes at most 2 NW - 2 times after the first
+constexpr int kCodeSetWin = 7;
+constexpr int kBandBadCode = 0xff;                      // SETWIN with a window byte past the last group: the loop's fail exit
+
+struct BandSchedule {
+    int n = 0;                        // windows of the query (0: band off)
+    int row[kBandMaxSwitches] = {};   // first query row (0-based) of each window
+    int win[kBandMaxSwitches] = {};   // its slot group
+};
+
+__host__ __device__ inline int band_window_index(int nw, int a, int b) { return a * nw - a * (a - 1) / 2 + (b - a); }
+
+// Default half-width for a length: the mean edit distance of random uniform ACGT pairs + 4.5 standard deviations
+// (rows_ir.py: myers_band_half, LABNOTES §11): 150 bp -> h = 48, B = 97.
+inline int band_default_half(int len) { return (9 * len + 192) / 32; }
+
+// The half-width of a launch: BGSA_MYERS_BAND=0 turns the band off, =N sets h = N (A/B knob); default by the
+// longer of the two lengths.
+inline int band_half(int m, int n)
+{
+    static const int knob = [] {
+        const char *e = getenv("BGSA_MYERS_BAND");
+        return e ? atoi(e) : -1;
+    }();
+    if (knob >= 0) return knob;
+    return band_default_half(m > n ? m : n);
+}
+
+// The windows of every row of an m-row query against nw-word subjects of length n: false (s->n = 0) when the band is off
+// for this shape — |n - m| > B, a width without windowed bodies, or windows that would not save a fifth of the word-rows.
+// rows_ir.py: myers_band_windows.
+inline bool band_schedule(int m, int n, int h, int nw, BandSchedule *s)
+{
+    s->n = 0;
+    const int B = 2 * h + 1, delta = n - m;
+    if (h <= 0 || m <= 0 || n <= 0 || abs(delta) > B || nw < kBandMinWords || nw > kBandMaxWords || (n + 31) / 32 != nw)
+        return false;
+    const int dlo = -((B - delta) / 2), dhi = (delta + B) / 2;   // ceil((delta - B) / 2), floor((delta + B) / 2): both numerators >= 0
+    long long words = 0;
+    int pa = -1, pb = -1;
+    for (int i = 1; i <= m; i++) {
+        const int jlo = i + dlo < 1 ? 1 : i + dlo, jhi = i + dhi > n ? n : i + dhi;
+        const int a = (jlo - 1) / 32, b = (jhi - 1) / 32;
+        words += b - a + 1;
+        if (a != pa || b != pb) {
+            if (s->n == kBandMaxSwitches) {
+                s->n = 0;
+                return false;
+            }
+            s->row[s->n] = i - 1;
+            s->win[s->n] = band_window_index(nw, a, b);
+            s->n++;
+            pa = a;
+            pb = b;
+        }
+    }
+    if (5 * words > 4ll * m * nw) {
+        s->n = 0;
+        return false;
+    }
+    return true;
+}
+
+// Bytes of one band stream, padded like the plain one: the codes, at most 3 bytes per window change (SETWIN, its byte, a
+// byte 7 skipped by an early REFILL), END, the spare window.
+inline size_t band_stream_stride(int ref_len) { return stream_stride(ref_len + 3 * kBandMaxSwitches); }
+
+// Writes bytes [first, first + count) of the band stream of one query (row = its mapped characters) to dst[0 .. count) when
+// dst != nullptr and returns the stream's length in bytes (<= band_stream_stride) — or, once the range is written, the position
+// after it.  Where the SETWIN and REFILL bytes go depends on the schedule only, so the packer gives every 8-byte window a
+// thread of its own, which reads the (at most seven) characters of its window and no others.  Shared by the packer kernel
+// and bgsa_hip_myers_band_stream.
+__host__ __device__ inline int band_stream_layout(int len, const BandSchedule &s, const char *row, unsigned char *dst,
+                                                  int first = 0, int count = 0x7fffffff)
+{
+    int pos = 0, sw = 0;
+    auto in = [&]() { return dst && pos >= first && pos - first < count; };
+    auto put = [&](int c) {
+        if (in()) dst[pos - first] = static_cast<unsigned char>(c);
+        pos++;
+    };
+    auto refill = [&]() {
+        put(kCodeRefill);
+        while (pos & 7) put(kCodeEnd);
+    };
+    for (int r = 0; r < len; r++) {
+        if (dst && pos - first >= count) return pos;
+        if (sw < s.n && s.row[sw] == r) {
+            if ((pos & 7) >= 6) refill();
+            put(kCodeSetWin);
+            put(s.win[sw]);
+            sw++;
+        }
+        if ((pos & 7) == 7) refill();
+        if (in()) {
+            const unsigned c = static_cast<unsigned char>(row[r]);
+            dst[pos - first] = static_cast<unsigned char>(c > 4 ? 0u : c);   // as plain_stream_window: out-of-alphabet bytes behave as 'A'
+        }
+        pos++;
+    }
+    if ((pos & 7) == 7) refill();
+    put(kCodeEnd);
+    while (pos & 7) put(kCodeEnd);
+    for (int j = 0; j < 8; j++) put(kCodeEnd);
+    return pos;
+}
+
+// The guard's pair of one launch, {queries redone, queries banded} (myers_global_asm_kernel<NW, 1, *, true>): 64 bytes behind
+// the task counter, inside the kTaskCounterBytes behind the streams; zeroed by the packer with the counter.
+__host__ __device__ inline unsigned long long *band_launch_words(unsigned *task_counter)
+{
+    return reinterpret_cast<unsigned long long *>(task_counter + 16);
+}
+
+// Packs the band streams of queries ref_start .. ref_end - 1 and zeroes the task counter d_words[0] and the guard's pair.
+int launch_pack_band(const char *d_content, int ref_len, const BandSchedule &s, int ref_start, int ref_end, void *d_streams,
+                     hipStream_t stream, unsigned *d_words);   // preprocess.hip
+
+// Certificate statistics, per device: [0] = queries a wave ran again with full rows, [1] = queries a wave ran banded.
+// They live behind the sticky fault word (bgsa_common.h: device_fault_word, a 64-byte allocation) and are read and
+// cleared by bgsa_hip_myers_band_stats().
+__host__ __device__ inline unsigned long long *band_stats_words(unsigned *fault_word)
+{
+    return reinterpret_cast<unsigned long long *>(fault_word + 2);
+}
+
+}  // namespace bgsa

@@ -34,6 +34,7 @@
 #include <algorithm>
 
 #include "bgsa_common.h"
+#include "myers_band.h"
 
 namespace bgsa {
 
@@ -171,18 +172,27 @@ constexpr int kPeqMaxWords = 32;
 constexpr int kSemiPeqMaxWords = 32;  // widest semi-global kernel with resident Peq planes (myers_semi_rows_asm; 26..32 words: chains in turns, round 5)
 constexpr int kPairMaxWords = 2;  // widths instantiated as myers_pair_rows_asm (gen_rows_asm.py: MYERS_PAIR_NW)
 #include "myers_rows_gen.inc"
+#include "_gen/myers_band_rows_gen.inc"   // the certified band's row loops (written by the Makefile: gen_rows_asm.py --band)
 
 // Same task decomposition as above, but all rows of a query run inside one generated asm block:
 // five in-place row bodies selected by a scalar jump per row, every VALU instruction full rate
 // (the inter-word shifts are add-with-carry chains instead of v_alignbit_b32), query characters
 // from the packed code stream.  This is the kernel the launcher picks whenever NW <= 8.
-template <int NW, int G, bool DYN = false>
+// BAND (3..8 words, myers_band.h): the rows run on the band stream, each on the words of its window; a wave whose lanes are not
+// all certified (score <= band_limit) runs the query again with full rows.  The guard: every such fallback is added to the
+// launch's pair band_launch = {queries redone, queries banded} (with the queries this wave banded since its last report), and
+// once the pair holds at least 64 banded queries of which more than one in eight were redone, the wave stops banding for the
+// rest of its tasks.  Pairs that are all far apart then cost about one fallback per wave over the full rows; where
+// (nearly) every wave is certified the pair is touched once per wave, at its end, when the wave adds the rest of its banded
+// queries.  band_stats_add_kernel then adds the launch's pair to the device's sticky counts (bgsa_hip_myers_band_stats).
+template <int NW, int G, bool DYN = false, bool BAND = false>
 __global__ __launch_bounds__(256) void myers_global_asm_kernel(
     const unsigned char *__restrict__ streams, const uint32_t *__restrict__ peq,
     int16_t *__restrict__ out, int ref_len, int read_len, long long ld, int n_groups, int word_num,
     int n_queries, int q_tile, int stream_stride_bytes, unsigned *__restrict__ fault_word,
-    unsigned *__restrict__ task_counter)
+    unsigned *__restrict__ task_counter, int band_limit = 0, unsigned long long *__restrict__ band_launch = nullptr)
 {
+    static_assert(!BAND || (G == 1 && NW >= kBandMinWords && NW <= kBandMaxWords), "band: one group, 3..8 words");
     const int lane = threadIdx.x & (kLanes - 1);
     // Static mapping (DYN = false): workgroup (x, y) = (four wave-groups, query tile).  Dynamic (bgsa_common.h "dynamic task
     // handout"; a separate instantiation, so that the static kernels keep their register counts: the loop costs 5-8 VGPRs,
@@ -195,6 +205,7 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
         task = first_wave_task();
         if (task >= n_tasks) return;
     }
+    int band_on = 1, unreported = 0;   // wave-uniform (BAND): the guard, and the banded queries not yet added to band_launch[1]
     do {
         int group0, tile;
         if constexpr (DYN) {
@@ -234,6 +245,43 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
             }
             const unsigned long long s =
                 reinterpret_cast<unsigned long long>(streams) + static_cast<unsigned long long>(q) * stream_stride_bytes;
+            if constexpr (BAND) {
+                // one asm block for both passes: band = 0 runs the same stream with full rows
+                const int tried = band_on;
+                int band = band_on, score;
+                for (;;) {
+                    const int left = myers_band_rows_asm<NW>(st, P, uniform_u64(s),
+                                                             __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2),
+                                                             __builtin_amdgcn_readfirstlane(band));
+                    note_stream_fault(fault_word, left);
+                    score = ref_len;
+#pragma unroll
+                    for (int w = 0; w < NW; w++) {
+                        const int rem = read_len - 32 * w;
+                        const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+                        score += __popc(st[2 * w] & m) - __popc(st[2 * w + 1] & m);
+                    }
+                    if (!band || __builtin_amdgcn_ballot_w64(score > band_limit) == 0) break;
+                    band = 0;   // a lane is not certified: the whole wave runs the query again with full rows
+                    unsigned long long r = 1, b = static_cast<unsigned long long>(unreported) + 1;
+                    if (lane == 0) {
+                        r += atomicAdd(&band_launch[0], 1ull);
+                        b += atomicAdd(&band_launch[1], b);
+                    }
+                    r = uniform_u64(r);   // lane 0's values: the first active lane, as every lane is
+                    b = uniform_u64(b);
+                    unreported = -1;   // this query is reported; banded += 1 below brings it to 0
+                    if (b >= 64 && 8 * r > b) band_on = 0;
+#pragma unroll
+                    for (int w = 0; w < NW; w++) {
+                        st[2 * w] = ~0u;
+                        st[2 * w + 1] = 0u;
+                    }
+                }
+                unreported += tried;
+                dst[static_cast<size_t>(q) * ld] = static_cast<int16_t>(-score);
+                continue;
+            }
             int left;
             if constexpr (NW <= kPairMaxWords)  // short rows: two per stream token (launch_asm packs it so)
                 left = myers_pair_rows_asm<NW, G>(st, P, uniform_u64(s), __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2));
@@ -255,6 +303,9 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
         }
         if constexpr (DYN) task = resolve_wave_task(task_issued);
     } while (DYN && task < n_tasks);
+    if constexpr (BAND) {
+        if (lane == 0 && unreported) atomicAdd(&band_launch[1], static_cast<unsigned long long>(unreported));
+    }
 }
 
 // ---- semi-global (the generator's -m 0 -s, MyersGenerator.java:56-223) -------------------------------------
@@ -662,6 +713,13 @@ static int long_query_tile()
     return v;
 }
 
+// The certificate statistics of one band launch into the device's sticky counts (myers_band.h: band_stats_words).
+__global__ void band_stats_add_kernel(const unsigned long long *__restrict__ launch, unsigned long long *__restrict__ stats)
+{
+    atomicAdd(&stats[0], launch[0]);   // launches on other streams may add at the same time
+    atomicAdd(&stats[1], launch[1]);
+}
+
 template <int NW, int G>
 int launch_asm(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
                int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
@@ -681,6 +739,41 @@ int launch_asm(const char *d_content, const uint32_t *d_peq, int16_t *d_results,
     if (grid.y > 65535u && !plan.dynamic) {
         set_error_text("myers: too many query tiles for one launch");
         return BGSA_HIP_EUNSUPPORTED;
+    }
+    if constexpr (G == 1 && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
+        BandSchedule sched;
+        const int h = band_half(ref_len, read_len);
+        if (band_schedule(ref_len, read_len, h, NW, &sched)) {
+            const int stride = static_cast<int>(band_stream_stride(ref_len));
+            // the task counter sits where the plain path keeps it, behind the streams, and the guard's pair 64 bytes further
+            // (both inside the kTaskCounterBytes the workspace reserves); the packer zeroes them
+            unsigned *words = task_counter_in(d_workspace, static_cast<size_t>(stride) * nq);
+            unsigned *counter = plan.dynamic ? words : nullptr;
+            unsigned long long *guard = band_launch_words(words);
+            if (plan.dynamic) {
+                const long long blocks = static_cast<long long>(grid.x) * grid.y;
+                const int resident = persistent_blocks_for(myers_global_asm_kernel<NW, G, true, true>, myers_lds_pad());
+                grid = dim3(static_cast<unsigned>(blocks < resident ? blocks : resident), 1u);
+            }
+            if (int rc = launch_pack_band(d_content, ref_len, sched, ref_start, ref_end, d_workspace, stream, words)) return rc;
+            unsigned *fault = nullptr;
+            if (int rc = stream_guard(d_workspace, stride, kCodeRefill, kBandBadCode, stream, &fault)) return rc;
+            if (counter)
+                hipLaunchKernelGGL((myers_global_asm_kernel<NW, G, true, true>), grid, dim3(256), myers_lds_pad(), stream,
+                                   static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
+                                   read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
+                                   nq, q_tile, stride, fault, counter, 2 * h + 1, guard);
+            else
+                hipLaunchKernelGGL((myers_global_asm_kernel<NW, G, false, true>), grid, dim3(256), 0, stream,
+                                   static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
+                                   read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
+                                   nq, q_tile, stride, fault, counter, 2 * h + 1, guard);
+            BGSA_HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(band_stats_add_kernel, dim3(1), dim3(1), 0, stream, static_cast<const unsigned long long *>(guard),
+                               band_stats_words(fault));
+            BGSA_HIP_TRY(hipGetLastError());
+            return BGSA_HIP_OK;
+        }
     }
     constexpr bool kPairs = NW <= kPairMaxWords;
     const int stride = static_cast<int>(kPairs ? pair_stream_stride(ref_len) : stream_stride(ref_len));

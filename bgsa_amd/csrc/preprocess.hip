@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "bgsa_common.h"
+#include "myers_band.h"
 
 namespace bgsa {
 
@@ -228,6 +229,44 @@ int launch_pack_banded(const char *d_content, int len, int k, int phase, int cut
     const int stride = banded_stream_layout(len, k, phase, cut, nullptr, nullptr);
     hipLaunchKernelGGL(pack_banded_kernel, dim3((nq + 63) / 64), dim3(64), 0, stream, d_content,
                        static_cast<unsigned char *>(d_streams), len, k, phase, cut, ref_start, nq, stride);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+// One thread per 8-byte window of a band stream (myers_band.h), END beyond the stream's end up to the stride.  The schedule
+// travels by value: it is the same for every query of a launch.
+__global__ __launch_bounds__(256) void pack_band_kernel(const char *__restrict__ content, unsigned long long *__restrict__ streams,
+                                                        int len, BandSchedule sched, int ref_start, int n_queries, int per,
+                                                        unsigned *__restrict__ words)
+{
+    const long long tid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (tid == 0) {   // the task counter and the guard's pair (myers_band.h: band_launch_words), as in pack_queries_kernel
+        words[0] = 0u;
+        band_launch_words(words)[0] = band_launch_words(words)[1] = 0ull;
+    }
+    if (tid >= static_cast<long long>(n_queries) * per) return;
+    const int q = static_cast<int>(tid / per), i = static_cast<int>(tid % per);
+    unsigned char win[8];
+    for (int j = 0; j < 8; j++) win[j] = kCodeEnd;
+    band_stream_layout(len, sched, content + static_cast<size_t>(ref_start + q) * (len + 1), win, 8 * i, 8);
+    unsigned long long w = 0;
+    for (int j = 0; j < 8; j++) w |= static_cast<unsigned long long>(win[j]) << (8 * j);
+    streams[tid] = w;
+}
+
+int launch_pack_band(const char *d_content, int ref_len, const BandSchedule &s, int ref_start, int ref_end, void *d_streams,
+                     hipStream_t stream, unsigned *d_words)
+{
+    const int nq = ref_end - ref_start;
+    if (nq <= 0) return BGSA_HIP_OK;
+    const int stride = static_cast<int>(band_stream_stride(ref_len));
+    if (band_stream_layout(ref_len, s, nullptr, nullptr) > stride) {
+        set_error_text("myers band: stream longer than its stride");
+        return BGSA_HIP_EINVAL;
+    }
+    const long long total = static_cast<long long>(nq) * (stride / 8);
+    hipLaunchKernelGGL(pack_band_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, d_content,
+                       static_cast<unsigned long long *>(d_streams), ref_len, s, ref_start, nq, stride / 8, d_words);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }

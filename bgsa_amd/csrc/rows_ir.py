@@ -593,6 +593,128 @@ def myers_body(nw: int, groups: int = 1, split: int = 0, park: str = "sgpr", bal
     return b
 
 
+# ---- certified diagonal band -------------------------------------------------------
+# A path through cell (i, j) of the m x n matrix holds at least |d| + |d - (n - m)| indels, d = j - i.  A pair whose distance
+# is <= B therefore has its optimal paths inside the band |d| + |d - (n - m)| <= B, and a row only needs the words that touch
+# the band's columns.  Words left of the row's window keep their last deltas (the lowest active word gets the row-edge
+# carry-ins: D[i][edge] = D[i-1][edge] + 1, a vertical step), words right of it keep their initial state (a horizontal
+# path): every column still holds the cost of a real path, so the score D' >= D, and D' <= B certifies D' = D.
+MYERS_BAND_MAX_WORDS = 8      # widths with windowed bodies (myers_band_rows_asm): 65..256 bp
+
+
+def myers_window_body(nw: int, a: int, b: int, balanced: bool = False) -> Body:
+    """myers_body(b - a + 1) on state words a..b of an nw-word row (S/E registers renumbered): the row-edge carry-ins
+    (0 into the addition, 1 into the HP shift) enter at word a."""
+    assert 0 <= a <= b < nw
+    src = myers_body(b - a + 1, balanced=balanced)
+
+    def ren(x: str) -> str:
+        if x.startswith("S"):
+            return f"S{int(x[1:]) + 2 * a}"
+        if x.startswith("E"):
+            return f"E{int(x[1:]) + a}"
+        return x
+
+    out = Body()
+    out.ops = [Op(op.kind, ren(op.dst), tuple(ren(s) for s in op.srcs), op.imm, op.dst2) for op in src.ops]
+    return out
+
+
+def myers_window_index(nw: int, a: int, b: int) -> int:
+    """Slot group of window [a, b] in myers_band_rows_asm: the windows a <= b < nw in lexicographic order."""
+    return a * nw - a * (a - 1) // 2 + (b - a)
+
+
+def myers_band_half(length: int) -> int:
+    """Default half-width h (B = 2h + 1) for subjects / queries of `length`: the mean edit distance of random uniform
+    ACGT pairs plus 4.5 standard deviations (20,000 pairs per length, 65..256 bp, LABNOTES §11).  Same formula as
+    myers_global.hip: band_default_half."""
+    return (9 * length + 192) // 32
+
+
+def myers_band_windows(m: int, n: int, h: int, nw: int):
+    """Per query row i = 1..m the window (a, b) of words that holds the band's columns, or None when the band is off for
+    this shape (the row windows would not save a fifth of the word-rows, or |n - m| leaves no room).  Same rule as
+    myers_global.hip: band_schedule."""
+    B = 2 * h + 1
+    delta = n - m
+    if h <= 0 or abs(delta) > B or nw > MYERS_BAND_MAX_WORDS or nw < 3:
+        return None
+    dlo, dhi = -((B - delta) // 2), (delta + B) // 2        # ceil((delta - B) / 2), floor((delta + B) / 2)
+    out = []
+    for i in range(1, m + 1):
+        jlo, jhi = max(1, i + dlo), min(n, i + dhi)
+        out.append(((jlo - 1) // 32, (jhi - 1) // 32))
+    if 5 * sum(b - a + 1 for a, b in out) > 4 * m * nw:
+        return None
+    return out
+
+
+def myers_band_stream(codes, m: int, n: int, h: int, nw: int) -> bytes | None:
+    """The band stream of one query (codes: m class codes 0..4): the plain stream's row codes, END and REFILL, plus
+    SETWIN (7) and a window byte wherever the row's window changes; a SETWIN never straddles a REFILL (a REFILL at byte 6
+    ends the window early).  One spare all-END window follows.  Restates myers_global.hip: band_stream_layout."""
+    win = myers_band_windows(m, n, h, nw)
+    if win is None:
+        return None
+    out = bytearray()
+
+    def refill():
+        out.append(6)
+        while len(out) % 8:
+            out.append(5)
+
+    def put(c):
+        if len(out) % 8 == 7:
+            refill()
+        out.append(c)
+
+    cur = None
+    for i in range(m):
+        if win[i] != cur:
+            if len(out) % 8 >= 6:
+                refill()
+            out += bytes([7, myers_window_index(nw, *win[i])])
+            cur = win[i]
+        put(int(codes[i]))
+    put(5)
+    while len(out) % 8:
+        out.append(5)
+    out += bytes([5] * 8)
+    return bytes(out)
+
+
+def run_band_stream(nw: int, state: list, peq: np.ndarray, stream: bytes, band: bool = True, balanced: bool = False,
+                    schedule=None) -> int:
+    """Interpret a band stream the way myers_band_rows_asm walks it (band = False: SETWIN keeps the full window; schedule:
+    the pass the generator applies to every body, gen_rows_asm.ilp); returns the number of word-rows executed."""
+    windows = [(a, b) for a in range(nw) for b in range(a, nw)]
+    bodies = {}
+    cur = (0, nw - 1)
+    pos, rows = 0, 0
+    while True:
+        c = stream[pos]
+        if c == 5:
+            return rows
+        if c == 6:
+            pos = (pos | 7) + 1
+            continue
+        if c == 7:
+            k = stream[pos + 1]
+            assert k < len(windows) and myers_window_index(nw, *windows[k]) == k
+            cur = windows[k] if band else (0, nw - 1)
+            pos += 2
+            continue
+        assert c < 5
+        if cur not in bodies:
+            bodies[cur] = myers_window_body(nw, *cur, balanced=balanced)
+            if schedule is not None:
+                bodies[cur] = schedule(bodies[cur])
+        bodies[cur].simulate(state, [peq[c, w] for w in range(nw)], cls=c)
+        rows += cur[1] - cur[0] + 1
+        pos += 1
+
+
 def myers_body10(nw: int, groups: int = 1) -> Body:
     """State layout: S[(g*nw + w)*2 + 0] = VP word w of group g, +1 = VN.  E[g*nw + w] = match mask.
 

@@ -333,6 +333,19 @@ int bgsa_hip_clock_probe_stop(double *mhz, int *xcc, int cap, int *n_out, double
  * Writes at most `cap` bytes to dst (may be NULL) and returns the stream length in bytes. */
 int bgsa_hip_query_stream(int algo, const char *mapped_row, int ref_len, int k, unsigned char *dst, int cap);
 
+/* The certified band of the Myers global kernels (subjects of 65..256 bp).  A row runs only on the words that
+ * hold the diagonal band |d| + |d - (n - m)| <= B = 2h + 1 of a query of ref_len = m against subjects of read_len = n; a wave
+ * with a score above B runs that query again with full rows, so the scores do not change.  h follows the lengths, or
+ * BGSA_MYERS_BAND (0 = off, N = half-width).
+ * bgsa_hip_myers_band_stream: the band stream of one mapped query row (host only, no GPU): the plain stream's codes plus
+ * 7 = SETWIN + a window byte; writes at most `cap` bytes and returns its length, or 0 when the band is off for the shape.
+ * bgsa_hip_myers_band_half: the half-width h a launch of these lengths uses (0: off).
+ * bgsa_hip_myers_band_stats: the current device's counts since the last clear — out[0] = queries a wave ran again with full
+ * rows, out[1] = queries a wave ran banded (call after synchronising). */
+int bgsa_hip_myers_band_stream(const char *mapped_row, int ref_len, int read_len, unsigned char *dst, int cap);
+int bgsa_hip_myers_band_half(int ref_len, int read_len);
+int bgsa_hip_myers_band_stats(unsigned long long *out, int clear);
+
 /* Queries a wave scores per load of its subject block in this thread's last scoring launch (0: none yet).  The launch's
  * HBM traffic follows from it: ceil(queries / tile) x block bytes + the scores (bench.py: traffic_model). */
 int bgsa_hip_last_query_tile(void);

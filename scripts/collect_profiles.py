@@ -17,7 +17,7 @@ from pathlib import Path
 src, prefix = Path(sys.argv[1]), sys.argv[2]
 dst = Path(__file__).resolve().parent.parent / "profiles"
 dst.mkdir(exist_ok=True)
-HELPERS = ("pack", "preprocess", "map_queries", "scale_scores", "corrupt_stream")
+HELPERS = ("pack", "preprocess", "map_queries", "scale_scores", "corrupt_stream", "band_stats_add")
 
 extra = src / "bench_cfg3_k31.json"
 if extra.exists() and extra.stat().st_size:
