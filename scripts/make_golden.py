@@ -7,8 +7,10 @@ Run in the build container only (needs /root/reference to have been compiled by
 
     python scripts/make_golden.py            # regenerate every fixture
     python scripts/make_golden.py --check    # regenerate in memory and compare with the files
+    python scripts/make_golden.py --only f10_   # ... only the fixtures whose names start so (with or without --check)
 
-Fixture list follows SURVEY.md §8(c) "Fixtures to mint" (F1..F9), plus F0: the reference's own sample data.
+Fixture list follows SURVEY.md §8(c) "Fixtures to mint" (F1..F9), plus F0: the reference's own sample data, and F10: the
+band-edge pairs of the Myers kernels' certified diagonal band (oracle/band_edge.py).
 """
 from __future__ import annotations
 
@@ -131,11 +133,43 @@ def fixtures():
         s[:16, :m] = O.mutate(q[np.arange(16) % 8][:, :m], np.arange(16) % 9, 90 + ql)
         yield f"f9_myers_{ql}x{sl}", "original_cpu", None, q, s
         yield f"f9_bitpal_{ql}x{sl}", "original_avx2", None, q, s
+    # F10: pairs whose optimal paths run along the edge of the Myers kernels' certified diagonal band, at the
+    # default half-width of each shape — two or more shapes per width of 3..8 words
+    for ql, sl in BAND_EDGE_SHAPES:
+        q, s = band_edge_fixture(ql, sl)
+        yield f"f10_myers_band_edge_{ql}x{sl}", "original_cpu", None, q, s
+
+
+BAND_EDGE_SHAPES = ((65, 65), (70, 70), (96, 97), (128, 128), (97, 129), (150, 150), (140, 150), (170, 181), (192, 192),
+                    (200, 210), (224, 220), (256, 256), (256, 225))
+
+
+def band_edge_fixture(ql: int, sl: int):
+    """Two low-entropy queries and, for each, its subjects in whole waves of 64 (oracle/band_edge.py: band_edge_waves): waves
+    where every lane is within B = 2h + 1 of its query, then four waves with one lane at B + 1 (lane 0, 31, 32, 63) — the same
+    number of waves for both queries, so that query i owns the i-th half of the subjects.
+    The queries are the three-run query and the seeded-runs query of seed 1; where the three-run query's ladders hold no pair
+    at exactly B or none at exactly B + 1 (the substitution of a rung is absorbed by a run boundary), seed 2 takes its place."""
+    from oracle import band_edge as E
+
+    h = (9 * max(ql, sl) + 192) // 32            # rows_ir.py: myers_band_half
+    B = 2 * h + 1
+    dist = lambda a, b: -O.dp_edit(a, b).astype(np.int64)
+    first = E.three_run_query(ql)
+    d = dist(first[None], E.band_edge_pairs(first, sl, h, full=False)[0])[0]
+    if not ((d == B).any() and (d == B + 1).any()):
+        first = E.seeded_runs_query(ql, 2)
+    queries = np.stack([first, E.seeded_runs_query(ql, 1)])
+    waves = lambda i, inside: E.band_edge_waves(queries[i], sl, h, dist, O.mutate, O.gen_reads, 0xB65A1A00 + ql + i,
+                                                inside_waves=inside)
+    inside = max(waves(i, 0)[1] for i in range(2))
+    return queries, np.concatenate([waves(i, inside)[0] for i in range(2)])
 
 
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--only", default="", help="name prefix of the fixtures to mint or check")
     args = ap.parse_args()
     for v in O.REF_VARIANTS:
         if not O.have_reference(v):
@@ -144,6 +178,8 @@ def main() -> int:
     GOLDEN.mkdir(parents=True, exist_ok=True)
     bad = 0
     for name, variant, k, q, s in fixtures():
+        if not name.startswith(args.only):
+            continue
         scores, _ = O.run_reference(variant, q, s, threads=2, k=k)
         # Cross-variant pin: the SSE Myers build must agree with the scalar one.
         # (The SSE build pads the subject file to a multiple of 4 inside a 2x-file-size buffer and

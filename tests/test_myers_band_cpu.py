@@ -6,6 +6,14 @@ The windowed row bodies (rows_ir.py: myers_window_body) are interpreted over the
   * with the band on the score D' is never below the distance D, and D' <= B = 2h + 1 implies D' = D —
     for equal and unequal lengths, 'N' bases, lengths that are not a multiple of 32, similar, random and far pairs.
 The library's band stream (bgsa_hip_myers_band_stream) is walked like the loop walks it: bounds, budget, SETWIN placement.
+
+Random and lightly mutated pairs keep their paths near the main diagonal and their distances far below B, so they see neither
+the outer word of a window, nor the row at which a window gains or loses a word, nor the comparison with B.  The band-edge
+pairs (oracle/band_edge.py) do: low-entropy queries against shifted copies behind a filler run, one path on every diagonal of
+the band and distances on both sides of B.  On them the band is exact BOTH ways (D <= B implies D' = D; D > B implies
+D' > B), and the corpus is held to having teeth: four deliberately broken window schedules must each change the score of a
+certifiable pair at every shape.  The on/off rule and the stream of the library are compared with the restatement over
+every subject length of 65..256 bp at the boundary values of n - m.
 """
 import sys
 from pathlib import Path
@@ -14,6 +22,7 @@ import numpy as np
 import pytest
 
 import bgsa_amd as B
+from oracle import band_edge as E
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "bgsa_amd" / "csrc"))
 import rows_ir as R  # noqa: E402
@@ -192,3 +201,164 @@ def test_library_stream_far_more_switches_than_rows(L):
         if raw is not None:
             assert len(raw) <= band_stride(qlen)
             assert walk(raw, band_stride(qlen), 8)[0] == qlen
+
+
+# ---- band-edge pairs: optimal paths along the outer diagonals, distances around B ---------------------------------------
+
+# (query length, subject length): all widths 3..8, both signs of n - m, small and large |n - m|
+EDGE_SHAPES = [(65, 65), (70, 70), (96, 97), (100, 97), (128, 128), (97, 129), (150, 150), (140, 150), (150, 140), (90, 150),
+               (129, 160), (160, 129), (170, 181), (180, 190), (192, 192), (200, 210), (224, 220), (215, 224), (240, 230),
+               (150, 240), (240, 150), (160, 256), (225, 256), (256, 225), (256, 256)]
+# the three-run query and the seeded-runs query of seed 1; (240, 150) needs seed 2 for the upper-word-late mutant
+EDGE_SEEDS = {(240, 150): (1, 2)}
+NARROW_SHAPES = [(150, 150), (100, 97), (240, 256)]
+
+_corpus_cache = {}
+
+
+def _edge_corpus(oracle, qlen, slen, h, narrow=False):
+    """[(query, subjects, distances)]: the full ladders and the near-B rungs of every query of the shape."""
+    key = (qlen, slen, h, narrow)
+    if key not in _corpus_cache:
+        if narrow:   # a band this narrow: random reads are far enough apart for the shifted alignment to be optimal
+            q = oracle.gen_reads(77 + qlen, 1, qlen)[0].copy()
+            q[q == E.FILLER] = ord("T")
+            queries = [q]
+        else:
+            queries = [E.three_run_query(qlen)] + [E.seeded_runs_query(qlen, s) for s in EDGE_SEEDS.get((qlen, slen), (1,))]
+        out = []
+        for q in queries:
+            s, _ = E.band_edge_pairs(q, slen, h)
+            out.append((q, s, -oracle.dp_edit(q[None], s).astype(np.int64)[0]))
+        _corpus_cache[key] = out
+    return _corpus_cache[key]
+
+
+def _assert_exact_both_ways(oracle, qlen, slen, h, narrow=False):
+    limit = 2 * h + 1
+    assert R.myers_band_windows(qlen, slen, h, (slen + 31) // 32) is not None
+    seen = set()
+    for q, s, want in _edge_corpus(oracle, qlen, slen, h, narrow):
+        got, rows = _band_scores(q, s, h)
+        assert rows < qlen * ((slen + 31) // 32)
+        assert (got >= want).all()
+        inside = want <= limit
+        assert np.array_equal(got[inside], want[inside])           # the optimal path lies inside the band
+        assert (got[~inside] > limit).all()                        # ... and nothing above B is let through
+        seen |= set((want - limit).tolist())
+    # the input condition: a path on both sides of the certificate, one exactly at B and one at B + 1
+    assert set(range(-2, 4)) <= seen, sorted(seen)
+
+
+@pytest.mark.parametrize("qlen,slen", EDGE_SHAPES)
+def test_band_edge_pairs_are_exact_both_ways(oracle, qlen, slen):
+    _assert_exact_both_ways(oracle, qlen, slen, R.myers_band_half(max(qlen, slen)))
+
+
+@pytest.mark.parametrize("qlen,slen", NARROW_SHAPES)
+@pytest.mark.parametrize("h", [12, 20])
+def test_band_edge_pairs_are_exact_both_ways_narrow_band(oracle, qlen, slen, h):
+    _assert_exact_both_ways(oracle, qlen, slen, h, narrow=True)
+
+
+def _window_mutant(kind):
+    """myers_band_windows, broken on purpose: the upper word one row late, the lower word dropped one row early, windows one
+    word short on the upper / on the lower side."""
+    orig = R.myers_band_windows
+
+    def windows(m, n, h, nw):
+        w = orig(m, n, h, nw)
+        if w is None:
+            return None
+        a, b = [x[0] for x in w], [x[1] for x in w]
+        if kind == "upper word one row late":
+            b = [b[0]] + b[:-1]
+        elif kind == "lower word one row early":
+            a = a[1:] + [a[-1]]
+        elif kind == "one word short on the upper side":
+            b = [max(x, y - 1) for x, y in zip(a, b)]
+        else:
+            assert kind == "one word short on the lower side"
+            a = [min(y, x + 1) for x, y in zip(a, b)]
+        assert all(x <= y for x, y in zip(a, b)) and list(zip(a, b)) != w
+        return list(zip(a, b))
+
+    return windows
+
+
+MUTANTS = ["upper word one row late", "lower word one row early", "one word short on the upper side",
+           "one word short on the lower side"]
+
+
+def _assert_teeth(oracle, monkeypatch, qlen, slen, h, narrow=False):
+    limit = 2 * h + 1
+    corpus = _edge_corpus(oracle, qlen, slen, h, narrow)
+    for kind in MUTANTS:
+        with monkeypatch.context() as mp:
+            mp.setattr(R, "myers_band_windows", _window_mutant(kind))
+            wrong = sum(int(((_band_scores(q, s, h)[0] != want) & (want <= limit)).sum()) for q, s, want in corpus)
+        assert wrong > 0, f"{qlen} x {slen}, h = {h}: no certifiable band-edge pair sees the schedule with the {kind}"
+
+
+@pytest.mark.parametrize("qlen,slen", EDGE_SHAPES)
+def test_band_edge_pairs_see_a_broken_window_schedule(oracle, monkeypatch, qlen, slen):
+    """A condition on the inputs, checked with the DP and the interpreter only: each broken schedule changes the score of at
+    least one pair with D <= B — the pairs an exact band must get right."""
+    _assert_teeth(oracle, monkeypatch, qlen, slen, R.myers_band_half(max(qlen, slen)))
+
+
+@pytest.mark.parametrize("qlen,slen", NARROW_SHAPES)
+@pytest.mark.parametrize("h", [12, 20])
+def test_band_edge_pairs_see_a_broken_window_schedule_narrow_band(oracle, monkeypatch, qlen, slen, h):
+    _assert_teeth(oracle, monkeypatch, qlen, slen, h, narrow=True)
+
+
+def test_band_edge_shapes_cover_every_width():
+    widths = [(slen + 31) // 32 for _, slen in EDGE_SHAPES]
+    assert all(widths.count(nw) >= 2 for nw in range(3, 9))
+
+
+# ---- schedule sweep: the library's on/off rule and stream against the restatement ------------------------------------------
+
+def _sweep_query_lengths(slen):
+    """m = n - delta for delta in {0, +-1, +-31, +-32, +-33, +-(B - 1), +-B, +-(B + 1)}, B by the longer of the two lengths."""
+    out = set()
+    for qlen in range(1, slen + 400):
+        d = abs(slen - qlen)
+        if d in (0, 1, 31, 32, 33) or abs(d - (2 * R.myers_band_half(max(qlen, slen)) + 1)) <= 1:
+            out.add(qlen)
+    return sorted(out)
+
+
+def test_sweep_reaches_both_sides_of_the_on_off_rule():
+    for slen in (65, 150, 256):
+        ds = {slen - m - (2 * R.myers_band_half(max(m, slen)) + 1) for m in _sweep_query_lengths(slen) if m < slen}
+        assert {-1, 0, 1} <= ds
+        ds = {m - slen - (2 * R.myers_band_half(max(m, slen)) + 1) for m in _sweep_query_lengths(slen) if m > slen}
+        assert {-1, 0, 1} <= ds
+
+
+@pytest.mark.parametrize("slen0", range(65, 257, 16))
+def test_library_schedule_sweep_matches_the_restatement(L, slen0):
+    on = off = 0
+    for slen in range(slen0, min(slen0 + 16, 257)):
+        nw = (slen + 31) // 32
+        for qlen in _sweep_query_lengths(slen):
+            h = R.myers_band_half(max(qlen, slen))
+            row = ((np.arange(qlen) * 7 + slen) % 5).astype(np.uint8)
+            want = R.myers_band_stream(row, qlen, slen, h, nw)
+            got_h = L.bgsa_hip_myers_band_half(qlen, slen)
+            assert (got_h > 0) == (want is not None), (qlen, slen)
+            raw = _lib_stream(L, row, slen)
+            if want is None:
+                assert raw is None and got_h == 0, (qlen, slen)
+                off += 1
+                continue
+            on += 1
+            assert got_h == h and bytes(raw) == want, (qlen, slen)
+            stride = band_stride(qlen)
+            assert len(raw) <= stride and len(raw) % 8 == 0
+            rows, left, touched = walk(raw, stride, nw)
+            assert rows == qlen and left >= 0 and touched <= stride, (qlen, slen)
+            assert all(raw[i] in (5, 6) for i in range(7, len(raw), 8)), (qlen, slen)
+    assert on > 0 and off > 0
