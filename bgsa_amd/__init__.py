@@ -89,6 +89,10 @@ def lib() -> ctypes.CDLL:
     L.bgsa_hip_workspace_bytes_ex.argtypes = [pp, i32, i32, i32]
     L.bgsa_hip_workspace_bytes_ex.restype = sz
     L.bgsa_hip_cal_align_score_ex.argtypes = [pp, vp, vp, vp, i32, i32, i64, i32, i32, i32, vp, sz, vp]
+    L.bgsa_hip_hits_workspace_bytes.argtypes = [i32, i64, i32, i32]
+    L.bgsa_hip_hits_workspace_bytes.restype = sz
+    L.bgsa_hip_top_hits_dev.argtypes = [vp, i32, i32, i64, i64, i64, i32, i32, i32, vp, vp, vp, sz, vp]
+    L.bgsa_hip_threshold_hits_dev.argtypes = [vp, i32, i32, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, sz, vp]
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -166,6 +170,11 @@ def word_num(algo: int, qlen: int, slen: int, k: int = 0) -> int:
 
 def group_words(algo: int, wn: int, k: int = 0) -> int:
     return int(lib().bgsa_hip_group_words(algo, wn, k))
+
+
+def default_smallest(algo: int, scores=None) -> bool:
+    """Whether the smaller score is the better one for hit selection: distances (the banded filter, Myers +distance)."""
+    return algo == ALGO_BANDED or (algo == ALGO_MYERS and scores is not None and tuple(scores) == (0, 1, 1))
 
 
 def pad_rows(rows: np.ndarray, multiple: int = V_NUM) -> tuple[np.ndarray, int]:
@@ -284,6 +293,71 @@ class DeviceAligner:
                                                 self.d_work.numel(), self._stream()), "cal_align_score_ex")
         return out
 
+    # ---- hit selection: the score matrix never exists, only one reused tile of block_rows x ns ----------------------
+    def _hit_blocks(self, block_rows: int):
+        """Scores the resident bucket block_rows queries at a time into one reused tile; yields (lo, hi, tile rows)."""
+        torch = self.torch
+        block_rows = max(1, min(int(block_rows), self.nq))
+        tile = getattr(self, "d_hit_tile", None)
+        if tile is None or tile.shape != (block_rows, self.ns) or tile.dtype != self.out_dtype:
+            self.d_hit_tile = tile = torch.empty((block_rows, self.ns), dtype=self.out_dtype, device=self.device)
+        need = int(lib().bgsa_hip_hits_workspace_bytes(block_rows, self.ns, tile.element_size(), V_NUM))
+        if getattr(self, "d_hit_work", None) is None or self.d_hit_work.numel() < need:
+            self.d_hit_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        for lo in range(0, self.nq, block_rows):
+            hi = min(lo + block_rows, self.nq)
+            yield lo, hi, self.score(lo, hi, out=tile[: hi - lo])
+
+    def _hit_lists(self, into, shapes, what: str):
+        """The output tensors of a selection call: fresh ones, or the caller's `into` (checked) to accumulate into."""
+        torch = self.torch
+        if into is None:
+            return [torch.empty(shape, dtype=dtype, device=self.device) for shape, dtype in shapes], 0
+        into = list(into)
+        if len(into) != len(shapes):
+            raise BgsaHipError(f"{what}: into= takes {len(shapes)} tensors")
+        for t, (shape, dtype) in zip(into, shapes):
+            if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise BgsaHipError(f"{what}: into= needs contiguous {dtype} tensors of shape {tuple(shape)} on {self.device}")
+        return into, 1
+
+    def top_hits(self, k_best: int, block_rows: int = 1000, smallest=None, subject_base: int = 0, into=None):
+        """The k_best (1..64) best subjects of the resident bucket per query, best first, ties to the smaller subject id:
+        (scores[nq, K] int32, subjects[nq, K] int64) device tensors; subjects are subject_base + index in the bucket, unused
+        slots hold -1.  The bucket is scored block_rows queries at a time into one reused tile and each block is selected
+        on the device (bgsa_hip_top_hits_dev).  into=(scores, subjects) of an earlier call: its entries join the
+        candidates, so walking several buckets ends with the K best overall.  smallest=None follows the aligner."""
+        torch = self.torch
+        smallest = default_smallest(self.algo, self.scores) if smallest is None else bool(smallest)
+        k_best = int(k_best)
+        if not 1 <= k_best <= V_NUM:    # before any tensor is sized by it; the C call's own answer (BGSA_HIP_EUNSUPPORTED)
+            raise BgsaHipError(f"top_hits: rc=-2: k_best must lie in 1..{V_NUM} (one wavefront holds the sorted list, one entry per lane)")
+        (scores, subjects), accumulate = self._hit_lists(into, [((self.nq, k_best), torch.int32), ((self.nq, k_best), torch.int64)], "top_hits")
+        for lo, hi, tile in self._hit_blocks(block_rows):
+            check(lib().bgsa_hip_top_hits_dev(tile.data_ptr(), tile.element_size(), hi - lo, self.ns, self.ns_real, int(subject_base),
+                                              k_best, int(smallest), accumulate, scores[lo:hi].data_ptr(), subjects[lo:hi].data_ptr(),
+                                              self.d_hit_work.data_ptr(), self.d_hit_work.numel(), self._stream()), "top_hits_dev")
+        return scores, subjects
+
+    def threshold_hits(self, cutoff: int, cap_per_query: int, block_rows: int = 1000, smallest=None, subject_base: int = 0, into=None):
+        """Every subject of the resident bucket at least as good as `cutoff`, per query in ascending subject order:
+        (counts[nq] int32, scores[nq, cap] int32, subjects[nq, cap] int64) device tensors.  counts are the true numbers
+        of hits even beyond cap_per_query; a row that overflows keeps its cap_per_query lowest-indexed hits.
+        into=(counts, scores, subjects) of an earlier call: this bucket's hits are appended behind them."""
+        torch = self.torch
+        smallest = default_smallest(self.algo, self.scores) if smallest is None else bool(smallest)
+        cap = int(cap_per_query)
+        if cap < 1:
+            raise BgsaHipError("threshold_hits: rc=-1: cap_per_query is not positive")
+        (counts, scores, subjects), accumulate = self._hit_lists(
+            into, [((self.nq,), torch.int32), ((self.nq, cap), torch.int32), ((self.nq, cap), torch.int64)], "threshold_hits")
+        for lo, hi, tile in self._hit_blocks(block_rows):
+            check(lib().bgsa_hip_threshold_hits_dev(tile.data_ptr(), tile.element_size(), hi - lo, self.ns, self.ns_real, int(subject_base),
+                                                    int(cutoff), int(smallest), accumulate, cap, counts[lo:hi].data_ptr(),
+                                                    scores[lo:hi].data_ptr(), subjects[lo:hi].data_ptr(),
+                                                    self.d_hit_work.data_ptr(), self.d_hit_work.numel(), self._stream()), "threshold_hits_dev")
+        return counts, scores, subjects
+
     def check_faults(self) -> None:
         """Synchronises and raises if a kernel reported a stream fault (bgsa_hip_stream_faults)."""
         self.torch.cuda.synchronize(self.device)
@@ -317,3 +391,16 @@ def align_all_pairs(queries: np.ndarray, subjects: np.ndarray, algo: int = ALGO_
     out = a.score()
     a.check_faults()
     return out[:, : a.ns_real].cpu().numpy()
+
+
+def align_top_hits(queries: np.ndarray, subjects: np.ndarray, k_best: int, algo: int = ALGO_MYERS, k: int = 0,
+                   device: str = "cuda:0", scores=None, semi_global: bool = False, smallest=None,
+                   block_rows: int = 1000) -> tuple[np.ndarray, np.ndarray]:
+    """Convenience: the k_best best subjects per query as (scores[nq, K] int32, subjects[nq, K] int64), selected on the
+    device block by block — the [nq, ns] score matrix is never built (DeviceAligner.top_hits)."""
+    a = DeviceAligner(algo, device, k, scores, semi_global)
+    a.set_queries(queries)
+    a.set_subjects(subjects)
+    hit_scores, hit_subjects = a.top_hits(k_best, block_rows=block_rows, smallest=smallest)
+    a.check_faults()
+    return hit_scores.cpu().numpy(), hit_subjects.cpu().numpy()

@@ -27,6 +27,10 @@ void set_error_text(const char *text);
         }                                                               \
     } while (0)
 
+// capi.hip: runs `launch(workspace, ctx)` on the library's own grow-only scratch of (current device, stream), at least
+// `need` bytes (what a call without a caller-owned workspace uses; allocates on first use and when it grows).
+int with_own_scratch(hipStream_t stream, size_t need, int (*launch)(void *workspace, void *ctx), void *ctx);
+
 // Launchers implemented in the per-algorithm .hip files.  All pointers are device pointers.
 int launch_myers(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
                  int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,

@@ -137,6 +137,16 @@ static int scratch_reserve(hipStream_t stream, size_t need, void **out)  // g_sc
     return BGSA_HIP_OK;
 }
 
+// The same scratch for the launch sequences of other files (hits.hip): `launch(workspace, ctx)` runs with at least `need`
+// bytes of it, under the lock, like a scoring call without a workspace of its own.
+int with_own_scratch(hipStream_t stream, size_t need, int (*launch)(void *workspace, void *ctx), void *ctx)
+{
+    std::lock_guard<std::mutex> own_scratch(g_scratch_mu);
+    void *workspace = nullptr;
+    if (int rc = scratch_reserve(stream, need, &workspace)) return rc;
+    return launch(workspace, ctx);
+}
+
 // ---- what a set of scoring parameters runs as ---------------------------------------------------------
 struct Plan {
     int kernel;               // BGSA_ALGO_* of the kernel family that runs

@@ -354,3 +354,76 @@ class ShardedAligner:
         gs.submit(local)
         gs.drain()
         return gs.last_block(), shards
+
+    # ---- hit lists instead of the matrix ------------------------------------------------------------------------------
+    def _hip_hits(self, queries: np.ndarray, subjects: np.ndarray, k_best: int, smallest: bool, subject_base: int):
+        import bgsa_amd as B
+        torch = self.torch
+        if subjects.shape[0] == 0:      # a rank without subjects (fewer groups than ranks) offers empty lists
+            return empty_hits(torch, queries.shape[0], k_best, smallest, self.device)
+        if self._aligner is None:
+            self._aligner = B.DeviceAligner(self.algo, str(self.device), self.k, self.scores, self.semi_global)
+        a = self._aligner
+        a.set_queries(queries)
+        a.set_subjects(subjects)        # run_hits hands over a fresh slice per call: the shard is uploaded each time
+        self._resident = None           # ... and _hip_score's resident shard is no longer the one in HBM
+        return a.top_hits(k_best, smallest=smallest, subject_base=subject_base)
+
+    def run_hits(self, queries: np.ndarray | None, subjects_all: np.ndarray, k_best: int, smallest=None, hits_fn=None):
+        """The k_best best subjects of the whole bucket per query: every rank selects the top-K of its shard on its GPU
+        (subject ids counted from the shard's start), the ranks all_gather their [nq, K] lists — the same size on every
+        rank — and the world x K candidates per query are merged with one sort on the composite key (merge_hits).
+        The exchange is nq x K x world entries instead of the score matrix.
+        hits_fn(queries, subjects, k_best, smallest, subject_base) -> (scores[nq, K] int32, subjects[nq, K] int64) is the
+        compute hook (default: the HIP path); CPU tests inject a checker.  smallest=None follows the aligner.
+        Returns ((scores, subjects) on rank 0, None elsewhere), shards."""
+        torch = self.torch
+        if smallest is None:
+            from . import default_smallest
+            smallest = default_smallest(self.algo, self.scores)
+        smallest = bool(smallest)
+        q = self.broadcast_queries(queries)
+        shards = plan_shards(subjects_all.shape[0], self.world)
+        mine = shards[self.rank]
+        fn = hits_fn if hits_fn is not None else self._hip_hits
+        sc, sj = fn(q, subjects_all[mine.start: mine.start + mine.count], int(k_best), smallest, mine.start)
+        sc = torch.as_tensor(sc).to(torch.int32).contiguous()
+        sj = torch.as_tensor(sj).to(torch.int64).contiguous()
+        if self.dist is None or self.world == 1:
+            return (sc, sj), shards
+        all_sc = [torch.empty_like(sc) for _ in range(self.world)]
+        all_sj = [torch.empty_like(sj) for _ in range(self.world)]
+        self.dist.all_gather(all_sc, sc)
+        self.dist.all_gather(all_sj, sj)
+        if self.rank != 0:
+            return None, shards
+        return merge_hits(torch, torch.cat(all_sc, dim=1), torch.cat(all_sj, dim=1), int(k_best), smallest), shards
+
+
+def empty_hits(torch, n_queries: int, k_best: int, smallest: bool, device=None):
+    """Lists of unused slots: subject -1, the worst int32 of the direction."""
+    worst = torch.iinfo(torch.int32).max if smallest else torch.iinfo(torch.int32).min
+    return (torch.full((n_queries, k_best), worst, dtype=torch.int32, device=device),
+            torch.full((n_queries, k_best), -1, dtype=torch.int64, device=device))
+
+
+def merge_hits(torch, scores, subjects, k_best: int, smallest: bool):
+    """The k_best best of [nq, n] candidate (score, subject id) lists in the library's total order (better score first,
+    among equal scores the smaller subject id; subject -1 = unused slot, last).  One sort on the composite key
+    (better-is-larger score above the complemented subject id, as in bgsa_amd/csrc/hits.hip) — plumbing on
+    nq x K x world elements."""
+    id_bits = 46
+    id_mask = (1 << id_bits) - 1
+    ordv = scores.to(torch.int64).clamp(-32768, 32767)
+    ordv = -ordv if smallest else ordv
+    key = ((ordv + 32769) << id_bits) | (id_mask - subjects.clamp(0, id_mask))
+    key = torch.where(subjects < 0, torch.zeros_like(key), key)
+    top = torch.sort(key, dim=1, descending=True).values[:, :k_best]
+    if top.shape[1] < k_best:
+        top = torch.cat([top, torch.zeros((top.shape[0], k_best - top.shape[1]), dtype=top.dtype, device=top.device)], dim=1)
+    out_ord = (top >> id_bits) - 32769
+    out_scores = (-out_ord if smallest else out_ord).to(torch.int32)
+    out_subjects = id_mask - (top & id_mask)
+    worst_scores, none = empty_hits(torch, top.shape[0], k_best, smallest, top.device)
+    empty = top == 0
+    return torch.where(empty, worst_scores, out_scores), torch.where(empty, none, out_subjects)

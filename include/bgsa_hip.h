@@ -297,6 +297,46 @@ int bgsa_hip_cal_align_score_ex(const bgsa_hip_params_t *params, const char *d_c
                                 int ref_start, int ref_end, int word_num,
                                 void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- hit selection: the K best subjects per query, or every subject within a cutoff, from a score tile in HBM ----
+ * d_results = a score tile as the scoring calls write it: n_queries rows of row_stride elements of elem_bytes bytes
+ * (2: int16 of Myers / BitPAl, 1: int8 of the banded filter).  Only columns [0, valid_count) are candidates: the columns
+ * behind them are the all-'N' padding reads of the last group (file.c:98-112) and never appear, whatever they scored.
+ * The reported subject id of column c is subject_base + c (ids lie in [0, 2^46)).  The tile is only read.
+ *
+ * ONE TOTAL ORDER makes every result unique: a candidate is (score, subject id); better = the larger score, or the
+ * smaller one when `smallest` is set (distances: the banded filter, Myers +distance); among equal scores the smaller
+ * subject id is better.
+ *
+ * bgsa_hip_top_hits_dev: for every row the k_best (1..64; else BGSA_HIP_EUNSUPPORTED) best candidates, best first, as
+ * d_hit_scores / d_hit_subjects [n_queries][k_best].  Slots beyond valid_count candidates hold subject -1 and the worst
+ * int32 of the direction (INT32_MIN, or INT32_MAX with `smallest`).
+ * bgsa_hip_threshold_hits_dev: for every row every candidate at least as good as `cutoff` (score >= cutoff, or <= with
+ * `smallest`), in ascending subject order, as d_hit_scores / d_hit_subjects [n_queries][cap_per_query]; d_counts[row] =
+ * the TRUE number of such candidates even when it exceeds cap_per_query — the list then holds the cap_per_query
+ * lowest-indexed ones (slots beyond the count are left as they were).
+ * accumulate != 0: what the outputs already hold joins in, with its subject ids as stored — a caller walking several
+ * subject buckets (subject_base = the bucket's first subject) ends with the k_best best overall; threshold hits are
+ * appended behind the row's current d_counts[row], which grows by this tile's count.  The first call passes 0 (or lists
+ * of subject -1 and counts of 0).
+ * d_workspace = caller-owned device scratch of at least bgsa_hip_hits_workspace_bytes() bytes (the same for both calls;
+ * the size depends only on n_queries and row_stride — elem_bytes and k_best are validated, 0 for a bad one, and
+ * otherwise ignored — and never shrinks when an argument grows), or NULL for the library's own grow-only scratch per (device, stream), as in
+ * bgsa_hip_cal_align_score_dev (allocates on first use: not graph-capture safe).  With a workspace the calls only launch
+ * kernels on `stream`: no allocation, no synchronisation, safe inside a stream capture.
+ * BGSA_HIP_EINVAL: a NULL pointer, a non-positive n_queries / row_stride / cap_per_query, valid_count outside
+ * [0, row_stride] or >= 2^31, elem_bytes other than 1 or 2, subject ids beyond 2^46, a workspace that is too small —
+ * all checked before the first HIP call. */
+size_t bgsa_hip_hits_workspace_bytes(int n_queries, int64_t row_stride, int elem_bytes, int k_best);
+int bgsa_hip_top_hits_dev(const void *d_results, int elem_bytes, int n_queries, int64_t row_stride,
+                          int64_t valid_count, int64_t subject_base, int k_best, int smallest, int accumulate,
+                          int32_t *d_hit_scores, int64_t *d_hit_subjects,
+                          void *d_workspace, size_t workspace_bytes, void *stream);
+int bgsa_hip_threshold_hits_dev(const void *d_results, int elem_bytes, int n_queries, int64_t row_stride,
+                                int64_t valid_count, int64_t subject_base, int cutoff, int smallest, int accumulate,
+                                int64_t cap_per_query, int32_t *d_counts,
+                                int32_t *d_hit_scores, int64_t *d_hit_subjects,
+                                void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
