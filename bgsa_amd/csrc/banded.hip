@@ -907,152 +907,165 @@ int banded_groups()
     return v;
 }
 
-#if BGSA_AB_KERNELS
-int launch_chunk(const char *d_content, const uint32_t *d_peq, int8_t *d_results, int len, int64_t read_count,
-                 int ref_start, int ref_end, int word_num, int k, void *d_workspace, hipStream_t stream)
+// The loop around the 64-bit funnel-shift rows (k >= 16).  BGSA_BANDED_PAIR_LOOP=1 (default): one group per wave on the task
+// counter; =0: round 2's loop; =2: two groups per wave (A/B flavour of the library only).  Measured
+// (scripts/r04_banded_funnel_ab.sh, r04_banded_pair_loop.sh; every pair surviving): the 32-bit rows gain 8 % from the two-group
+// loop (random pairs 14-24 %); the 64-bit pair LOSES 4.5 % with two groups, loses 1.4 % with one group on a static grid and
+// gains 2.2 % with one group on the task counter (k = 31: 660.8 -> 646.4 ms): that is its default.
+int banded_pair_loop()
 {
-    const int nq = ref_end - ref_start;
-    const int64_t n_groups = read_count / kLanes;
-    const int q_tile = pick_query_tile(nq, n_groups, len, 32);
-    note_query_tile(q_tile);
-    dim3 grid(static_cast<unsigned>((n_groups + kWavesPerBlock - 1) / kWavesPerBlock),
-              static_cast<unsigned>((nq + q_tile - 1) / q_tile));
-    if (grid.y > 65535u) {
-        set_error_text("banded: too many query tiles for one launch");
-        return BGSA_HIP_EUNSUPPORTED;
+    static const int v = [] { const char *e = getenv("BGSA_BANDED_PAIR_LOOP"); return e ? atoi(e) : 1; }();
+    return v;
+}
+
+// ---- which kernel scores a launch of threshold k: decided here, once; launch_banded switches on the answer,
+// banded_kernel_name formats it ----
+enum class BandedForm {
+    kCut,       // banded_cut_kernel<G>: one-word windows, cut every `cut` rows (k <= 12)
+    kFunnel32,  // banded_cut_kernel<2, DYN, 1>: the two-group loop around the 32-bit funnel-shift rows (13 <= k <= 15)
+    kFunnel64,  // banded_cut_kernel<G, DYN, 2>: ... around the 64-bit pair (k >= 16)
+    kRowLoop,   // banded_asm_kernel<wide, phase > 0>: round 2's one-group loops (BGSA_BANDED_IMPL=a at every k, =p: band held in place)
+    kChunk,     // banded_chunk_kernel: straight-line rows (BGSA_BANDED_IMPL=s, k <= 15)
+    kCompiler,  // banded_kernel<uint32_t | uint64_t> (BGSA_BANDED_IMPL=c)
+};
+struct BandedChoice {
+    BandedForm form;
+    int G;            // subject groups per wave
+    int phase, cut;   // the stream's re-anchor and cut periods (banded_stream_phase / banded_stream_cut)
+    bool wide;        // k > 15: the band does not fit 32 bits, 64-bit rows
+    const char *refused;   // not nullptr: this flavour of the library does not carry that kernel — the knob, as ab_knob_refused names it
+};
+
+// Precedence: BGSA_BANDED_IMPL (c, then s for k <= 15, p and a through the stream's phase and cut), then the width of the band,
+// then BGSA_BANDED_GROUPS / BGSA_BANDED_PAIR_LOOP.
+BandedChoice banded_select(int k)
+{
+    const int impl = banded_impl();
+    BandedChoice c = {BandedForm::kRowLoop, 1, banded_stream_phase(k), banded_stream_cut(k), k > 15, nullptr};
+    if (impl == 1)
+        c.form = BandedForm::kCompiler;
+    else if (impl == 2 && k <= 15)
+        c.form = BandedForm::kChunk;
+    else if (c.cut > 0) {
+        c.form = BandedForm::kCut;
+        c.G = banded_groups();
+    } else if (impl == 0 && !c.wide && banded_groups() == 2) {
+        c.form = BandedForm::kFunnel32;
+        c.G = 2;
+    } else if (impl == 0 && c.wide && (banded_pair_loop() == 1 || banded_pair_loop() == 2)) {
+        c.form = BandedForm::kFunnel64;
+        c.G = banded_pair_loop();
     }
+    if (!BGSA_AB_KERNELS) {
+        if (impl >= 1 && impl <= 3) c.refused = "BGSA_BANDED_IMPL=c/s/p";
+        else if (c.form == BandedForm::kFunnel64 && c.G == 2) c.refused = "BGSA_BANDED_PAIR_LOOP=2";
+    }
+    return c;
+}
+
+using CutKernel = decltype(&banded_cut_kernel<1, false>);
+CutKernel cut_kernel(const BandedChoice &c, bool counter)
+{
+    switch (c.form) {
+    case BandedForm::kFunnel64:
+#if BGSA_AB_KERNELS
+        if (c.G == 2) return counter ? banded_cut_kernel<2, true, 2> : banded_cut_kernel<2, false, 2>;
+#endif
+        return counter ? banded_cut_kernel<1, true, 2> : banded_cut_kernel<1, false, 2>;
+    case BandedForm::kFunnel32: return counter ? banded_cut_kernel<2, true, 1> : banded_cut_kernel<2, false, 1>;
+    default:
+        return c.G == 2 ? (counter ? banded_cut_kernel<2, true> : banded_cut_kernel<2, false>)
+                        : (counter ? banded_cut_kernel<1, true> : banded_cut_kernel<1, false>);
+    }
+}
+
+#if BGSA_AB_KERNELS
+int launch_chunk(const ScoreArgs &a, int k)
+{
+    const int nq = a.nq(), len = a.read_len;
+    const int q_tile = pick_query_tile(nq, a.n_groups(), len, 32);
+    note_query_tile(q_tile);
+    LaunchGrid lg;
+    if (int rc = plan_grid({q_tile, false}, a.n_groups(), nq, nullptr, no_counter_kernel, "banded", &lg)) return rc;
     const int rows_padded = (len + 31) / 32 * 32;
     const long long total = static_cast<long long>(nq) * rows_padded;
-    hipLaunchKernelGGL(pack_banded_tokens_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream,
-                       d_content, static_cast<uint32_t *>(d_workspace), len, ref_start, nq, rows_padded);
+    hipLaunchKernelGGL(pack_banded_tokens_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, a.stream,
+                       a.d_content, static_cast<uint32_t *>(a.d_workspace), len, a.ref_start, nq, rows_padded);
     BGSA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(banded_chunk_kernel, grid, dim3(256), 0, stream, static_cast<const uint32_t *>(d_workspace), d_peq,
-                       d_results, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num, nq, q_tile, k,
-                       rows_padded * 4, d_content, ref_start, len, static_cast<uint32_t>(k + banded_push_row_offset()),
+    hipLaunchKernelGGL(banded_chunk_kernel, lg.grid, dim3(256), 0, a.stream, static_cast<const uint32_t *>(a.d_workspace), a.d_peq,
+                       a.results<int8_t>(), static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq,
+                       q_tile, k, rows_padded * 4, a.d_content, a.ref_start, len, static_cast<uint32_t>(k + banded_push_row_offset()),
                        static_cast<uint32_t>(banded_push_max()));
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
+
+int launch_compiler(const ScoreArgs &a, int k, bool wide)
+{
+    const int q_tile = pick_query_tile(a.nq(), a.n_groups(), a.read_len, 32);
+    note_query_tile(q_tile);
+    LaunchGrid lg;
+    if (int rc = plan_grid({q_tile, false}, a.n_groups(), a.nq(), nullptr, no_counter_kernel, "banded", &lg)) return rc;
+    auto kernel = wide ? banded_kernel<uint64_t> : banded_kernel<uint32_t>;
+    hipLaunchKernelGGL(kernel, lg.grid, dim3(256), 0, a.stream, a.d_content, a.d_peq,
+                       a.results<int8_t>(), a.read_len, static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()),
+                       a.word_num, a.ref_start, a.ref_end, q_tile, k);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
 #endif  // BGSA_AB_KERNELS
 
-int launch_asm(const char *d_content, const uint32_t *d_peq, int8_t *d_results, int len, int64_t read_count,
-               int ref_start, int ref_end, int word_num, int k, void *d_workspace, hipStream_t stream)
+// The threaded row loops: the one-word-window kernels (kCut, kFunnel32, kFunnel64) and round 2's loops (kRowLoop).
+int launch_rows(const ScoreArgs &a, int k, const BandedChoice &c)
 {
-    const int nq = ref_end - ref_start;
-    const int64_t n_groups = read_count / kLanes;
-    const int phase = banded_stream_phase(k), cut = banded_stream_cut(k);
-    // the two-group loop around the funnel-shift rows (k >= 13): the default since round 4; BGSA_BANDED_IMPL=a keeps round 2's
-    // one-group loops (banded_asm_kernel) at every k, BGSA_BANDED_GROUPS=1 at k >= 13
-    // measured (scripts/r04_banded_funnel_ab.sh, r04_banded_pair_loop.sh; every pair surviving): the 32-bit rows gain 8 % from the
-    // two-group loop (random pairs 14-24 %); the 64-bit pair LOSES 4.5 % with two groups, loses 1.4 % with one group on a static
-    // grid and gains 2.2 % with one group on the task counter (k = 31: 660.8 -> 646.4 ms): that is its default.
-    // BGSA_BANDED_PAIR_LOOP=0: round 2's loop; =2: two groups (A/B flavour of the library only)
-    static const int pair_loop = [] { const char *e = getenv("BGSA_BANDED_PAIR_LOOP"); return e ? atoi(e) : 1; }();
-    int form = -1, G = 1;
-    if (cut > 0) { form = 0; G = banded_groups(); }
-    else if (phase == 0 && banded_impl() == 0 && banded_groups() == 2 && k <= 15) { form = 1; G = 2; }
-    else if (phase == 0 && banded_impl() == 0 && k > 15 && (pair_loop == 1 || pair_loop == 2)) { form = 2; G = pair_loop; }
-#if !BGSA_AB_KERNELS
-    if (form == 2 && G == 2) return ab_knob_refused("BGSA_BANDED_PAIR_LOOP=2");
-#endif
-    const int64_t n_waves = (n_groups + G - 1) / G;
-    const int q_tile = pick_query_tile(nq, n_waves, static_cast<long long>(len) * G, 32);
-    if (int rc = launch_pack_banded(d_content, len, k, phase, cut, ref_start, ref_end, d_workspace, stream)) return rc;
-    const int stride = banded_stream_layout(len, k, phase, cut, nullptr, nullptr);
+    const int nq = a.nq(), len = a.read_len;
+    const bool windows = c.form != BandedForm::kRowLoop;
+    const int64_t n_waves = (a.n_groups() + c.G - 1) / c.G;
+    const int q_tile = pick_query_tile(nq, n_waves, static_cast<long long>(len) * c.G, 32);
+    if (int rc = launch_pack_banded(a.d_content, len, k, c.phase, c.cut, a.ref_start, a.ref_end, a.d_workspace, a.stream)) return rc;
+    const int stride = banded_stream_layout(len, k, c.phase, c.cut, nullptr, nullptr);
     unsigned *fault = nullptr;
-    if (int rc = stream_guard(d_workspace, stride, kBandedRefill, 40, stream, &fault)) return rc;
+    if (int rc = stream_guard(a.d_workspace, stride, kBandedRefill, 40, a.stream, &fault)) return rc;
 
     note_query_tile(q_tile);
-    dim3 grid(static_cast<unsigned>((n_waves + kWavesPerBlock - 1) / kWavesPerBlock),
-              static_cast<unsigned>((nq + q_tile - 1) / q_tile));
-    if (grid.y > 65535u) {
-        set_error_text("banded: too many query tiles for one launch");
-        return BGSA_HIP_EUNSUPPORTED;
-    }
+    // the counter for the one-word-window kernels, on launches long enough to gain from it (and within the static grid's tile range)
+    const int64_t tiles = (nq + q_tile - 1) / q_tile;
+    const TaskPlan plan = {q_tile, windows && tiles <= 65535 && banded_dynamic_tasks() &&
+                                       dynamic_tasks_fit((n_waves + kWavesPerBlock - 1) / kWavesPerBlock * tiles * kWavesPerBlock)};
+    LaunchGrid lg;
+    if (int rc = plan_grid(plan, n_waves, nq, task_counter_in(a.d_workspace, static_cast<size_t>(stride) * nq),
+                           [&] { return persistent_blocks_for(cut_kernel(c, true)); }, "banded", &lg))
+        return rc;
     const uint32_t push_row = static_cast<uint32_t>(k + banded_push_row_offset());
     const uint32_t push_max = static_cast<uint32_t>(banded_push_max());
-    // one-word-window kernels: already from this row on if an alive lane is a solid survivor (gen_rows_asm.py: push_or)
-    const uint32_t push_row_solid = std::min(push_row, static_cast<uint32_t>(k + banded_push_solid_offset()));
-    // a solid survivor: at most this many errors since row k — by default about half the limit of k + 1 (swept on
-    // 10k x 1M, k = 8, scripts/r03_solid.sh: rows k + 16 ... k + 32 with margins 4 ... 6 all give 128-129 ms on the 1 %
-    // mix and 88 ms on random pairs; with margin 2 random stragglers pass for survivors: 107 ms from row k + 32)
-    const int margin = banded_push_solid_margin() >= 0 ? banded_push_solid_margin() : (k + 2) / 2;
-    const uint32_t solid_limit = static_cast<uint32_t>(k + 1 > margin ? k + 1 - margin : 0);
-    if (cut > 0 || form > 0) {
-        unsigned *counter = nullptr;
-        const long long blocks = static_cast<long long>(grid.x) * grid.y;
-        if (banded_dynamic_tasks() && dynamic_tasks_fit(blocks * kWavesPerBlock)) {
-            counter = task_counter_in(d_workspace, static_cast<size_t>(stride) * nq);
-            BGSA_HIP_TRY(hipMemsetAsync(counter, 0, 8, stream));
-#if BGSA_AB_KERNELS
-            const int resident = (form == 2 && G == 2) ? persistent_blocks_for(banded_cut_kernel<2, true, 2>)
-                               : form == 2 ? persistent_blocks_for(banded_cut_kernel<1, true, 2>)
-#else
-            const int resident = form == 2 ? persistent_blocks_for(banded_cut_kernel<1, true, 2>)
-#endif
-                               : form == 1 ? persistent_blocks_for(banded_cut_kernel<2, true, 1>)
-                               : G == 2 ? persistent_blocks_for(banded_cut_kernel<2, true>) : persistent_blocks_for(banded_cut_kernel<1, true>);
-            grid = dim3(static_cast<unsigned>(blocks < resident ? blocks : resident), 1u);
-        }
-#if BGSA_AB_KERNELS
-        auto kernel = (form == 2 && G == 2) ? (counter ? banded_cut_kernel<2, true, 2> : banded_cut_kernel<2, false, 2>)
-                    : form == 2 ? (counter ? banded_cut_kernel<1, true, 2> : banded_cut_kernel<1, false, 2>)
-#else
-        auto kernel = form == 2 ? (counter ? banded_cut_kernel<1, true, 2> : banded_cut_kernel<1, false, 2>)
-#endif
-                    : form == 1 ? (counter ? banded_cut_kernel<2, true, 1> : banded_cut_kernel<2, false, 1>)
-                    : G == 2 ? (counter ? banded_cut_kernel<2, true> : banded_cut_kernel<2, false>)
-                             : (counter ? banded_cut_kernel<1, true> : banded_cut_kernel<1, false>);
+    if (windows) {
+        // one-word-window kernels: already from this row on if an alive lane is a solid survivor (gen_rows_asm.py: push_or)
+        const uint32_t push_row_solid = std::min(push_row, static_cast<uint32_t>(k + banded_push_solid_offset()));
+        // a solid survivor: at most this many errors since row k — by default about half the limit of k + 1 (swept on
+        // 10k x 1M, k = 8, scripts/r03_solid.sh: rows k + 16 ... k + 32 with margins 4 ... 6 all give 128-129 ms on the 1 %
+        // mix and 88 ms on random pairs; with margin 2 random stragglers pass for survivors: 107 ms from row k + 32)
+        const int margin = banded_push_solid_margin() >= 0 ? banded_push_solid_margin() : (k + 2) / 2;
+        const uint32_t solid_limit = static_cast<uint32_t>(k + 1 > margin ? k + 1 - margin : 0);
+        if (lg.counter) BGSA_HIP_TRY(hipMemsetAsync(lg.counter, 0, 8, a.stream));
         static const unsigned lds_pad = [] { const char *e = getenv("BGSA_BANDED_LDS_PAD"); return e ? static_cast<unsigned>(atoi(e)) : 0u; }();
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds_pad, stream,
-                           static_cast<const unsigned char *>(d_workspace), d_peq, d_results,
-                           static_cast<long long>(read_count), static_cast<int>(n_groups), word_num, nq, q_tile, k, stride,
-                           fault, d_content, ref_start, len, push_row, push_row_solid, solid_limit, push_max, static_cast<uint32_t>(cut),
-                           counter);
-    }
+        hipLaunchKernelGGL(cut_kernel(c, lg.counter != nullptr), lg.grid, dim3(256), lds_pad, a.stream,
+                           static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int8_t>(),
+                           static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq, q_tile, k, stride,
+                           fault, a.d_content, a.ref_start, len, push_row, push_row_solid, solid_limit, push_max,
+                           static_cast<uint32_t>(c.cut), lg.counter);
+    } else {
+        auto kernel = c.wide ? banded_asm_kernel<true, false> : banded_asm_kernel<false, false>;
 #if BGSA_AB_KERNELS
-    else if (phase > 0)
-        hipLaunchKernelGGL((banded_asm_kernel<false, true>), grid, dim3(256), 0, stream,
-                           static_cast<const unsigned char *>(d_workspace), d_peq, d_results,
-                           static_cast<long long>(read_count), static_cast<int>(n_groups), word_num, nq, q_tile, k, stride,
-                           fault, d_content, ref_start, len, push_row, push_max, phase);
+        if (c.phase > 0) kernel = banded_asm_kernel<false, true>;
 #endif
-    else if (k <= 15)
-        hipLaunchKernelGGL((banded_asm_kernel<false, false>), grid, dim3(256), 0, stream,
-                           static_cast<const unsigned char *>(d_workspace), d_peq, d_results,
-                           static_cast<long long>(read_count), static_cast<int>(n_groups), word_num, nq, q_tile, k, stride,
-                           fault, d_content, ref_start, len, push_row, push_max, 0);
-    else
-        hipLaunchKernelGGL((banded_asm_kernel<true, false>), grid, dim3(256), 0, stream,
-                           static_cast<const unsigned char *>(d_workspace), d_peq, d_results,
-                           static_cast<long long>(read_count), static_cast<int>(n_groups), word_num, nq, q_tile, k, stride,
-                           fault, d_content, ref_start, len, push_row, push_max, 0);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
-}
-
-#if BGSA_AB_KERNELS
-template <typename T>
-int launch_t(const char *d_content, const uint32_t *d_peq, int8_t *d_results, int len,
-              int64_t read_count, int ref_start, int ref_end, int word_num, int k, hipStream_t stream)
-{
-    const int nq = ref_end - ref_start;
-    const int64_t n_groups = read_count / kLanes;
-    const int q_tile = pick_query_tile(nq, n_groups, len, 32);
-    note_query_tile(q_tile);
-    dim3 grid(static_cast<unsigned>((n_groups + kWavesPerBlock - 1) / kWavesPerBlock),
-              static_cast<unsigned>((nq + q_tile - 1) / q_tile));
-    if (grid.y > 65535u) {
-        set_error_text("banded: too many query tiles for one launch");
-        return BGSA_HIP_EUNSUPPORTED;
+        hipLaunchKernelGGL(kernel, lg.grid, dim3(256), 0, a.stream,
+                           static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int8_t>(),
+                           static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq, q_tile, k, stride,
+                           fault, a.d_content, a.ref_start, len, push_row, push_max, c.phase);
     }
-    hipLaunchKernelGGL((banded_kernel<T>), grid, dim3(256), 0, stream, d_content, d_peq, d_results, len,
-                       static_cast<long long>(read_count), static_cast<int>(n_groups), word_num, ref_start,
-                       ref_end, q_tile, k);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
-#endif  // BGSA_AB_KERNELS
 
 }  // namespace
 
@@ -1071,49 +1084,39 @@ int banded_stream_cut(int k)
 const char *banded_kernel_name(int word_num)
 {
     (void)word_num;
-    if (banded_impl() == 1) return g_last_k <= 15 ? "banded_kernel<uint32_t>" : "banded_kernel<uint64_t>";
-    if (banded_impl() == 2 && g_last_k <= 15) return "banded_chunk_kernel";
-    if (banded_stream_phase(g_last_k) > 0) return "banded_asm_kernel<false, true>";
-    if (banded_stream_cut(g_last_k) > 0) return banded_groups() == 2 ? "banded_cut_kernel<2>" : "banded_cut_kernel<1>";
-    if (banded_impl() == 0 && banded_groups() == 2 && g_last_k <= 15) return "banded_cut_kernel<2, funnel32>";
-    if (banded_impl() == 0 && g_last_k > 15) {
-        static const int pair_loop = [] { const char *e = getenv("BGSA_BANDED_PAIR_LOOP"); return e ? atoi(e) : 1; }();
-        if (pair_loop == 1) return "banded_cut_kernel<1, funnel64>";
-        if (pair_loop == 2) return "banded_cut_kernel<2, funnel64>";
+    const BandedChoice c = banded_select(g_last_k);
+    switch (c.form) {
+    case BandedForm::kCompiler: return c.wide ? "banded_kernel<uint64_t>" : "banded_kernel<uint32_t>";
+    case BandedForm::kChunk: return "banded_chunk_kernel";
+    case BandedForm::kCut: return c.G == 2 ? "banded_cut_kernel<2>" : "banded_cut_kernel<1>";
+    case BandedForm::kFunnel32: return "banded_cut_kernel<2, funnel32>";
+    case BandedForm::kFunnel64: return c.G == 2 ? "banded_cut_kernel<2, funnel64>" : "banded_cut_kernel<1, funnel64>";
+    case BandedForm::kRowLoop: break;
     }
-    return g_last_k <= 15 ? "banded_asm_kernel<false, false>" : "banded_asm_kernel<true, false>";
+    return c.phase > 0 ? "banded_asm_kernel<false, true>" : c.wide ? "banded_asm_kernel<true, false>" : "banded_asm_kernel<false, false>";
 }
 
-int launch_banded(const char *d_content, const uint32_t *d_peq, int8_t *d_results, int ref_len,
-                  int read_len, int64_t read_count, int ref_start, int ref_end, int word_num, int k,
-                  void *d_workspace, hipStream_t stream)
+int launch_banded(const ScoreArgs &a, int k)
 {
-    if (ref_end <= ref_start || read_count == 0) return BGSA_HIP_OK;
-    if (ref_len != read_len) {
+    if (a.ref_end <= a.ref_start || a.read_count == 0) return BGSA_HIP_OK;
+    if (a.ref_len != a.read_len) {
         set_error_text("banded: query_len must equal subject_len (the reference's band is mis-aligned otherwise)");
         return BGSA_HIP_EUNSUPPORTED;
     }
-    if (k < 1 || k > 31 || 2 * k + 1 >= read_len) {
+    if (k < 1 || k > 31 || 2 * k + 1 >= a.read_len) {
         set_error_text("banded: threshold must satisfy 1 <= k <= 31 and 2k+1 < length");
         return BGSA_HIP_EUNSUPPORTED;
     }
     g_last_k = k;
-#if !BGSA_AB_KERNELS
-    if (banded_impl() >= 1 && banded_impl() <= 3) return ab_knob_refused("BGSA_BANDED_IMPL=c/s/p");
-    return launch_asm(d_content, d_peq, d_results, read_len, read_count, ref_start, ref_end, word_num, k, d_workspace, stream);
-#else
-    if (banded_impl() == 2 && k <= 15)
-        return launch_chunk(d_content, d_peq, d_results, read_len, read_count, ref_start, ref_end, word_num, k,
-                            d_workspace, stream);
-    if (banded_impl() != 1)   // 0, 3 and 4: the threaded loops
-        return launch_asm(d_content, d_peq, d_results, read_len, read_count, ref_start, ref_end, word_num, k,
-                          d_workspace, stream);
-    if (k <= 15)
-        return launch_t<uint32_t>(d_content, d_peq, d_results, read_len, read_count, ref_start, ref_end,
-                                  word_num, k, stream);
-    return launch_t<uint64_t>(d_content, d_peq, d_results, read_len, read_count, ref_start, ref_end,
-                              word_num, k, stream);
+    const BandedChoice c = banded_select(k);
+    if (c.refused) return ab_knob_refused(c.refused);
+    switch (c.form) {
+#if BGSA_AB_KERNELS   // (the default flavour was refused above)
+    case BandedForm::kChunk: return launch_chunk(a, k);
+    case BandedForm::kCompiler: return launch_compiler(a, k, c.wide);
 #endif
+    default: return launch_rows(a, k, c);
+    }
 }
 
 }  // namespace bgsa

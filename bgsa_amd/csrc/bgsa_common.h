@@ -6,6 +6,8 @@
 #include <stdlib.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/bgsa_hip.h"
 
 namespace bgsa {
@@ -31,10 +33,69 @@ void set_error_text(const char *text);
 // `need` bytes (what a call without a caller-owned workspace uses; allocates on first use and when it grows).
 int with_own_scratch(hipStream_t stream, size_t need, int (*launch)(void *workspace, void *ctx), void *ctx);
 
-// Launchers implemented in the per-algorithm .hip files.  All pointers are device pointers.
-int launch_myers(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-                 int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-                 void *d_workspace, hipStream_t stream, int semi_global = 0);
+// What every scoring launch gets (bgsa_hip_cal_align_score_ex builds it once).  All pointers are device pointers.
+struct ScoreArgs {
+    const char *d_content;      // mapped query rows, stride ref_len + 1
+    const uint32_t *d_peq;      // the bucket's Peq / Mext blocks
+    void *d_results;            // int16_t scores (Myers, BitPAl) or int8_t distances (banded)
+    int ref_len, read_len;      // query and subject length
+    int64_t read_count;         // subjects, a multiple of kLanes
+    int ref_start, ref_end;     // the query window
+    int word_num;
+    void *d_workspace;
+    hipStream_t stream;
+    int nq() const { return ref_end - ref_start; }
+    int64_t n_groups() const { return read_count / kLanes; }
+    template <typename T> T *results() const { return static_cast<T *>(d_results); }
+};
+
+// Kernel widths (32-bit words per subject or per column block) as a type: the ONE list a family's selection picks from
+// and its launcher dispatches on, so a width cannot be picked that has no instantiation behind it.
+template <int... N>
+struct Widths {
+    // the smallest listed width that holds word_num words, or -1
+    static int pick(int word_num)
+    {
+        int nw = -1;
+        (void)((N >= word_num ? (nw = N, true) : false) || ...);
+        return nw;
+    }
+    static bool has(int nw) { return ((N == nw) || ...); }
+    // Column blocks: the narrowest listed width that covers word_num words with the fewest blocks (35 words over widths
+    // up to 28 -> 2 x 18, not 2 x 28).
+    static int pick_blocks(int word_num, int *n_blocks)
+    {
+        static_assert(sizeof...(N) > 0, "block widths of an empty list");
+        int widest = 0;
+        (void)((widest = N, false) || ...);   // the last one: the lists ascend
+        const int blocks = (word_num + widest - 1) / widest;
+        const int nw = pick((word_num + blocks - 1) / blocks);
+        *n_blocks = (word_num + nw - 1) / nw;
+        return nw;
+    }
+    // f(std::integral_constant<int, nw>{}) for the listed nw; any other value is an error that names the family and the width.
+    template <typename F>
+    static int dispatch(int nw, const char *family, F &&f)
+    {
+        int rc = BGSA_HIP_EUNSUPPORTED;
+        if (((N == nw ? (rc = f(std::integral_constant<int, N>{}), true) : false) || ...)) return rc;
+        char msg[128];
+        snprintf(msg, sizeof msg, "%s: no kernel of %d words in this build", family, nw);
+        set_error_text(msg);
+        return BGSA_HIP_EUNSUPPORTED;
+    }
+    template <int M>
+    constexpr Widths<N..., M> with() const { return {}; }   // builds a list from a generated X-macro (bitpal_kernels.inl)
+};
+template <typename A, typename B> struct JoinWidths;
+template <int... A, int... B> struct JoinWidths<Widths<A...>, Widths<B...>> { using type = Widths<A..., B...>; };
+template <typename A, typename B> using Join = typename JoinWidths<A, B>::type;
+
+// Launchers implemented in the per-algorithm .hip files.  Which kernel a launch runs is decided by ONE function per algorithm
+// (myers_select, banded_select, the per-set bitpal_select); the launcher switches on its answer and *_kernel_name formats it.
+int launch_myers(const ScoreArgs &a, int semi_global = 0);
+// The name of the kernel the knobs select for a launch with at least two subject groups (no read count here: a bucket of
+// ONE group of <= 64 bp subjects runs <NW, 1> where this says <NW, 2>).
 const char *myers_kernel_name(int word_num, int semi_global = 0);
 
 // Packed query stream (one per query, 8-byte windows): codes 0..4 = A C G T N row, 5 = END,
@@ -245,10 +306,8 @@ int launch_pack_blocked(const char *d_content, int len, int ref_start, int ref_e
 int launch_pack_banded(const char *d_content, int len, int k, int phase, int cut, int ref_start, int ref_end, void *d_streams,
                        hipStream_t stream);
 
-int launch_banded(const char *d_content, const uint32_t *d_peq, int8_t *d_results, int ref_len,
-                  int read_len, int64_t read_count, int ref_start, int ref_end, int word_num, int k,
-                  void *d_workspace, hipStream_t stream);
-const char *banded_kernel_name(int word_num);
+int launch_banded(const ScoreArgs &a, int k);
+const char *banded_kernel_name(int word_num);   // for the threshold of this thread's last banded launch
 
 // One compiled BitPAl score set (bitpal.hip; the kernels come from gen_bitpal_sets.py).
 struct BitpalSet {
@@ -258,9 +317,7 @@ struct BitpalSet {
     int carry_words; // > 0: packed-carry column blocks — this many carry words per direction and ROW (rows_ir.py: make_blocked_packed)
     int max_plain;   // widest subject, in words, whose state stays in registers; beyond: column blocks
     int valu_per_word;
-    int (*launch)(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len, int read_len,
-                  int64_t read_count, int ref_start, int ref_end, int word_num, void *d_workspace,
-                  hipStream_t stream, int semi_global);
+    int (*launch)(const ScoreArgs &a, int semi_global);
     const char *(*kernel_name)(int word_num);
 };
 int bitpal_set_count();
@@ -269,9 +326,7 @@ const BitpalSet *bitpal_find_set(int match, int mismatch, int gap);  // nullptr:
 int bitpal_common_factor(int match, int mismatch, int gap);  // the generator's commonFactor (Main.java:213-238)
 
 // Scores with the kernels of compiled set `s` (capi.hip: make_plan picks it and the result factor).
-int launch_bitpal(const BitpalSet *s, const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-                  int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-                  void *d_workspace, hipStream_t stream, int semi_global);
+int launch_bitpal(const BitpalSet *s, const ScoreArgs &a, int semi_global);
 const char *bitpal_kernel_name(const BitpalSet *s, int word_num);
 
 // Widest subject (in words) the Myers kernels keep whole in registers; wider ones run as column blocks.
@@ -436,6 +491,35 @@ inline TaskPlan plan_tasks(int nq, long long wave_tasks_per_tile, long long row_
     return {pick_query_tile(nq, wave_tasks_per_tile, row_words, q_max), false};
 }
 constexpr size_t kTaskCounterBytes = 512;   // what plan_workspace_bytes adds for it (alignment included)
+// The grid of a launch of n_waves wave tasks per query tile.  Static plan: (four waves per workgroup, query tiles), refused
+// beyond blockIdx.y's range with an error that carries the caller's algorithm name.  Counter plan: a persistent grid of at
+// most resident() workgroups (persistent_blocks_for the kernel that will run) and the launch's counter word.
+struct LaunchGrid {
+    dim3 grid;
+    unsigned *counter;   // nullptr: static grid
+};
+inline int no_counter_kernel() { return 0; }   // resident() of the launchers whose kernels have no counter instantiation
+template <typename Resident>
+inline int plan_grid(const TaskPlan &plan, int64_t n_waves, int nq, unsigned *counter_word, Resident &&resident, const char *algo,
+                     LaunchGrid *out)
+{
+    const unsigned x = static_cast<unsigned>((n_waves + kWavesPerBlock - 1) / kWavesPerBlock);
+    const unsigned y = static_cast<unsigned>((nq + plan.q_tile - 1) / plan.q_tile);
+    if (!plan.dynamic) {
+        if (y > 65535u) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "%s: too many query tiles for one launch", algo);
+            set_error_text(msg);
+            return BGSA_HIP_EUNSUPPORTED;
+        }
+        *out = {dim3(x, y), nullptr};
+        return BGSA_HIP_OK;
+    }
+    const long long blocks = static_cast<long long>(x) * y;
+    const int res = resident();
+    *out = {dim3(static_cast<unsigned>(blocks < res ? blocks : res), 1u), counter_word};
+    return BGSA_HIP_OK;
+}
 
 // Tasks of a column-block kernel are handed out from a device-wide counter (zeroed by the launcher, it
 // sits behind the carry buffers in the workspace): the XCDs do not sustain exactly the same clock, and with
@@ -472,15 +556,20 @@ size_t long_state_bytes(int algo, int word_num);
 //                      code-plane kernels below 29 words (BGSA_MYERS_PEQ_MAX_WORDS) and code-plane column blocks
 //                      (BGSA_MYERS_BLOCK_FORM=planes) — and the score sets of BITPAL_SETS_AB.
 // A knob that asks the default flavour for a kernel it does not carry fails loudly (ab_knob_refused), it is never ignored.
+// Which kernel the knobs select is decided in myers_select (myers_global.hip), banded_select (banded.hip) and bitpal_select
+// (bitpal_kernels.inl); the width lists next to them carry the flavour distinction (AbOnly).
 #ifndef BGSA_AB_KERNELS
 #define BGSA_AB_KERNELS 0
+#endif
+#if BGSA_AB_KERNELS
+template <typename W> using AbOnly = W;          // widths only the A/B flavour instantiates
+#else
+template <typename W> using AbOnly = Widths<>;
 #endif
 // `what` names the knob as the caller set it; returns BGSA_HIP_EUNSUPPORTED with the error text set.
 int ab_knob_refused(const char *what);
 
-int launch_long(int algo, const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-                int read_len, int64_t read_count, int ref_start, int ref_end, int word_num, void *d_state,
-                hipStream_t stream);
+int launch_long(int algo, const ScoreArgs &a);   // the state slices are the workspace
 
 // Queries per Peq / Mext load of this thread's last scoring launch (bgsa_hip_last_query_tile: bench.py models the
 // launch's HBM traffic from it — tiles x block bytes + scores — where no PMC pass is at hand, e.g. per rank at N > 1).

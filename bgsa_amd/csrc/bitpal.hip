@@ -62,20 +62,17 @@ const char *bitpal_kernel_name(const BitpalSet *s, int word_num)
     return s->kernel_name(word_num);
 }
 
-int launch_bitpal(const BitpalSet *s, const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-                  int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-                  void *d_workspace, hipStream_t stream, int semi_global)
+int launch_bitpal(const BitpalSet *s, const ScoreArgs &a, int semi_global)
 {
-    if (ref_end <= ref_start || read_count == 0) return BGSA_HIP_OK;
+    if (a.ref_end <= a.ref_start || a.read_count == 0) return BGSA_HIP_OK;
+    if (a.word_num > s->max_plain && bitpal_c_impl(s) && !semi_global) {   // A/B: the state-in-memory C++ kernel
 #if BGSA_AB_KERNELS
-    if (word_num > s->max_plain && bitpal_c_impl(s) && !semi_global)  // A/B: the state-in-memory C++ kernel
-        return launch_long(BGSA_ALGO_BITPAL, d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start,
-                           ref_end, word_num, d_workspace, stream);
+        return launch_long(BGSA_ALGO_BITPAL, a);
 #else
-    if (word_num > s->max_plain && bitpal_c_impl(s) && !semi_global) return ab_knob_refused("BGSA_BITPAL_IMPL=c");
+        return ab_knob_refused("BGSA_BITPAL_IMPL=c");
 #endif
-    return s->launch(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, ref_end, word_num,
-                     d_workspace, stream, semi_global);
+    }
+    return s->launch(a, semi_global);
 }
 
 }  // namespace bgsa

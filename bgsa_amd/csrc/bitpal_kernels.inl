@@ -275,39 +275,23 @@ __global__ __launch_bounds__(256) void bitpal_packed_blocked_kernel(
 
 namespace {
 
-// Narrowest instantiated block width that covers word_num words with the fewest blocks.
-inline int pick_block_nw(int word_num, int *n_blocks)
-{
-    const int blocks = (word_num + kBitpalBlockMax - 1) / kBitpalBlockMax;
-    const int need = (word_num + blocks - 1) / blocks;
-    const int nw = need < kBitpalBlockMin ? kBitpalBlockMin : need;
-    *n_blocks = (word_num + nw - 1) / nw;
-    return nw;
-}
+// The set's kernel widths, from the generated lists (gen_rows_asm.py writes them as X-macros): what bitpal_select picks
+// from and what the launchers dispatch on.
+#define BGSA_WIDTH(N) .with<N>()
+using PlainWidths = decltype(Widths<>{} BGSA_BITPAL_PLAIN_WIDTHS(BGSA_WIDTH));
+using BlockWidths = decltype(Widths<>{} BGSA_BITPAL_BLOCK_WIDTHS(BGSA_WIDTH));
+#undef BGSA_WIDTH
 
-template <int NW>
-int launch_blocked(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len, int read_len,
-                   int64_t read_count, int ref_start, int ref_end, int word_num, int n_blocks, void *d_workspace,
-                   hipStream_t stream, int semi)
+// Which kernel scores a subject of word_num words: set_launch dispatches on it, set_kernel_name formats it.
+struct BitpalChoice {
+    bool blocks;   // column blocks (in the set's carry form, kBitpalPackedBlocks) instead of the register-resident kernel
+    int nw, n_blocks;
+};
+inline BitpalChoice bitpal_select(int word_num)
 {
-    const int nq = ref_end - ref_start;
-    const int stride = blocked_stream_layout(ref_len, nullptr, nullptr);
-    const size_t stream_bytes = (static_cast<size_t>(stride) * nq + 255) & ~static_cast<size_t>(255);
-    if (int rc = launch_pack_blocked(d_content, ref_len, ref_start, ref_end, d_workspace, stream)) return rc;
-    uint32_t *carry = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d_workspace) + stream_bytes);
-    unsigned long long *counter = reinterpret_cast<unsigned long long *>(
-        reinterpret_cast<unsigned char *>(carry) + blocked_carry_bytes(ref_len, kBitpalChains));
-    BGSA_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned long long), stream));
-    unsigned *fault = nullptr;
-    if (int rc = stream_guard(d_workspace, stride, kCodeRefill, -1, stream, &fault)) return rc;
-    auto kernel = semi ? bitpal_blocked_kernel<NW, true> : bitpal_blocked_kernel<NW, false>;
-    hipLaunchKernelGGL(kernel, dim3(blocked_workgroups()), dim3(256), 0, stream,
-                       static_cast<const unsigned char *>(d_workspace), d_peq, d_results, carry, ref_len, read_len,
-                       static_cast<long long>(read_count), static_cast<int>(read_count / kLanes), word_num, nq,
-                       (note_query_tile(blocked_q_tile(nq, read_count / kLanes)), blocked_q_tile(nq, read_count / kLanes)),
-                       stride, n_blocks, counter, fault);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
+    BitpalChoice c = {word_num > kBitpalMaxPlain, word_num, 1};   // the plain kernels are exact widths: every word count has its own
+    if (c.blocks) c.nw = BlockWidths::pick_blocks(word_num, &c.n_blocks);
+    return c;
 }
 
 // Bytes of the packed-carry buffers (capi.hip sizes the workspace with the same formula: BitpalSet::carry_words).
@@ -316,97 +300,69 @@ inline size_t packed_carry_bytes(int ref_len)
     return static_cast<size_t>(ref_len + 1) * kBitpalCarryWords * kLanes * sizeof(uint32_t) * kWavesPerBlock * blocked_workgroups();
 }
 
-template <int NW>
-int launch_packed_blocked(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len, int read_len,
-                          int64_t read_count, int ref_start, int ref_end, int word_num, int n_blocks, void *d_workspace,
-                          hipStream_t stream, int semi)
+// Column blocks in the set's carry form (PACKED a template parameter so that only that form's row loops are instantiated):
+// carry-token streams and a register pair per chain, or plain streams and the carries of a row packed into kBitpalCarryWords words.
+template <int NW, bool PACKED>
+int launch_blocked(const ScoreArgs &a, int n_blocks, int semi)
 {
-    const int nq = ref_end - ref_start;
-    const int stride = static_cast<int>(stream_stride(ref_len));
-    // the same workspace split as launch_blocked (capi.hip sizes the stream part for the longer CARRY-token stream)
-    const size_t stream_bytes = (static_cast<size_t>(blocked_stream_layout(ref_len, nullptr, nullptr)) * nq + 255) & ~static_cast<size_t>(255);
-    if (int rc = launch_pack_queries(d_content, ref_len, ref_start, ref_end, d_workspace, stream)) return rc;
-    uint32_t *carry = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d_workspace) + stream_bytes);
-    unsigned long long *counter = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(carry) + packed_carry_bytes(ref_len));
-    BGSA_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned long long), stream));
+    const int nq = a.nq();
+    const int token_stride = blocked_stream_layout(a.ref_len, nullptr, nullptr);
+    const int stride = PACKED ? static_cast<int>(stream_stride(a.ref_len)) : token_stride;
+    // one workspace split for both forms (capi.hip sizes the stream part for the longer CARRY-token stream)
+    const size_t stream_bytes = (static_cast<size_t>(token_stride) * nq + 255) & ~static_cast<size_t>(255);
+    if (int rc = PACKED ? launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream)
+                        : launch_pack_blocked(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream))
+        return rc;
+    uint32_t *carry = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(a.d_workspace) + stream_bytes);
+    unsigned long long *counter = reinterpret_cast<unsigned long long *>(
+        reinterpret_cast<unsigned char *>(carry) + (PACKED ? packed_carry_bytes(a.ref_len) : blocked_carry_bytes(a.ref_len, kBitpalChains)));
+    BGSA_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned long long), a.stream));
     unsigned *fault = nullptr;
-    if (int rc = stream_guard(d_workspace, stride, kCodeRefill, 7, stream, &fault)) return rc;
-    auto kernel = semi ? bitpal_packed_blocked_kernel<NW, true> : bitpal_packed_blocked_kernel<NW, false>;
-    hipLaunchKernelGGL(kernel, dim3(blocked_workgroups()), dim3(256), 0, stream,
-                       static_cast<const unsigned char *>(d_workspace), d_peq, d_results, carry, ref_len, read_len,
-                       static_cast<long long>(read_count), static_cast<int>(read_count / kLanes), word_num, nq,
-                       (note_query_tile(blocked_q_tile(nq, read_count / kLanes)), blocked_q_tile(nq, read_count / kLanes)), stride, n_blocks, counter, fault);
+    if (int rc = stream_guard(a.d_workspace, stride, kCodeRefill, PACKED ? 7 : -1, a.stream, &fault)) return rc;
+    const int q_tile = blocked_q_tile(nq, a.n_groups());
+    note_query_tile(q_tile);
+    auto kernel = [semi] {
+        if constexpr (PACKED) return semi ? bitpal_packed_blocked_kernel<NW, true> : bitpal_packed_blocked_kernel<NW, false>;
+        else return semi ? bitpal_blocked_kernel<NW, true> : bitpal_blocked_kernel<NW, false>;
+    }();
+    hipLaunchKernelGGL(kernel, dim3(blocked_workgroups()), dim3(256), 0, a.stream,
+                       static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), carry, a.ref_len, a.read_len,
+                       static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq, q_tile, stride, n_blocks,
+                       counter, fault);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
 
-// Column blocks in the set's carry form (a template so that only that form's row loops are instantiated).
-template <bool PACKED>
-int launch_blocks(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len, int read_len,
-                  int64_t read_count, int ref_start, int ref_end, int word_num, void *d_workspace, hipStream_t stream, int semi)
-{
-    int n_blocks = 0;
-    switch (pick_block_nw(word_num, &n_blocks)) {
-#define X(N)                                                                                                    \
-    case N:                                                                                                     \
-        if constexpr (PACKED)                                                                                   \
-            return launch_packed_blocked<N>(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, \
-                                            ref_end, word_num, n_blocks, d_workspace, stream, semi);           \
-        else                                                                                                    \
-            return launch_blocked<N>(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start,       \
-                                     ref_end, word_num, n_blocks, d_workspace, stream, semi);
-        BGSA_BITPAL_BLOCK_WIDTHS(X)
-#undef X
-    default: break;
-    }
-    set_error_text("bitpal: no column-block kernel for this word count");
-    return BGSA_HIP_EUNSUPPORTED;
-}
-
-
 template <int NW>
-int launch_nw(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-              int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-              void *d_workspace, hipStream_t stream, int semi)
+int launch_nw(const ScoreArgs &a, int semi)
 {
-    const int nq = ref_end - ref_start;
-    const int64_t n_groups = read_count / kLanes;
+    const int nq = a.nq(), stride = static_cast<int>(stream_stride(a.ref_len));
     // a BitPAl row is 2-4x a Myers row.  Counter where the loop's registers cost no wave — asked of the runtime per score set,
     // width and mode, once (2/-3/-5: 5 words 98 -> 108 VGPRs, four waves per SIMD either way; 8 words 155 -> 169 would be
     // three -> two: 256 bp ran 10 % slower with it, profiles/r03_length_sweep.txt)
     static const bool counter_costs_no_wave[2] = {
-        [] { int a = 0, b = 0;
-             return hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, bitpal_asm_kernel<NW, false, false>, 256, 0) == hipSuccess &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, bitpal_asm_kernel<NW, false, true>, 256, 0) == hipSuccess && b >= a && a > 0; }(),
-        [] { int a = 0, b = 0;
-             return hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, bitpal_asm_kernel<NW, true, false>, 256, 0) == hipSuccess &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, bitpal_asm_kernel<NW, true, true>, 256, 0) == hipSuccess && b >= a && a > 0; }()};
-    const TaskPlan plan = plan_tasks(nq, n_groups, static_cast<long long>(ref_len) * NW * 2, 16, NW <= 8 && counter_costs_no_wave[semi ? 1 : 0],
+        [] { int plain = 0, counter = 0;
+             return hipOccupancyMaxActiveBlocksPerMultiprocessor(&plain, bitpal_asm_kernel<NW, false, false>, 256, 0) == hipSuccess &&
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&counter, bitpal_asm_kernel<NW, false, true>, 256, 0) == hipSuccess && counter >= plain && plain > 0; }(),
+        [] { int plain = 0, counter = 0;
+             return hipOccupancyMaxActiveBlocksPerMultiprocessor(&plain, bitpal_asm_kernel<NW, true, false>, 256, 0) == hipSuccess &&
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&counter, bitpal_asm_kernel<NW, true, true>, 256, 0) == hipSuccess && counter >= plain && plain > 0; }()};
+    const TaskPlan plan = plan_tasks(nq, a.n_groups(), static_cast<long long>(a.ref_len) * NW * 2, 16, NW <= 8 && counter_costs_no_wave[semi ? 1 : 0],
                                      query_tile_max());
-    const int q_tile = plan.q_tile;
-    note_query_tile(q_tile);
-    dim3 grid(static_cast<unsigned>((n_groups + kWavesPerBlock - 1) / kWavesPerBlock),
-              static_cast<unsigned>((nq + q_tile - 1) / q_tile));
-    if (grid.y > 65535u && !plan.dynamic) {
-        set_error_text("bitpal: too many query tiles for one launch");
-        return BGSA_HIP_EUNSUPPORTED;
-    }
-    unsigned *counter = nullptr;   // zeroed by the packer
-    if (plan.dynamic) {
-        const long long blocks = static_cast<long long>(grid.x) * grid.y;
-        counter = task_counter_in(d_workspace, stream_stride(ref_len) * static_cast<size_t>(nq));
-        const int resident = semi ? persistent_blocks_for(bitpal_asm_kernel<NW, true, true>) : persistent_blocks_for(bitpal_asm_kernel<NW, false, true>);
-        grid = dim3(static_cast<unsigned>(blocks < resident ? blocks : resident), 1u);
-    }
-    if (int rc = launch_pack_queries(d_content, ref_len, ref_start, ref_end, d_workspace, stream, counter)) return rc;
+    note_query_tile(plan.q_tile);
+    const auto on_counter = semi ? bitpal_asm_kernel<NW, true, true> : bitpal_asm_kernel<NW, false, true>;
+    LaunchGrid lg;   // the counter is zeroed by the packer
+    if (int rc = plan_grid(plan, a.n_groups(), nq, task_counter_in(a.d_workspace, static_cast<size_t>(stride) * nq),
+                           [&] { return persistent_blocks_for(on_counter); }, "bitpal", &lg))
+        return rc;
+    if (int rc = launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter)) return rc;
     unsigned *fault = nullptr;
-    if (int rc = stream_guard(d_workspace, static_cast<int>(stream_stride(ref_len)), kCodeRefill, 7, stream, &fault)) return rc;
-    auto kernel = counter ? (semi ? bitpal_asm_kernel<NW, true, true> : bitpal_asm_kernel<NW, false, true>)
-                          : (semi ? bitpal_asm_kernel<NW, true, false> : bitpal_asm_kernel<NW, false, false>);
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream,
-                       static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                       read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                       nq, q_tile, static_cast<int>(stream_stride(ref_len)), fault, counter);
+    if (int rc = stream_guard(a.d_workspace, stride, kCodeRefill, 7, a.stream, &fault)) return rc;
+    const auto kernel = lg.counter ? on_counter : (semi ? bitpal_asm_kernel<NW, true, false> : bitpal_asm_kernel<NW, false, false>);
+    hipLaunchKernelGGL(kernel, lg.grid, dim3(256), 0, a.stream,
+                       static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len,
+                       a.read_len, static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num,
+                       nq, plan.q_tile, stride, fault, lg.counter);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
@@ -416,32 +372,17 @@ int launch_nw(const char *d_content, const uint32_t *d_peq, int16_t *d_results, 
 const char *set_kernel_name(int word_num)
 {
     static thread_local char name[64];
-    if (word_num > kBitpalMaxPlain) {
-        int n_blocks = 0;
-        snprintf(name, sizeof name, kBitpalPackedBlocks ? "bitpal_packed_blocked_kernel<%d>" : "bitpal_blocked_kernel<%d>",
-                 pick_block_nw(word_num, &n_blocks));
-        return name;
-    }
-    snprintf(name, sizeof name, "bitpal_asm_kernel<%d>", word_num);
+    const BitpalChoice c = bitpal_select(word_num);
+    snprintf(name, sizeof name, !c.blocks ? "bitpal_asm_kernel<%d>" : kBitpalPackedBlocks ? "bitpal_packed_blocked_kernel<%d>" : "bitpal_blocked_kernel<%d>",
+             c.nw);
     return name;
 }
 
-int set_launch(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-               int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-               void *d_workspace, hipStream_t stream, int semi)
+int set_launch(const ScoreArgs &a, int semi)
 {
-    if (word_num > kBitpalMaxPlain)
-        return launch_blocks<kBitpalPackedBlocks>(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, ref_end,
-                                                  word_num, d_workspace, stream, semi);
-    switch (word_num) {
-#define X(N)                                                                                    \
-    case N:                                                                                     \
-        return launch_nw<N>(d_content, d_peq, d_results, ref_len, read_len, read_count,         \
-                            ref_start, ref_end, word_num, d_workspace, stream, semi);
-        BGSA_BITPAL_PLAIN_WIDTHS(X)
-#undef X
-    default:
-        set_error_text("bitpal: no kernel for this word count");
-        return BGSA_HIP_EUNSUPPORTED;
-    }
+    const BitpalChoice c = bitpal_select(a.word_num);
+    if (c.blocks)
+        return BlockWidths::dispatch(c.nw, "bitpal column blocks",
+                                     [&](auto nw) { return launch_blocked<decltype(nw)::value, kBitpalPackedBlocks>(a, c.n_blocks, semi); });
+    return PlainWidths::dispatch(c.nw, "bitpal_asm_kernel", [&](auto nw) { return launch_nw<decltype(nw)::value>(a, semi); });
 }

@@ -77,6 +77,18 @@ unsigned *device_fault_word()
     return p;
 }
 
+// The fault word of the current device if any launch ever made one (*word stays nullptr otherwise): what the entry points
+// that only read it back use — they do not allocate.
+static int existing_fault_word(int *dev, unsigned **word)
+{
+    *word = nullptr;
+    BGSA_HIP_TRY(hipGetDevice(dev));
+    std::lock_guard<std::mutex> lock(g_fault_mu);
+    auto it = g_fault_words.find(*dev);
+    if (it != g_fault_words.end()) *word = it->second;
+    return BGSA_HIP_OK;
+}
+
 int take_injected_stream_fault()
 {
     std::lock_guard<std::mutex> lock(g_fault_mu);
@@ -569,14 +581,9 @@ int bgsa_hip_stream_wait_event(void *stream, void *event)
 int bgsa_hip_stream_faults(int clear)
 {
     int dev = 0;
-    BGSA_HIP_TRY(hipGetDevice(&dev));
     unsigned *word = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_fault_mu);
-        auto it = g_fault_words.find(dev);
-        if (it == g_fault_words.end()) return 0;  // nothing was ever launched on this device
-        word = it->second;
-    }
+    if (int rc = existing_fault_word(&dev, &word)) return rc;
+    if (!word) return 0;  // nothing was ever launched on this device
     unsigned value = 0;
     BGSA_HIP_TRY(hipMemcpy(&value, word, sizeof value, hipMemcpyDeviceToHost));
     if (value && clear) BGSA_HIP_TRY(hipMemset(word, 0, sizeof value));
@@ -617,14 +624,9 @@ int bgsa_hip_myers_band_stats(unsigned long long *out, int clear)
     if (!out) return BGSA_HIP_EINVAL;
     out[0] = out[1] = 0;
     int dev = 0;
-    BGSA_HIP_TRY(hipGetDevice(&dev));
     unsigned *word = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_fault_mu);
-        auto it = g_fault_words.find(dev);
-        if (it == g_fault_words.end()) return BGSA_HIP_OK;  // nothing was ever launched on this device
-        word = it->second;
-    }
+    if (int rc = existing_fault_word(&dev, &word)) return rc;
+    if (!word) return BGSA_HIP_OK;  // nothing was ever launched on this device
     BGSA_HIP_TRY(hipMemcpy(out, band_stats_words(word), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (clear) BGSA_HIP_TRY(hipMemset(band_stats_words(word), 0, 2 * sizeof(unsigned long long)));
     return BGSA_HIP_OK;
@@ -718,19 +720,15 @@ int bgsa_hip_cal_align_score_ex(const bgsa_hip_params_t *params, const char *d_c
         if (int rc = scratch_reserve(s, need, &d_workspace)) return rc;
     }
     const int64_t n_scores = static_cast<int64_t>(ref_end - ref_start) * read_count;
+    const ScoreArgs args = {d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, ref_end, word_num, d_workspace, s};
     switch (plan.kernel) {
     case BGSA_ALGO_MYERS:
-        if (int rc = launch_myers(d_content, d_peq, static_cast<int16_t *>(d_results), ref_len, read_len,
-                                  read_count, ref_start, ref_end, word_num, d_workspace, s, plan.semi))
-            return rc;
+        if (int rc = launch_myers(args, plan.semi)) return rc;
         return launch_scale_scores(static_cast<int16_t *>(d_results), n_scores, plan.factor, s);
     case BGSA_ALGO_BANDED:
-        return launch_banded(d_content, d_peq, static_cast<int8_t *>(d_results), ref_len, read_len,
-                             read_count, ref_start, ref_end, word_num, params->k, d_workspace, s);
+        return launch_banded(args, params->k);
     case BGSA_ALGO_BITPAL:
-        if (int rc = launch_bitpal(plan.set, d_content, d_peq, static_cast<int16_t *>(d_results), ref_len,
-                                   read_len, read_count, ref_start, ref_end, word_num, d_workspace, s, plan.semi))
-            return rc;
+        if (int rc = launch_bitpal(plan.set, args, plan.semi)) return rc;
         return launch_scale_scores(static_cast<int16_t *>(d_results), n_scores, plan.factor, s);
     default:
         set_error_text("cal_align_score_dev: unknown algorithm");

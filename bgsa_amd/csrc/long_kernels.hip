@@ -187,20 +187,12 @@ size_t long_state_bytes(int algo, int word_num)
     return per_wave * kWavesPerBlock * kLongBlocks;
 }
 
-int launch_long(int algo, const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-                int read_len, int64_t read_count, int ref_start, int ref_end, int word_num, void *d_state,
-                hipStream_t stream)
+int launch_long(int algo, const ScoreArgs &a)
 {
-    const int n_groups = static_cast<int>(read_count / kLanes);
-    const int q_tile = 4;
-    if (algo == BGSA_ALGO_BITPAL)
-        hipLaunchKernelGGL(bitpal_long_kernel, dim3(kLongBlocks), dim3(256), 0, stream, d_content, d_peq, d_results,
-                           static_cast<uint32_t *>(d_state), ref_len, read_len, static_cast<long long>(read_count),
-                           n_groups, word_num, ref_start, ref_end, q_tile);
-    else
-        hipLaunchKernelGGL(myers_long_kernel, dim3(kLongBlocks), dim3(256), 0, stream, d_content, d_peq, d_results,
-                           static_cast<uint32_t *>(d_state), ref_len, read_len, static_cast<long long>(read_count),
-                           n_groups, word_num, ref_start, ref_end, q_tile);
+    auto kernel = algo == BGSA_ALGO_BITPAL ? bitpal_long_kernel : myers_long_kernel;
+    hipLaunchKernelGGL(kernel, dim3(kLongBlocks), dim3(256), 0, a.stream, a.d_content, a.d_peq, a.results<int16_t>(),
+                       static_cast<uint32_t *>(a.d_workspace), a.ref_len, a.read_len, static_cast<long long>(a.read_count),
+                       static_cast<int>(a.n_groups()), a.word_num, a.ref_start, a.ref_end, 4 /* queries per task */);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }

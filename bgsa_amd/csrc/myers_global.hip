@@ -17,7 +17,7 @@
 //   * The score is not tracked per row (align_core.c:121-124); after the last row
 //     D[m][n] = m + popcount(VP & mask) - popcount(VN & mask), two v_bcnt per word.
 //
-// Three kernels, chosen by launch_myers():
+// The kernels, chosen by myers_select() (launch_myers switches on its answer, myers_kernel_name formats it):
 //   myers_global_asm_kernel<NW,1>   1..1024 bp   generated asm row loop, Peq planes resident, 8 VALU per (row, word); 30 and 32 words
 //                                                (897..1024 bp) with the two carry chains in turns over blocks of 9 words
 //   myers_global_planes_kernel<NW>  (A/B)        generated asm row loop on 3-bit character-code planes, 9 VALU per (row, word):
@@ -651,16 +651,24 @@ __global__ __launch_bounds__(256) void myers_blocked_kernel(
 
 namespace {
 
-// Register-resident word counts that are instantiated; a subject uses the smallest one that
-// holds it (extra words are all-zero Peq and masked out of the score).
-constexpr int kMyersNW[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32};
-
-int pick_nw(int word_num)
-{
-    for (int nw : kMyersNW)
-        if (nw >= word_num) return nw;
-    return -1;
-}
+// ---- the kernel widths: each list is what its family's selection picks from AND what its launcher dispatches on ----
+// Resident Peq planes (myers_global_asm_kernel, myers_semi_asm_kernel).  A subject uses the smallest width that holds it
+// (extra words are all-zero Peq and masked out of the score).
+using PeqWidths = Widths<1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20, 22, 24, 25, 26, 28, 30, 32>;
+using PairWidths = Widths<1, 2>;   // two rows per token and two subject groups per wave (kPairMaxWords)
+// Code planes (myers_global_planes_kernel).  Below 29 words only BGSA_MYERS_PEQ_MAX_WORDS gets there (resident Peq planes
+// measured faster): those widths ship in the A/B flavour.
+using PlanesAbWidths = Widths<10, 12, 14, 16, 18, 20, 22, 24, 26, 28>;
+using PlanesWidths = Widths<30, 32>;
+using SemiPlanesWidths = Widths<26, 28, 30, 32>;   // myers_semi_planes_kernel
+// Column blocks with resident Peq planes: 20 words = 238 VGPRs, two waves per SIMD (22 words would need 256).
+using PeqBlockWidths = Widths<12, 14, 16, 18, 20>;
+// ... on the code planes (BGSA_MYERS_BLOCK_FORM=planes, A/B flavour): 28 words is the widest block that keeps two waves
+// per SIMD (32 needs 256 VGPRs: measured 93 vs 168 TCUPS).
+using PlaneBlockWidths = Widths<12, 14, 16, 18, 20, 22, 24, 26, 28>;
+// The compiler-scheduled kernel (BGSA_MYERS_IMPL=c, A/B flavour).
+using CompilerWidths = Widths<1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32>;
+static_assert(kPairMaxWords == 2 && kPeqMaxWords == 32 && kSemiPeqMaxWords == 32, "the width lists above restate these");
 
 // Queries per task.  Small enough that the grid has >> 256 CUs x 8 waves of tasks even for a
 // few thousand subjects, large enough that the 5*NW Peq loads are noise next to
@@ -713,212 +721,6 @@ static int long_query_tile()
     return v;
 }
 
-// The certificate statistics of one band launch into the device's sticky counts (myers_band.h: band_stats_words).
-__global__ void band_stats_add_kernel(const unsigned long long *__restrict__ launch, unsigned long long *__restrict__ stats)
-{
-    atomicAdd(&stats[0], launch[0]);   // launches on other streams may add at the same time
-    atomicAdd(&stats[1], launch[1]);
-}
-
-template <int NW, int G>
-int launch_asm(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-               int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-               void *d_workspace, hipStream_t stream)
-{
-    const int nq = ref_end - ref_start;
-    const int64_t n_groups = read_count / kLanes;
-    // the widths with registers to spare have a counter instantiation, and so have the split-chain widths (30, 32 words: two
-    // waves per SIMD with or without the task loop's registers)
-    constexpr bool kCounter = NW <= 8 || NW >= 30;
-    const TaskPlan plan = plan_tasks(nq, (n_groups + G - 1) / G, static_cast<long long>(ref_len) * NW * G, NW >= 30 ? 8 : 32, kCounter,
-                                     NW >= 30 ? long_query_tile() : query_tile_max());
-    const int q_tile = plan.q_tile;
-    note_query_tile(q_tile);
-    dim3 grid(static_cast<unsigned>((n_groups + kWavesPerBlock * G - 1) / (kWavesPerBlock * G)),
-              static_cast<unsigned>((nq + q_tile - 1) / q_tile));
-    if (grid.y > 65535u && !plan.dynamic) {
-        set_error_text("myers: too many query tiles for one launch");
-        return BGSA_HIP_EUNSUPPORTED;
-    }
-    if constexpr (G == 1 && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
-        BandSchedule sched;
-        const int h = band_half(ref_len, read_len);
-        if (band_schedule(ref_len, read_len, h, NW, &sched)) {
-            const int stride = static_cast<int>(band_stream_stride(ref_len));
-            // the task counter sits where the plain path keeps it, behind the streams, and the guard's pair 64 bytes further
-            // (both inside the kTaskCounterBytes the workspace reserves); the packer zeroes them
-            unsigned *words = task_counter_in(d_workspace, static_cast<size_t>(stride) * nq);
-            unsigned *counter = plan.dynamic ? words : nullptr;
-            unsigned long long *guard = band_launch_words(words);
-            if (plan.dynamic) {
-                const long long blocks = static_cast<long long>(grid.x) * grid.y;
-                const int resident = persistent_blocks_for(myers_global_asm_kernel<NW, G, true, true>, myers_lds_pad());
-                grid = dim3(static_cast<unsigned>(blocks < resident ? blocks : resident), 1u);
-            }
-            if (int rc = launch_pack_band(d_content, ref_len, sched, ref_start, ref_end, d_workspace, stream, words)) return rc;
-            unsigned *fault = nullptr;
-            if (int rc = stream_guard(d_workspace, stride, kCodeRefill, kBandBadCode, stream, &fault)) return rc;
-            if (counter)
-                hipLaunchKernelGGL((myers_global_asm_kernel<NW, G, true, true>), grid, dim3(256), myers_lds_pad(), stream,
-                                   static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                                   read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                                   nq, q_tile, stride, fault, counter, 2 * h + 1, guard);
-            else
-                hipLaunchKernelGGL((myers_global_asm_kernel<NW, G, false, true>), grid, dim3(256), 0, stream,
-                                   static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                                   read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                                   nq, q_tile, stride, fault, counter, 2 * h + 1, guard);
-            BGSA_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(band_stats_add_kernel, dim3(1), dim3(1), 0, stream, static_cast<const unsigned long long *>(guard),
-                               band_stats_words(fault));
-            BGSA_HIP_TRY(hipGetLastError());
-            return BGSA_HIP_OK;
-        }
-    }
-    constexpr bool kPairs = NW <= kPairMaxWords;
-    const int stride = static_cast<int>(kPairs ? pair_stream_stride(ref_len) : stream_stride(ref_len));
-    unsigned *counter = nullptr;   // the task counter behind the streams; the packer zeroes it
-    if (plan.dynamic) {
-        const long long blocks = static_cast<long long>(grid.x) * grid.y;
-        counter = task_counter_in(d_workspace, static_cast<size_t>(stride) * nq);
-        int resident = persistent_blocks();
-        if constexpr (kCounter) resident = persistent_blocks_for(myers_global_asm_kernel<NW, G, true>, myers_lds_pad());
-        grid = dim3(static_cast<unsigned>(blocks < resident ? blocks : resident), 1u);
-    }
-    if (int rc = kPairs ? launch_pack_query_pairs(d_content, ref_len, ref_start, ref_end, d_workspace, stream, counter)
-                        : launch_pack_queries(d_content, ref_len, ref_start, ref_end, d_workspace, stream, counter))
-        return rc;
-    unsigned *fault = nullptr;
-    if (int rc = stream_guard(d_workspace, stride, kPairs ? kPairRefill : kCodeRefill, kPairs ? -1 : 7, stream, &fault)) return rc;
-    if constexpr (kCounter) {
-        if (counter) {
-            hipLaunchKernelGGL((myers_global_asm_kernel<NW, G, true>), grid, dim3(256), myers_lds_pad(), stream,
-                               static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                               read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                               nq, q_tile, stride, fault, counter);
-            BGSA_HIP_TRY(hipGetLastError());
-            return BGSA_HIP_OK;
-        }
-    }
-    hipLaunchKernelGGL((myers_global_asm_kernel<NW, G, false>), grid, dim3(256), 0, stream,
-                       static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                       read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                       nq, q_tile, stride, fault, counter);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
-}
-
-template <int NW>
-int launch_semi_asm(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-                    int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-                    void *d_workspace, hipStream_t stream)
-{
-    const int nq = ref_end - ref_start;
-    const int64_t n_groups = read_count / kLanes;
-    const int q_tile = pick_q_tile(nq, n_groups, ref_len, NW);
-    note_query_tile(q_tile);
-    dim3 grid(static_cast<unsigned>((n_groups + kWavesPerBlock - 1) / kWavesPerBlock),
-              static_cast<unsigned>((nq + q_tile - 1) / q_tile));
-    if (grid.y > 65535u) {
-        set_error_text("myers: too many query tiles for one launch");
-        return BGSA_HIP_EUNSUPPORTED;
-    }
-    if (int rc = launch_pack_queries(d_content, ref_len, ref_start, ref_end, d_workspace, stream)) return rc;
-    unsigned *fault = nullptr;
-    if (int rc = stream_guard(d_workspace, static_cast<int>(stream_stride(ref_len)), kCodeRefill, 7, stream, &fault)) return rc;
-    hipLaunchKernelGGL((myers_semi_asm_kernel<NW>), grid, dim3(256), 0, stream,
-                       static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                       read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                       nq, q_tile, static_cast<int>(stream_stride(ref_len)), fault);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
-}
-
-template <int NW, bool SEMI = false>
-int launch_planes(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-                  int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-                  void *d_workspace, hipStream_t stream)
-{
-    const int nq = ref_end - ref_start;
-    const int64_t n_groups = read_count / kLanes;
-    // a task is already long: 8 queries x ref_len rows x 11*NW instructions.  Counter: two waves per SIMD with or without the
-    // loop's registers from 26 words up; narrower A/B widths keep theirs
-    const TaskPlan plan = plan_tasks(nq, n_groups, static_cast<long long>(ref_len) * NW, 8, !SEMI && NW >= 26);
-    const int q_tile = plan.q_tile;
-    note_query_tile(q_tile);
-    dim3 grid(static_cast<unsigned>((n_groups + kWavesPerBlock - 1) / kWavesPerBlock),
-              static_cast<unsigned>((nq + q_tile - 1) / q_tile));
-    const bool dynamic = plan.dynamic;
-    if (grid.y > 65535u && !dynamic) {
-        set_error_text("myers: too many query tiles for one launch");
-        return BGSA_HIP_EUNSUPPORTED;
-    }
-    unsigned *counter = dynamic ? task_counter_in(d_workspace, stream_stride(ref_len) * static_cast<size_t>(nq)) : nullptr;
-    if (int rc = launch_pack_queries(d_content, ref_len, ref_start, ref_end, d_workspace, stream, counter)) return rc;
-    unsigned *fault = nullptr;
-    if (int rc = stream_guard(d_workspace, static_cast<int>(stream_stride(ref_len)), kCodeRefill, 7, stream, &fault)) return rc;
-    if constexpr (SEMI)
-        hipLaunchKernelGGL((myers_semi_planes_kernel<NW>), grid, dim3(256), 0, stream,
-                           static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                           read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                           nq, q_tile, static_cast<int>(stream_stride(ref_len)), fault);
-    else if (dynamic) {
-        const long long blocks = static_cast<long long>(grid.x) * grid.y;
-        const int resident = persistent_blocks_for(myers_global_planes_kernel<NW, true>);
-        hipLaunchKernelGGL((myers_global_planes_kernel<NW, true>), dim3(static_cast<unsigned>(blocks < resident ? blocks : resident)),
-                           dim3(256), 0, stream, static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                           read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                           nq, q_tile, static_cast<int>(stream_stride(ref_len)), fault, counter);
-    } else
-        hipLaunchKernelGGL((myers_global_planes_kernel<NW, false>), grid, dim3(256), 0, stream,
-                           static_cast<const unsigned char *>(d_workspace), d_peq, d_results, ref_len,
-                           read_len, static_cast<long long>(read_count), static_cast<int>(n_groups), word_num,
-                           nq, q_tile, static_cast<int>(stream_stride(ref_len)), fault, nullptr);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
-}
-
-template <int NW, bool PEQ = false, bool SEMI = false>
-int launch_blocked(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len, int read_len,
-                   int64_t read_count, int ref_start, int ref_end, int word_num, int n_blocks, void *d_workspace,
-                   hipStream_t stream)
-{
-    const int nq = ref_end - ref_start;
-    const int stride = blocked_stream_layout(ref_len, nullptr, nullptr);
-    const size_t stream_bytes = (static_cast<size_t>(stride) * nq + 255) & ~static_cast<size_t>(255);
-    if (int rc = launch_pack_blocked(d_content, ref_len, ref_start, ref_end, d_workspace, stream)) return rc;
-    uint32_t *carry = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d_workspace) + stream_bytes);
-    unsigned long long *counter = reinterpret_cast<unsigned long long *>(
-        reinterpret_cast<unsigned char *>(carry) + blocked_carry_bytes(ref_len, 3));
-    BGSA_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned long long), stream));
-    unsigned *fault = nullptr;
-    if (int rc = stream_guard(d_workspace, stride, kCodeRefill, -1, stream, &fault)) return rc;
-    hipLaunchKernelGGL((myers_blocked_kernel<NW, PEQ, SEMI>), dim3(blocked_workgroups()), dim3(256), 0, stream,
-                       static_cast<const unsigned char *>(d_workspace), d_peq, d_results, carry, ref_len, read_len,
-                       static_cast<long long>(read_count), static_cast<int>(read_count / kLanes), word_num, nq,
-                       (note_query_tile(blocked_q_tile(nq, read_count / kLanes)), blocked_q_tile(nq, read_count / kLanes)),
-                       stride, n_blocks, counter, fault);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
-}
-
-// Block width for a subject of word_num > 32 words: the narrowest instantiated width that covers
-// it with the fewest blocks (35 words -> 2 x 20, not 2 x 28).  28 words is the widest block that
-// keeps two waves per SIMD (32 needs 256 VGPRs: measured 93 vs 168 TCUPS).
-int pick_block_nw(int word_num, int *n_blocks)
-{
-    constexpr int kWidest = 28;
-    const int blocks = (word_num + kWidest - 1) / kWidest;
-    const int need = (word_num + blocks - 1) / blocks;
-    for (int nw : {12, 14, 16, 18, 20, 22, 24, 26, 28})
-        if (nw >= need) {
-            *n_blocks = (word_num + nw - 1) / nw;
-            return nw;
-        }
-    *n_blocks = blocks;
-    return kWidest;
-}
-
 // Column blocks with resident Peq planes: 12..20 words (BGSA_MYERS_BLOCK_FORM=planes selects the
 // code-plane blocks of up to 28 words instead, the A/B reference).
 bool peq_blocks()
@@ -929,48 +731,163 @@ bool peq_blocks()
     }();
     return on;
 }
-int pick_peq_block_nw(int word_num, int *n_blocks)
+
+// The certificate statistics of one band launch into the device's sticky counts (myers_band.h: band_stats_words).
+__global__ void band_stats_add_kernel(const unsigned long long *__restrict__ launch, unsigned long long *__restrict__ stats)
 {
-    constexpr int kWidest = 20;  // 238 VGPRs: two waves per SIMD (22 words would need 256)
-    const int blocks = (word_num + kWidest - 1) / kWidest;
-    const int need = (word_num + blocks - 1) / blocks;
-    for (int nw : {12, 14, 16, 18, 20})
-        if (nw >= need) {
-            *n_blocks = (word_num + nw - 1) / nw;
-            return nw;
+    atomicAdd(&stats[0], launch[0]);   // launches on other streams may add at the same time
+    atomicAdd(&stats[1], launch[1]);
+}
+
+// Every instantiation of myers_global_asm_kernel through one pointer type (a function pointer has no default arguments: the
+// plain kernels get their two band parameters passed as 0 / nullptr).
+using AsmKernel = void (*)(const unsigned char *, const uint32_t *, int16_t *, int, int, long long, int, int, int, int, int,
+                           unsigned *, unsigned *, int, unsigned long long *);
+
+template <int NW, int G>
+int launch_asm(const ScoreArgs &a)
+{
+    const int nq = a.nq();
+    // the widths with registers to spare have a counter instantiation, and so have the split-chain widths (30, 32 words: two
+    // waves per SIMD with or without the task loop's registers)
+    constexpr bool kCounter = NW <= 8 || NW >= 30;
+    constexpr bool kPairs = NW <= kPairMaxWords;
+    const int64_t n_waves = (a.n_groups() + G - 1) / G;
+    const TaskPlan plan = plan_tasks(nq, n_waves, static_cast<long long>(a.ref_len) * NW * G, NW >= 30 ? 8 : 32, kCounter,
+                                     NW >= 30 ? long_query_tile() : query_tile_max());
+    note_query_tile(plan.q_tile);
+    AsmKernel on_grid = myers_global_asm_kernel<NW, G, false>, on_counter = nullptr;
+    if constexpr (kCounter) on_counter = myers_global_asm_kernel<NW, G, true>;
+    BandSchedule sched;
+    int h = 0;
+    bool band = false;
+    if constexpr (G == 1 && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
+        h = band_half(a.ref_len, a.read_len);
+        band = band_schedule(a.ref_len, a.read_len, h, NW, &sched);
+        if (band) {
+            on_grid = myers_global_asm_kernel<NW, G, false, true>;
+            on_counter = myers_global_asm_kernel<NW, G, true, true>;
         }
-    *n_blocks = blocks;
-    return kWidest;
-}
-
-int pick_planes_nw(int word_num)
-{
-    for (int nw : {10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32})
-        if (nw >= word_num) return nw;
-    return -1;
-}
-
-template <int NW, int G, bool SEMI = false>
-int launch_nw(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-              int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-              hipStream_t stream)
-{
-    const int nq = ref_end - ref_start;
-    const int64_t n_groups = read_count / kLanes;
-    const int q_tile = pick_q_tile(nq, (n_groups + G - 1) / G, ref_len, NW * G);
-    note_query_tile(q_tile);
-    dim3 grid(static_cast<unsigned>((n_groups + kWavesPerBlock * G - 1) / (kWavesPerBlock * G)),
-              static_cast<unsigned>((nq + q_tile - 1) / q_tile));
-    if (grid.y > 65535u) {
-        set_error_text("myers: too many query tiles for one launch");
-        return BGSA_HIP_EUNSUPPORTED;
     }
-    hipLaunchKernelGGL((myers_global_kernel<NW, G, SEMI>), grid, dim3(256), 0, stream, d_content, d_peq,
-                       d_results, ref_len, read_len, static_cast<long long>(read_count),
-                       static_cast<int>(n_groups), word_num, ref_start, ref_end, q_tile);
+    const int stride = static_cast<int>(band ? band_stream_stride(a.ref_len) : kPairs ? pair_stream_stride(a.ref_len) : stream_stride(a.ref_len));
+    // the task counter sits behind the streams, and the band's guard pair 64 bytes further (both inside the kTaskCounterBytes
+    // the workspace reserves); the packer zeroes them
+    unsigned *words = task_counter_in(a.d_workspace, static_cast<size_t>(stride) * nq);
+    LaunchGrid lg;
+    if (int rc = plan_grid(plan, n_waves, nq, words,
+                           [&] { return on_counter ? persistent_blocks_for(on_counter, myers_lds_pad()) : persistent_blocks(); }, "myers", &lg))
+        return rc;
+    if (int rc = band     ? launch_pack_band(a.d_content, a.ref_len, sched, a.ref_start, a.ref_end, a.d_workspace, a.stream, words)
+                 : kPairs ? launch_pack_query_pairs(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter)
+                          : launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter))
+        return rc;
+    unsigned *fault = nullptr;
+    if (int rc = stream_guard(a.d_workspace, stride, kPairs ? kPairRefill : kCodeRefill, band ? kBandBadCode : kPairs ? -1 : 7, a.stream, &fault))
+        return rc;
+    unsigned long long *guard = band ? band_launch_words(words) : nullptr;
+    const AsmKernel kernel = lg.counter ? on_counter : on_grid;
+    hipLaunchKernelGGL(kernel, lg.grid, dim3(256), lg.counter ? myers_lds_pad() : 0u, a.stream,
+                       static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len, a.read_len,
+                       static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq, plan.q_tile, stride,
+                       fault, lg.counter, band ? 2 * h + 1 : 0, guard);
+    BGSA_HIP_TRY(hipGetLastError());
+    if (band) {
+        hipLaunchKernelGGL(band_stats_add_kernel, dim3(1), dim3(1), 0, a.stream, static_cast<const unsigned long long *>(guard),
+                           band_stats_words(fault));
+        BGSA_HIP_TRY(hipGetLastError());
+    }
+    return BGSA_HIP_OK;
+}
+
+template <int NW>
+int launch_semi_asm(const ScoreArgs &a)
+{
+    const int nq = a.nq(), stride = static_cast<int>(stream_stride(a.ref_len));
+    const int q_tile = pick_q_tile(nq, a.n_groups(), a.ref_len, NW);
+    note_query_tile(q_tile);
+    LaunchGrid lg;
+    if (int rc = plan_grid({q_tile, false}, a.n_groups(), nq, nullptr, no_counter_kernel, "myers", &lg)) return rc;
+    if (int rc = launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream)) return rc;
+    unsigned *fault = nullptr;
+    if (int rc = stream_guard(a.d_workspace, stride, kCodeRefill, 7, a.stream, &fault)) return rc;
+    hipLaunchKernelGGL((myers_semi_asm_kernel<NW>), lg.grid, dim3(256), 0, a.stream,
+                       static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len,
+                       a.read_len, static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num,
+                       nq, q_tile, stride, fault);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
+
+template <int NW, bool SEMI = false>
+int launch_planes(const ScoreArgs &a)
+{
+    const int nq = a.nq(), stride = static_cast<int>(stream_stride(a.ref_len));
+    // a task is already long: 8 queries x ref_len rows x 11*NW instructions.  Counter: two waves per SIMD with or without the
+    // loop's registers from 26 words up; narrower A/B widths keep theirs
+    const TaskPlan plan = plan_tasks(nq, a.n_groups(), static_cast<long long>(a.ref_len) * NW, 8, !SEMI && NW >= 26);
+    note_query_tile(plan.q_tile);
+    LaunchGrid lg;
+    if (int rc = plan_grid(plan, a.n_groups(), nq, task_counter_in(a.d_workspace, static_cast<size_t>(stride) * nq),
+                           [] { if constexpr (SEMI) return 0; else return persistent_blocks_for(myers_global_planes_kernel<NW, true>); },
+                           "myers", &lg))
+        return rc;
+    if (int rc = launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter)) return rc;
+    unsigned *fault = nullptr;
+    if (int rc = stream_guard(a.d_workspace, stride, kCodeRefill, 7, a.stream, &fault)) return rc;
+    if constexpr (SEMI)
+        hipLaunchKernelGGL((myers_semi_planes_kernel<NW>), lg.grid, dim3(256), 0, a.stream,
+                           static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len,
+                           a.read_len, static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num,
+                           nq, plan.q_tile, stride, fault);
+    else {
+        auto kernel = lg.counter ? myers_global_planes_kernel<NW, true> : myers_global_planes_kernel<NW, false>;
+        hipLaunchKernelGGL(kernel, lg.grid, dim3(256), 0, a.stream, static_cast<const unsigned char *>(a.d_workspace), a.d_peq,
+                           a.results<int16_t>(), a.ref_len, a.read_len, static_cast<long long>(a.read_count),
+                           static_cast<int>(a.n_groups()), a.word_num, nq, plan.q_tile, stride, fault, lg.counter);
+    }
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+template <int NW, bool PEQ = false, bool SEMI = false>
+int launch_blocked(const ScoreArgs &a, int n_blocks)
+{
+    const int nq = a.nq();
+    const int stride = blocked_stream_layout(a.ref_len, nullptr, nullptr);
+    const size_t stream_bytes = (static_cast<size_t>(stride) * nq + 255) & ~static_cast<size_t>(255);
+    if (int rc = launch_pack_blocked(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream)) return rc;
+    uint32_t *carry = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(a.d_workspace) + stream_bytes);
+    unsigned long long *counter = reinterpret_cast<unsigned long long *>(
+        reinterpret_cast<unsigned char *>(carry) + blocked_carry_bytes(a.ref_len, 3));
+    BGSA_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned long long), a.stream));
+    unsigned *fault = nullptr;
+    if (int rc = stream_guard(a.d_workspace, stride, kCodeRefill, -1, a.stream, &fault)) return rc;
+    const int q_tile = blocked_q_tile(nq, a.n_groups());
+    note_query_tile(q_tile);
+    hipLaunchKernelGGL((myers_blocked_kernel<NW, PEQ, SEMI>), dim3(blocked_workgroups()), dim3(256), 0, a.stream,
+                       static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), carry, a.ref_len,
+                       a.read_len, static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq,
+                       q_tile, stride, n_blocks, counter, fault);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+#if BGSA_AB_KERNELS
+template <int NW, int G, bool SEMI = false>
+int launch_nw(const ScoreArgs &a)
+{
+    const int64_t n_waves = (a.n_groups() + G - 1) / G;
+    const int q_tile = pick_q_tile(a.nq(), n_waves, a.ref_len, NW * G);
+    note_query_tile(q_tile);
+    LaunchGrid lg;
+    if (int rc = plan_grid({q_tile, false}, n_waves, a.nq(), nullptr, no_counter_kernel, "myers", &lg)) return rc;
+    hipLaunchKernelGGL((myers_global_kernel<NW, G, SEMI>), lg.grid, dim3(256), 0, a.stream, a.d_content, a.d_peq,
+                       a.results<int16_t>(), a.ref_len, a.read_len, static_cast<long long>(a.read_count),
+                       static_cast<int>(a.n_groups()), a.word_num, a.ref_start, a.ref_end, q_tile);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+#endif
 
 }  // namespace
 
@@ -1000,208 +917,131 @@ int myers_peq_max_words()
 // to myers_peq_max_words(), the code planes (myers_semi_planes_kernel) up to 32 words; wider ones run as column blocks.
 int myers_semi_max_plain_words() { return 32; }
 
-int pick_semi_planes_nw(int word_num)
+namespace {
+
+// ---- which kernel scores a launch: decided here, once; launch_myers switches on the answer, myers_kernel_name formats it ----
+enum class MyersFamily {
+    kAsm,            // myers_global_asm_kernel<nw, 1>: resident Peq planes (the certified band where it applies)
+    kAsmPairs,       // myers_global_asm_kernel<nw, 2>: <= 64 bp, two rows per token, two subject groups per wave
+    kSemiAsm,        // myers_semi_asm_kernel<nw>
+    kPlanes,         // myers_global_planes_kernel<nw>
+    kSemiPlanes,     // myers_semi_planes_kernel<nw>
+    kBlockedPeq,     // myers_blocked_kernel<nw, true> / <nw, true, true>: n_blocks column blocks, resident Peq planes
+    kBlockedPlanes,  // myers_blocked_kernel<nw>: ... on the code planes
+    kCompiler,       // myers_global_kernel<nw, 1> / <nw, 1, true>: compiler-scheduled (BGSA_MYERS_IMPL=c)
+    kStateInMemory,  // myers_long_kernel (long_kernels.hip): BGSA_MYERS_IMPL=c beyond the register-resident limit
+};
+struct MyersChoice {
+    MyersFamily family;
+    int nw, G, n_blocks;
+    bool semi;
+    const char *refused;   // not nullptr: this flavour of the library does not carry that kernel — the knob, as ab_knob_refused names it
+};
+
+// Precedence: BGSA_MYERS_IMPL=c first; then the alignment mode; global subjects beyond BGSA_MYERS_MAX_PLAIN_WORDS run as
+// column blocks in the form BGSA_MYERS_BLOCK_FORM names; the others on resident Peq planes up to BGSA_MYERS_PEQ_MAX_WORDS
+// (<= 64 bp: two groups per wave unless BGSA_MYERS_PAIR_GROUPS=1 or the bucket has one group only) and on the code planes beyond.
+MyersChoice myers_select(int word_num, int semi, int64_t read_count)
 {
-    for (int nw : {26, 28, 30, 32})
-        if (nw >= word_num) return nw;
-    return -1;
+    auto ab_only = [](const char *knob) -> const char * { return BGSA_AB_KERNELS ? nullptr : knob; };   // kernels of the A/B flavour
+    MyersChoice c = {MyersFamily::kAsm, -1, 1, 0, semi != 0, nullptr};
+    const bool c_impl = myers_impl() == 1;
+    const int peq_max = semi ? std::min(myers_peq_max_words(), kSemiPeqMaxWords) : myers_peq_max_words();
+    if (!semi && word_num > myers_max_plain_words()) {
+        c.family = peq_blocks() ? MyersFamily::kBlockedPeq : MyersFamily::kBlockedPlanes;
+        c.nw = peq_blocks() ? PeqBlockWidths::pick_blocks(word_num, &c.n_blocks) : PlaneBlockWidths::pick_blocks(word_num, &c.n_blocks);
+        if (!peq_blocks()) c.refused = ab_only("BGSA_MYERS_BLOCK_FORM=planes");
+        if (c_impl) {   // keeps nw: bgsa_hip_kernel_name has always answered with the column-block kernel it stands in for
+            c.family = MyersFamily::kStateInMemory;
+            c.refused = ab_only("BGSA_MYERS_IMPL=c");
+        }
+    } else if (c_impl) {
+        c.family = MyersFamily::kCompiler;
+        c.nw = CompilerWidths::pick(word_num);   // -1 beyond 1024 bp (semi-global only: global subjects went above)
+        c.refused = ab_only("BGSA_MYERS_IMPL=c");
+    } else if (word_num <= peq_max) {
+        c.nw = PeqWidths::pick(word_num);
+        if (semi)
+            c.family = MyersFamily::kSemiAsm;
+        else if (word_num <= kPairMaxWords && pair_groups() == 2 && read_count >= 2 * kLanes) {
+            c.family = MyersFamily::kAsmPairs;
+            c.G = 2;
+        }
+    } else if (semi && word_num > myers_semi_max_plain_words()) {
+        c.family = MyersFamily::kBlockedPeq;
+        c.nw = PeqBlockWidths::pick_blocks(word_num, &c.n_blocks);
+    } else if (semi) {
+        c.family = MyersFamily::kSemiPlanes;
+        c.nw = SemiPlanesWidths::pick(word_num);
+    } else {
+        c.family = MyersFamily::kPlanes;
+        c.nw = Join<PlanesAbWidths, PlanesWidths>::pick(word_num);
+        if (!PlanesWidths::has(c.nw)) c.refused = ab_only("BGSA_MYERS_PEQ_MAX_WORDS");
+    }
+    return c;
 }
 
-int pick_peq_nw(int word_num)
-{
-    if (word_num > myers_peq_max_words()) return -1;
-    for (int nw : {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20, 22, 24, 25, 26, 28, 30, 32})
-        if (nw >= word_num) return nw;
-    return -1;
-}
+}  // namespace
 
 const char *myers_kernel_name(int word_num, int semi_global)
 {
     static thread_local char name[64];
-    const int nw = pick_nw(word_num);
-    if (semi_global) {
-        int n_blocks = 0;
-        if (myers_impl() != 0)
-            snprintf(name, sizeof name, "myers_global_kernel<%d, 1, true>", nw);
-        else if (word_num <= std::min(myers_peq_max_words(), kSemiPeqMaxWords))
-            snprintf(name, sizeof name, "myers_semi_asm_kernel<%d>", pick_peq_nw(word_num));
-        else if (word_num <= myers_semi_max_plain_words())
-            snprintf(name, sizeof name, "myers_semi_planes_kernel<%d>", pick_semi_planes_nw(word_num));
-        else
-            snprintf(name, sizeof name, "myers_blocked_kernel<%d, true, true>", pick_peq_block_nw(word_num, &n_blocks));
-        return name;
+    const MyersChoice c = myers_select(word_num, semi_global, 2 * kLanes);   // "at least two groups": see bgsa_common.h
+    switch (c.family) {
+    case MyersFamily::kAsm:
+    case MyersFamily::kAsmPairs: snprintf(name, sizeof name, "myers_global_asm_kernel<%d, %d>", c.nw, c.G); break;
+    case MyersFamily::kSemiAsm: snprintf(name, sizeof name, "myers_semi_asm_kernel<%d>", c.nw); break;
+    case MyersFamily::kPlanes: snprintf(name, sizeof name, "myers_global_planes_kernel<%d>", c.nw); break;
+    case MyersFamily::kSemiPlanes: snprintf(name, sizeof name, "myers_semi_planes_kernel<%d>", c.nw); break;
+    case MyersFamily::kStateInMemory:   // named after the column blocks of the selected form (myers_select)
+        snprintf(name, sizeof name, peq_blocks() ? "myers_blocked_kernel<%d, true>" : "myers_blocked_kernel<%d>", c.nw);
+        break;
+    case MyersFamily::kBlockedPeq: snprintf(name, sizeof name, c.semi ? "myers_blocked_kernel<%d, true, true>" : "myers_blocked_kernel<%d, true>", c.nw); break;
+    case MyersFamily::kBlockedPlanes: snprintf(name, sizeof name, "myers_blocked_kernel<%d>", c.nw); break;
+    case MyersFamily::kCompiler: snprintf(name, sizeof name, c.semi ? "myers_global_kernel<%d, 1, true>" : "myers_global_kernel<%d, 1>", c.nw); break;
     }
-    if (word_num > myers_max_plain_words()) {
-        int n_blocks = 0;
-        if (peq_blocks())
-            snprintf(name, sizeof name, "myers_blocked_kernel<%d, true>", pick_peq_block_nw(word_num, &n_blocks));
-        else
-            snprintf(name, sizeof name, "myers_blocked_kernel<%d>", pick_block_nw(word_num, &n_blocks));
-        return name;
-    }
-    if (myers_impl() == 0 && pick_peq_nw(word_num) > 0)
-        snprintf(name, sizeof name, "myers_global_asm_kernel<%d, %d>", pick_peq_nw(word_num),
-                 (word_num <= kPairMaxWords && pair_groups() == 2) ? 2 : 1);
-    else if (myers_impl() == 0 && pick_planes_nw(word_num) > 0)
-        snprintf(name, sizeof name, "myers_global_planes_kernel<%d>", pick_planes_nw(word_num));
-    else
-        snprintf(name, sizeof name, "myers_global_kernel<%d, 1>", nw);
     return name;
 }
 
-int launch_myers(const char *d_content, const uint32_t *d_peq, int16_t *d_results, int ref_len,
-                 int read_len, int64_t read_count, int ref_start, int ref_end, int word_num,
-                 void *d_workspace, hipStream_t stream, int semi_global)
+int launch_myers(const ScoreArgs &a, int semi_global)
 {
-    if (ref_end <= ref_start || read_count == 0) return BGSA_HIP_OK;
-    if (semi_global && myers_impl() == 0) {
-        // generated-asm kernels: resident Peq planes up to 24 words, code planes up to 32, column blocks (any length) beyond
-        if (word_num > std::min(myers_peq_max_words(), kSemiPeqMaxWords) && word_num <= myers_semi_max_plain_words()) {
-            switch (pick_semi_planes_nw(word_num)) {
-#define BGSA_SEMI_PLANES_CASE(N)                                                                \
-    case N:                                                                                     \
-        return launch_planes<N, true>(d_content, d_peq, d_results, ref_len, read_len, read_count, \
-                                      ref_start, ref_end, word_num, d_workspace, stream);
-                BGSA_SEMI_PLANES_CASE(26) BGSA_SEMI_PLANES_CASE(28) BGSA_SEMI_PLANES_CASE(30) BGSA_SEMI_PLANES_CASE(32)
-#undef BGSA_SEMI_PLANES_CASE
-            default: break;
-            }
-        }
-        if (word_num <= std::min(myers_peq_max_words(), kSemiPeqMaxWords)) {
-            switch (pick_peq_nw(word_num)) {
-#define BGSA_SEMI_CASE(N)                                                                       \
-    case N:                                                                                     \
-        return launch_semi_asm<N>(d_content, d_peq, d_results, ref_len, read_len, read_count,   \
-                                  ref_start, ref_end, word_num, d_workspace, stream);
-                BGSA_SEMI_CASE(1) BGSA_SEMI_CASE(2) BGSA_SEMI_CASE(3) BGSA_SEMI_CASE(4) BGSA_SEMI_CASE(5)
-                BGSA_SEMI_CASE(6) BGSA_SEMI_CASE(7) BGSA_SEMI_CASE(8) BGSA_SEMI_CASE(10) BGSA_SEMI_CASE(12)
-                BGSA_SEMI_CASE(14) BGSA_SEMI_CASE(16) BGSA_SEMI_CASE(18) BGSA_SEMI_CASE(20) BGSA_SEMI_CASE(22)
-                BGSA_SEMI_CASE(24) BGSA_SEMI_CASE(25) BGSA_SEMI_CASE(26) BGSA_SEMI_CASE(28) BGSA_SEMI_CASE(30) BGSA_SEMI_CASE(32)
-#undef BGSA_SEMI_CASE
-            default: break;
-            }
-        }
-        int n_blocks = 0;
-        switch (pick_peq_block_nw(word_num, &n_blocks)) {
-#define BGSA_BLOCK_CASE(N)                                                                       \
-    case N:                                                                                      \
-        return launch_blocked<N, true, true>(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, \
-                                             ref_end, word_num, n_blocks, d_workspace, stream);
-            BGSA_BLOCK_CASE(12) BGSA_BLOCK_CASE(14) BGSA_BLOCK_CASE(16) BGSA_BLOCK_CASE(18) BGSA_BLOCK_CASE(20)
-#undef BGSA_BLOCK_CASE
-        default: break;
-        }
-    }
-#if !BGSA_AB_KERNELS
-    if (myers_impl() == 1) return ab_knob_refused("BGSA_MYERS_IMPL=c");
-    if (semi_global) {
-        set_error_text("myers: no semi-global kernel for this word count");
-        return BGSA_HIP_EUNSUPPORTED;
-    }
-#else
-    if (semi_global) {  // BGSA_MYERS_IMPL=c: the compiler-scheduled kernel, subjects up to 1024 bp (A/B reference)
-        switch (pick_nw(word_num)) {
-#define BGSA_CASE(N)                                                                            \
-    case N:                                                                                     \
-        return launch_nw<N, 1, true>(d_content, d_peq, d_results, ref_len, read_len, read_count, \
-                                     ref_start, ref_end, word_num, stream);
-            BGSA_CASE(1) BGSA_CASE(2) BGSA_CASE(3) BGSA_CASE(4) BGSA_CASE(5) BGSA_CASE(6)
-            BGSA_CASE(7) BGSA_CASE(8) BGSA_CASE(10) BGSA_CASE(12) BGSA_CASE(14) BGSA_CASE(16)
-            BGSA_CASE(20) BGSA_CASE(24) BGSA_CASE(28) BGSA_CASE(32)
-#undef BGSA_CASE
-        default:
+    if (a.ref_end <= a.ref_start || a.read_count == 0) return BGSA_HIP_OK;
+    const MyersChoice c = myers_select(a.word_num, semi_global, a.read_count);
+    if (c.refused) return ab_knob_refused(c.refused);
+    switch (c.family) {
+    case MyersFamily::kAsm:
+        return PeqWidths::dispatch(c.nw, "myers_global_asm_kernel", [&](auto nw) { return launch_asm<decltype(nw)::value, 1>(a); });
+    case MyersFamily::kAsmPairs:
+        return PairWidths::dispatch(c.nw, "myers_global_asm_kernel (pairs)", [&](auto nw) { return launch_asm<decltype(nw)::value, 2>(a); });
+    case MyersFamily::kSemiAsm:
+        return PeqWidths::dispatch(c.nw, "myers_semi_asm_kernel", [&](auto nw) { return launch_semi_asm<decltype(nw)::value>(a); });
+    case MyersFamily::kPlanes:
+        return Join<AbOnly<PlanesAbWidths>, PlanesWidths>::dispatch(c.nw, "myers_global_planes_kernel",
+                                                                   [&](auto nw) { return launch_planes<decltype(nw)::value>(a); });
+    case MyersFamily::kSemiPlanes:
+        return SemiPlanesWidths::dispatch(c.nw, "myers_semi_planes_kernel", [&](auto nw) { return launch_planes<decltype(nw)::value, true>(a); });
+    case MyersFamily::kBlockedPeq:
+        return PeqBlockWidths::dispatch(c.nw, "myers_blocked_kernel (Peq planes)", [&](auto nw) {
+            return c.semi ? launch_blocked<decltype(nw)::value, true, true>(a, c.n_blocks) : launch_blocked<decltype(nw)::value, true>(a, c.n_blocks);
+        });
+    case MyersFamily::kBlockedPlanes:
+        return AbOnly<PlaneBlockWidths>::dispatch(c.nw, "myers_blocked_kernel (code planes)",
+                                                  [&](auto nw) { return launch_blocked<decltype(nw)::value>(a, c.n_blocks); });
+#if BGSA_AB_KERNELS   // (the default flavour was refused above)
+    case MyersFamily::kCompiler:
+        if (c.nw < 0) {
             set_error_text("myers: the compiler-scheduled semi-global kernel (BGSA_MYERS_IMPL=c) covers subjects up to 1024 bp");
             return BGSA_HIP_EUNSUPPORTED;
         }
-    }
-    if (word_num > myers_max_plain_words() && myers_impl() == 1)  // A/B: the state-in-memory C++ kernel
-        return launch_long(BGSA_ALGO_MYERS, d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start,
-                           ref_end, word_num, d_workspace, stream);
+        return CompilerWidths::dispatch(c.nw, "myers_global_kernel", [&](auto nw) {
+            return c.semi ? launch_nw<decltype(nw)::value, 1, true>(a) : launch_nw<decltype(nw)::value, 1>(a);
+        });
+    case MyersFamily::kStateInMemory: return launch_long(BGSA_ALGO_MYERS, a);
 #endif
-    if (word_num > myers_max_plain_words() && peq_blocks()) {
-        int n_blocks = 0;
-        switch (pick_peq_block_nw(word_num, &n_blocks)) {
-#define BGSA_BLOCK_CASE(N)                                                                       \
-    case N:                                                                                      \
-        return launch_blocked<N, true>(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, \
-                                       ref_end, word_num, n_blocks, d_workspace, stream);
-            BGSA_BLOCK_CASE(12) BGSA_BLOCK_CASE(14) BGSA_BLOCK_CASE(16) BGSA_BLOCK_CASE(18) BGSA_BLOCK_CASE(20)
-#undef BGSA_BLOCK_CASE
-        default: break;
-        }
+    default: break;
     }
-#if !BGSA_AB_KERNELS
-    if (word_num > myers_max_plain_words()) return ab_knob_refused("BGSA_MYERS_BLOCK_FORM=planes");
-#else
-    if (word_num > myers_max_plain_words()) {
-        int n_blocks = 0;
-        switch (pick_block_nw(word_num, &n_blocks)) {
-#define BGSA_BLOCK_CASE(N)                                                                       \
-    case N:                                                                                      \
-        return launch_blocked<N>(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, \
-                                 ref_end, word_num, n_blocks, d_workspace, stream);
-            BGSA_BLOCK_CASE(12) BGSA_BLOCK_CASE(14) BGSA_BLOCK_CASE(16) BGSA_BLOCK_CASE(18) BGSA_BLOCK_CASE(20)
-            BGSA_BLOCK_CASE(22) BGSA_BLOCK_CASE(24) BGSA_BLOCK_CASE(26) BGSA_BLOCK_CASE(28)
-#undef BGSA_BLOCK_CASE
-        default: break;
-        }
-    }
-#endif
-    if (myers_impl() == 0) {
-        if (word_num <= kPairMaxWords && pair_groups() == 2 && read_count >= 2 * kLanes) {   // short subjects: two groups per wave
-            if (word_num == 1)
-                return launch_asm<1, 2>(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, ref_end, word_num,
-                                        d_workspace, stream);
-            return launch_asm<2, 2>(d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, ref_end, word_num,
-                                    d_workspace, stream);
-        }
-        switch (pick_peq_nw(word_num)) {
-#define BGSA_ASM_CASE(N)                                                                        \
-    case N:                                                                                     \
-        return launch_asm<N, 1>(d_content, d_peq, d_results, ref_len, read_len, read_count,     \
-                                ref_start, ref_end, word_num, d_workspace, stream);
-            BGSA_ASM_CASE(1) BGSA_ASM_CASE(2) BGSA_ASM_CASE(3) BGSA_ASM_CASE(4) BGSA_ASM_CASE(5)
-            BGSA_ASM_CASE(6) BGSA_ASM_CASE(7) BGSA_ASM_CASE(8) BGSA_ASM_CASE(10) BGSA_ASM_CASE(12)
-            BGSA_ASM_CASE(14) BGSA_ASM_CASE(16) BGSA_ASM_CASE(18) BGSA_ASM_CASE(20) BGSA_ASM_CASE(22)
-            BGSA_ASM_CASE(24) BGSA_ASM_CASE(25) BGSA_ASM_CASE(26) BGSA_ASM_CASE(28) BGSA_ASM_CASE(30) BGSA_ASM_CASE(32)
-#undef BGSA_ASM_CASE
-        default: break;
-        }
-        switch (pick_planes_nw(word_num)) {
-#define BGSA_PLANES_CASE(N)                                                                     \
-    case N:                                                                                     \
-        return launch_planes<N>(d_content, d_peq, d_results, ref_len, read_len, read_count,     \
-                                ref_start, ref_end, word_num, d_workspace, stream);
-#if BGSA_AB_KERNELS   // the code planes below 29 words: only under BGSA_MYERS_PEQ_MAX_WORDS (resident Peq planes measured faster)
-            BGSA_PLANES_CASE(10) BGSA_PLANES_CASE(12) BGSA_PLANES_CASE(14) BGSA_PLANES_CASE(16)
-            BGSA_PLANES_CASE(18) BGSA_PLANES_CASE(20) BGSA_PLANES_CASE(22) BGSA_PLANES_CASE(24)
-            BGSA_PLANES_CASE(26) BGSA_PLANES_CASE(28)
-#endif
-            BGSA_PLANES_CASE(30) BGSA_PLANES_CASE(32)
-#undef BGSA_PLANES_CASE
-        default: break;
-        }
-    }
-#if !BGSA_AB_KERNELS
-    if (myers_impl() == 1) return ab_knob_refused("BGSA_MYERS_IMPL=c");
-    if (myers_peq_max_words() != kPeqMaxWords) return ab_knob_refused("BGSA_MYERS_PEQ_MAX_WORDS");
     set_error_text("myers: no kernel for this word count");
     return BGSA_HIP_EUNSUPPORTED;
-#else
-    switch (pick_nw(word_num)) {
-#define BGSA_CASE(N)                                                                            \
-    case N:                                                                                     \
-        return launch_nw<N, 1>(d_content, d_peq, d_results, ref_len, read_len, read_count,         \
-                            ref_start, ref_end, word_num, stream);
-        BGSA_CASE(1) BGSA_CASE(2) BGSA_CASE(3) BGSA_CASE(4) BGSA_CASE(5) BGSA_CASE(6)
-        BGSA_CASE(7) BGSA_CASE(8) BGSA_CASE(10) BGSA_CASE(12) BGSA_CASE(14) BGSA_CASE(16)
-        BGSA_CASE(20) BGSA_CASE(24) BGSA_CASE(28) BGSA_CASE(32)
-#undef BGSA_CASE
-    default:
-        set_error_text("myers: no kernel for this word count");
-        return BGSA_HIP_EUNSUPPORTED;
-    }
-#endif
 }
 
 }  // namespace bgsa

@@ -1404,6 +1404,42 @@ def test_default_library_refuses_knobs_for_kernels_it_does_not_carry(env, algo, 
     assert p.returncode == 0 and "refused:" in p.stdout and "A/B flavour" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
 
 
+# ---- every width the Myers dispatch tables list (myers_global.hip: PeqWidths, SemiPlanesWidths, PeqBlockWidths ...) is launched at
+# least once, at the smallest shape that reaches it ----
+def _score_every_listed_width(oracle):
+    """3 queries of 40 bp against 128 subjects of 32 w - 5 bp: every register-resident word count, and 33 / 41 / 57 / 125 words for
+    the column blocks of 18, 14, 20 and 18 words; global and semi-global, against the edit-distance DP.  w <= 2 also with 64
+    subjects: one group per wave, myers_global_asm_kernel<NW, 1> where two groups or more run <NW, 2>."""
+    q = oracle.gen_reads(0x51D7, 3, 40)
+    for w, ns in [(w, 128) for w in list(range(1, 33)) + [33, 41, 57, 125]] + [(1, 64), (2, 64)]:
+        slen = 32 * w - 5
+        s = oracle.gen_reads(0x51D8 + w, ns, slen)
+        if slen >= 40:
+            s[:6, :40] = oracle.mutate(q[np.arange(6) % 3], np.arange(6), 0x51D9 + w)
+        assert np.array_equal(B.align_all_pairs(q, s, algo=B.ALGO_MYERS), oracle.dp_edit(q, s)), ("global", w, ns)
+        assert np.array_equal(B.align_all_pairs(q, s, algo=B.ALGO_MYERS, semi_global=True), oracle.dp_edit_semiglobal(q, s)), ("semi-global", w, ns)
+    assert B.lib().bgsa_hip_stream_faults(1) == 0, B.lib().bgsa_hip_last_error().decode()
+
+
+_WIDTHS_CHILD = ("import sys; sys.path[:0] = [sys.argv[1], sys.argv[1] + '/tests']\n"
+                 "import oracle, test_gpu_parity as T\n"
+                 "oracle.lib(); T._score_every_listed_width(oracle); print('widths ok')\n")
+
+
+def test_every_listed_myers_width_is_launched(oracle):
+    """... on the static grids here, and in a child with BGSA_DYNAMIC_MIN_TASKS=1, where every launch that has a counter
+    instantiation takes it (the grid helper's persistent branch)."""
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    _score_every_listed_width(oracle)
+    root = Path(B.__file__).resolve().parent.parent
+    p = subprocess.run([sys.executable, "-c", _WIDTHS_CHILD, str(root)], env=dict(os.environ, BGSA_DYNAMIC_MIN_TASKS="1"),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "widths ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
+
+
 def test_score_sets_of_the_ab_flavour(oracle):
     """The default flavour compiles five BitPAl score sets; the two others of round 3 (1/-3/-2, 5/-4/-10) ship in the A/B flavour.  Their global and semi-global suites run here against that library, in a child pytest."""
     import os
