@@ -93,6 +93,11 @@ def lib() -> ctypes.CDLL:
     L.bgsa_hip_hits_workspace_bytes.restype = sz
     L.bgsa_hip_top_hits_dev.argtypes = [vp, i32, i32, i64, i64, i64, i32, i32, i32, vp, vp, vp, sz, vp]
     L.bgsa_hip_threshold_hits_dev.argtypes = [vp, i32, i32, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, sz, vp]
+    L.bgsa_hip_align_pairs_workspace_bytes.argtypes = [i32, i32, i64]
+    L.bgsa_hip_align_pairs_workspace_bytes.restype = sz
+    L.bgsa_hip_align_pairs_min_workspace_bytes.argtypes = [i32, i32]
+    L.bgsa_hip_align_pairs_min_workspace_bytes.restype = sz
+    L.bgsa_hip_myers_align_pairs_dev.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, i32, vp, sz, vp]
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -358,6 +363,69 @@ class DeviceAligner:
                                                     self.d_hit_work.data_ptr(), self.d_hit_work.numel(), self._stream()), "threshold_hits_dev")
         return counts, scores, subjects
 
+    # ---- edit scripts of selected pairs (bgsa_hip_myers_align_pairs_dev) ----------------------------------------------
+    def align_pairs(self, pair_queries, pair_subjects, cigar_cap=None, subject_base: int = 0, into=None, workspace_bytes=None):
+        """The canonical edit script of every pair (pair_queries[p], pair_subjects[p]) against the resident bucket:
+        (distance[n] int32, n_ops[n] int32, cigar[n, cap] uint32 runs `length << 4 | BAM op` held as int32) device tensors.
+        Subject ids are as the hit lists report them (column = id - subject_base); a pair whose subject is -1 or belongs to
+        another bucket is left as it was — fresh outputs hold distance -1, n_ops 0 and cigar 0 there.  into= the triple of
+        an earlier call, for walking buckets.  cigar_cap=None: qlen + slen, which can never overflow; n_ops is the true
+        number of runs even beyond the cap.  workspace_bytes: None = what all pairs need in one pass (at most 1 GiB), a
+        size from bgsa_hip_align_pairs_min_workspace_bytes() up = that much (more chunks), 0 = the library's own scratch.
+        Myers global only: any other aligner raises, and so does (0, 1, 1) +distance — the alignment is the same."""
+        torch = self.torch
+        if self.algo != ALGO_MYERS or self.semi_global or self.scores == (0, 1, 1):
+            raise BgsaHipError("align_pairs: rc=-2: only Myers unit-cost global alignment is traced back (no semi-global mode, no "
+                               "BitPAl score sets, no banded filter; +distance aligns the same as -distance: use that aligner)")
+        pq = torch.as_tensor(pair_queries).to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        ps = torch.as_tensor(pair_subjects).to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+        if pq.numel() != ps.numel():
+            raise BgsaHipError("align_pairs: pair_queries and pair_subjects differ in length")
+        n = pq.numel()
+        cap = self.qlen + self.slen if cigar_cap is None else int(cigar_cap)
+        if cap < 1:
+            raise BgsaHipError("align_pairs: rc=-1: cigar_cap is not positive")
+        shapes = [((n,), torch.int32), ((n,), torch.int32), ((n, cap), torch.int32)]
+        if into is None:
+            distance, n_ops, cigar = (torch.full(shape, fill, dtype=dtype, device=self.device) for (shape, dtype), fill in zip(shapes, (-1, 0, 0)))
+        else:
+            (distance, n_ops, cigar), _ = self._hit_lists(into, shapes, "align_pairs")
+        if n == 0:
+            return distance, n_ops, cigar
+        if workspace_bytes is None:
+            workspace_bytes = int(lib().bgsa_hip_align_pairs_workspace_bytes(self.qlen, self.slen, n))
+        work, work_bytes = None, 0
+        if workspace_bytes:
+            if getattr(self, "d_align_work", None) is None or self.d_align_work.numel() < workspace_bytes:
+                self.d_align_work = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
+            work, work_bytes = self.d_align_work.data_ptr(), int(workspace_bytes)
+        check(lib().bgsa_hip_myers_align_pairs_dev(self.d_content.data_ptr(), self.d_peq.data_ptr(), self.qlen, self.slen, self.ns, self.wn,
+                                                   pq.data_ptr(), ps.data_ptr(), n, self.nq, int(subject_base), distance.data_ptr(),
+                                                   n_ops.data_ptr(), cigar.data_ptr(), cap, work, work_bytes, self._stream()),
+              "myers_align_pairs_dev")
+        return distance, n_ops, cigar
+
+    def align_hits(self, hit_subjects, cigar_cap=None, subject_base: int = 0, into=None, workspace_bytes=None):
+        """align_pairs for the subjects[nq, K] tensor of top_hits / threshold_hits: row q holds subjects of query q (the
+        query index is built on the device).  Returns (distance[nq, K], n_ops[nq, K], cigar[nq, K, cap]); unused slots
+        (subject -1) keep distance -1, n_ops 0.  into= the triple of an earlier call, for walking buckets."""
+        torch = self.torch
+        hs = torch.as_tensor(hit_subjects).to(device=self.device, dtype=torch.int64)
+        if hs.dim() != 2 or hs.shape[0] != self.nq:
+            raise BgsaHipError(f"align_hits: hit_subjects must be [nq = {self.nq}, K]")
+        nq, k = hs.shape
+        pq = torch.arange(nq, dtype=torch.int32, device=self.device).repeat_interleave(k)
+        if into is not None:
+            into = list(into)
+            if len(into) != 3 or any(not t.is_contiguous() for t in into) or tuple(into[0].shape) != (nq, k) or \
+                    tuple(into[1].shape) != (nq, k) or into[2].dim() != 3 or tuple(into[2].shape[:2]) != (nq, k):
+                raise BgsaHipError(f"align_hits: into= needs contiguous tensors of shape ({nq}, {k}), ({nq}, {k}), ({nq}, {k}, cap)")
+            if cigar_cap is None:
+                cigar_cap = into[2].shape[2]
+            into = (into[0].view(-1), into[1].view(-1), into[2].view(nq * k, -1))
+        distance, n_ops, cigar = self.align_pairs(pq, hs.contiguous().view(-1), cigar_cap, subject_base, into, workspace_bytes)
+        return distance.view(nq, k), n_ops.view(nq, k), cigar.view(nq, k, -1)
+
     def check_faults(self) -> None:
         """Synchronises and raises if a kernel reported a stream fault (bgsa_hip_stream_faults)."""
         self.torch.cuda.synchronize(self.device)
@@ -391,6 +459,44 @@ def align_all_pairs(queries: np.ndarray, subjects: np.ndarray, algo: int = ALGO_
     out = a.score()
     a.check_faults()
     return out[:, : a.ns_real].cpu().numpy()
+
+
+CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}   # the BAM op codes bgsa_hip_myers_align_pairs_dev writes
+
+
+def cigar_strings(n_ops, cigar) -> list[str]:
+    """Host helper: the runs of align_pairs / align_hits as text, e.g. "97=1X30=2D22=" — one string per pair in row-major
+    order of the leading dimensions ("" for a pair with no runs: an unused slot).  Raises if a row overflowed its cap."""
+    def host(x):
+        return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+    counts = host(n_ops).reshape(-1)
+    runs = host(cigar)
+    runs = np.ascontiguousarray(runs).view(np.uint32).reshape(counts.size, -1) if counts.size else np.zeros((0, 1), np.uint32)
+    cap = runs.shape[1]
+    out = []
+    for p, n in enumerate(counts.tolist()):
+        if n > cap:
+            raise BgsaHipError(f"cigar_strings: pair {p} has {n} runs, its row holds {cap} (raise cigar_cap)")
+        out.append("".join(f"{w >> 4}{CIGAR_OPS[w & 15]}" for w in runs[p, :n].tolist()))
+    return out
+
+
+def align_top_alignments(queries: np.ndarray, subjects: np.ndarray, k_best: int, device: str = "cuda:0", block_rows: int = 1000,
+                         cigar_cap=None):
+    """Convenience beside align_top_hits (Myers global): the k_best best subjects per query AND their alignments, as
+    (scores[nq, K] int32, subjects[nq, K] int64, cigars) with cigars[q][r] the edit script of query q against its r-th hit
+    as a string, or None for an unused slot.  Selected and traced back on the device."""
+    a = DeviceAligner(ALGO_MYERS, device)
+    a.set_queries(queries)
+    a.set_subjects(subjects)
+    hit_scores, hit_subjects = a.top_hits(k_best, block_rows=block_rows)
+    _, n_ops, cigar = a.align_hits(hit_subjects, cigar_cap=cigar_cap)
+    a.check_faults()
+    subj = hit_subjects.cpu().numpy()
+    text = cigar_strings(n_ops, cigar)
+    k = subj.shape[1]
+    cigars = [[text[q * k + r] if subj[q, r] >= 0 else None for r in range(k)] for q in range(subj.shape[0])]
+    return hit_scores.cpu().numpy(), subj, cigars
 
 
 def align_top_hits(queries: np.ndarray, subjects: np.ndarray, k_best: int, algo: int = ALGO_MYERS, k: int = 0,

@@ -1,0 +1,316 @@
+// align_pairs.hip — edit scripts (CIGAR) for a list of (query, subject) pairs, traced back on the GPU
+// (include/bgsa_hip.h "alignment of selected pairs").
+//
+// Myers unit-cost GLOBAL alignment, subjects of up to 32 words.  The row kernels score one query against 64 subjects
+// per wave with a wave-uniform query character; here a lane owns one PAIR, so every lane has its own query character
+// and its own subject, and the threaded-code row loops do not apply.  Two kernels per chunk of pairs:
+//
+//   forward    the 8-operation Myers row in compiler-scheduled C++, the subject's five Peq planes held in
+//              VGPRs and selected per lane by the lane's query class.  After every row the lane stores, per word, the
+//              two bit vectors the traceback needs (below) and at the end the distance.
+//   traceback  walks back from (m, n), one history bit pair per step, writes one op byte per step backwards into the
+//              pair's scratch and then run-length encodes forwards into the cigar row.
+//
+// History.  With D0 = [D[i][j] == D[i-1][j-1]], Eq = [q_i matches s_j] and Hp = [D[i][j] - D[i-1][j] == +1] of the row
+// recurrence, the canonical step at a cell (i, j > 0) is: diagonal iff Eq | ~D0 (a mismatch is taken exactly when the
+// diagonal delta is 1), else up iff Hp, else left.  Four outcomes are two bits, so a row keeps two vectors per word:
+//     A = Eq | ~D0           the step is diagonal
+//     B = Eq | (D0 & Hp)     diagonal: '=' (1) or 'X' (0); otherwise: up 'I' (1) or left 'D' (0)
+// 8 * word_num bytes per row and pair, laid out [chunk wave][row][vector][word][lane] uint32: every wave store is one
+// coalesced 256-byte row, and a traceback step is two loads and two bit tests.
+#include "bgsa_common.h"
+
+namespace bgsa {
+
+namespace {
+
+constexpr int kOpI = 1, kOpD = 2, kOpEq = 7, kOpX = 8;   // BAM op codes
+constexpr int kRowBlock = 8;                             // query characters fetched ahead of their rows
+constexpr int64_t kMaxChunkWaves = 1 << 22;              // waves of one launch, whatever the workspace would hold
+
+// one instantiation per word count: the row loop is straight-line code over exactly the subject's words
+using PairWidths = Widths<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32>;
+
+struct PairArgs {
+    const char *content;
+    const uint32_t *peq;
+    int ref_len, read_len;
+    int64_t read_count;
+    int word_num;
+    const int32_t *pair_query;
+    const int64_t *pair_subject;
+    int64_t n_pairs;
+    int n_queries;
+    int64_t subject_base;
+    int32_t *distance, *n_ops;
+    uint32_t *cigar;
+    int cigar_cap;
+    unsigned char *workspace;
+    size_t wave_bytes, hist_bytes;   // one wave's slice, and the history at its head (the op bytes follow)
+    unsigned *fault_word;
+};
+
+inline size_t pair_hist_bytes(int ref_len, int read_len)
+{
+    return static_cast<size_t>(ref_len) * 2 * ((read_len + 31) / 32) * kLanes * sizeof(uint32_t);
+}
+inline size_t pair_wave_bytes(int ref_len, int read_len)
+{
+    const size_t ops = (static_cast<size_t>(ref_len) + static_cast<size_t>(read_len)) * kLanes;   // one byte per step and lane
+    return (pair_hist_bytes(ref_len, read_len) + ops + 255) & ~static_cast<size_t>(255);
+}
+
+// Whether this call owns pair p, and its query and column.  A pair of another bucket (or the unused slot -1) is not
+// owned; an owned pair whose query index is out of range is skipped too and — in the forward kernel — reported.
+__device__ __forceinline__ bool owned_pair(const PairArgs &a, int64_t p, bool report, int *q, int64_t *col)
+{
+    if (p >= a.n_pairs) return false;
+    const int64_t s = a.pair_subject[p];
+    if (s < a.subject_base || static_cast<unsigned long long>(s) - static_cast<unsigned long long>(a.subject_base) >=
+                                  static_cast<unsigned long long>(a.read_count))
+        return false;
+    *col = s - a.subject_base;
+    *q = a.pair_query[p];
+    if (*q < 0 || *q >= a.n_queries) {
+        if (report) atomicOr(a.fault_word, static_cast<unsigned>(BGSA_HIP_FAULT_PAIR));
+        return false;
+    }
+    return true;
+}
+
+template <int NW>
+__global__ __launch_bounds__(kLanes) void align_pairs_forward_kernel(PairArgs a, int64_t first)
+{
+    const int lane = threadIdx.x;
+    const int64_t p = first + static_cast<int64_t>(blockIdx.x) * kLanes + lane;
+    int q = 0;
+    int64_t col = 0;
+    if (!owned_pair(a, p, true, &q, &col)) return;
+    constexpr int wn = NW;   // == a.word_num: the launcher dispatches on it
+    const int m = a.ref_len;
+
+    // the subject's Peq planes: [group][class][word][lane]
+    const uint32_t *g = a.peq + static_cast<size_t>(col >> 6) * kChars * wn * kLanes + (col & (kLanes - 1));
+    uint32_t peq[kChars][NW], pv[NW], mv[NW];
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+#pragma unroll
+        for (int c = 0; c < kChars; c++) peq[c][w] = g[(static_cast<size_t>(c) * wn + w) * kLanes];
+        pv[w] = ~0u;
+        mv[w] = 0u;
+    }
+
+    const unsigned char *row = reinterpret_cast<const unsigned char *>(a.content) + static_cast<size_t>(q) * (m + 1);
+    uint32_t *h = reinterpret_cast<uint32_t *>(a.workspace + static_cast<size_t>(blockIdx.x) * a.wave_bytes) + lane;
+    const size_t row_words = static_cast<size_t>(2) * wn * kLanes;
+    for (int i0 = 0; i0 < m; i0 += kRowBlock) {
+        // the block's characters first, four bits each: a load waits for every older store of the wave, so one wait per
+        // block instead of one per row
+        uint32_t codes = 0;
+#pragma unroll
+        for (int r = 0; r < kRowBlock; r++) {
+            uint32_t c = i0 + r < m ? row[i0 + r] : 0u;
+            if (c > 4) c = 0;   // as the packed streams: out-of-alphabet bytes behave as 'A'
+            codes |= c << (4 * r);
+        }
+        const int rows = m - i0 < kRowBlock ? m - i0 : kRowBlock;
+#pragma unroll 1
+        for (int r = 0; r < rows; r++) {
+            const uint32_t c = (codes >> (4 * r)) & 15u;
+            // the lane's class as five all-or-nothing masks: the Eq word is a branch-free and/or over the planes
+            const uint32_t k1 = 0u - (c == 1), k2 = 0u - (c == 2), k3 = 0u - (c == 3), k4 = 0u - (c == 4), k0 = ~(k1 | k2 | k3 | k4);
+            uint32_t carry = 0, hp_in = 1, hn_in = 0;
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+                const uint32_t e = (peq[0][w] & k0) | (peq[1][w] & k1) | (peq[2][w] & k2) | (peq[3][w] & k3) | (peq[4][w] & k4);
+                const uint32_t x = pv[w];
+                const unsigned long long s = static_cast<unsigned long long>(x & e) + x + carry;
+                carry = static_cast<uint32_t>(s >> 32);
+                const uint32_t d0 = (static_cast<uint32_t>(s) ^ x) | e | mv[w];
+                const uint32_t hp = ~(d0 | x) | mv[w];
+                const uint32_t hn = d0 & x;
+                const uint32_t hps = (hp << 1) | hp_in;
+                const uint32_t hns = (hn << 1) | hn_in;
+                hp_in = hp >> 31;
+                hn_in = hn >> 31;
+                pv[w] = ~(d0 | hps) | hns;
+                mv[w] = d0 & hps;
+                h[static_cast<size_t>(w) * kLanes] = e | ~d0;
+                h[static_cast<size_t>(wn + w) * kLanes] = e | (d0 & hp);
+            }
+            h += row_words;
+        }
+    }
+
+    int score = m;
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+        const int rem = a.read_len - 32 * w;
+        const uint32_t mask = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+        score += __popc(pv[w] & mask) - __popc(mv[w] & mask);
+    }
+    a.distance[p] = score;
+}
+
+__global__ __launch_bounds__(kLanes) void align_pairs_traceback_kernel(PairArgs a, int64_t first)
+{
+    const int lane = threadIdx.x;
+    const int64_t p = first + static_cast<int64_t>(blockIdx.x) * kLanes + lane;
+    int q = 0;
+    int64_t col = 0;
+    if (!owned_pair(a, p, false, &q, &col)) return;
+    const int wn = a.word_num;
+    unsigned char *slice = a.workspace + static_cast<size_t>(blockIdx.x) * a.wave_bytes;
+    const uint32_t *hist = reinterpret_cast<const uint32_t *>(slice) + lane;
+    unsigned char *ops = slice + a.hist_bytes + lane;   // [step][lane]
+    const size_t row_words = static_cast<size_t>(2) * wn * kLanes;
+
+    int i = a.ref_len, j = a.read_len;
+    size_t steps = 0;
+    while (i > 0 || j > 0) {
+        int op;
+        if (i == 0) {
+            op = kOpD;
+            j--;
+        } else if (j == 0) {
+            op = kOpI;
+            i--;
+        } else {
+            const uint32_t *cell = hist + static_cast<size_t>(i - 1) * row_words + static_cast<size_t>((j - 1) >> 5) * kLanes;
+            const uint32_t diag = (cell[0] >> ((j - 1) & 31)) & 1u;
+            const uint32_t which = (cell[static_cast<size_t>(wn) * kLanes] >> ((j - 1) & 31)) & 1u;
+            if (diag) {
+                op = which ? kOpEq : kOpX;
+                i--;
+                j--;
+            } else if (which) {
+                op = kOpI;
+                i--;
+            } else {
+                op = kOpD;
+                j--;
+            }
+        }
+        ops[steps * kLanes] = static_cast<unsigned char>(op);
+        steps++;
+    }
+
+    // run-length encode forwards: the last step written is the first column
+    uint32_t *out = a.cigar + static_cast<size_t>(p) * a.cigar_cap;
+    int n_runs = 0;
+    uint32_t run_op = 0, run_len = 0;
+    for (size_t t = steps; t-- > 0;) {
+        const uint32_t op = ops[t * kLanes];
+        if (op == run_op) {
+            run_len++;
+            continue;
+        }
+        if (run_len) {
+            if (n_runs < a.cigar_cap) out[n_runs] = (run_len << 4) | run_op;
+            n_runs++;
+        }
+        run_op = op;
+        run_len = 1;
+    }
+    if (run_len) {
+        if (n_runs < a.cigar_cap) out[n_runs] = (run_len << 4) | run_op;
+        n_runs++;
+    }
+    a.n_ops[p] = n_runs;
+}
+
+struct PairRun {
+    PairArgs args;
+    size_t workspace_bytes;
+    hipStream_t stream;
+};
+
+// The pair list in chunks of as many whole waves as the workspace holds, one after the other on the stream.
+int run_pairs(void *workspace, void *ctx)
+{
+    const PairRun &r = *static_cast<const PairRun *>(ctx);
+    PairArgs a = r.args;
+    a.workspace = static_cast<unsigned char *>(workspace);
+    int64_t chunk_waves = static_cast<int64_t>(r.workspace_bytes / a.wave_bytes);
+    if (chunk_waves > kMaxChunkWaves) chunk_waves = kMaxChunkWaves;
+    for (int64_t first = 0; first < a.n_pairs; first += chunk_waves * kLanes) {
+        const int64_t left = (a.n_pairs - first + kLanes - 1) / kLanes;
+        const dim3 grid(static_cast<unsigned>(left < chunk_waves ? left : chunk_waves));
+        const int rc = PairWidths::dispatch(a.word_num, "myers_align_pairs", [&](auto width) {
+            hipLaunchKernelGGL((align_pairs_forward_kernel<decltype(width)::value>), grid, dim3(kLanes), 0, r.stream, a, first);
+            BGSA_HIP_TRY(hipGetLastError());
+            return BGSA_HIP_OK;
+        });
+        if (rc) return rc;
+        hipLaunchKernelGGL(align_pairs_traceback_kernel, grid, dim3(kLanes), 0, r.stream, a, first);
+        BGSA_HIP_TRY(hipGetLastError());
+    }
+    return BGSA_HIP_OK;
+}
+
+int refuse(int rc, const char *why)
+{
+    char msg[200];
+    snprintf(msg, sizeof msg, "myers_align_pairs_dev: %s", why);
+    set_error_text(msg);
+    return rc;
+}
+
+}  // namespace
+
+}  // namespace bgsa
+
+using namespace bgsa;
+
+extern "C" {
+
+size_t bgsa_hip_align_pairs_min_workspace_bytes(int ref_len, int read_len)
+{
+    if (ref_len <= 0 || read_len <= 0) return 0;
+    return pair_wave_bytes(ref_len, read_len);
+}
+
+size_t bgsa_hip_align_pairs_workspace_bytes(int ref_len, int read_len, int64_t n_pairs)
+{
+    if (ref_len <= 0 || read_len <= 0 || n_pairs < 0) return 0;
+    const size_t per = pair_wave_bytes(ref_len, read_len);
+    const size_t cap = BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE;
+    const unsigned long long waves = n_pairs > 0 ? (static_cast<unsigned long long>(n_pairs) + kLanes - 1) / kLanes : 1;
+    const size_t want = waves > cap / per ? cap : static_cast<size_t>(waves) * per;   // min(all pairs in one pass, the cap)
+    return want > per ? want : per;                                                    // one wave always fits
+}
+
+int bgsa_hip_myers_align_pairs_dev(const char *d_content, const hip_read_t *d_peq, int ref_len, int read_len, int64_t read_count,
+                                   int word_num, const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs,
+                                   int n_queries, int64_t subject_base, int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar,
+                                   int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (!d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_distance || !d_n_ops || !d_cigar)
+        return refuse(BGSA_HIP_EINVAL, "a NULL pointer (only the workspace may be NULL)");
+    if (n_pairs < 0) return refuse(BGSA_HIP_EINVAL, "n_pairs is negative");
+    if (ref_len <= 0 || read_len <= 0 || n_queries <= 0 || cigar_cap <= 0)
+        return refuse(BGSA_HIP_EINVAL, "ref_len, read_len, n_queries and cigar_cap must be positive");
+    if (read_count <= 0 || read_count % HIP_V_NUM != 0) return refuse(BGSA_HIP_EINVAL, "read_count must be a positive multiple of 64");
+    if (word_num != bgsa_hip_word_num(BGSA_ALGO_MYERS, ref_len, read_len, 0))
+        return refuse(BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(BGSA_ALGO_MYERS, ...)");
+    if (word_num > kMaxWords) return refuse(BGSA_HIP_EUNSUPPORTED, "subjects beyond 1,024 bp (word_num > 32) are not covered");
+    const size_t per = pair_wave_bytes(ref_len, read_len);
+    if (d_workspace && workspace_bytes < per)
+        return refuse(BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_align_pairs_min_workspace_bytes()");
+    if (n_pairs == 0) return BGSA_HIP_OK;
+
+    PairRun r{};
+    r.args = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
+                      subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), nullptr};
+    r.stream = static_cast<hipStream_t>(stream);
+    r.args.fault_word = device_fault_word();
+    if (!r.args.fault_word) return BGSA_HIP_EHIP;
+    if (d_workspace) {
+        r.workspace_bytes = workspace_bytes;
+        return run_pairs(d_workspace, &r);
+    }
+    r.workspace_bytes = bgsa_hip_align_pairs_workspace_bytes(ref_len, read_len, n_pairs);
+    return with_own_scratch(r.stream, r.workspace_bytes, run_pairs, &r);
+}
+
+}  // extern "C"

@@ -337,6 +337,46 @@ int bgsa_hip_threshold_hits_dev(const void *d_results, int elem_bytes, int n_que
                                 int32_t *d_hit_scores, int64_t *d_hit_subjects,
                                 void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- alignment of selected pairs: the edit script (CIGAR) of every (query, subject) pair of a list, traced back on the GPU ----
+ * Myers unit-cost GLOBAL alignment only, subjects of 1..1024 bp (word_num <= 32; beyond: BGSA_HIP_EUNSUPPORTED), any query
+ * length.  Semi-global mode, BitPAl score sets, the banded filter and longer subjects are not offered.
+ * d_content = the mapped query rows (stride ref_len + 1) and d_peq = the Myers Peq blocks of the resident bucket of read_count
+ * subjects, exactly as bgsa_hip_cal_align_score_dev takes them.  The subject rows are not needed: whether query character i
+ * matches subject column j is bit j of the subject's Peq plane of class q_i, so the alignment agrees with the scores by
+ * construction ('N' and out-of-alphabet bytes included).
+ * Pair p = (d_pair_query[p], d_pair_subject[p]); subject ids are as the hit lists report them, column = id - subject_base.  A
+ * pair whose subject id is -1 (the unused top-K slot) or lies outside [subject_base, subject_base + read_count) — another
+ * bucket's — is left untouched in all three outputs, so a caller walking several buckets calls once per bucket on the same
+ * outputs and ends with every pair filled (read_count counts the padding reads of the last group: cut such buckets at
+ * multiples of 64, or keep padding ids out of the list as the hit lists do, so that no id belongs to two buckets).  A query index outside [0, n_queries) on an otherwise owned pair touches nothing
+ * either and raises BGSA_HIP_FAULT_PAIR in the sticky word bgsa_hip_stream_faults() reads (an argument check inside the kernel).
+ * Per owned pair: d_distance[p] = the edit distance D[m][n] (the negated score); d_n_ops[p] = the TRUE number of runs of the
+ * edit script even beyond cigar_cap; d_cigar[p * cigar_cap ...] = its first min(n_ops, cigar_cap) runs in query order from the
+ * first column, each `length << 4 | op` with the BAM op codes 7 '=' (query and subject character of the same class), 8 'X'
+ * (of different classes), 1 'I' (a query character only), 2 'D' (a subject character only); adjacent runs differ in op;
+ * slots behind the runs are left as they were.  cigar_cap = ref_len + read_len can never overflow.
+ * ONE CANONICAL SCRIPT: the path found walking back from (m, n); at a cell (i, j), i, j > 0: the diagonal if
+ * D[i-1][j-1] + [q_i != s_j] == D[i][j], otherwise the step up ('I') if D[i-1][j] + 1 == D[i][j], otherwise the step left
+ * ('D'); at i == 0 only 'D' and at j == 0 only 'I' remain.
+ * d_workspace = caller-owned device scratch, or NULL for the library's grow-only scratch per (device, stream) (not capture
+ * safe).  ..._min_workspace_bytes() = what 64 pairs need; ..._workspace_bytes() = what all n_pairs need in one pass, at most
+ * BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE unless 64 pairs alone need more.  ANY size from the minimum up is accepted: the call walks
+ * the list in chunks of as many whole waves as the workspace holds, launched on `stream` one after the other; the outputs do
+ * not depend on the chunking.  With a caller workspace the call only launches kernels: no allocation, no synchronisation,
+ * safe inside a stream capture (the device's fault word is allocated by the first launch of any kind on that device).
+ * BGSA_HIP_EINVAL: a NULL pointer (the workspace excepted), negative n_pairs, non-positive lengths / n_queries / cigar_cap,
+ * read_count not a positive multiple of 64, word_num other than bgsa_hip_word_num(BGSA_ALGO_MYERS, ...), a workspace below the
+ * minimum — all checked before the first HIP call.  n_pairs == 0 is BGSA_HIP_OK and launches nothing. */
+#define BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE ((size_t)1 << 30)
+size_t bgsa_hip_align_pairs_workspace_bytes(int ref_len, int read_len, int64_t n_pairs);
+size_t bgsa_hip_align_pairs_min_workspace_bytes(int ref_len, int read_len);
+int bgsa_hip_myers_align_pairs_dev(const char *d_content, const hip_read_t *d_peq,
+                                   int ref_len, int read_len, int64_t read_count, int word_num,
+                                   const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs,
+                                   int n_queries, int64_t subject_base,
+                                   int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
+                                   void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
@@ -348,6 +388,9 @@ int bgsa_hip_threshold_hits_dev(const void *d_results, int elem_bytes, int n_que
  * its first stream overwritten with REFILL tokens (1) or with a byte that is no token (2). */
 #define BGSA_HIP_FAULT_BUDGET 1
 #define BGSA_HIP_FAULT_CODE 2
+/* bgsa_hip_myers_align_pairs_dev: a pair this call owned named a query outside [0, n_queries); that pair was skipped (an
+ * argument check inside the kernel, not a damaged stream — the other pairs of the call are good). */
+#define BGSA_HIP_FAULT_PAIR 4
 int bgsa_hip_stream_faults(int clear);
 int bgsa_hip_debug_inject_stream_fault(int kind);
 
