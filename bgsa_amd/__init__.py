@@ -98,6 +98,7 @@ def lib() -> ctypes.CDLL:
     L.bgsa_hip_align_pairs_min_workspace_bytes.argtypes = [i32, i32]
     L.bgsa_hip_align_pairs_min_workspace_bytes.restype = sz
     L.bgsa_hip_myers_align_pairs_dev.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, i32, vp, sz, vp]
+    L.bgsa_hip_trace_pairs_dev.argtypes = [pp, vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, sz, vp]
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -426,6 +427,78 @@ class DeviceAligner:
         distance, n_ops, cigar = self.align_pairs(pq, hs.contiguous().view(-1), cigar_cap, subject_base, into, workspace_bytes)
         return distance.view(nq, k), n_ops.view(nq, k), cigar.view(nq, k, -1)
 
+    # ---- score, span and edit script of selected pairs, every aligner with an alignment (bgsa_hip_trace_pairs_dev) --------
+    def _trace_refusals(self, what: str) -> None:
+        # the C call's own answers (BGSA_HIP_EUNSUPPORTED), given before anything is allocated or launched
+        if self.algo == ALGO_BANDED:
+            raise BgsaHipError(f"{what}: rc=-2: the banded filter's pairs are not traced back")
+        if self.algo == ALGO_MYERS and self.scores == (0, 1, 1):
+            raise BgsaHipError(f"{what}: rc=-2: Myers +distance (0, 1, 1) aligns the same as -distance: use that aligner")
+
+    def trace_pairs(self, pair_queries, pair_subjects, cigar_cap=None, subject_base: int = 0, into=None, workspace_bytes=None):
+        """Score, aligned span and canonical edit script of every pair (pair_queries[p], pair_subjects[p]) against the
+        resident bucket, under THIS aligner's scoring (self.params()): BitPAl with any score set, global or semi-global,
+        Myers semi-global, and Myers global (there a cross-check of align_pairs from another kernel).  Returns
+        (score[n] int32 — as score() reports the pair —, span[n, 4] int32 = (q_begin, q_end, s_begin, s_end) half-open,
+        n_ops[n] int32, cigar[n, cap] runs `length << 4 | BAM op` held as int32) device tensors; the runs cover the aligned
+        span only.  Subject ids, subject_base, into= (the quadruple of an earlier call), cigar_cap and workspace_bytes are
+        as in align_pairs; fresh outputs hold score 0, span -1, n_ops 0 and cigar 0 for pairs nobody owns.  The banded
+        filter and Myers +distance raise (rc=-2) before any launch or allocation."""
+        torch = self.torch
+        self._trace_refusals("trace_pairs")
+        pq = torch.as_tensor(pair_queries).to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        ps = torch.as_tensor(pair_subjects).to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+        if pq.numel() != ps.numel():
+            raise BgsaHipError("trace_pairs: pair_queries and pair_subjects differ in length")
+        n = pq.numel()
+        cap = self.qlen + self.slen if cigar_cap is None else int(cigar_cap)
+        if cap < 1:
+            raise BgsaHipError("trace_pairs: rc=-1: cigar_cap is not positive")
+        shapes = [((n,), torch.int32), ((n, 4), torch.int32), ((n,), torch.int32), ((n, cap), torch.int32)]
+        if into is None:
+            score, span, n_ops, cigar = (torch.full(shape, fill, dtype=dtype, device=self.device)
+                                         for (shape, dtype), fill in zip(shapes, (0, -1, 0, 0)))
+        else:
+            (score, span, n_ops, cigar), _ = self._hit_lists(into, shapes, "trace_pairs")
+        if n == 0:
+            return score, span, n_ops, cigar
+        if workspace_bytes is None:
+            workspace_bytes = int(lib().bgsa_hip_align_pairs_workspace_bytes(self.qlen, self.slen, n))
+        work, work_bytes = None, 0
+        if workspace_bytes:
+            if getattr(self, "d_align_work", None) is None or self.d_align_work.numel() < workspace_bytes:
+                self.d_align_work = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
+            work, work_bytes = self.d_align_work.data_ptr(), int(workspace_bytes)
+        p = self.params()
+        check(lib().bgsa_hip_trace_pairs_dev(ctypes.byref(p), self.d_content.data_ptr(), self.d_peq.data_ptr(), self.qlen, self.slen,
+                                             self.ns, self.wn, pq.data_ptr(), ps.data_ptr(), n, self.nq, int(subject_base),
+                                             score.data_ptr(), span.data_ptr(), n_ops.data_ptr(), cigar.data_ptr(), cap, work, work_bytes,
+                                             self._stream()), "trace_pairs_dev")
+        return score, span, n_ops, cigar
+
+    def trace_hits(self, hit_subjects, cigar_cap=None, subject_base: int = 0, into=None, workspace_bytes=None):
+        """trace_pairs for the subjects[nq, K] tensor of top_hits / threshold_hits: row q holds subjects of query q.  Returns
+        (score[nq, K], span[nq, K, 4], n_ops[nq, K], cigar[nq, K, cap]); unused slots (subject -1) keep score 0, span -1,
+        n_ops 0.  into= the quadruple of an earlier call, for walking buckets."""
+        torch = self.torch
+        self._trace_refusals("trace_hits")
+        hs = torch.as_tensor(hit_subjects).to(device=self.device, dtype=torch.int64)
+        if hs.dim() != 2 or hs.shape[0] != self.nq:
+            raise BgsaHipError(f"trace_hits: hit_subjects must be [nq = {self.nq}, K]")
+        nq, k = hs.shape
+        pq = torch.arange(nq, dtype=torch.int32, device=self.device).repeat_interleave(k)
+        if into is not None:
+            into = list(into)
+            if len(into) != 4 or any(not t.is_contiguous() for t in into) or tuple(into[0].shape) != (nq, k) or \
+                    tuple(into[1].shape) != (nq, k, 4) or tuple(into[2].shape) != (nq, k) or into[3].dim() != 3 or \
+                    tuple(into[3].shape[:2]) != (nq, k):
+                raise BgsaHipError(f"trace_hits: into= needs contiguous tensors of shape ({nq}, {k}), ({nq}, {k}, 4), ({nq}, {k}), ({nq}, {k}, cap)")
+            if cigar_cap is None:
+                cigar_cap = into[3].shape[2]
+            into = (into[0].view(-1), into[1].view(nq * k, 4), into[2].view(-1), into[3].view(nq * k, -1))
+        score, span, n_ops, cigar = self.trace_pairs(pq, hs.contiguous().view(-1), cigar_cap, subject_base, into, workspace_bytes)
+        return score.view(nq, k), span.view(nq, k, 4), n_ops.view(nq, k), cigar.view(nq, k, -1)
+
     def check_faults(self) -> None:
         """Synchronises and raises if a kernel reported a stream fault (bgsa_hip_stream_faults)."""
         self.torch.cuda.synchronize(self.device)
@@ -461,11 +534,11 @@ def align_all_pairs(queries: np.ndarray, subjects: np.ndarray, algo: int = ALGO_
     return out[:, : a.ns_real].cpu().numpy()
 
 
-CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}   # the BAM op codes bgsa_hip_myers_align_pairs_dev writes
+CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}   # the BAM op codes bgsa_hip_myers_align_pairs_dev / bgsa_hip_trace_pairs_dev write
 
 
 def cigar_strings(n_ops, cigar) -> list[str]:
-    """Host helper: the runs of align_pairs / align_hits as text, e.g. "97=1X30=2D22=" — one string per pair in row-major
+    """Host helper: the runs of align_pairs / align_hits / trace_pairs / trace_hits as text, e.g. "97=1X30=2D22=" — one string per pair in row-major
     order of the leading dimensions ("" for a pair with no runs: an unused slot).  Raises if a row overflowed its cap."""
     def host(x):
         return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
@@ -497,6 +570,25 @@ def align_top_alignments(queries: np.ndarray, subjects: np.ndarray, k_best: int,
     k = subj.shape[1]
     cigars = [[text[q * k + r] if subj[q, r] >= 0 else None for r in range(k)] for q in range(subj.shape[0])]
     return hit_scores.cpu().numpy(), subj, cigars
+
+
+def trace_top_hits(queries: np.ndarray, subjects: np.ndarray, k_best: int, algo: int, scores=None,
+                   semi_global: bool = False, k: int = 0, device: str = "cuda:0", block_rows: int = 1000, cigar_cap=None):
+    """The counterpart of align_top_alignments for the other aligners (BitPAl score sets, the semi-global modes): the
+    k_best best subjects per query AND where and how they align, as (scores[nq, K] int32, subjects[nq, K] int64,
+    spans[nq, K, 4] int32 = (q_begin, q_end, s_begin, s_end), cigars) with cigars[q][r] the edit script of the aligned span
+    as a string, or None for an unused slot (its span is -1).  Selected and traced back on the device."""
+    a = DeviceAligner(algo, device, k, scores, semi_global)
+    a.set_queries(queries)
+    a.set_subjects(subjects)
+    hit_scores, hit_subjects = a.top_hits(k_best, block_rows=block_rows)
+    _, span, n_ops, cigar = a.trace_hits(hit_subjects, cigar_cap=cigar_cap)
+    a.check_faults()
+    subj = hit_subjects.cpu().numpy()
+    text = cigar_strings(n_ops, cigar)
+    kk = subj.shape[1]
+    cigars = [[text[q * kk + r] if subj[q, r] >= 0 else None for r in range(kk)] for q in range(subj.shape[0])]
+    return hit_scores.cpu().numpy(), subj, span.cpu().numpy(), cigars
 
 
 def align_top_hits(queries: np.ndarray, subjects: np.ndarray, k_best: int, algo: int = ALGO_MYERS, k: int = 0,

@@ -18,65 +18,14 @@
 //     B = Eq | (D0 & Hp)     diagonal: '=' (1) or 'X' (0); otherwise: up 'I' (1) or left 'D' (0)
 // 8 * word_num bytes per row and pair, laid out [chunk wave][row][vector][word][lane] uint32: every wave store is one
 // coalesced 256-byte row, and a traceback step is two loads and two bit tests.
-#include "bgsa_common.h"
+#include "pair_trace.h"   // the argument block, owned_pair, the history's addressing and the run-length tail
 
 namespace bgsa {
 
 namespace {
 
-constexpr int kOpI = 1, kOpD = 2, kOpEq = 7, kOpX = 8;   // BAM op codes
-constexpr int kRowBlock = 8;                             // query characters fetched ahead of their rows
-constexpr int64_t kMaxChunkWaves = 1 << 22;              // waves of one launch, whatever the workspace would hold
-
 // one instantiation per word count: the row loop is straight-line code over exactly the subject's words
 using PairWidths = Widths<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32>;
-
-struct PairArgs {
-    const char *content;
-    const uint32_t *peq;
-    int ref_len, read_len;
-    int64_t read_count;
-    int word_num;
-    const int32_t *pair_query;
-    const int64_t *pair_subject;
-    int64_t n_pairs;
-    int n_queries;
-    int64_t subject_base;
-    int32_t *distance, *n_ops;
-    uint32_t *cigar;
-    int cigar_cap;
-    unsigned char *workspace;
-    size_t wave_bytes, hist_bytes;   // one wave's slice, and the history at its head (the op bytes follow)
-    unsigned *fault_word;
-};
-
-inline size_t pair_hist_bytes(int ref_len, int read_len)
-{
-    return static_cast<size_t>(ref_len) * 2 * ((read_len + 31) / 32) * kLanes * sizeof(uint32_t);
-}
-inline size_t pair_wave_bytes(int ref_len, int read_len)
-{
-    const size_t ops = (static_cast<size_t>(ref_len) + static_cast<size_t>(read_len)) * kLanes;   // one byte per step and lane
-    return (pair_hist_bytes(ref_len, read_len) + ops + 255) & ~static_cast<size_t>(255);
-}
-
-// Whether this call owns pair p, and its query and column.  A pair of another bucket (or the unused slot -1) is not
-// owned; an owned pair whose query index is out of range is skipped too and — in the forward kernel — reported.
-__device__ __forceinline__ bool owned_pair(const PairArgs &a, int64_t p, bool report, int *q, int64_t *col)
-{
-    if (p >= a.n_pairs) return false;
-    const int64_t s = a.pair_subject[p];
-    if (s < a.subject_base || static_cast<unsigned long long>(s) - static_cast<unsigned long long>(a.subject_base) >=
-                                  static_cast<unsigned long long>(a.read_count))
-        return false;
-    *col = s - a.subject_base;
-    *q = a.pair_query[p];
-    if (*q < 0 || *q >= a.n_queries) {
-        if (report) atomicOr(a.fault_word, static_cast<unsigned>(BGSA_HIP_FAULT_PAIR));
-        return false;
-    }
-    return true;
-}
 
 template <int NW>
 __global__ __launch_bounds__(kLanes) void align_pairs_forward_kernel(PairArgs a, int64_t first)
@@ -176,47 +125,13 @@ __global__ __launch_bounds__(kLanes) void align_pairs_traceback_kernel(PairArgs 
             op = kOpI;
             i--;
         } else {
-            const uint32_t *cell = hist + static_cast<size_t>(i - 1) * row_words + static_cast<size_t>((j - 1) >> 5) * kLanes;
-            const uint32_t diag = (cell[0] >> ((j - 1) & 31)) & 1u;
-            const uint32_t which = (cell[static_cast<size_t>(wn) * kLanes] >> ((j - 1) & 31)) & 1u;
-            if (diag) {
-                op = which ? kOpEq : kOpX;
-                i--;
-                j--;
-            } else if (which) {
-                op = kOpI;
-                i--;
-            } else {
-                op = kOpD;
-                j--;
-            }
+            op = history_step(hist, row_words, wn, &i, &j);
         }
         ops[steps * kLanes] = static_cast<unsigned char>(op);
         steps++;
     }
 
-    // run-length encode forwards: the last step written is the first column
-    uint32_t *out = a.cigar + static_cast<size_t>(p) * a.cigar_cap;
-    int n_runs = 0;
-    uint32_t run_op = 0, run_len = 0;
-    for (size_t t = steps; t-- > 0;) {
-        const uint32_t op = ops[t * kLanes];
-        if (op == run_op) {
-            run_len++;
-            continue;
-        }
-        if (run_len) {
-            if (n_runs < a.cigar_cap) out[n_runs] = (run_len << 4) | run_op;
-            n_runs++;
-        }
-        run_op = op;
-        run_len = 1;
-    }
-    if (run_len) {
-        if (n_runs < a.cigar_cap) out[n_runs] = (run_len << 4) | run_op;
-        n_runs++;
-    }
-    a.n_ops[p] = n_runs;
+    a.n_ops[p] = encode_runs(ops, steps, a.cigar + static_cast<size_t>(p) * a.cigar_cap, a.cigar_cap);
 }
 
 struct PairRun {

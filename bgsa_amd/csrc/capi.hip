@@ -592,7 +592,7 @@ int bgsa_hip_stream_faults(int clear)
         snprintf(msg, sizeof msg, "stream fault on device %d: flags 0x%x (%s%s%s) — at least one query was not scored", dev, value,
                  (value & BGSA_HIP_FAULT_BUDGET) ? "window budget exhausted before END " : "",
                  (value & BGSA_HIP_FAULT_CODE) ? "byte that is no stream code dispatched " : "",
-                 (value & BGSA_HIP_FAULT_PAIR) ? "align_pairs: query index outside [0, n_queries)" : "");
+                 (value & BGSA_HIP_FAULT_PAIR) ? "align_pairs / trace_pairs: query index outside [0, n_queries)" : "");
         set_error_text(msg);
     }
     return static_cast<int>(value);

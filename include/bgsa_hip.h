@@ -366,7 +366,9 @@ int bgsa_hip_threshold_hits_dev(const void *d_results, int elem_bytes, int n_que
  * safe inside a stream capture (the device's fault word is allocated by the first launch of any kind on that device).
  * BGSA_HIP_EINVAL: a NULL pointer (the workspace excepted), negative n_pairs, non-positive lengths / n_queries / cigar_cap,
  * read_count not a positive multiple of 64, word_num other than bgsa_hip_word_num(BGSA_ALGO_MYERS, ...), a workspace below the
- * minimum — all checked before the first HIP call.  n_pairs == 0 is BGSA_HIP_OK and launches nothing. */
+ * minimum — all checked before the first HIP call.  n_pairs == 0 is BGSA_HIP_OK and launches nothing.
+ * The two ..._workspace_bytes() functions size bgsa_hip_trace_pairs_dev (below) too, with the same rules: its history and op
+ * bytes have the same size and layout. */
 #define BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE ((size_t)1 << 30)
 size_t bgsa_hip_align_pairs_workspace_bytes(int ref_len, int read_len, int64_t n_pairs);
 size_t bgsa_hip_align_pairs_min_workspace_bytes(int ref_len, int read_len);
@@ -376,6 +378,50 @@ int bgsa_hip_myers_align_pairs_dev(const char *d_content, const hip_read_t *d_pe
                                    int n_queries, int64_t subject_base,
                                    int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
                                    void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---- score, span and edit script of selected pairs, for every aligner that has an alignment to report ----
+ * What bgsa_hip_myers_align_pairs_dev does for Myers global, for: BitPAl with ANY score set (compiled in or not), global;
+ * BitPAl semi-global (query end to end, free subject overhangs); Myers semi-global (subject end to end inside the query); and
+ * Myers global itself (the same scripts as bgsa_hip_myers_align_pairs_dev, from another kernel).  Subjects of 1..1024 bp.
+ * d_content, d_peq, the pair list, ownership (subject_base, the -1 slot, pairs of other buckets left untouched in all FOUR
+ * outputs) and BGSA_HIP_FAULT_PAIR for a query index outside [0, n_queries) are exactly as there; d_peq is the bucket's block
+ * as the aligner of params->algo scores it (Myers and BitPAl share the Peq layout).
+ * THE MODEL is the linear-gap DP over the character classes, rows i = 1..m query characters, columns j = 1..n subject columns:
+ * s(i, j) = match if q_i and s_j are of the same class — bit j of the subject's Peq plane of class q_i, so the alignment agrees
+ * with the bit-parallel scores by construction, 'N' and out-of-alphabet bytes included — else mismatch;
+ * H[i][j] = max(H[i-1][j-1] + s(i, j), H[i-1][j] + gap, H[i][j-1] + gap).  Three modes, from params (algo, alignment, match,
+ * mismatch, gap; BGSA_ALGO_MYERS scores 0 / -1 / -1 whatever the three ints hold, as the scoring calls):
+ *   BitPAl or Myers, global:    H[0][j] = j*gap, H[i][0] = i*gap; the score is H[m][n], the end cell (m, n); the walk back
+ *                               stops at (0, 0).
+ *   Myers, semi-global:         H[0][j] = j*gap, H[i][0] = 0; the score is the max over i in [0, m] of H[i][n], the end cell
+ *                               the SMALLEST such i; the walk back stops at the first cell with j = 0.
+ *   BitPAl, semi-global:        H[0][j] = 0, H[i][0] = i*gap; the score is the max over j in [0, n] of H[m][j], the end cell
+ *                               the SMALLEST such j; the walk back stops at the first cell with i = 0.
+ * ONE CANONICAL SCRIPT, the preference order of bgsa_hip_myers_align_pairs_dev: at a cell (i, j), i, j > 0: the diagonal if
+ * H[i-1][j-1] + s(i, j) == H[i][j], otherwise the step up ('I') if H[i-1][j] + gap == H[i][j], otherwise the step left ('D');
+ * on a non-free edge only 'D' (i = 0) or only 'I' (j = 0) remains.  At 0 / -1 / -1 in global mode this is that call's script.
+ * Per owned pair: d_score[p] = the score as the scoring calls report it for the pair (Myers: minus the distance);
+ * d_span[4p .. 4p+3] = (q_begin, q_end, s_begin, s_end), half-open, the aligned parts of query and subject — (0, m, 0, n) in
+ * global mode; d_n_ops[p] = the TRUE number of runs even beyond cigar_cap; d_cigar[p * cigar_cap ...] = the first
+ * min(n_ops, cigar_cap) runs, `length << 4 | op` with the BAM ops 7 '=' / 8 'X' / 1 'I' / 2 'D', covering the aligned span
+ * only (no clip ops), in query order, adjacent runs differing in op; slots behind the runs are left as they were.
+ * cigar_cap = ref_len + read_len can never overflow.
+ * The workspace is sized by bgsa_hip_align_pairs_workspace_bytes() / ..._min_workspace_bytes() and follows their rules: any
+ * size from the minimum up (chunks of whole waves), NULL = the library's own scratch (not capture safe); with a caller
+ * workspace the call only launches kernels.  (Subjects from 512 bp keep a DP row beyond 64 KiB of LDS; the kernel's limit is
+ * raised by the first such call per device and mode, ahead of its launches.)
+ * BGSA_HIP_EINVAL: a NULL pointer (workspace and stream excepted), negative n_pairs, non-positive lengths / n_queries /
+ * cigar_cap, read_count not a positive multiple of 64, an unknown algo or alignment, gap >= 0 or match <= mismatch, word_num
+ * other than bgsa_hip_word_num(params->algo, ...), a workspace below the minimum.  BGSA_HIP_EUNSUPPORTED: the banded filter;
+ * Myers +distance (0, 1, 1) — it aligns as the -distance aligner does; word_num > 32; max(|match|, |mismatch|, |gap|) *
+ * (ref_len + read_len) > 32767 (the DP row is kept in 16 bits).  All checked before the first HIP call; n_pairs == 0 is
+ * BGSA_HIP_OK and launches nothing. */
+int bgsa_hip_trace_pairs_dev(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                             int ref_len, int read_len, int64_t read_count, int word_num,
+                             const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs,
+                             int n_queries, int64_t subject_base,
+                             int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
+                             void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
@@ -388,7 +434,7 @@ int bgsa_hip_myers_align_pairs_dev(const char *d_content, const hip_read_t *d_pe
  * its first stream overwritten with REFILL tokens (1) or with a byte that is no token (2). */
 #define BGSA_HIP_FAULT_BUDGET 1
 #define BGSA_HIP_FAULT_CODE 2
-/* bgsa_hip_myers_align_pairs_dev: a pair this call owned named a query outside [0, n_queries); that pair was skipped (an
+/* bgsa_hip_myers_align_pairs_dev / bgsa_hip_trace_pairs_dev: a pair this call owned named a query outside [0, n_queries); that pair was skipped (an
  * argument check inside the kernel, not a damaged stream — the other pairs of the call are good). */
 #define BGSA_HIP_FAULT_PAIR 4
 int bgsa_hip_stream_faults(int clear);
