@@ -99,6 +99,12 @@ def lib() -> ctypes.CDLL:
     L.bgsa_hip_align_pairs_min_workspace_bytes.restype = sz
     L.bgsa_hip_myers_align_pairs_dev.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, i32, vp, sz, vp]
     L.bgsa_hip_trace_pairs_dev.argtypes = [pp, vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, sz, vp]
+    # mixed-length buckets (an older build loaded through BGSA_HIP_LIB for an A/B lacks them: calling one then raises AttributeError)
+    for name, types in (("bgsa_hip_cal_align_score_lens_ex", [pp, vp, vp, vp, vp, i32, i32, i64, i32, i32, i32, vp, sz, vp]),
+                        ("bgsa_hip_myers_align_pairs_lens_dev", [vp, vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, i32, vp, sz, vp]),
+                        ("bgsa_hip_trace_pairs_lens_dev", [pp, vp, vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, sz, vp])):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -194,6 +200,36 @@ def pad_rows(rows: np.ndarray, multiple: int = V_NUM) -> tuple[np.ndarray, int]:
     return rows, extra
 
 
+def pad_ragged(subjects) -> tuple[np.ndarray, np.ndarray]:
+    """Subjects of mixed lengths (byte strings or 1-D uint8 arrays) as one bucket: (rows[ns, max_len] uint8, lens[ns] int32),
+    every subject padded behind its own end with 'N'.  What the pad holds never enters a score (DeviceAligner.set_subjects_ragged).
+    Raises on an empty list and on an empty subject."""
+    seqs = [np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else np.asarray(x, dtype=np.uint8)
+            for x in subjects]
+    if not seqs:
+        raise BgsaHipError("pad_ragged: no subjects")
+    for i, x in enumerate(seqs):
+        if x.ndim != 1:
+            raise BgsaHipError(f"pad_ragged: subject {i} is not one-dimensional")
+        if x.size == 0:
+            raise BgsaHipError(f"pad_ragged: subject {i} is empty")
+    lens = np.array([x.size for x in seqs], dtype=np.int32)
+    rows = np.full((len(seqs), int(lens.max())), ord("N"), dtype=np.uint8)
+    for i, x in enumerate(seqs):
+        rows[i, : x.size] = x
+    return rows, lens
+
+
+def bin_by_words(lens) -> list[np.ndarray]:
+    """The caller's subject indices grouped by ceil(len / 32) — the 32-bit words a subject occupies, which is what a bucket's
+    kernel width and cost follow —, ascending groups, the caller's order kept within a group."""
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    if lens.size and lens.min() < 1:
+        raise BgsaHipError("bin_by_words: a length is not positive")
+    words = (lens + 31) // 32
+    return [np.flatnonzero(words == w) for w in np.unique(words)]
+
+
 def rows_to_buffer(rows: np.ndarray) -> np.ndarray:
     """[n, len] ASCII -> the reference's row buffer (len bytes + '\\n' per row), flat uint8."""
     rows = np.ascontiguousarray(rows, dtype=np.uint8)
@@ -235,6 +271,7 @@ class DeviceAligner:
         torch.cuda.set_device(self.device)
         check(lib().bgsa_hip_set_device(self.device.index or 0), "set_device")
         self.out_dtype = torch.int8 if algo == ALGO_BANDED else torch.int16
+        self.d_lens = None    # per-column subject lengths of a mixed-length bucket (set_subjects_ragged)
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -260,9 +297,32 @@ class DeviceAligner:
         d_rows = torch.from_numpy(buf).to(self.device)
         self.set_subject_rows_device(d_rows, self.ns, self.slen, qlen)
 
-    def set_subject_rows_device(self, d_rows, ns: int, slen: int, qlen: int | None = None) -> None:
-        """d_rows: uint8 device tensor holding ns rows of slen+1 bytes; ns % 64 == 0."""
+    def set_subjects_ragged(self, subjects, qlen: int | None = None) -> None:
+        """subjects: byte strings or 1-D uint8 arrays of MIXED lengths, as one bucket of the longest one's width (pad_ragged, then
+        padded to a multiple of 64 with 'N' reads of that width).  From here on score, top_hits, threshold_hits, align_pairs,
+        align_hits, trace_pairs and trace_hits treat column c as the subject's own first lens[c] characters: scores, hit lists and
+        edit scripts are those of the unpadded subject, bit for bit.  Global modes only (Myers -distance / +distance, BitPAl with
+        any compiled set, subjects up to 1,024 bp): the banded filter and the semi-global modes raise rc=-2 at the first scoring
+        call.  The certified Myers band is off for such a bucket (full rows).  If all lengths are equal this IS set_subjects: no
+        lengths are passed and the band stays available.  Queries keep one length per aligner: group queries by length.  To keep a
+        short read from being scored at the width of the longest, bin the subjects first (bin_by_words, align_all_pairs_ragged)."""
         torch = self.torch
+        rows, lens = pad_ragged(subjects)
+        if (lens == lens[0]).all():
+            return self.set_subjects(rows, qlen)
+        s, self.extra = pad_rows(rows)
+        self.ns_real = rows.shape[0]
+        lens = np.concatenate([lens, np.full(self.extra, rows.shape[1], dtype=np.int32)])
+        d_rows = torch.from_numpy(rows_to_buffer(s)).to(self.device)
+        self.set_subject_rows_device(d_rows, s.shape[0], s.shape[1], qlen, d_lens=torch.from_numpy(lens).to(self.device))
+
+    def set_subject_rows_device(self, d_rows, ns: int, slen: int, qlen: int | None = None, d_lens=None) -> None:
+        """d_rows: uint8 device tensor holding ns rows of slen+1 bytes; ns % 64 == 0.  d_lens: None (every subject is slen long), or
+        an int32 device tensor of ns subject lengths (a mixed-length bucket, slen the longest: set_subjects_ragged)."""
+        torch = self.torch
+        if d_lens is not None and (d_lens.dtype != torch.int32 or d_lens.numel() != int(ns) or not d_lens.is_contiguous()):
+            raise BgsaHipError("set_subject_rows_device: d_lens must be a contiguous int32 tensor of ns entries")
+        self.d_lens = d_lens
         self.ns, self.slen = int(ns), int(slen)
         qlen = self.qlen if qlen is None else qlen
         self.wn = word_num(self.algo, qlen, self.slen, self.k)
@@ -293,6 +353,12 @@ class DeviceAligner:
         need = int(lib().bgsa_hip_workspace_bytes_ex(ctypes.byref(p), self.qlen, self.slen, ref_end - ref_start))
         if getattr(self, "d_work", None) is None or self.d_work.numel() < need:
             self.d_work = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        if self.d_lens is not None:
+            check(lib().bgsa_hip_cal_align_score_lens_ex(ctypes.byref(p), self.d_content.data_ptr(), self.d_peq.data_ptr(),
+                                                         out.data_ptr(), self.d_lens.data_ptr(), self.qlen, self.slen, self.ns,
+                                                         ref_start, ref_end, self.wn, self.d_work.data_ptr(),
+                                                         self.d_work.numel(), self._stream()), "cal_align_score_lens_ex")
+            return out
         check(lib().bgsa_hip_cal_align_score_ex(ctypes.byref(p), self.d_content.data_ptr(), self.d_peq.data_ptr(),
                                                 out.data_ptr(), self.qlen, self.slen, self.ns, ref_start,
                                                 ref_end, self.wn, self.d_work.data_ptr(),
@@ -400,6 +466,13 @@ class DeviceAligner:
             if getattr(self, "d_align_work", None) is None or self.d_align_work.numel() < workspace_bytes:
                 self.d_align_work = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
             work, work_bytes = self.d_align_work.data_ptr(), int(workspace_bytes)
+        if self.d_lens is not None:
+            check(lib().bgsa_hip_myers_align_pairs_lens_dev(self.d_content.data_ptr(), self.d_peq.data_ptr(), self.d_lens.data_ptr(),
+                                                            self.qlen, self.slen, self.ns, self.wn, pq.data_ptr(), ps.data_ptr(), n,
+                                                            self.nq, int(subject_base), distance.data_ptr(), n_ops.data_ptr(),
+                                                            cigar.data_ptr(), cap, work, work_bytes, self._stream()),
+                  "myers_align_pairs_lens_dev")
+            return distance, n_ops, cigar
         check(lib().bgsa_hip_myers_align_pairs_dev(self.d_content.data_ptr(), self.d_peq.data_ptr(), self.qlen, self.slen, self.ns, self.wn,
                                                    pq.data_ptr(), ps.data_ptr(), n, self.nq, int(subject_base), distance.data_ptr(),
                                                    n_ops.data_ptr(), cigar.data_ptr(), cap, work, work_bytes, self._stream()),
@@ -470,6 +543,13 @@ class DeviceAligner:
                 self.d_align_work = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
             work, work_bytes = self.d_align_work.data_ptr(), int(workspace_bytes)
         p = self.params()
+        if self.d_lens is not None:
+            check(lib().bgsa_hip_trace_pairs_lens_dev(ctypes.byref(p), self.d_content.data_ptr(), self.d_peq.data_ptr(),
+                                                      self.d_lens.data_ptr(), self.qlen, self.slen, self.ns, self.wn, pq.data_ptr(),
+                                                      ps.data_ptr(), n, self.nq, int(subject_base), score.data_ptr(), span.data_ptr(),
+                                                      n_ops.data_ptr(), cigar.data_ptr(), cap, work, work_bytes, self._stream()),
+                  "trace_pairs_lens_dev")
+            return score, span, n_ops, cigar
         check(lib().bgsa_hip_trace_pairs_dev(ctypes.byref(p), self.d_content.data_ptr(), self.d_peq.data_ptr(), self.qlen, self.slen,
                                              self.ns, self.wn, pq.data_ptr(), ps.data_ptr(), n, self.nq, int(subject_base),
                                              score.data_ptr(), span.data_ptr(), n_ops.data_ptr(), cigar.data_ptr(), cap, work, work_bytes,
@@ -532,6 +612,46 @@ def align_all_pairs(queries: np.ndarray, subjects: np.ndarray, algo: int = ALGO_
     out = a.score()
     a.check_faults()
     return out[:, : a.ns_real].cpu().numpy()
+
+
+def align_all_pairs_ragged(queries: np.ndarray, subjects, algo: int = ALGO_MYERS, scores=None, device: str = "cuda:0") -> np.ndarray:
+    """scores[nq, ns] of queries (ONE length: group queries by length) against subjects of mixed lengths (byte strings or 1-D
+    uint8 arrays), columns in the caller's order.  Global modes (DeviceAligner.set_subjects_ragged).  The subjects are binned by
+    the words they occupy (bin_by_words) and every bin is one bucket of its own longest read, so a short read is not scored at
+    the width of the longest."""
+    seqs = list(subjects)
+    lens = pad_ragged(seqs)[1]
+    a = DeviceAligner(algo, device, 0, scores)
+    a.set_queries(queries)
+    out = np.empty((a.nq, len(seqs)), dtype=np.int16)
+    for idx in bin_by_words(lens):
+        a.set_subjects_ragged([seqs[i] for i in idx])
+        out[:, idx] = a.score()[:, : a.ns_real].cpu().numpy()
+    a.check_faults()
+    return out
+
+
+def align_top_hits_ragged(queries: np.ndarray, subjects, k_best: int, algo: int = ALGO_MYERS, scores=None, device: str = "cuda:0",
+                          smallest=None, block_rows: int = 1000) -> tuple[np.ndarray, np.ndarray]:
+    """The k_best best subjects per query as (scores[nq, K] int32, subjects[nq, K] int64 — the caller's indices, -1 in an unused
+    slot) over subjects of mixed lengths, binned as in align_all_pairs_ragged: the bins are walked with top_hits(into=,
+    subject_base=) and the reported ids are mapped back to the caller's indices on the host.  Ties between equal scores go to
+    the earlier position in the BINNED order (ascending word count, the caller's order within a bin), not to the smaller caller
+    index.  Queries keep one length per call."""
+    seqs = list(subjects)
+    lens = pad_ragged(seqs)[1]
+    bins = bin_by_words(lens)
+    order = np.concatenate(bins)
+    a = DeviceAligner(algo, device, 0, scores)
+    a.set_queries(queries)
+    into, base = None, 0
+    for idx in bins:
+        a.set_subjects_ragged([seqs[i] for i in idx])
+        into = a.top_hits(k_best, block_rows=block_rows, smallest=smallest, subject_base=base, into=into)
+        base += len(idx)
+    a.check_faults()
+    hit_scores, ids = into[0].cpu().numpy(), into[1].cpu().numpy()
+    return hit_scores, np.where(ids >= 0, order[np.clip(ids, 0, order.size - 1)], -1)
 
 
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}   # the BAM op codes bgsa_hip_myers_align_pairs_dev / bgsa_hip_trace_pairs_dev write

@@ -92,9 +92,10 @@ __global__ __launch_bounds__(kLanes) void align_pairs_forward_kernel(PairArgs a,
     }
 
     int score = m;
+    const int n = pair_read_len(a, col);   // the columns behind the subject's own end never enter: column j depends on columns <= j
 #pragma unroll
     for (int w = 0; w < NW; w++) {
-        const int rem = a.read_len - 32 * w;
+        const int rem = n - 32 * w;
         const uint32_t mask = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
         score += __popc(pv[w] & mask) - __popc(mv[w] & mask);
     }
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(kLanes) void align_pairs_traceback_kernel(PairArgs 
     unsigned char *ops = slice + a.hist_bytes + lane;   // [step][lane]
     const size_t row_words = static_cast<size_t>(2) * wn * kLanes;
 
-    int i = a.ref_len, j = a.read_len;
+    int i = a.ref_len, j = pair_read_len(a, col);
     size_t steps = 0;
     while (i > 0 || j > 0) {
         int op;
@@ -200,6 +201,17 @@ int bgsa_hip_myers_align_pairs_dev(const char *d_content, const hip_read_t *d_pe
                                    int n_queries, int64_t subject_base, int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar,
                                    int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream)
 {
+    return bgsa_hip_myers_align_pairs_lens_dev(d_content, d_peq, nullptr, ref_len, read_len, read_count, word_num, d_pair_query,
+                                               d_pair_subject, n_pairs, n_queries, subject_base, d_distance, d_n_ops, d_cigar, cigar_cap,
+                                               d_workspace, workspace_bytes, stream);
+}
+
+int bgsa_hip_myers_align_pairs_lens_dev(const char *d_content, const hip_read_t *d_peq, const int32_t *d_read_lens, int ref_len,
+                                        int read_len, int64_t read_count, int word_num, const int32_t *d_pair_query,
+                                        const int64_t *d_pair_subject, int64_t n_pairs, int n_queries, int64_t subject_base,
+                                        int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap, void *d_workspace,
+                                        size_t workspace_bytes, void *stream)
+{
     if (!d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_distance || !d_n_ops || !d_cigar)
         return refuse(BGSA_HIP_EINVAL, "a NULL pointer (only the workspace may be NULL)");
     if (n_pairs < 0) return refuse(BGSA_HIP_EINVAL, "n_pairs is negative");
@@ -216,7 +228,7 @@ int bgsa_hip_myers_align_pairs_dev(const char *d_content, const hip_read_t *d_pe
 
     PairRun r{};
     r.args = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
-                      subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), nullptr};
+                      subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), nullptr, d_read_lens};
     r.stream = static_cast<hipStream_t>(stream);
     r.args.fault_word = device_fault_word();
     if (!r.args.fault_word) return BGSA_HIP_EHIP;

@@ -44,6 +44,9 @@ struct ScoreArgs {
     int word_num;
     void *d_workspace;
     hipStream_t stream;
+    // Mixed-length bucket (bgsa_hip_cal_align_score_lens_ex): the length of every subject column, padding columns included
+    // (read_count entries); read_len is then the longest one, the row stride minus one.  nullptr: every subject is read_len long.
+    const int32_t *d_read_lens = nullptr;
     int nq() const { return ref_end - ref_start; }
     int64_t n_groups() const { return read_count / kLanes; }
     template <typename T> T *results() const { return static_cast<T *>(d_results); }
@@ -480,13 +483,17 @@ inline int query_tile_max()
     }();
     return v;
 }
-inline TaskPlan plan_tasks(int nq, long long wave_tasks_per_tile, long long row_words, int q_max, bool counter_kernel, int q_max_counter = 0)
+// force_counter: the caller has the counter instantiation only (the length-aware kernels: one task mapping per width), so the
+// counter is used whatever BGSA_DYNAMIC_TASKS and the launch's size say, as long as the task numbers fit 32 bits.
+inline TaskPlan plan_tasks(int nq, long long wave_tasks_per_tile, long long row_words, int q_max, bool counter_kernel, int q_max_counter = 0,
+                           bool force_counter = false)
 {
     static const long long target = [] { const char *e = getenv("BGSA_DYNAMIC_TASK_TARGET"); const long long v = e ? atoll(e) : 0; return v > 0 ? v : 262144ll; }();
     static const long long words = [] { const char *e = getenv("BGSA_DYNAMIC_TASK_WORDS"); const long long v = e ? atoll(e) : 0; return v > 0 ? v : 3000ll; }();
-    if (counter_kernel && dynamic_tasks()) {
+    if (counter_kernel && (force_counter || dynamic_tasks())) {
         const int q = pick_query_tile(nq, wave_tasks_per_tile, row_words, q_max_counter > 0 ? q_max_counter : q_max, target, words);
-        if (dynamic_tasks_fit(((nq + q - 1) / q) * wave_tasks_per_tile)) return {q, true};
+        const long long n_tasks = ((nq + q - 1) / q) * wave_tasks_per_tile;
+        if (force_counter ? n_tasks < 0xffffffffll : dynamic_tasks_fit(n_tasks)) return {q, true};
     }
     return {pick_query_tile(nq, wave_tasks_per_tile, row_words, q_max), false};
 }
@@ -596,6 +603,14 @@ unsigned *device_fault_word();   // capi.hip; nullptr + error text if the alloca
 // its dispatch sends to a fail slot, or -1 if the format has none (then kind 2 degrades to kind 1).
 int stream_guard(void *d_streams, int stride_bytes, int refill_code, int bad_code, hipStream_t stream,
                  unsigned **fault_word);
+
+// The length of this lane's subject in a mixed-length bucket, clamped to [0, read_len]: it only ever forms a mask, a
+// constant term or a traceback start, never an address, so no value in read_lens can take an access out of bounds.
+__device__ __forceinline__ int lane_read_len(const int32_t *read_lens, size_t column, int read_len)
+{
+    const int n = read_lens[column];
+    return n < 0 ? 0 : (n > read_len ? read_len : n);
+}
 
 __device__ __forceinline__ void note_stream_fault(unsigned *fault_word, int left)
 {

@@ -55,13 +55,17 @@ __device__ __forceinline__ uint32_t bitpal_init_plane(int plane, int semi)
     return (semi && ((stored >> plane) & 1u)) ? ~0u : 0u;
 }
 
-template <int NW, bool SEMI, bool DYN = false>
+// LENS (global mode, a bucket of mixed subject lengths): the rows run over the padded width as ever; the lane's score is the
+// column sum under the mask of its OWN length read_lens[column], and the constant term uses that length (column j of a global
+// DP depends on columns <= j only).  A separate instantiation, so that the equal-length kernels keep their register counts.
+template <int NW, bool SEMI, bool DYN = false, bool LENS = false>
 __global__ __launch_bounds__(256) void bitpal_asm_kernel(
     const unsigned char *__restrict__ streams, const uint32_t *__restrict__ peq,
     int16_t *__restrict__ out, int ref_len, int read_len, long long ld, int n_groups, int word_num,
     int n_queries, int q_tile, int stream_stride_bytes, unsigned *__restrict__ fault_word,
-    unsigned *__restrict__ task_counter)
+    unsigned *__restrict__ task_counter, const int32_t *__restrict__ read_lens = nullptr)
 {
+    static_assert(!(LENS && SEMI), "semi-global walks the last row over a wave-uniform column count");
     constexpr int semi = SEMI;
     const int lane = threadIdx.x & (kLanes - 1);
     // DYN: the waves of a persistent grid take (group, tile) tasks from a counter (bgsa_common.h "dynamic task handout")
@@ -99,6 +103,8 @@ __global__ __launch_bounds__(256) void bitpal_asm_kernel(
 #pragma unroll
             for (int w = 0; w < NW; w++)
                 P[c][w] = (w < wn) ? g[(c * wn + w) * kLanes] : 0u;
+        int n_cols = read_len;   // LENS: the lane's own length, loaded once per task
+        if constexpr (LENS) n_cols = lane_read_len(read_lens, static_cast<size_t>(group) * kLanes + lane_t, read_len);
 
         const int q0 = tile * q_tile;
         const int q1 = (q0 + q_tile < n_queries) ? q0 + q_tile : n_queries;
@@ -123,7 +129,9 @@ __global__ __launch_bounds__(256) void bitpal_asm_kernel(
                 score = run;
                 bitpal_last_row_max<NW>(st, 0, read_len, run, score);
             } else {
-                score = kBitpalGap * (ref_len + read_len) + bitpal_column_sum<NW>(st, 0, read_len);
+                int n_own = n_cols;   // (laundered: the per-word masks are otherwise formed once per task and kept, NW more VGPRs)
+                if constexpr (LENS) asm volatile("" : "+v"(n_own));
+                score = kBitpalGap * (ref_len + n_own) + bitpal_column_sum<NW>(st, 0, n_own);
             }
             unsigned lane_s = static_cast<unsigned>(lane);
             if constexpr (DYN) asm volatile("" : "+v"(lane_s));      // (the lane's byte offset is formed here, not kept)
@@ -347,10 +355,21 @@ int launch_nw(const ScoreArgs &a, int semi)
         [] { int plain = 0, counter = 0;
              return hipOccupancyMaxActiveBlocksPerMultiprocessor(&plain, bitpal_asm_kernel<NW, true, false>, 256, 0) == hipSuccess &&
                     hipOccupancyMaxActiveBlocksPerMultiprocessor(&counter, bitpal_asm_kernel<NW, true, true>, 256, 0) == hipSuccess && counter >= plain && plain > 0; }()};
-    const TaskPlan plan = plan_tasks(nq, a.n_groups(), static_cast<long long>(a.ref_len) * NW * 2, 16, NW <= 8 && counter_costs_no_wave[semi ? 1 : 0],
-                                     query_tile_max());
+    // A mixed-length bucket (global mode; capi.hip refused the rest) runs the LENS instantiation, of which a width has ONE: on the
+    // counter up to 8 words — whatever the occupancy answer above and BGSA_DYNAMIC_TASKS say —, on the static grid beyond.
+    const bool lens = a.d_read_lens != nullptr;
+    if (lens && semi) {
+        set_error_text("bitpal: per-subject lengths are scored in global mode only");
+        return BGSA_HIP_EUNSUPPORTED;
+    }
+    const TaskPlan plan = plan_tasks(nq, a.n_groups(), static_cast<long long>(a.ref_len) * NW * 2, 16,
+                                     NW <= 8 && (lens || counter_costs_no_wave[semi ? 1 : 0]), query_tile_max(), lens);
+    if (lens && NW <= 8 && !plan.dynamic) {
+        set_error_text("bitpal: too many tasks for one length-aware launch (split the query window)");
+        return BGSA_HIP_EUNSUPPORTED;
+    }
     note_query_tile(plan.q_tile);
-    const auto on_counter = semi ? bitpal_asm_kernel<NW, true, true> : bitpal_asm_kernel<NW, false, true>;
+    const auto on_counter = lens ? bitpal_asm_kernel<NW, false, NW <= 8, true> : semi ? bitpal_asm_kernel<NW, true, true> : bitpal_asm_kernel<NW, false, true>;
     LaunchGrid lg;   // the counter is zeroed by the packer
     if (int rc = plan_grid(plan, a.n_groups(), nq, task_counter_in(a.d_workspace, static_cast<size_t>(stride) * nq),
                            [&] { return persistent_blocks_for(on_counter); }, "bitpal", &lg))
@@ -358,11 +377,11 @@ int launch_nw(const ScoreArgs &a, int semi)
     if (int rc = launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter)) return rc;
     unsigned *fault = nullptr;
     if (int rc = stream_guard(a.d_workspace, stride, kCodeRefill, 7, a.stream, &fault)) return rc;
-    const auto kernel = lg.counter ? on_counter : (semi ? bitpal_asm_kernel<NW, true, false> : bitpal_asm_kernel<NW, false, false>);
+    const auto kernel = (lg.counter || lens) ? on_counter : (semi ? bitpal_asm_kernel<NW, true, false> : bitpal_asm_kernel<NW, false, false>);
     hipLaunchKernelGGL(kernel, lg.grid, dim3(256), 0, a.stream,
                        static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len,
                        a.read_len, static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num,
-                       nq, plan.q_tile, stride, fault, lg.counter);
+                       nq, plan.q_tile, stride, fault, lg.counter, a.d_read_lens);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
@@ -381,6 +400,10 @@ const char *set_kernel_name(int word_num)
 int set_launch(const ScoreArgs &a, int semi)
 {
     const BitpalChoice c = bitpal_select(a.word_num);
+    if (a.d_read_lens && c.blocks) {
+        set_error_text("bitpal: per-subject lengths are scored by the register-resident kernel only; this score set's reaches fewer words");
+        return BGSA_HIP_EUNSUPPORTED;
+    }
     if (c.blocks)
         return BlockWidths::dispatch(c.nw, "bitpal column blocks",
                                      [&](auto nw) { return launch_blocked<decltype(nw)::value, kBitpalPackedBlocks>(a, c.n_blocks, semi); });

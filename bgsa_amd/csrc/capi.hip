@@ -687,6 +687,38 @@ int bgsa_hip_cal_align_score_ex(const bgsa_hip_params_t *params, const char *d_c
                                 int ref_start, int ref_end, int word_num,
                                 void *d_workspace, size_t workspace_bytes, void *stream)
 {
+    return bgsa_hip_cal_align_score_lens_ex(params, d_content, d_peq, d_results, nullptr, ref_len, read_len, read_count, ref_start,
+                                            ref_end, word_num, d_workspace, workspace_bytes, stream);
+}
+
+// What a bucket of mixed subject lengths cannot run as; the text names the reason.  Before anything is allocated or launched.
+static int lens_refused(const Plan &plan, int word_num)
+{
+    const char *why = nullptr;
+    char set_text[200];
+    if (plan.kernel == BGSA_ALGO_BANDED)
+        why = "the banded filter takes subjects of one length (its band and checkpoints are derived from it)";
+    else if (plan.semi)
+        why = "semi-global scoring takes subjects of one length (Myers shifts the subject by a wave-uniform count, BitPAl walks the "
+              "last row over a wave-uniform column count)";
+    else if (word_num > kMaxWords)
+        why = "subjects beyond 1,024 bp (word_num > 32) run as column blocks, which have no length-aware form";
+    else if (plan.kernel == BGSA_ALGO_BITPAL && word_num > plan.set->max_plain) {
+        snprintf(set_text, sizeof set_text, "the register-resident BitPAl kernel of score set %d/%d/%d reaches %d words, the bucket has %d "
+                 "(wider subjects run as column blocks, which have no length-aware form)", plan.set->match, plan.set->mismatch,
+                 plan.set->gap, plan.set->max_plain, word_num);
+        why = set_text;
+    }
+    if (!why) return BGSA_HIP_OK;
+    set_error_text((std::string("cal_align_score_lens_ex: per-subject lengths: ") + why).c_str());
+    return BGSA_HIP_EUNSUPPORTED;
+}
+
+int bgsa_hip_cal_align_score_lens_ex(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                                     void *d_results, const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count,
+                                     int ref_start, int ref_end, int word_num,
+                                     void *d_workspace, size_t workspace_bytes, void *stream)
+{
     if (!params) {
         set_error_text("cal_align_score: params is NULL");
         return BGSA_HIP_EINVAL;
@@ -708,6 +740,8 @@ int bgsa_hip_cal_align_score_ex(const bgsa_hip_params_t *params, const char *d_c
                            : "cal_align_score_dev: word_num does not match read_len");
         return BGSA_HIP_EINVAL;
     }
+    if (d_read_lens)
+        if (int rc = lens_refused(plan, word_num)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t need = plan_workspace_bytes(plan, ref_len, read_len, ref_end - ref_start);
     std::unique_lock<std::mutex> own_scratch(g_scratch_mu, std::defer_lock);
@@ -721,7 +755,7 @@ int bgsa_hip_cal_align_score_ex(const bgsa_hip_params_t *params, const char *d_c
         if (int rc = scratch_reserve(s, need, &d_workspace)) return rc;
     }
     const int64_t n_scores = static_cast<int64_t>(ref_end - ref_start) * read_count;
-    const ScoreArgs args = {d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, ref_end, word_num, d_workspace, s};
+    const ScoreArgs args = {d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, ref_end, word_num, d_workspace, s, d_read_lens};
     switch (plan.kernel) {
     case BGSA_ALGO_MYERS:
         if (int rc = launch_myers(args, plan.semi)) return rc;

@@ -185,14 +185,25 @@ constexpr int kPairMaxWords = 2;  // widths instantiated as myers_pair_rows_asm 
 // rest of its tasks.  Pairs that are all far apart then cost about one fallback per wave over the full rows; where
 // (nearly) every wave is certified the pair is touched once per wave, at its end, when the wave adds the rest of its banded
 // queries.  band_stats_add_kernel then adds the launch's pair to the device's sticky counts (bgsa_hip_myers_band_stats).
-template <int NW, int G, bool DYN = false, bool BAND = false>
+// LENS (a bucket of mixed subject lengths, bgsa_hip_cal_align_score_lens_ex): the rows run as ever over the bucket's padded width;
+// column j of a global DP depends on columns <= j only, so the lane's score is the epilogue's sum under the mask of the lane's OWN
+// length read_lens[column] — per lane instead of wave-uniform, once per query.  What lies behind a subject's end never enters.
+// A separate instantiation: the equal-length kernels keep their code and their register counts.  Never with BAND: the window
+// schedule and the limit certify one (m, n), DESIGN §4.2.
+template <int NW, int G, bool DYN = false, bool BAND = false, bool LENS = false>
 __global__ __launch_bounds__(256) void myers_global_asm_kernel(
     const unsigned char *__restrict__ streams, const uint32_t *__restrict__ peq,
     int16_t *__restrict__ out, int ref_len, int read_len, long long ld, int n_groups, int word_num,
     int n_queries, int q_tile, int stream_stride_bytes, unsigned *__restrict__ fault_word,
-    unsigned *__restrict__ task_counter, int band_limit = 0, unsigned long long *__restrict__ band_launch = nullptr)
+    unsigned *__restrict__ task_counter, int band_limit = 0, unsigned long long *__restrict__ band_launch = nullptr,
+    const int32_t *__restrict__ read_lens = nullptr)
 {
     static_assert(!BAND || (G == 1 && NW >= kBandMinWords && NW <= kBandMaxWords), "band: one group, 3..8 words");
+    static_assert(!(LENS && BAND), "the certified band is derived from one (m, n): a length-aware launch runs full rows");
+    // LENS: the lane's length is loaded once per task and kept across the row loops, one VGPR per group — except beyond 8 words,
+    // where the widths sit at their occupancy steps (20 words 238, 28 and 32 words 255 VGPRs): there the epilogue loads it again
+    // per query, one dword per lane against >= 10 words x ref_len rows.
+    constexpr bool kLenPerQuery = LENS && NW > 8;
     const int lane = threadIdx.x & (kLanes - 1);
     // Static mapping (DYN = false): workgroup (x, y) = (four wave-groups, query tile).  Dynamic (bgsa_common.h "dynamic task
     // handout"; a separate instantiation, so that the static kernels keep their register counts: the loop costs 5-8 VGPRs,
@@ -227,6 +238,13 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
 #pragma unroll
                 for (int w = 0; w < NW; w++)
                     P[c][gi * NW + w] = (live && w < word_num) ? g[(c * word_num + w) * kLanes] : 0u;
+        }
+
+        [[maybe_unused]] int own_len[G];   // LENS: this lane's subject length per group (a group past the end of the bucket is not stored)
+        if constexpr (LENS && !kLenPerQuery) {
+#pragma unroll
+            for (int gi = 0; gi < G; gi++)
+                own_len[gi] = group0 + gi < n_groups ? lane_read_len(read_lens, static_cast<size_t>(group0 + gi) * kLanes + lane, read_len) : 0;
         }
 
         const int q0 = tile * q_tile;
@@ -291,9 +309,22 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
 #pragma unroll
             for (int gi = 0; gi < G; gi++) {
                 int score = ref_len;  // D[m][n] = m + sum over the n subject columns of (VP - VN)
+                int n_cols = read_len;   // LENS: the lane's own n
+                if constexpr (kLenPerQuery) {
+                    // (the lane number formed here: an address kept per lane across the row loop is two VGPRs these widths lack —
+                    // 28 words: 255 -> 326, 32 words: 255 -> 258, one wave per SIMD instead of two)
+                    unsigned lane_e;
+                    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+                    n_cols = group0 + gi < n_groups ? lane_read_len(read_lens, static_cast<size_t>(group0 + gi) * kLanes + lane_e, read_len) : 0;
+                }
+                else if constexpr (LENS)
+                    n_cols = own_len[gi];
+                // (the NW masks depend on the task only: laundered, or the compiler forms them once per task and keeps NW more
+                // VGPRs across the row loop — 28 words: 255 -> 423)
+                if constexpr (LENS) asm volatile("" : "+v"(n_cols));
 #pragma unroll
                 for (int w = 0; w < NW; w++) {
-                    const int rem = read_len - 32 * w;
+                    const int rem = n_cols - 32 * w;
                     const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
                     score += __popc(st[2 * (gi * NW + w)] & m) - __popc(st[2 * (gi * NW + w) + 1] & m);
                 }
@@ -742,7 +773,7 @@ __global__ void band_stats_add_kernel(const unsigned long long *__restrict__ lau
 // Every instantiation of myers_global_asm_kernel through one pointer type (a function pointer has no default arguments: the
 // plain kernels get their two band parameters passed as 0 / nullptr).
 using AsmKernel = void (*)(const unsigned char *, const uint32_t *, int16_t *, int, int, long long, int, int, int, int, int,
-                           unsigned *, unsigned *, int, unsigned long long *);
+                           unsigned *, unsigned *, int, unsigned long long *, const int32_t *);
 
 template <int NW, int G>
 int launch_asm(const ScoreArgs &a)
@@ -752,18 +783,30 @@ int launch_asm(const ScoreArgs &a)
     // waves per SIMD with or without the task loop's registers)
     constexpr bool kCounter = NW <= 8 || NW >= 30;
     constexpr bool kPairs = NW <= kPairMaxWords;
+    // A mixed-length bucket runs the LENS instantiation, of which a width has ONE: on the counter where the width has a counter
+    // kernel (the default selection's choice for every launch long enough to matter; a short launch pays the counter's fixed
+    // cost, and BGSA_DYNAMIC_TASKS=0 does not reach it), on the static grid elsewhere.  Full rows always: no band.
+    const bool lens = a.d_read_lens != nullptr;
     const int64_t n_waves = (a.n_groups() + G - 1) / G;
     const TaskPlan plan = plan_tasks(nq, n_waves, static_cast<long long>(a.ref_len) * NW * G, NW >= 30 ? 8 : 32, kCounter,
-                                     NW >= 30 ? long_query_tile() : query_tile_max());
+                                     NW >= 30 ? long_query_tile() : query_tile_max(), lens);
+    if (lens && kCounter && !plan.dynamic) {
+        set_error_text("myers: too many tasks for one length-aware launch (split the query window)");
+        return BGSA_HIP_EUNSUPPORTED;
+    }
     note_query_tile(plan.q_tile);
     AsmKernel on_grid = myers_global_asm_kernel<NW, G, false>, on_counter = nullptr;
     if constexpr (kCounter) on_counter = myers_global_asm_kernel<NW, G, true>;
+    if (lens) {
+        if constexpr (kCounter) on_grid = nullptr, on_counter = myers_global_asm_kernel<NW, G, true, false, true>;
+        else on_grid = myers_global_asm_kernel<NW, G, false, false, true>;
+    }
     BandSchedule sched;
     int h = 0;
     bool band = false;
     if constexpr (G == 1 && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
         h = band_half(a.ref_len, a.read_len);
-        band = band_schedule(a.ref_len, a.read_len, h, NW, &sched);
+        band = !lens && band_schedule(a.ref_len, a.read_len, h, NW, &sched);
         if (band) {
             on_grid = myers_global_asm_kernel<NW, G, false, true>;
             on_counter = myers_global_asm_kernel<NW, G, true, true>;
@@ -789,7 +832,7 @@ int launch_asm(const ScoreArgs &a)
     hipLaunchKernelGGL(kernel, lg.grid, dim3(256), lg.counter ? myers_lds_pad() : 0u, a.stream,
                        static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len, a.read_len,
                        static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq, plan.q_tile, stride,
-                       fault, lg.counter, band ? 2 * h + 1 : 0, guard);
+                       fault, lg.counter, band ? 2 * h + 1 : 0, guard, a.d_read_lens);
     BGSA_HIP_TRY(hipGetLastError());
     if (band) {
         hipLaunchKernelGGL(band_stats_add_kernel, dim3(1), dim3(1), 0, a.stream, static_cast<const unsigned long long *>(guard),
@@ -1008,6 +1051,11 @@ int launch_myers(const ScoreArgs &a, int semi_global)
     if (a.ref_end <= a.ref_start || a.read_count == 0) return BGSA_HIP_OK;
     const MyersChoice c = myers_select(a.word_num, semi_global, a.read_count);
     if (c.refused) return ab_knob_refused(c.refused);
+    if (a.d_read_lens && c.family != MyersFamily::kAsm && c.family != MyersFamily::kAsmPairs) {
+        set_error_text("myers: per-subject lengths are scored by myers_global_asm_kernel only (global mode, word_num <= 32, no "
+                       "BGSA_MYERS_IMPL / BGSA_MYERS_PEQ_MAX_WORDS / BGSA_MYERS_MAX_PLAIN_WORDS alternative)");
+        return BGSA_HIP_EUNSUPPORTED;
+    }
     switch (c.family) {
     case MyersFamily::kAsm:
         return PeqWidths::dispatch(c.nw, "myers_global_asm_kernel", [&](auto nw) { return launch_asm<decltype(nw)::value, 1>(a); });

@@ -28,7 +28,14 @@ struct PairArgs {
     unsigned char *workspace;
     size_t wave_bytes, hist_bytes;   // one wave's slice, and the history at its head (the op bytes follow)
     unsigned *fault_word;
+    const int32_t *read_lens;        // a bucket of mixed subject lengths: one entry per column (read_len = the longest), or nullptr
 };
+
+// The subject length of the pair in column `col`: its own in a mixed-length bucket (lane_read_len: clamped to [0, read_len]).
+__device__ __forceinline__ int pair_read_len(const PairArgs &a, int64_t col)
+{
+    return a.read_lens ? lane_read_len(a.read_lens, static_cast<size_t>(col), a.read_len) : a.read_len;
+}
 
 // History: two bit vectors per row and word, [chunk wave][row][vector A|B][word][lane] uint32.  A bit j = the step at
 // (row, column j) is diagonal; B bit j = on a diagonal step '=' (1) or 'X' (0), otherwise up 'I' (1) or left 'D' (0).

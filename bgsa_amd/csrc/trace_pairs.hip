@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kLanes) void trace_pairs_forward_kernel(TraceArgs t
     int q = 0;
     int64_t col = 0;
     if (!owned_pair(a, p, true, &q, &col)) return;   // no barrier below: a lane's DP row is its own
-    const int wn = a.word_num, m = a.ref_len, n = a.read_len;
+    const int wn = a.word_num, m = a.ref_len, n = pair_read_len(a, col);   // a mixed-length bucket (global mode): the pair's own n
     const int match = t.match, mismatch = t.mismatch, gap = t.gap;
 
     int16_t *hrow = dp_row + lane;
@@ -258,6 +258,17 @@ int bgsa_hip_trace_pairs_dev(const bgsa_hip_params_t *params, const char *d_cont
                              int64_t n_pairs, int n_queries, int64_t subject_base, int32_t *d_score, int32_t *d_span, int32_t *d_n_ops,
                              uint32_t *d_cigar, int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream)
 {
+    return bgsa_hip_trace_pairs_lens_dev(params, d_content, d_peq, nullptr, ref_len, read_len, read_count, word_num, d_pair_query,
+                                         d_pair_subject, n_pairs, n_queries, subject_base, d_score, d_span, d_n_ops, d_cigar, cigar_cap,
+                                         d_workspace, workspace_bytes, stream);
+}
+
+int bgsa_hip_trace_pairs_lens_dev(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                                  const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count, int word_num,
+                                  const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs, int n_queries,
+                                  int64_t subject_base, int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar,
+                                  int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream)
+{
     if (!params || !d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_score || !d_span || !d_n_ops || !d_cigar)
         return refuse(BGSA_HIP_EINVAL, "a NULL pointer (only the workspace and the stream may be NULL)");
     if (n_pairs < 0) return refuse(BGSA_HIP_EINVAL, "n_pairs is negative");
@@ -276,6 +287,8 @@ int bgsa_hip_trace_pairs_dev(const bgsa_hip_params_t *params, const char *d_cont
     if (word_num != bgsa_hip_word_num(params->algo, ref_len, read_len, params->k))
         return refuse(BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(params->algo, ...)");
     if (word_num > kMaxWords) return refuse(BGSA_HIP_EUNSUPPORTED, "subjects beyond 1,024 bp (word_num > 32) are not covered");
+    if (d_read_lens && params->alignment != BGSA_ALIGN_GLOBAL)
+        return refuse(BGSA_HIP_EUNSUPPORTED, "per-subject lengths are traced in global mode only (semi-global buckets take subjects of one length)");
     // Myers scores -distance whatever the three ints hold (as the scoring calls: make_plan)
     const bool myers = params->algo == BGSA_ALGO_MYERS;
     const int match = myers ? 0 : params->match, mismatch = myers ? -1 : params->mismatch, gap = myers ? -1 : params->gap;
@@ -294,7 +307,7 @@ int bgsa_hip_trace_pairs_dev(const bgsa_hip_params_t *params, const char *d_cont
 
     TraceRun r{};
     r.args.p = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
-                        subject_base, d_score, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), nullptr};
+                        subject_base, d_score, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), nullptr, d_read_lens};
     r.args.span = d_span;
     r.args.match = match;
     r.args.mismatch = mismatch;

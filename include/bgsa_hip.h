@@ -297,6 +297,26 @@ int bgsa_hip_cal_align_score_ex(const bgsa_hip_params_t *params, const char *d_c
                                 int ref_start, int ref_end, int word_num,
                                 void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- subject buckets of mixed read lengths (GLOBAL modes: Myers -distance / +distance, BitPAl with every compiled set) ----
+ * A bucket whose subjects differ in length is preprocessed as ever — read_count rows of read_len + 1 bytes, read_len the
+ * LONGEST subject, every shorter one padded behind its own end with any bytes — and scored with d_read_lens: read_count
+ * int32 device entries, the length of every subject column, the padding columns up to the multiple of 64 included (give those
+ * read_len).  Pair (query, column c) then scores exactly as the query against the first d_read_lens[c] characters of the row:
+ * column j of a global DP depends on columns <= j only, so the rows run over the padded width and the score is formed under the
+ * lane's own length; what lies behind a subject's end never enters.  An entry is clamped to [0, read_len] inside the kernel
+ * (it forms a mask, never an address).  Queries keep ONE length per call: group them by length.
+ * d_read_lens == NULL is exactly bgsa_hip_cal_align_score_ex: same kernel, the certified Myers band included.  With lengths
+ * a Myers launch always runs full rows — the band's window schedule and limit certify one (m, n) — and leaves
+ * bgsa_hip_myers_band_stats() untouched.  Everything else (workspace, word_num = bgsa_hip_word_num(algo, ref_len, read_len, k),
+ * results layout, stream) is as there.
+ * BGSA_HIP_EUNSUPPORTED with non-NULL lengths, before anything is allocated or launched, bgsa_hip_last_error() naming the
+ * reason: the banded filter; either semi-global mode; word_num > 32; a BitPAl set whose register-resident kernel does not
+ * reach word_num words. */
+int bgsa_hip_cal_align_score_lens_ex(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                                     void *d_results, const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count,
+                                     int ref_start, int ref_end, int word_num,
+                                     void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- hit selection: the K best subjects per query, or every subject within a cutoff, from a score tile in HBM ----
  * d_results = a score tile as the scoring calls write it: n_queries rows of row_stride elements of elem_bytes bytes
  * (2: int16 of Myers / BitPAl, 1: int8 of the banded filter).  Only columns [0, valid_count) are candidates: the columns
@@ -378,6 +398,14 @@ int bgsa_hip_myers_align_pairs_dev(const char *d_content, const hip_read_t *d_pe
                                    int n_queries, int64_t subject_base,
                                    int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
                                    void *d_workspace, size_t workspace_bytes, void *stream);
+/* The same for a bucket of mixed subject lengths (bgsa_hip_cal_align_score_lens_ex): d_read_lens[column] is the pair's n, so the
+ * script consumes exactly ref_len query and d_read_lens[column] subject characters.  NULL: the call above. */
+int bgsa_hip_myers_align_pairs_lens_dev(const char *d_content, const hip_read_t *d_peq, const int32_t *d_read_lens,
+                                        int ref_len, int read_len, int64_t read_count, int word_num,
+                                        const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs,
+                                        int n_queries, int64_t subject_base,
+                                        int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
+                                        void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---- score, span and edit script of selected pairs, for every aligner that has an alignment to report ----
  * What bgsa_hip_myers_align_pairs_dev does for Myers global, for: BitPAl with ANY score set (compiled in or not), global;
@@ -422,6 +450,14 @@ int bgsa_hip_trace_pairs_dev(const bgsa_hip_params_t *params, const char *d_cont
                              int n_queries, int64_t subject_base,
                              int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
                              void *d_workspace, size_t workspace_bytes, void *stream);
+/* The same for a bucket of mixed subject lengths, GLOBAL mode only (semi-global with lengths: BGSA_HIP_EUNSUPPORTED): the pair's
+ * n is d_read_lens[column], the span reports s_end = that length.  NULL: the call above. */
+int bgsa_hip_trace_pairs_lens_dev(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                                  const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count, int word_num,
+                                  const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs,
+                                  int n_queries, int64_t subject_base,
+                                  int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
+                                  void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
