@@ -23,6 +23,7 @@ LIB_AB_PATH = HERE / "libbgsa_hip_ab.so"
 INCLUDE = HERE.parent / "include" / "bgsa_hip.h"
 
 ALGO_MYERS, ALGO_BANDED, ALGO_BITPAL = 0, 1, 2
+DISTANCE_BEYOND = -2   # BGSA_HIP_DISTANCE_BEYOND: align_pairs_banded's distance of a pair beyond max_distance
 V_NUM = 64
 
 _lib = None
@@ -105,6 +106,15 @@ def lib() -> ctypes.CDLL:
                         ("bgsa_hip_trace_pairs_lens_dev", [pp, vp, vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, sz, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = types
+    # band-limited pair alignment (the same: an older build lacks it)
+    for name, types, restype in (("bgsa_hip_align_pairs_band_words", [i32, i32, i32], i32),
+                                 ("bgsa_hip_align_pairs_banded_min_workspace_bytes", [i32, i32, i32], sz),
+                                 ("bgsa_hip_align_pairs_banded_workspace_bytes", [i32, i32, i32, i64], sz),
+                                 ("bgsa_hip_myers_align_pairs_banded_dev",
+                                  [vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, i32, vp, vp, vp, i32, vp, sz, vp], i32)):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = restype
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -440,32 +450,13 @@ class DeviceAligner:
         number of runs even beyond the cap.  workspace_bytes: None = what all pairs need in one pass (at most 1 GiB), a
         size from bgsa_hip_align_pairs_min_workspace_bytes() up = that much (more chunks), 0 = the library's own scratch.
         Myers global only: any other aligner raises, and so does (0, 1, 1) +distance — the alignment is the same."""
-        torch = self.torch
-        if self.algo != ALGO_MYERS or self.semi_global or self.scores == (0, 1, 1):
-            raise BgsaHipError("align_pairs: rc=-2: only Myers unit-cost global alignment is traced back (no semi-global mode, no "
-                               "BitPAl score sets, no banded filter; +distance aligns the same as -distance: use that aligner)")
-        pq = torch.as_tensor(pair_queries).to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
-        ps = torch.as_tensor(pair_subjects).to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
-        if pq.numel() != ps.numel():
-            raise BgsaHipError("align_pairs: pair_queries and pair_subjects differ in length")
-        n = pq.numel()
-        cap = self.qlen + self.slen if cigar_cap is None else int(cigar_cap)
-        if cap < 1:
-            raise BgsaHipError("align_pairs: rc=-1: cigar_cap is not positive")
-        shapes = [((n,), torch.int32), ((n,), torch.int32), ((n, cap), torch.int32)]
-        if into is None:
-            distance, n_ops, cigar = (torch.full(shape, fill, dtype=dtype, device=self.device) for (shape, dtype), fill in zip(shapes, (-1, 0, 0)))
-        else:
-            (distance, n_ops, cigar), _ = self._hit_lists(into, shapes, "align_pairs")
+        self._myers_global_only("align_pairs")
+        pq, ps, n, cap, (distance, n_ops, cigar) = self._pair_lists("align_pairs", pair_queries, pair_subjects, cigar_cap, into)
         if n == 0:
             return distance, n_ops, cigar
         if workspace_bytes is None:
             workspace_bytes = int(lib().bgsa_hip_align_pairs_workspace_bytes(self.qlen, self.slen, n))
-        work, work_bytes = None, 0
-        if workspace_bytes:
-            if getattr(self, "d_align_work", None) is None or self.d_align_work.numel() < workspace_bytes:
-                self.d_align_work = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
-            work, work_bytes = self.d_align_work.data_ptr(), int(workspace_bytes)
+        work, work_bytes = self._align_workspace(workspace_bytes)
         if self.d_lens is not None:
             check(lib().bgsa_hip_myers_align_pairs_lens_dev(self.d_content.data_ptr(), self.d_peq.data_ptr(), self.d_lens.data_ptr(),
                                                             self.qlen, self.slen, self.ns, self.wn, pq.data_ptr(), ps.data_ptr(), n,
@@ -483,21 +474,99 @@ class DeviceAligner:
         """align_pairs for the subjects[nq, K] tensor of top_hits / threshold_hits: row q holds subjects of query q (the
         query index is built on the device).  Returns (distance[nq, K], n_ops[nq, K], cigar[nq, K, cap]); unused slots
         (subject -1) keep distance -1, n_ops 0.  into= the triple of an earlier call, for walking buckets."""
+        pq, ps, cigar_cap, into, (nq, k) = self._hits_as_pairs("align_hits", hit_subjects, cigar_cap, into)
+        distance, n_ops, cigar = self.align_pairs(pq, ps, cigar_cap, subject_base, into, workspace_bytes)
+        return distance.view(nq, k), n_ops.view(nq, k), cigar.view(nq, k, -1)
+
+    # what align_pairs / align_hits and their band-limited counterparts share: the refusal, the lists, the workspace
+    def _myers_global_only(self, what: str) -> None:
+        if self.algo != ALGO_MYERS or self.semi_global or self.scores == (0, 1, 1):
+            raise BgsaHipError(f"{what}: rc=-2: only Myers unit-cost global alignment is traced back (no semi-global mode, no "
+                               "BitPAl score sets, no banded filter; +distance aligns the same as -distance: use that aligner)")
+
+    def _pair_lists(self, what: str, pair_queries, pair_subjects, cigar_cap, into):
+        """(pair queries int32[n], pair subjects int64[n], n, cap, (distance, n_ops, cigar)): the outputs fresh (-1 / 0 / 0) or the
+        caller's `into`, checked."""
+        torch = self.torch
+        pq = torch.as_tensor(pair_queries).to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        ps = torch.as_tensor(pair_subjects).to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+        if pq.numel() != ps.numel():
+            raise BgsaHipError(f"{what}: pair_queries and pair_subjects differ in length")
+        n = pq.numel()
+        cap = self.qlen + self.slen if cigar_cap is None else int(cigar_cap)
+        if cap < 1:
+            raise BgsaHipError(f"{what}: rc=-1: cigar_cap is not positive")
+        shapes = [((n,), torch.int32), ((n,), torch.int32), ((n, cap), torch.int32)]
+        if into is None:
+            outs = tuple(torch.full(shape, fill, dtype=dtype, device=self.device) for (shape, dtype), fill in zip(shapes, (-1, 0, 0)))
+        else:
+            outs, _ = self._hit_lists(into, shapes, what)
+        return pq, ps, n, cap, tuple(outs)
+
+    def _align_workspace(self, workspace_bytes: int):
+        """(device pointer, bytes) of the aligner's own pair workspace grown to workspace_bytes; (None, 0) = the library's scratch."""
+        if not workspace_bytes:
+            return None, 0
+        if getattr(self, "d_align_work", None) is None or self.d_align_work.numel() < workspace_bytes:
+            self.d_align_work = self.torch.empty(int(workspace_bytes), dtype=self.torch.uint8, device=self.device)
+        return self.d_align_work.data_ptr(), int(workspace_bytes)
+
+    def _hits_as_pairs(self, what: str, hit_subjects, cigar_cap, into):
+        """A subjects[nq, K] tensor as a pair list: (pair queries, pair subjects, cigar_cap, into flattened, (nq, K))."""
         torch = self.torch
         hs = torch.as_tensor(hit_subjects).to(device=self.device, dtype=torch.int64)
         if hs.dim() != 2 or hs.shape[0] != self.nq:
-            raise BgsaHipError(f"align_hits: hit_subjects must be [nq = {self.nq}, K]")
+            raise BgsaHipError(f"{what}: hit_subjects must be [nq = {self.nq}, K]")
         nq, k = hs.shape
         pq = torch.arange(nq, dtype=torch.int32, device=self.device).repeat_interleave(k)
         if into is not None:
             into = list(into)
             if len(into) != 3 or any(not t.is_contiguous() for t in into) or tuple(into[0].shape) != (nq, k) or \
                     tuple(into[1].shape) != (nq, k) or into[2].dim() != 3 or tuple(into[2].shape[:2]) != (nq, k):
-                raise BgsaHipError(f"align_hits: into= needs contiguous tensors of shape ({nq}, {k}), ({nq}, {k}), ({nq}, {k}, cap)")
+                raise BgsaHipError(f"{what}: into= needs contiguous tensors of shape ({nq}, {k}), ({nq}, {k}), ({nq}, {k}, cap)")
             if cigar_cap is None:
                 cigar_cap = into[2].shape[2]
             into = (into[0].view(-1), into[1].view(-1), into[2].view(nq * k, -1))
-        distance, n_ops, cigar = self.align_pairs(pq, hs.contiguous().view(-1), cigar_cap, subject_base, into, workspace_bytes)
+        return pq, hs.contiguous().view(-1), cigar_cap, into, (nq, k)
+
+    # ---- the same within a distance bound, subjects of any length (bgsa_hip_myers_align_pairs_banded_dev) ------------------
+    def align_pairs_banded(self, pair_queries, pair_subjects, max_distance: int, cigar_cap=None, subject_base: int = 0, into=None,
+                           workspace_bytes=None):
+        """align_pairs with the history limited to the band of max_distance: subjects of any length the scoring kernels
+        take.  Same tensors and ownership rules; a pair whose distance is <= max_distance gets exactly align_pairs'
+        distance, n_ops and runs, any other owned pair distance DISTANCE_BEYOND (-2), n_ops 0 and an untouched cigar row.
+        max_distance is what the caller already knows: the cutoff of threshold_hits, the worst distance of top_hits.
+        workspace_bytes: None = what all pairs need in one pass (at most 1 GiB), a size from
+        bgsa_hip_align_pairs_banded_min_workspace_bytes() up = that much (more chunks), 0 = the library's own scratch.
+        Myers global only, one subject length per bucket (no set_subjects_ragged)."""
+        self._myers_global_only("align_pairs_banded")
+        if self.d_lens is not None:
+            raise BgsaHipError("align_pairs_banded: rc=-2: a bucket of mixed read lengths has no band-limited variant (one (m, n) "
+                               "per window schedule): use align_pairs up to 1,024 bp")
+        max_distance = min(int(max_distance), 2 ** 31 - 1)
+        if max_distance < 0:
+            raise BgsaHipError("align_pairs_banded: rc=-1: max_distance is negative")
+        pq, ps, n, cap, (distance, n_ops, cigar) = self._pair_lists("align_pairs_banded", pair_queries, pair_subjects, cigar_cap, into)
+        if n == 0:
+            return distance, n_ops, cigar
+
+        def call(n_pairs, work, work_bytes):
+            check(lib().bgsa_hip_myers_align_pairs_banded_dev(self.d_content.data_ptr(), self.d_peq.data_ptr(), self.qlen, self.slen, self.ns,
+                                                              self.wn, pq.data_ptr(), ps.data_ptr(), n_pairs, self.nq, int(subject_base),
+                                                              max_distance, distance.data_ptr(), n_ops.data_ptr(), cigar.data_ptr(), cap,
+                                                              work, work_bytes, self._stream()),
+                  "myers_align_pairs_banded_dev")
+        if workspace_bytes is None:
+            call(0, None, 0)   # an empty list runs the C call's checks alone: a window too wide is refused before a workspace is allocated for it
+            workspace_bytes = int(lib().bgsa_hip_align_pairs_banded_workspace_bytes(self.qlen, self.slen, max_distance, n))
+        call(n, *self._align_workspace(workspace_bytes))
+        return distance, n_ops, cigar
+
+    def align_hits_banded(self, hit_subjects, max_distance: int, cigar_cap=None, subject_base: int = 0, into=None, workspace_bytes=None):
+        """align_pairs_banded for the subjects[nq, K] tensor of top_hits / threshold_hits, as align_hits is for align_pairs:
+        (distance[nq, K], n_ops[nq, K], cigar[nq, K, cap]); unused slots (subject -1) keep distance -1, n_ops 0."""
+        pq, ps, cigar_cap, into, (nq, k) = self._hits_as_pairs("align_hits_banded", hit_subjects, cigar_cap, into)
+        distance, n_ops, cigar = self.align_pairs_banded(pq, ps, max_distance, cigar_cap, subject_base, into, workspace_bytes)
         return distance.view(nq, k), n_ops.view(nq, k), cigar.view(nq, k, -1)
 
     # ---- score, span and edit script of selected pairs, every aligner with an alignment (bgsa_hip_trace_pairs_dev) --------
@@ -689,6 +758,27 @@ def align_top_alignments(queries: np.ndarray, subjects: np.ndarray, k_best: int,
     text = cigar_strings(n_ops, cigar)
     k = subj.shape[1]
     cigars = [[text[q * k + r] if subj[q, r] >= 0 else None for r in range(k)] for q in range(subj.shape[0])]
+    return hit_scores.cpu().numpy(), subj, cigars
+
+
+def align_top_alignments_banded(queries: np.ndarray, subjects: np.ndarray, k_best: int, max_distance=None, device: str = "cuda:0",
+                                block_rows: int = 1000, cigar_cap=None):
+    """align_top_alignments for subjects of any length: the k_best best subjects per query and their alignments within
+    max_distance, as (scores[nq, K] int32, subjects[nq, K] int64, cigars); cigars[q][r] is None for an unused slot and for
+    a hit beyond max_distance.  max_distance=None: the worst distance in the hit lists, so that every hit is aligned —
+    one scalar read back from the device, the only synchronisation before the results are copied out."""
+    a = DeviceAligner(ALGO_MYERS, device)
+    a.set_queries(queries)
+    a.set_subjects(subjects)
+    hit_scores, hit_subjects = a.top_hits(k_best, block_rows=block_rows)
+    if max_distance is None:
+        max_distance = -int(a.torch.where(hit_subjects >= 0, hit_scores, a.torch.zeros_like(hit_scores)).min().item())
+    distance, n_ops, cigar = a.align_hits_banded(hit_subjects, max_distance, cigar_cap=cigar_cap)
+    a.check_faults()
+    subj, dist = hit_subjects.cpu().numpy(), distance.cpu().numpy()
+    text = cigar_strings(n_ops, cigar)
+    k = subj.shape[1]
+    cigars = [[text[q * k + r] if subj[q, r] >= 0 and dist[q, r] >= 0 else None for r in range(k)] for q in range(subj.shape[0])]
     return hit_scores.cpu().numpy(), subj, cigars
 
 

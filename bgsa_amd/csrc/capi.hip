@@ -588,11 +588,12 @@ int bgsa_hip_stream_faults(int clear)
     BGSA_HIP_TRY(hipMemcpy(&value, word, sizeof value, hipMemcpyDeviceToHost));
     if (value && clear) BGSA_HIP_TRY(hipMemset(word, 0, sizeof value));
     if (value) {
-        char msg[260];
-        snprintf(msg, sizeof msg, "stream fault on device %d: flags 0x%x (%s%s%s) — at least one query was not scored", dev, value,
+        char msg[340];
+        snprintf(msg, sizeof msg, "stream fault on device %d: flags 0x%x (%s%s%s%s) — at least one query was not scored", dev, value,
                  (value & BGSA_HIP_FAULT_BUDGET) ? "window budget exhausted before END " : "",
                  (value & BGSA_HIP_FAULT_CODE) ? "byte that is no stream code dispatched " : "",
-                 (value & BGSA_HIP_FAULT_PAIR) ? "align_pairs / trace_pairs: query index outside [0, n_queries)" : "");
+                 (value & BGSA_HIP_FAULT_PAIR) ? "align_pairs / trace_pairs: query index outside [0, n_queries) " : "",
+                 (value & BGSA_HIP_FAULT_BAND) ? "align_pairs_banded: a traceback step left its block's window" : "");
         set_error_text(msg);
     }
     return static_cast<int>(value);

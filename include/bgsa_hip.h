@@ -407,6 +407,55 @@ int bgsa_hip_myers_align_pairs_lens_dev(const char *d_content, const hip_read_t 
                                         int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
                                         void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- band-limited history: the same edit scripts for subjects of ANY length, within a caller-given distance bound ----
+ * bgsa_hip_myers_align_pairs_dev keeps the whole subject in registers and a history of ref_len x 2 x word_num x 256 B per 64
+ * pairs: it stops at 1,024 bp.  Every caller of a pair call already holds a bound on the distance — the cutoff of its threshold
+ * hits, the worst score of its top hits — and a pair whose distance is <= B = max_distance has all its optimal paths inside the
+ * diagonal band |d| + |d - (n - m)| <= B, d = j - i (n = read_len, m = ref_len; the inequality the Myers scoring kernels certify
+ * their band with).  This call runs the rows on the words that hold the band only and keeps history for those words only; it
+ * takes every subject length the scoring calls take, short ones too (there it is a cross-check of the call above from another
+ * kernel, with a smaller workspace).  Myers unit-cost GLOBAL alignment; no mixed-length variant.
+ * THE RULE.  delta = n - m, dlo = -((B - delta) / 2), dhi = (delta + B) / 2 (C division; both numerators are >= 0 when
+ * |delta| <= B).  Rows run in blocks of 32: the block of 0-based rows i0 .. last - 1, i0 % 32 == 0, last = min(i0 + 32, m), has
+ * the WINDOW of words [a, b], a = (max(1, i0 + 1 + dlo) - 1) / 32, b = (min(n, last + dhi) - 1) / 32.  Every row of the block is
+ * the Myers row on exactly these words: the lowest window word takes the row-edge carry-ins (hp_in = 1, hn_in = 0, add-carry 0)
+ * whether or not a == 0, words left of the window keep their last deltas, words right of it their initial state (pv = ~0,
+ * mv = 0).  D' = m + the sum over all word_num words of popc(pv & mask) - popc(mv & mask) is the cost of a real path, so
+ * D' >= D, and D' <= B certifies D' = D: the pair is then traced back from (m, n) with the preference of the call above and
+ * gets that call's canonical script.  Otherwise the pair is beyond the bound.
+ * bgsa_hip_align_pairs_band_words: the widest block window of the shape in words, <= word_num; 0 for non-positive lengths, a
+ * negative max_distance, or |delta| > max_distance (no pair of that shape can be within the bound).
+ * Arguments, pair ownership (subject_base, the slot -1, pairs of other buckets untouched), BGSA_HIP_FAULT_PAIR for a query index
+ * out of range, the cigar format and the chunking (any workspace from the minimum up, whole waves per chunk, forward and
+ * traceback kernels one after the other on `stream`; with a caller workspace only kernel launches: capture safe) are those of
+ * bgsa_hip_myers_align_pairs_dev.  Per owned pair:
+ *   D <= max_distance: d_distance[p] = D, d_n_ops[p] = the TRUE number of runs even beyond cigar_cap, d_cigar[p * cigar_cap ...] =
+ *     the first min(n_ops, cigar_cap) runs — bit for bit what bgsa_hip_myers_align_pairs_dev writes where that call applies;
+ *   D >  max_distance — every pair when |delta| > max_distance, which is still BGSA_HIP_OK: d_distance[p] =
+ *     BGSA_HIP_DISTANCE_BEYOND, d_n_ops[p] = 0, the cigar row untouched.
+ * The workspace: one wave's slice = history (ref_len x 2 x band_words x 256 B) + state (2 x word_num x 256 B) + op bytes
+ * ((ref_len + read_len) x 64), rounded up to 256 = ..._banded_min_workspace_bytes(); ..._banded_workspace_bytes() = what all
+ * n_pairs need in one pass, at most BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE, never below one wave; NULL = the library's own grow-only
+ * scratch (not capture safe).  10,000 x 10,000 bp at max_distance 500: 17 words, 88 MB per wave instead of 1.6 GB.
+ * BGSA_HIP_EINVAL, checked in this order before the first HIP call: a NULL pointer (the workspace excepted), negative n_pairs,
+ * non-positive lengths / n_queries / cigar_cap, read_count not a positive multiple of 64, word_num other than
+ * bgsa_hip_word_num(BGSA_ALGO_MYERS, ...), a negative max_distance; then BGSA_HIP_EUNSUPPORTED: ref_len + read_len beyond
+ * 2^31 - 1 (the op bytes are counted in int), a window wider than the 32 words the kernels hold (bgsa_hip_last_error() names the largest max_distance the shape takes: 961 for 4,000 x 4,000 bp); then
+ * BGSA_HIP_EINVAL: a workspace below the minimum.  n_pairs == 0 is BGSA_HIP_OK once the checks pass and launches nothing.
+ * BGSA_HIP_FAULT_BAND (sticky, bgsa_hip_stream_faults()): a traceback step asked for a word outside its block's window; the
+ * step is not read, the pair keeps n_ops = 0.  By the rule this cannot happen for a certified pair: the bit means a bug, never
+ * an input. */
+#define BGSA_HIP_DISTANCE_BEYOND (-2)
+int bgsa_hip_align_pairs_band_words(int ref_len, int read_len, int max_distance);
+size_t bgsa_hip_align_pairs_banded_min_workspace_bytes(int ref_len, int read_len, int max_distance);
+size_t bgsa_hip_align_pairs_banded_workspace_bytes(int ref_len, int read_len, int max_distance, int64_t n_pairs);
+int bgsa_hip_myers_align_pairs_banded_dev(const char *d_content, const hip_read_t *d_peq,
+                                          int ref_len, int read_len, int64_t read_count, int word_num,
+                                          const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs,
+                                          int n_queries, int64_t subject_base, int max_distance,
+                                          int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
+                                          void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- score, span and edit script of selected pairs, for every aligner that has an alignment to report ----
  * What bgsa_hip_myers_align_pairs_dev does for Myers global, for: BitPAl with ANY score set (compiled in or not), global;
  * BitPAl semi-global (query end to end, free subject overhangs); Myers semi-global (subject end to end inside the query); and
@@ -473,6 +522,8 @@ int bgsa_hip_trace_pairs_lens_dev(const bgsa_hip_params_t *params, const char *d
 /* bgsa_hip_myers_align_pairs_dev / bgsa_hip_trace_pairs_dev: a pair this call owned named a query outside [0, n_queries); that pair was skipped (an
  * argument check inside the kernel, not a damaged stream — the other pairs of the call are good). */
 #define BGSA_HIP_FAULT_PAIR 4
+/* bgsa_hip_myers_align_pairs_banded_dev: a traceback step left its block's window (a bug guard, see there). */
+#define BGSA_HIP_FAULT_BAND 8
 int bgsa_hip_stream_faults(int clear);
 int bgsa_hip_debug_inject_stream_fault(int kind);
 
