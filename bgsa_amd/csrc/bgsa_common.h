@@ -100,6 +100,8 @@ int launch_myers(const ScoreArgs &a, int semi_global = 0);
 // The name of the kernel the knobs select for a launch with at least two subject groups (no read count here: a bucket of
 // ONE group of <= 64 bp subjects runs <NW, 1> where this says <NW, 2>).
 const char *myers_kernel_name(int word_num, int semi_global = 0);
+// Subject groups per wave (1 | 2) of a global Myers launch on the certified band: myers_select's answer for this bucket (host only).
+int myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_len, int mixed_lengths);
 
 // Packed query stream (one per query, 8-byte windows): codes 0..4 = A C G T N row, 5 = END,
 // 6 = REFILL.  Window i < n_windows-1 holds characters 7i..7i+6 and a REFILL; the last window

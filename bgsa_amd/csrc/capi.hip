@@ -607,6 +607,12 @@ int bgsa_hip_myers_band_half(int ref_len, int read_len)
     return band_schedule(ref_len, read_len, h, (read_len + 31) / 32, &s) ? h : 0;
 }
 
+int bgsa_hip_myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_len, int mixed_lengths)
+{
+    if (word_num <= 0 || read_count < 0 || ref_len <= 0 || read_len <= 0) return BGSA_HIP_EINVAL;
+    return myers_band_groups(word_num, read_count, ref_len, read_len, mixed_lengths);
+}
+
 int bgsa_hip_myers_band_stream(const char *mapped_row, int ref_len, int read_len, unsigned char *dst, int cap)
 {
     if (!mapped_row || ref_len <= 0 || read_len <= 0) return BGSA_HIP_EINVAL;

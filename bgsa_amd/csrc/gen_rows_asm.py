@@ -66,6 +66,11 @@ def ilp_planes(body: R.Body) -> R.Body:      # BGSA_GEN_MYERS_ILP_PLANES=1: the 
 MYERS_PLANES_SPLIT = int(os.environ.get("BGSA_GEN_MYERS_PLANES_SPLIT", "0"))   # A/B: the code-plane rows of 30 / 32 words with the chains in turns
 MYERS_PEQ_BLOCK_NW = [12, 14, 16, 18, 20]  # column blocks with resident Peq planes (20 words: 238 VGPRs; 22 would need 256)
 MYERS_BAND_NW = list(range(3, R.MYERS_BAND_MAX_WORDS + 1))   # windowed rows of the certified band (gen_band_function): 65..256 bp
+MYERS_BAND_PAIR_NW = [3, 4, 5]   # ... with two subject groups per wave behind every dispatch, REFILL and SETWIN (65..160 bp)
+# the scheduler's window for the two-group band bodies: how far the second group's instructions may move into the first group's wait states
+# (full rows of 3 / 4 / 5 words, temporaries and hazard nops: window 8: 7 / 8 / 10 and 2 / 1 / 1 — the one-group bodies hold 6 / 8 / 10 and 2 / 2 / 1;
+# 16: 10 / 11 / 12 and 2 / 3 / 2; 24: 11 / 14 / 15 and 0 / 2 / 2.  Every temporary beyond the one-group count is a VGPR of the 96 that five waves per SIMD allow.)
+MYERS_BAND_PAIR_WINDOW = int(os.environ.get("BGSA_GEN_MYERS_BAND_PAIR_WINDOW", "8"))
 MYERS_PAIR_NW = [1, 2]  # two rows per stream token: the 10-20 VALU row cannot hide the scalar dispatch
 MYERS_PLANES_NW = [10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32]  # at most one padding word
 MYERS_SEMI_PLANES_NW = [26, 28, 30, 32]  # semi-global beyond the resident Peq planes (24 words), up to 1024 bp
@@ -234,17 +239,25 @@ __device__ __forceinline__ int {fn_name}<{template_args}>(uint32_t (&state)[{n_s
 """
 
 
-def gen_band_function(nw: int) -> str:
+def gen_band_function(nw: int, groups: int = 1) -> str:
     """Row loop of the certified band (rows_ir.py: myers_window_body): one slot group per window [a, b] of
     the nw words, in the order of rows_ir.myers_window_index.  A group is the plain loop's eight slots — five row bodies of
     that window, END, REFILL — and SETWIN (code 7) in place of the fail slot: it reads the window byte that follows and moves
     the dispatch base to that window's group.  Every slot has the stride of the full window's slot (the shorter bodies are
     padded, never executed), so the dispatch is the plain loop's.  %[band] = 0 makes every SETWIN pick the full window: the
-    same stream then runs full rows (the certificate's fallback).  A window byte past the last group leaves with S_LEFT = -2."""
+    same stream then runs full rows (the certificate's fallback).  A window byte past the last group leaves with S_LEFT = -2.
+    groups = 2: every body is the window of TWO subject groups (rows_ir.myers_window_body(groups = 2)): the same slots, stride
+    rule, SETWIN / REFILL / END code and stream, twice the vector work behind each of them."""
     windows = [(a, b) for a in range(nw) for b in range(a, nw)]
     assert all(R.myers_window_index(nw, a, b) == k for k, (a, b) in enumerate(windows))
     k_full = R.myers_window_index(nw, 0, nw - 1)
-    full = ilp(R.myers_body(nw, 1, balanced=MYERS_BALANCED))
+    def sched(body: R.Body) -> R.Body:
+        if groups == 1:
+            return ilp(body)
+        return R.schedule_ilp(body, MYERS_ILP[0], MYERS_BAND_PAIR_WINDOW, *MYERS_ILP[2:3]) if MYERS_ILP[0] > 0 else body
+
+    full = sched(R.myers_body(nw, 1, balanced=MYERS_BALANCED) if groups == 1 else
+                 R.myers_window_body(nw, 0, nw - 1, groups=groups, balanced=MYERS_BALANCED))
     slot_of, n_slots = full.allocate_temps()
     stride = f"(L_g{k_full}s1_%= - L_g{k_full}s0_%=)"
 
@@ -283,7 +296,7 @@ def gen_band_function(nw: int) -> str:
     ]
     asm += disp()
     for k, (a, b) in enumerate(windows):
-        body = full if (a, b) == (0, nw - 1) else ilp(R.myers_window_body(nw, a, b, balanced=MYERS_BALANCED))
+        body = full if (a, b) == (0, nw - 1) else sched(R.myers_window_body(nw, a, b, groups=groups, balanced=MYERS_BALANCED))
         slots, n = (slot_of, n_slots) if body is full else body.allocate_temps()
         assert n <= n_slots
         for c in range(5):
@@ -334,17 +347,17 @@ def gen_band_function(nw: int) -> str:
     asm += done()
 
     text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(2 * nw)]
+    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(2 * groups * nw)]
     outs += ['[left] "=s"(left)']
     outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
-    ins = [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(nw)]
+    ins = [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(groups * nw)]
     ins += ['[qp] "s"(stream)', '[nwin] "s"(n_windows)', '[band] "s"(band)']
     clob = ", ".join(f'"{c}"' for c in CLOBBERS)
     return f"""
 // {len(windows)} windows; full rows {full.valu_count()} VALU, {n_slots} temporaries
 template <>
-__device__ __forceinline__ int myers_band_rows_asm<{nw}>(uint32_t (&state)[{2 * nw}],
-                                                  const uint32_t (&P)[5][{nw}],
+__device__ __forceinline__ int myers_band_rows_asm<{nw}, {groups}>(uint32_t (&state)[{2 * groups * nw}],
+                                                  const uint32_t (&P)[5][{groups * nw}],
                                                   const unsigned long long stream,
                                                   const int n_windows, const int band)
 {{
@@ -1608,12 +1621,14 @@ def band_inc_text() -> str:
     parts = ["// GENERATED by gen_rows_asm.py --band from rows_ir.py at build time — do not edit.\n",
              "// Certified band (DESIGN §4.2): the rows of one query on the band stream (myers_band.h), each row on the words of its\n"
              "// window only; band = 0: every row on all NW words (the fallback of a wave whose certificate failed).\n"
-             "template <int NW>\n"
-             "__device__ __forceinline__ int myers_band_rows_asm(uint32_t (&state)[2 * NW],\n"
-             "                                                    const uint32_t (&P)[5][NW],\n"
+             "// G = 2 (3..5 words): the same loop on two subject groups per wave, state[(g*NW+w)*2] and P[c][g*NW+w] as myers_rows_asm.\n"
+             "template <int NW, int G>\n"
+             "__device__ __forceinline__ int myers_band_rows_asm(uint32_t (&state)[2 * G * NW],\n"
+             "                                                    const uint32_t (&P)[5][G * NW],\n"
              "                                                    const unsigned long long stream, const int n_windows,\n"
              "                                                    const int band);\n"]
     parts += [gen_band_function(nw) for nw in MYERS_BAND_NW]
+    parts += [gen_band_function(nw, 2) for nw in MYERS_BAND_PAIR_NW]
     return "".join(parts)
 
 

@@ -171,6 +171,7 @@ __global__ __launch_bounds__(256) void myers_global_kernel(
 constexpr int kPeqMaxWords = 32;
 constexpr int kSemiPeqMaxWords = 32;  // widest semi-global kernel with resident Peq planes (myers_semi_rows_asm; 26..32 words: chains in turns, round 5)
 constexpr int kPairMaxWords = 2;  // widths instantiated as myers_pair_rows_asm (gen_rows_asm.py: MYERS_PAIR_NW)
+constexpr int kBandPairMaxWords = 5;  // widest band loop with two subject groups per wave (gen_rows_asm.py: MYERS_BAND_PAIR_NW = 3..5)
 #include "myers_rows_gen.inc"
 #include "_gen/myers_band_rows_gen.inc"   // the certified band's row loops (written by the Makefile: gen_rows_asm.py --band)
 
@@ -198,7 +199,8 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
     unsigned *__restrict__ task_counter, int band_limit = 0, unsigned long long *__restrict__ band_launch = nullptr,
     const int32_t *__restrict__ read_lens = nullptr)
 {
-    static_assert(!BAND || (G == 1 && NW >= kBandMinWords && NW <= kBandMaxWords), "band: one group, 3..8 words");
+    static_assert(!BAND || (NW >= kBandMinWords && NW <= kBandMaxWords && (G == 1 || (G == 2 && NW <= kBandPairMaxWords))),
+                  "band: 3..8 words, one subject group per wave — or two up to 5 words");
     static_assert(!(LENS && BAND), "the certified band is derived from one (m, n): a length-aware launch runs full rows");
     // LENS: the lane's length is loaded once per task and kept across the row loops, one VGPR per group — except beyond 8 words,
     // where the widths sit at their occupancy steps (20 words 238, 28 and 32 words 255 VGPRs): there the epilogue loads it again
@@ -264,72 +266,88 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
             const unsigned long long s =
                 reinterpret_cast<unsigned long long>(streams) + static_cast<unsigned long long>(q) * stream_stride_bytes;
             if constexpr (BAND) {
-                // one asm block for both passes: band = 0 runs the same stream with full rows
-                const int tried = band_on;
-                int band = band_on, score;
+                // one asm block for both passes: band = 0 runs the same stream with full rows.  G = 2: the wave carries two subject
+                // groups through every row; score and certificate are per group, the statistics stay in units of (64-subject group,
+                // query), and a second group past the end of the bucket (odd group count: zero masks) is neither stored, nor tested,
+                // nor counted.  One live group with a lane above B sends the WAVE — both groups — through the full rows.
+                const int n_live = G == 1 ? 1 : (group0 + 1 < n_groups ? 2 : 1);
+                const int tried = band_on * n_live;
+                int band = band_on, score[G];
                 for (;;) {
-                    const int left = myers_band_rows_asm<NW>(st, P, uniform_u64(s),
-                                                             __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2),
-                                                             __builtin_amdgcn_readfirstlane(band));
+                    const int left = myers_band_rows_asm<NW, G>(st, P, uniform_u64(s),
+                                                                __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2),
+                                                                __builtin_amdgcn_readfirstlane(band));
                     note_stream_fault(fault_word, left);
-                    score = ref_len;
 #pragma unroll
-                    for (int w = 0; w < NW; w++) {
-                        const int rem = read_len - 32 * w;
-                        const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
-                        score += __popc(st[2 * w] & m) - __popc(st[2 * w + 1] & m);
+                    for (int gi = 0; gi < G; gi++) {
+                        score[gi] = ref_len;
+#pragma unroll
+                        for (int w = 0; w < NW; w++) {
+                            const int rem = read_len - 32 * w;
+                            const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+                            score[gi] += __popc(st[2 * (gi * NW + w)] & m) - __popc(st[2 * (gi * NW + w) + 1] & m);
+                        }
                     }
-                    if (!band || __builtin_amdgcn_ballot_w64(score > band_limit) == 0) break;
+                    if (!band) break;
+                    int n_over = 0;   // live groups with a lane above B
+#pragma unroll
+                    for (int gi = 0; gi < G; gi++)
+                        if (gi < n_live && __builtin_amdgcn_ballot_w64(score[gi] > band_limit) != 0) n_over++;
+                    if (n_over == 0) break;
+                    if constexpr (G == 1) n_over = 1;   // (what it is: said so that the one-group kernels keep their code)
                     band = 0;   // a lane is not certified: the whole wave runs the query again with full rows
-                    unsigned long long r = 1, b = static_cast<unsigned long long>(unreported) + 1;
+                    unsigned long long r = static_cast<unsigned long long>(n_over),
+                                       b = static_cast<unsigned long long>(unreported) + n_live;
                     if (lane == 0) {
-                        r += atomicAdd(&band_launch[0], 1ull);
+                        r += atomicAdd(&band_launch[0], r);
                         b += atomicAdd(&band_launch[1], b);
                     }
                     r = uniform_u64(r);   // lane 0's values: the first active lane, as every lane is
                     b = uniform_u64(b);
-                    unreported = -1;   // this query is reported; banded += 1 below brings it to 0
+                    unreported = -n_live;   // this query is reported; banded += n_live below brings it to 0
                     if (b >= 64 && 8 * r > b) band_on = 0;
 #pragma unroll
-                    for (int w = 0; w < NW; w++) {
+                    for (int w = 0; w < G * NW; w++) {
                         st[2 * w] = ~0u;
                         st[2 * w + 1] = 0u;
                     }
                 }
                 unreported += tried;
-                dst[static_cast<size_t>(q) * ld] = static_cast<int16_t>(-score);
-                continue;
-            }
-            int left;
-            if constexpr (NW <= kPairMaxWords)  // short rows: two per stream token (launch_asm packs it so)
-                left = myers_pair_rows_asm<NW, G>(st, P, uniform_u64(s), __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2));
-            else
-                left = myers_rows_asm<NW, G>(st, P, uniform_u64(s), __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2));
-            note_stream_fault(fault_word, left);
 #pragma unroll
-            for (int gi = 0; gi < G; gi++) {
-                int score = ref_len;  // D[m][n] = m + sum over the n subject columns of (VP - VN)
-                int n_cols = read_len;   // LENS: the lane's own n
-                if constexpr (kLenPerQuery) {
-                    // (the lane number formed here: an address kept per lane across the row loop is two VGPRs these widths lack —
-                    // 28 words: 255 -> 326, 32 words: 255 -> 258, one wave per SIMD instead of two)
-                    unsigned lane_e;
-                    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
-                    n_cols = group0 + gi < n_groups ? lane_read_len(read_lens, static_cast<size_t>(group0 + gi) * kLanes + lane_e, read_len) : 0;
-                }
-                else if constexpr (LENS)
-                    n_cols = own_len[gi];
-                // (the NW masks depend on the task only: laundered, or the compiler forms them once per task and keeps NW more
-                // VGPRs across the row loop — 28 words: 255 -> 423)
-                if constexpr (LENS) asm volatile("" : "+v"(n_cols));
+                for (int gi = 0; gi < G; gi++)
+                    if (gi < n_live) dst[static_cast<size_t>(q) * ld + gi * kLanes] = static_cast<int16_t>(-score[gi]);
+            } else {
+                int left;
+                if constexpr (NW <= kPairMaxWords)  // short rows: two per stream token (launch_asm packs it so)
+                    left = myers_pair_rows_asm<NW, G>(st, P, uniform_u64(s), __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2));
+                else
+                    left = myers_rows_asm<NW, G>(st, P, uniform_u64(s), __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2));
+                note_stream_fault(fault_word, left);
 #pragma unroll
-                for (int w = 0; w < NW; w++) {
-                    const int rem = n_cols - 32 * w;
-                    const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
-                    score += __popc(st[2 * (gi * NW + w)] & m) - __popc(st[2 * (gi * NW + w) + 1] & m);
+                for (int gi = 0; gi < G; gi++) {
+                    int score = ref_len;  // D[m][n] = m + sum over the n subject columns of (VP - VN)
+                    int n_cols = read_len;   // LENS: the lane's own n
+                    if constexpr (kLenPerQuery) {
+                        // (the lane number formed here: an address kept per lane across the row loop is two VGPRs these widths lack —
+                        // 28 words: 255 -> 326, 32 words: 255 -> 258, one wave per SIMD instead of two)
+                        unsigned lane_e;
+                        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+                        n_cols = group0 + gi < n_groups ? lane_read_len(read_lens, static_cast<size_t>(group0 + gi) * kLanes + lane_e, read_len) : 0;
+                    }
+                    else if constexpr (LENS)
+                        n_cols = own_len[gi];
+                    // (the NW masks depend on the task only: laundered, or the compiler forms them once per task and keeps NW more
+                    // VGPRs across the row loop — 28 words: 255 -> 423)
+                    if constexpr (LENS) asm volatile("" : "+v"(n_cols));
+#pragma unroll
+                    for (int w = 0; w < NW; w++) {
+                        const int rem = n_cols - 32 * w;
+                        const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+                        score += __popc(st[2 * (gi * NW + w)] & m) - __popc(st[2 * (gi * NW + w) + 1] & m);
+                    }
+                    if (group0 + gi < n_groups)
+                        dst[static_cast<size_t>(q) * ld + gi * kLanes] = static_cast<int16_t>(-score);
                 }
-                if (group0 + gi < n_groups)
-                    dst[static_cast<size_t>(q) * ld + gi * kLanes] = static_cast<int16_t>(-score);
             }
         }
         if constexpr (DYN) task = resolve_wave_task(task_issued);
@@ -687,6 +705,7 @@ namespace {
 // (extra words are all-zero Peq and masked out of the score).
 using PeqWidths = Widths<1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20, 22, 24, 25, 26, 28, 30, 32>;
 using PairWidths = Widths<1, 2>;   // two rows per token and two subject groups per wave (kPairMaxWords)
+using BandPairWidths = Widths<3, 4, 5>;   // the certified band with two subject groups per wave (kBandPairMaxWords)
 // Code planes (myers_global_planes_kernel).  Below 29 words only BGSA_MYERS_PEQ_MAX_WORDS gets there (resident Peq planes
 // measured faster): those widths ship in the A/B flavour.
 using PlanesAbWidths = Widths<10, 12, 14, 16, 18, 20, 22, 24, 26, 28>;
@@ -699,7 +718,7 @@ using PeqBlockWidths = Widths<12, 14, 16, 18, 20>;
 using PlaneBlockWidths = Widths<12, 14, 16, 18, 20, 22, 24, 26, 28>;
 // The compiler-scheduled kernel (BGSA_MYERS_IMPL=c, A/B flavour).
 using CompilerWidths = Widths<1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32>;
-static_assert(kPairMaxWords == 2 && kPeqMaxWords == 32 && kSemiPeqMaxWords == 32, "the width lists above restate these");
+static_assert(kPairMaxWords == 2 && kBandPairMaxWords == 5 && kPeqMaxWords == 32 && kSemiPeqMaxWords == 32, "the width lists above restate these");
 
 // Queries per task.  Small enough that the grid has >> 256 CUs x 8 waves of tasks even for a
 // few thousand subjects, large enough that the 5*NW Peq loads are noise next to
@@ -728,6 +747,25 @@ static int pair_groups()
     }();
     return g;
 }
+
+// Subject groups per wave of the certified band's kernels, 65..160 bp (3..5 words).  Two groups share every dispatch, REFILL,
+// SETWIN, stream load and task — the scalar work that the windowed rows spread over 16..32 VALU instructions instead of 40 —
+// at five waves per SIMD instead of eight (LABNOTES §19).  BGSA_MYERS_BAND_GROUPS=1|2 forces the choice for every
+// banded bucket of at least two groups (A/B; read once); without it the bucket's size decides (kBandPairMinReads).
+static int band_groups_knob()
+{
+    static const int g = [] {
+        const char *e = getenv("BGSA_MYERS_BAND_GROUPS");
+        return (e && (e[0] == '1' || e[0] == '2') && e[1] == 0) ? e[0] - '0' : 0;
+    }();
+    return g;
+}
+// The smallest bucket (subjects) whose banded launch carries two groups per wave by default.  Measured, 2,000 queries x 150 bp,
+// kernel ms with one / two groups, two runs each (profiles/r09_band_groups_sweep.txt): 125k subjects 15.34, 15.38 / 15.10, 15.14
+// (-1.5 %); 250k 30.43, 30.48 / 29.88, 29.99 (-1.7 %); 500k 60.63, 60.64 / 59.65, 59.33 (-1.9 %); 1M 121.19, 121.01 / 117.76,
+// 117.52 (-2.9 %).  No crossover down to 125k: the gain shrinks with the bucket but stays ten times the run-to-run spread.
+// Smaller buckets were not measured and keep one group per wave.
+constexpr int64_t kBandPairMinReads = 125000;
 
 // Measurement knob: bytes of unused dynamic LDS per workgroup of the counter kernels — caps the waves per SIMD (160 KB of LDS
 // per CU: 40960 -> four workgroups = four waves per SIMD).  Round 4 asked whether the 150 bp kernel, which issues at 98 % of
@@ -783,6 +821,10 @@ int launch_asm(const ScoreArgs &a)
     // waves per SIMD with or without the task loop's registers)
     constexpr bool kCounter = NW <= 8 || NW >= 30;
     constexpr bool kPairs = NW <= kPairMaxWords;
+    // two subject groups per wave of the band loop (myers_select: large buckets of 65..160 bp): these widths have no two-group
+    // kernel on full-row streams, so the launch is banded or refused
+    constexpr bool kBandPair = G == 2 && !kPairs;
+    static_assert(!kBandPair || NW <= kBandPairMaxWords, "two groups per wave: the pair kernels, or the band up to 5 words");
     // A mixed-length bucket runs the LENS instantiation, of which a width has ONE: on the counter where the width has a counter
     // kernel (the default selection's choice for every launch long enough to matter; a short launch pays the counter's fixed
     // cost, and BGSA_DYNAMIC_TASKS=0 does not reach it), on the static grid elsewhere.  Full rows always: no band.
@@ -795,22 +837,29 @@ int launch_asm(const ScoreArgs &a)
         return BGSA_HIP_EUNSUPPORTED;
     }
     note_query_tile(plan.q_tile);
-    AsmKernel on_grid = myers_global_asm_kernel<NW, G, false>, on_counter = nullptr;
-    if constexpr (kCounter) on_counter = myers_global_asm_kernel<NW, G, true>;
-    if (lens) {
-        if constexpr (kCounter) on_grid = nullptr, on_counter = myers_global_asm_kernel<NW, G, true, false, true>;
-        else on_grid = myers_global_asm_kernel<NW, G, false, false, true>;
+    AsmKernel on_grid = nullptr, on_counter = nullptr;
+    if constexpr (!kBandPair) {
+        on_grid = myers_global_asm_kernel<NW, G, false>;
+        if constexpr (kCounter) on_counter = myers_global_asm_kernel<NW, G, true>;
+        if (lens) {
+            if constexpr (kCounter) on_grid = nullptr, on_counter = myers_global_asm_kernel<NW, G, true, false, true>;
+            else on_grid = myers_global_asm_kernel<NW, G, false, false, true>;
+        }
     }
     BandSchedule sched;
     int h = 0;
     bool band = false;
-    if constexpr (G == 1 && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
+    if constexpr ((G == 1 || kBandPair) && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
         h = band_half(a.ref_len, a.read_len);
         band = !lens && band_schedule(a.ref_len, a.read_len, h, NW, &sched);
         if (band) {
             on_grid = myers_global_asm_kernel<NW, G, false, true>;
             on_counter = myers_global_asm_kernel<NW, G, true, true>;
         }
+    }
+    if (kBandPair && !band) {   // myers_band_groups answers 2 for banded launches only
+        set_error_text("myers: two subject groups per wave selected for a launch without the certified band");
+        return BGSA_HIP_EUNSUPPORTED;
     }
     const int stride = static_cast<int>(band ? band_stream_stride(a.ref_len) : kPairs ? pair_stream_stride(a.ref_len) : stream_stride(a.ref_len));
     // the task counter sits behind the streams, and the band's guard pair 64 bytes further (both inside the kTaskCounterBytes
@@ -966,6 +1015,7 @@ namespace {
 enum class MyersFamily {
     kAsm,            // myers_global_asm_kernel<nw, 1>: resident Peq planes (the certified band where it applies)
     kAsmPairs,       // myers_global_asm_kernel<nw, 2>: <= 64 bp, two rows per token, two subject groups per wave
+    kAsmBandPairs,   // myers_global_asm_kernel<nw, 2>: 65..160 bp, the certified band with two subject groups per wave (large buckets)
     kSemiAsm,        // myers_semi_asm_kernel<nw>
     kPlanes,         // myers_global_planes_kernel<nw>
     kSemiPlanes,     // myers_semi_planes_kernel<nw>
@@ -981,10 +1031,24 @@ struct MyersChoice {
     const char *refused;   // not nullptr: this flavour of the library does not carry that kernel — the knob, as ab_knob_refused names it
 };
 
+// Groups per wave of a launch on resident Peq planes of width nw (global mode): 2 where the certified band applies to these
+// lengths, the width has a two-group band loop and the bucket is large enough (or BGSA_MYERS_BAND_GROUPS says so); else 1.
+// Lengths 0 (bgsa_hip_kernel_name: no launch in sight) answer 1, and so does its bucket of 128 reads: the name is the
+// small-bucket kernel's.
+int band_groups_for(int nw, int64_t read_count, int ref_len, int read_len, bool mixed_lengths)
+{
+    if (nw < kBandMinWords || nw > kBandPairMaxWords || mixed_lengths || read_count < 2 * kLanes || ref_len <= 0 || read_len <= 0) return 1;
+    BandSchedule sched;
+    if (!band_schedule(ref_len, read_len, band_half(ref_len, read_len), nw, &sched)) return 1;
+    if (band_groups_knob()) return band_groups_knob();
+    return read_count >= kBandPairMinReads ? 2 : 1;
+}
+
 // Precedence: BGSA_MYERS_IMPL=c first; then the alignment mode; global subjects beyond BGSA_MYERS_MAX_PLAIN_WORDS run as
 // column blocks in the form BGSA_MYERS_BLOCK_FORM names; the others on resident Peq planes up to BGSA_MYERS_PEQ_MAX_WORDS
-// (<= 64 bp: two groups per wave unless BGSA_MYERS_PAIR_GROUPS=1 or the bucket has one group only) and on the code planes beyond.
-MyersChoice myers_select(int word_num, int semi, int64_t read_count)
+// (<= 64 bp: two groups per wave unless BGSA_MYERS_PAIR_GROUPS=1 or the bucket has one group only; 65..160 bp: band_groups_for) and on
+// the code planes beyond.
+MyersChoice myers_select(int word_num, int semi, int64_t read_count, int ref_len = 0, int read_len = 0, bool mixed_lengths = false)
 {
     auto ab_only = [](const char *knob) -> const char * { return BGSA_AB_KERNELS ? nullptr : knob; };   // kernels of the A/B flavour
     MyersChoice c = {MyersFamily::kAsm, -1, 1, 0, semi != 0, nullptr};
@@ -1009,6 +1073,9 @@ MyersChoice myers_select(int word_num, int semi, int64_t read_count)
         else if (word_num <= kPairMaxWords && pair_groups() == 2 && read_count >= 2 * kLanes) {
             c.family = MyersFamily::kAsmPairs;
             c.G = 2;
+        } else if (band_groups_for(c.nw, read_count, ref_len, read_len, mixed_lengths) == 2) {
+            c.family = MyersFamily::kAsmBandPairs;
+            c.G = 2;
         }
     } else if (semi && word_num > myers_semi_max_plain_words()) {
         c.family = MyersFamily::kBlockedPeq;
@@ -1026,12 +1093,20 @@ MyersChoice myers_select(int word_num, int semi, int64_t read_count)
 
 }  // namespace
 
+int myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_len, int mixed_lengths)
+{
+    if (word_num < 1 || word_num > kMaxWords) return 1;
+    const MyersChoice c = myers_select(word_num, 0, read_count, ref_len, read_len, mixed_lengths != 0);
+    return c.family == MyersFamily::kAsmBandPairs ? 2 : 1;
+}
+
 const char *myers_kernel_name(int word_num, int semi_global)
 {
     static thread_local char name[64];
     const MyersChoice c = myers_select(word_num, semi_global, 2 * kLanes);   // "at least two groups": see bgsa_common.h
     switch (c.family) {
     case MyersFamily::kAsm:
+    case MyersFamily::kAsmBandPairs:
     case MyersFamily::kAsmPairs: snprintf(name, sizeof name, "myers_global_asm_kernel<%d, %d>", c.nw, c.G); break;
     case MyersFamily::kSemiAsm: snprintf(name, sizeof name, "myers_semi_asm_kernel<%d>", c.nw); break;
     case MyersFamily::kPlanes: snprintf(name, sizeof name, "myers_global_planes_kernel<%d>", c.nw); break;
@@ -1049,9 +1124,9 @@ const char *myers_kernel_name(int word_num, int semi_global)
 int launch_myers(const ScoreArgs &a, int semi_global)
 {
     if (a.ref_end <= a.ref_start || a.read_count == 0) return BGSA_HIP_OK;
-    const MyersChoice c = myers_select(a.word_num, semi_global, a.read_count);
+    const MyersChoice c = myers_select(a.word_num, semi_global, a.read_count, a.ref_len, a.read_len, a.d_read_lens != nullptr);
     if (c.refused) return ab_knob_refused(c.refused);
-    if (a.d_read_lens && c.family != MyersFamily::kAsm && c.family != MyersFamily::kAsmPairs) {
+    if (a.d_read_lens && c.family != MyersFamily::kAsm && c.family != MyersFamily::kAsmPairs) {   // (never kAsmBandPairs: no band on mixed lengths)
         set_error_text("myers: per-subject lengths are scored by myers_global_asm_kernel only (global mode, word_num <= 32, no "
                        "BGSA_MYERS_IMPL / BGSA_MYERS_PEQ_MAX_WORDS / BGSA_MYERS_MAX_PLAIN_WORDS alternative)");
         return BGSA_HIP_EUNSUPPORTED;
@@ -1061,6 +1136,8 @@ int launch_myers(const ScoreArgs &a, int semi_global)
         return PeqWidths::dispatch(c.nw, "myers_global_asm_kernel", [&](auto nw) { return launch_asm<decltype(nw)::value, 1>(a); });
     case MyersFamily::kAsmPairs:
         return PairWidths::dispatch(c.nw, "myers_global_asm_kernel (pairs)", [&](auto nw) { return launch_asm<decltype(nw)::value, 2>(a); });
+    case MyersFamily::kAsmBandPairs:
+        return BandPairWidths::dispatch(c.nw, "myers_global_asm_kernel (band, two groups)", [&](auto nw) { return launch_asm<decltype(nw)::value, 2>(a); });
     case MyersFamily::kSemiAsm:
         return PeqWidths::dispatch(c.nw, "myers_semi_asm_kernel", [&](auto nw) { return launch_semi_asm<decltype(nw)::value>(a); });
     case MyersFamily::kPlanes:

@@ -602,21 +602,26 @@ def myers_body(nw: int, groups: int = 1, split: int = 0, park: str = "sgpr", bal
 MYERS_BAND_MAX_WORDS = 8      # widths with windowed bodies (myers_band_rows_asm): 65..256 bp
 
 
-def myers_window_body(nw: int, a: int, b: int, balanced: bool = False) -> Body:
+def myers_window_body(nw: int, a: int, b: int, groups: int = 1, balanced: bool = False) -> Body:
     """myers_body(b - a + 1) on state words a..b of an nw-word row (S/E registers renumbered): the row-edge carry-ins
-    (0 into the addition, 1 into the HP shift) enter at word a."""
-    assert 0 <= a <= b < nw
+    (0 into the addition, 1 into the HP shift) enter at word a.
+    groups = G > 1: the same window of G subject groups, one after the other, registers laid out as myers_body(nw, G) lays
+    them out — S[(g*nw + w)*2], E[g*nw + w].  Each group's two carry chains stay whole: they share VCC, which orders them, so
+    a scheduler can only move the other group's chain-free instructions into a chain's wait states."""
+    assert 0 <= a <= b < nw and groups >= 1
     src = myers_body(b - a + 1, balanced=balanced)
-
-    def ren(x: str) -> str:
-        if x.startswith("S"):
-            return f"S{int(x[1:]) + 2 * a}"
-        if x.startswith("E"):
-            return f"E{int(x[1:]) + a}"
-        return x
-
     out = Body()
-    out.ops = [Op(op.kind, ren(op.dst), tuple(ren(s) for s in op.srcs), op.imm, op.dst2) for op in src.ops]
+    for g in range(groups):
+        def ren(x: str) -> str:
+            if x.startswith("S"):
+                return f"S{int(x[1:]) + 2 * (g * nw + a)}"
+            if x.startswith("E"):
+                return f"E{int(x[1:]) + g * nw + a}"
+            if g and x and not x.startswith("$"):      # the temporaries a0_<w>, m0_<w> of the one-group body
+                return f"{x[0]}{g}{x[2:]}"
+            return x
+
+        out.ops += [Op(op.kind, ren(op.dst), tuple(ren(s) for s in op.srcs), op.imm, op.dst2) for op in src.ops]
     return out
 
 
@@ -685,9 +690,10 @@ def myers_band_stream(codes, m: int, n: int, h: int, nw: int) -> bytes | None:
 
 
 def run_band_stream(nw: int, state: list, peq: np.ndarray, stream: bytes, band: bool = True, balanced: bool = False,
-                    schedule=None) -> int:
+                    schedule=None, groups: int = 1) -> int:
     """Interpret a band stream the way myers_band_rows_asm walks it (band = False: SETWIN keeps the full window; schedule:
-    the pass the generator applies to every body, gen_rows_asm.ilp); returns the number of word-rows executed."""
+    the pass the generator applies to every body, gen_rows_asm.ilp); returns the number of word-rows executed (per group).  groups = G: state and peq hold the
+    G groups of one wave, myers_body(nw, G)'s layout (peq[c, g*nw + w])."""
     windows = [(a, b) for a in range(nw) for b in range(a, nw)]
     bodies = {}
     cur = (0, nw - 1)
@@ -707,10 +713,10 @@ def run_band_stream(nw: int, state: list, peq: np.ndarray, stream: bytes, band: 
             continue
         assert c < 5
         if cur not in bodies:
-            bodies[cur] = myers_window_body(nw, *cur, balanced=balanced)
+            bodies[cur] = myers_window_body(nw, *cur, groups=groups, balanced=balanced)
             if schedule is not None:
                 bodies[cur] = schedule(bodies[cur])
-        bodies[cur].simulate(state, [peq[c, w] for w in range(nw)], cls=c)
+        bodies[cur].simulate(state, [peq[c, w] for w in range(groups * nw)], cls=c)
         rows += cur[1] - cur[0] + 1
         pos += 1
 

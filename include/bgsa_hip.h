@@ -556,10 +556,16 @@ int bgsa_hip_query_stream(int algo, const char *mapped_row, int ref_len, int k, 
  * bgsa_hip_myers_band_stream: the band stream of one mapped query row (host only, no GPU): the plain stream's codes plus
  * 7 = SETWIN + a window byte; writes at most `cap` bytes and returns its length, or 0 when the band is off for the shape.
  * bgsa_hip_myers_band_half: the half-width h a launch of these lengths uses (0: off).
- * bgsa_hip_myers_band_stats: the current device's counts since the last clear — out[0] = queries a wave ran again with full
- * rows, out[1] = queries a wave ran banded (call after synchronising). */
+ * bgsa_hip_myers_band_stats: the current device's counts since the last clear, in units of (64-subject group, query) whichever
+ * kernel ran — out[0] = group-queries with a score above B (their wave ran the query again with full rows), out[1] =
+ * group-queries run banded (call after synchronising).
+ * bgsa_hip_myers_band_groups: the subject groups a wave carries (1 | 2) in a global launch of word_num-word subjects, this bucket
+ * size and these lengths (mixed_lengths != 0: a bucket with per-subject lengths) — 2 only where the band applies, word_num <= 5
+ * and the bucket is large, or BGSA_MYERS_BAND_GROUPS=1|2 forces it (host only, no GPU).  bgsa_hip_kernel_name names the
+ * one-group kernel, the small bucket's. */
 int bgsa_hip_myers_band_stream(const char *mapped_row, int ref_len, int read_len, unsigned char *dst, int cap);
 int bgsa_hip_myers_band_half(int ref_len, int read_len);
+int bgsa_hip_myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_len, int mixed_lengths);
 int bgsa_hip_myers_band_stats(unsigned long long *out, int clear);
 
 /* Queries a wave scores per load of its subject block in this thread's last scoring launch (0: none yet).  The launch's
