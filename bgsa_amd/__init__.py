@@ -115,6 +115,14 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
+    # hit lists per subject (the same: an older build lacks them)
+    for name, types, restype in (("bgsa_hip_query_hits_workspace_bytes", [i32, i64, i32, i32], sz),
+                                 ("bgsa_hip_top_queries_dev", [vp, i32, i32, i64, i64, i32, i32, i32, i32, vp, vp, vp, sz, vp], i32),
+                                 ("bgsa_hip_threshold_queries_dev",
+                                  [vp, i32, i32, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp], i32)):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = restype
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -441,6 +449,76 @@ class DeviceAligner:
                                                     scores[lo:hi].data_ptr(), subjects[lo:hi].data_ptr(),
                                                     self.d_hit_work.data_ptr(), self.d_hit_work.numel(), self._stream()), "threshold_hits_dev")
         return counts, scores, subjects
+
+    # ---- hit lists per subject: the same tile reduced along its columns (bgsa_hip_top_queries_dev) -------------------------
+    def _query_hit_work(self, block_rows: int, k_best: int):
+        need = int(lib().bgsa_hip_query_hits_workspace_bytes(max(1, min(int(block_rows), self.nq)), self.ns, 1 if self.algo == ALGO_BANDED else 2, k_best))
+        if getattr(self, "d_query_hit_work", None) is None or self.d_query_hit_work.numel() < need:
+            self.d_query_hit_work = self.torch.empty(max(need, 8), dtype=self.torch.uint8, device=self.device)
+        return self.d_query_hit_work
+
+    def top_queries(self, k_best: int, block_rows: int = 1000, smallest=None, query_base: int = 0, into=None):
+        """The k_best (1..64) best QUERIES per subject of the resident bucket, best first, ties to the smaller query id:
+        (scores[ns_real, K] int32, queries[ns_real, K] int32) device tensors; queries are query_base + index in this aligner's
+        query set, unused slots (fewer than K queries) hold -1 and the worst int32 of the direction.  The bucket is scored
+        block_rows queries at a time into one reused tile and every block joins the lists on the device
+        (bgsa_hip_top_queries_dev, accumulate from the second block on).  into=(scores, queries) of an earlier call: its
+        entries join the candidates with their ids as stored, so several query sets (set_queries, another query_base) end with
+        the K best overall.  Several subject buckets need no into=: their lists are concatenated.  smallest=None follows the
+        aligner."""
+        torch = self.torch
+        smallest = default_smallest(self.algo, self.scores) if smallest is None else bool(smallest)
+        k_best = int(k_best)
+        if not 1 <= k_best <= V_NUM:    # before any tensor is sized by it; the C call's own answer (BGSA_HIP_EUNSUPPORTED)
+            raise BgsaHipError(f"top_queries: rc=-2: k_best must lie in 1..{V_NUM}")
+        shape = (self.ns_real, k_best)
+        (scores, queries), accumulate = self._hit_lists(into, [(shape, torch.int32), (shape, torch.int32)], "top_queries")
+        work = self._query_hit_work(block_rows, k_best)
+        for lo, hi, tile in self._hit_blocks(block_rows):
+            check(lib().bgsa_hip_top_queries_dev(tile.data_ptr(), tile.element_size(), hi - lo, self.ns, self.ns_real, int(query_base) + lo,
+                                                 k_best, int(smallest), accumulate, scores.data_ptr(), queries.data_ptr(),
+                                                 work.data_ptr(), work.numel(), self._stream()), "top_queries_dev")
+            accumulate = 1
+        return scores, queries
+
+    def threshold_queries(self, cutoff: int, cap_per_subject: int, block_rows: int = 1000, smallest=None, query_base: int = 0, into=None):
+        """Every query at least as good as `cutoff`, per subject of the resident bucket in ascending query order:
+        (counts[ns_real] int32, scores[ns_real, cap] int32, queries[ns_real, cap] int32) device tensors.  counts are the true
+        numbers of hits even beyond cap_per_subject; a subject that overflows keeps its cap_per_subject lowest-indexed hits,
+        slots behind a subject's hits are left as they were.  into=(counts, scores, queries) of an earlier call: this query
+        set's hits are appended behind them."""
+        torch = self.torch
+        smallest = default_smallest(self.algo, self.scores) if smallest is None else bool(smallest)
+        cap = int(cap_per_subject)
+        if not 1 <= cap < 2 ** 31:
+            raise BgsaHipError("threshold_queries: rc=-1: cap_per_subject is not a positive int32")
+        (counts, scores, queries), accumulate = self._hit_lists(
+            into, [((self.ns_real,), torch.int32), ((self.ns_real, cap), torch.int32), ((self.ns_real, cap), torch.int32)], "threshold_queries")
+        work = self._query_hit_work(block_rows, 1)
+        for lo, hi, tile in self._hit_blocks(block_rows):
+            check(lib().bgsa_hip_threshold_queries_dev(tile.data_ptr(), tile.element_size(), hi - lo, self.ns, self.ns_real,
+                                                       int(query_base) + lo, int(cutoff), int(smallest), accumulate, cap, counts.data_ptr(),
+                                                       scores.data_ptr(), queries.data_ptr(), work.data_ptr(), work.numel(),
+                                                       self._stream()), "threshold_queries_dev")
+            accumulate = 1
+        return counts, scores, queries
+
+    def query_hits_as_pairs(self, hit_queries, subject_base: int = 0):
+        """The queries[ns_real, K] tensor of top_queries / threshold_queries as a pair list, built on the device:
+        (pair_queries int32[ns_real * K], pair_subjects int64[ns_real * K]); entry [c, r] becomes the pair (hit_queries[c, r],
+        subject_base + c).  An unused slot (query -1) becomes query 0 with subject -1, which align_pairs, align_pairs_banded and
+        trace_pairs skip (a negative query on an owned pair would raise BGSA_HIP_FAULT_PAIR).  Both vectors go to those calls
+        unchanged; their outputs reshape to [ns_real, K, ...].  Slots of threshold_queries behind a subject's count hold
+        whatever the caller put there: fill the tensor with -1 first (into=)."""
+        torch = self.torch
+        hq = torch.as_tensor(hit_queries).to(device=self.device)
+        if hq.dim() != 2 or hq.shape[0] != self.ns_real or hq.dtype not in (torch.int32, torch.int64):
+            raise BgsaHipError(f"query_hits_as_pairs: hit_queries must be an integer tensor [ns_real = {self.ns_real}, K]")
+        used = hq >= 0
+        columns = torch.arange(self.ns_real, dtype=torch.int64, device=self.device).add_(int(subject_base)).unsqueeze(1).expand_as(hq)
+        pair_queries = torch.where(used, hq, torch.zeros_like(hq)).to(torch.int32).contiguous().view(-1)
+        pair_subjects = torch.where(used, columns, torch.full_like(columns, -1)).contiguous().view(-1)
+        return pair_queries, pair_subjects
 
     # ---- edit scripts of selected pairs (bgsa_hip_myers_align_pairs_dev) ----------------------------------------------
     def align_pairs(self, pair_queries, pair_subjects, cigar_cap=None, subject_base: int = 0, into=None, workspace_bytes=None):
@@ -814,3 +892,60 @@ def align_top_hits(queries: np.ndarray, subjects: np.ndarray, k_best: int, algo:
     hit_scores, hit_subjects = a.top_hits(k_best, block_rows=block_rows, smallest=smallest)
     a.check_faults()
     return hit_scores.cpu().numpy(), hit_subjects.cpu().numpy()
+
+
+def align_top_queries(queries: np.ndarray, subjects: np.ndarray, k_best: int, algo: int = ALGO_MYERS, k: int = 0,
+                      device: str = "cuda:0", scores=None, semi_global: bool = False, smallest=None,
+                      block_rows: int = 1000) -> tuple[np.ndarray, np.ndarray]:
+    """Convenience: the k_best best queries per SUBJECT as (scores[ns, K] int32, queries[ns, K] int32), selected on the
+    device block by block — the [nq, ns] score matrix is never built (DeviceAligner.top_queries)."""
+    a = DeviceAligner(algo, device, k, scores, semi_global)
+    a.set_queries(queries)
+    a.set_subjects(subjects)
+    hit_scores, hit_queries = a.top_queries(k_best, block_rows=block_rows, smallest=smallest)
+    a.check_faults()
+    return hit_scores.cpu().numpy(), hit_queries.cpu().numpy()
+
+
+def align_top_queries_ragged(queries: np.ndarray, subjects, k_best: int, algo: int = ALGO_MYERS, scores=None, device: str = "cuda:0",
+                             smallest=None, block_rows: int = 1000) -> tuple[np.ndarray, np.ndarray]:
+    """The k_best best queries per subject as (scores[ns, K] int32, queries[ns, K] int32) over subjects of mixed lengths, rows
+    in the caller's subject order.  The subjects are binned as in align_all_pairs_ragged; a bin's lists belong to its own
+    subjects, so they are scattered to the caller's positions and nothing is merged: the ids are query ids and ties go to the
+    smaller one, whatever the binning.  Queries keep one length per call."""
+    seqs = list(subjects)
+    lens = pad_ragged(seqs)[1]
+    a = DeviceAligner(algo, device, 0, scores)
+    a.set_queries(queries)
+    k_best = int(k_best)
+    out_scores = np.empty((len(seqs), k_best), dtype=np.int32)
+    out_queries = np.empty((len(seqs), k_best), dtype=np.int32)
+    for idx in bin_by_words(lens):
+        a.set_subjects_ragged([seqs[i] for i in idx])
+        hit_scores, hit_queries = a.top_queries(k_best, block_rows=block_rows, smallest=smallest)
+        out_scores[idx] = hit_scores.cpu().numpy()
+        out_queries[idx] = hit_queries.cpu().numpy()
+    a.check_faults()
+    return out_scores, out_queries
+
+
+def trace_top_queries(queries: np.ndarray, subjects: np.ndarray, k_best: int, algo: int, scores=None,
+                      semi_global: bool = False, k: int = 0, device: str = "cuda:0", block_rows: int = 1000, cigar_cap=None):
+    """The counterpart of trace_top_hits per SUBJECT: the k_best best queries of every subject AND where and how they align, as
+    (scores[ns, K] int32, queries[ns, K] int32, spans[ns, K, 4] int32 = (q_begin, q_end, s_begin, s_end), cigars) with
+    cigars[c][r] the edit script of the aligned span as a string, or None for an unused slot (its span is -1).  Selected and
+    traced back on the device (top_queries, query_hits_as_pairs, trace_pairs).  With ALGO_MYERS and semi_global=True this is
+    read placement: windows of a reference as queries, reads as subjects — every read's best windows, the read's begin and end
+    inside the window and its edit script."""
+    a = DeviceAligner(algo, device, k, scores, semi_global)
+    a.set_queries(queries)
+    a.set_subjects(subjects)
+    hit_scores, hit_queries = a.top_queries(k_best, block_rows=block_rows)
+    pair_queries, pair_subjects = a.query_hits_as_pairs(hit_queries)
+    _, span, n_ops, cigar = a.trace_pairs(pair_queries, pair_subjects, cigar_cap=cigar_cap)
+    a.check_faults()
+    ids = hit_queries.cpu().numpy()
+    text = cigar_strings(n_ops, cigar)
+    ns, kk = ids.shape
+    cigars = [[text[c * kk + r] if ids[c, r] >= 0 else None for r in range(kk)] for c in range(ns)]
+    return hit_scores.cpu().numpy(), ids, span.cpu().numpy().reshape(ns, kk, 4), cigars

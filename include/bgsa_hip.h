@@ -357,6 +357,47 @@ int bgsa_hip_threshold_hits_dev(const void *d_results, int elem_bytes, int n_que
                                 int32_t *d_hit_scores, int64_t *d_hit_subjects,
                                 void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- hit lists per subject: the K best queries of every column, or every query within a cutoff, from a score tile in HBM ----
+ * The column counterpart of the block above: the same tile (n_queries rows of row_stride elements of elem_bytes bytes, 2 or 1)
+ * reduced along its COLUMNS.  Row r of the tile is query query_base + r; ids are int32, as the pair calls take them.  Only
+ * columns [0, valid_count) have lists: the columns behind them (the all-'N' padding reads) are not read for any purpose, and
+ * nothing is written at or beyond valid_count * k_best (valid_count * cap_per_subject; valid_count for d_counts).  The tile is
+ * only read.
+ *
+ * ONE TOTAL ORDER makes every result unique: a candidate is (score, query id); better = the larger score, or the smaller one
+ * when `smallest` is set; among equal scores the smaller query id is better.
+ *
+ * bgsa_hip_top_queries_dev: for every column the k_best (1..64; else BGSA_HIP_EUNSUPPORTED) best candidates, best first, as
+ * d_hit_scores / d_hit_queries [valid_count][k_best].  Slots beyond n_queries candidates hold query -1 and the worst int32 of
+ * the direction (INT32_MIN, or INT32_MAX with `smallest`).
+ * bgsa_hip_threshold_queries_dev: for every column every candidate at least as good as `cutoff` (score >= cutoff, or <= with
+ * `smallest`), in ascending query order, as d_hit_scores / d_hit_queries [valid_count][cap_per_subject]; d_counts[column] =
+ * the TRUE number of such candidates even when it exceeds cap_per_subject — the list then holds the cap_per_subject
+ * lowest-indexed ones (slots beyond the count are left as they were).
+ * accumulate != 0: what the outputs already hold joins in, with its query ids as stored — a caller walking query blocks
+ * (query_base = the block's first query; every call after the first) or several query sets ends with the k_best best overall;
+ * threshold hits are appended behind the column's current d_counts[column], which grows by this tile's count.  The first call
+ * passes 0 (or lists of query -1 and counts of 0).  Stored scores outside the element's range are clamped to it.  Several
+ * subject buckets need no accumulate: their columns are disjoint, the lists are concatenated.
+ * d_workspace = caller-owned device scratch of at least bgsa_hip_query_hits_workspace_bytes() bytes, or NULL.  The size is 0
+ * for a non-positive n_queries / row_stride / k_best or a bad elem_bytes and never shrinks when an argument grows.  The lists
+ * are kept on chip and rows are not split among wavefronts, so today nothing is stored there and NULL allocates nothing
+ * either: with or without a workspace the calls only launch kernels on `stream` — no allocation, no synchronisation, safe
+ * inside a stream capture.  (The parallelism is the tile's width: 128 int16 or 256 int8 columns per wavefront.)
+ * BGSA_HIP_EINVAL: a NULL pointer, a non-positive n_queries / row_stride / cap_per_subject, valid_count outside
+ * [0, row_stride], query_base < 0 or query_base + n_queries beyond INT32_MAX, elem_bytes other than 1 or 2, a workspace that
+ * is too small — all checked before the first HIP call. */
+size_t bgsa_hip_query_hits_workspace_bytes(int n_queries, int64_t row_stride, int elem_bytes, int k_best);
+int bgsa_hip_top_queries_dev(const void *d_results, int elem_bytes, int n_queries, int64_t row_stride,
+                             int64_t valid_count, int query_base, int k_best, int smallest, int accumulate,
+                             int32_t *d_hit_scores, int32_t *d_hit_queries,
+                             void *d_workspace, size_t workspace_bytes, void *stream);
+int bgsa_hip_threshold_queries_dev(const void *d_results, int elem_bytes, int n_queries, int64_t row_stride,
+                                   int64_t valid_count, int query_base, int cutoff, int smallest, int accumulate,
+                                   int cap_per_subject, int32_t *d_counts,
+                                   int32_t *d_hit_scores, int32_t *d_hit_queries,
+                                   void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- alignment of selected pairs: the edit script (CIGAR) of every (query, subject) pair of a list, traced back on the GPU ----
  * Myers unit-cost GLOBAL alignment only, subjects of 1..1024 bp (word_num <= 32; beyond: BGSA_HIP_EUNSUPPORTED), any query
  * length.  Semi-global mode, BitPAl score sets, the banded filter and longer subjects are not offered.
