@@ -115,6 +115,15 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
+    # band-limited semi-global placement (the same: an older build lacks it)
+    for name, types, restype in (("bgsa_hip_place_pairs_band_words", [i32, i32], i32),
+                                 ("bgsa_hip_place_pairs_banded_min_workspace_bytes", [i32, i32, i32], sz),
+                                 ("bgsa_hip_place_pairs_banded_workspace_bytes", [i32, i32, i32, i64], sz),
+                                 ("bgsa_hip_myers_place_pairs_banded_dev",
+                                  [vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, i32, vp, sz, vp], i32)):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = restype
     # hit lists per subject (the same: an older build lacks them)
     for name, types, restype in (("bgsa_hip_query_hits_workspace_bytes", [i32, i64, i32, i32], sz),
                                  ("bgsa_hip_top_queries_dev", [vp, i32, i32, i64, i64, i32, i32, i32, i32, vp, vp, vp, sz, vp], i32),
@@ -728,6 +737,80 @@ class DeviceAligner:
         score, span, n_ops, cigar = self.trace_pairs(pq, hs.contiguous().view(-1), cigar_cap, subject_base, into, workspace_bytes)
         return score.view(nq, k), span.view(nq, k, 4), n_ops.view(nq, k), cigar.view(nq, k, -1)
 
+    # ---- the Myers semi-global placement within a distance bound, reads of any length (bgsa_hip_myers_place_pairs_banded_dev) ----
+    def place_pairs_banded(self, pair_queries, pair_subjects, max_distance: int, cigar_cap=None, subject_base: int = 0, into=None,
+                           workspace_bytes=None):
+        """trace_pairs for the Myers semi-global aligner with the history limited to the band of max_distance: reads of any
+        length the scoring call takes.  Returns (distance[n] int32 = minus the score score() reports, exact whatever the bound,
+        span[n, 4] int32 = (q_begin, q_end, 0, slen), n_ops[n] int32, cigar[n, cap]) device tensors.  A pair whose distance is
+        <= min(max_distance, slen) gets exactly trace_pairs' span, n_ops and runs; any other owned pair keeps its exact distance
+        and q_end and gets q_begin -1, n_ops 0 and an untouched cigar row.  Subject ids, subject_base, into= (the quadruple of an
+        earlier call), cigar_cap and workspace_bytes are as in align_pairs_banded; fresh outputs hold distance -1, span -1,
+        n_ops 0 and cigar 0 for pairs nobody owns.  Only ALGO_MYERS with semi_global=True (not +distance), one read length per
+        bucket: anything else raises rc=-2 before any launch."""
+        torch = self.torch
+        if self.algo != ALGO_MYERS or not self.semi_global or self.scores == (0, 1, 1):
+            raise BgsaHipError("place_pairs_banded: rc=-2: only the Myers unit-cost semi-global aligner places reads (no global mode "
+                               "— align_pairs_banded —, no BitPAl score sets, no banded filter; +distance aligns the same as "
+                               "-distance: use that aligner)")
+        if self.d_lens is not None:
+            raise BgsaHipError("place_pairs_banded: rc=-2: a bucket of mixed read lengths has no band-limited variant (one window "
+                               "schedule per read length)")
+        max_distance = min(int(max_distance), 2 ** 31 - 1)
+        if max_distance < 0:
+            raise BgsaHipError("place_pairs_banded: rc=-1: max_distance is negative")
+        pq = torch.as_tensor(pair_queries).to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        ps = torch.as_tensor(pair_subjects).to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+        if pq.numel() != ps.numel():
+            raise BgsaHipError("place_pairs_banded: pair_queries and pair_subjects differ in length")
+        n = pq.numel()
+        cap = self.qlen + self.slen if cigar_cap is None else int(cigar_cap)
+        if cap < 1:
+            raise BgsaHipError("place_pairs_banded: rc=-1: cigar_cap is not positive")
+        shapes = [((n,), torch.int32), ((n, 4), torch.int32), ((n,), torch.int32), ((n, cap), torch.int32)]
+        if into is None:
+            distance, span, n_ops, cigar = (torch.full(shape, fill, dtype=dtype, device=self.device)
+                                            for (shape, dtype), fill in zip(shapes, (-1, -1, 0, 0)))
+        else:
+            (distance, span, n_ops, cigar), _ = self._hit_lists(into, shapes, "place_pairs_banded")
+        if n == 0:
+            return distance, span, n_ops, cigar
+
+        def call(n_pairs, work, work_bytes):
+            check(lib().bgsa_hip_myers_place_pairs_banded_dev(self.d_content.data_ptr(), self.d_peq.data_ptr(), self.qlen, self.slen, self.ns,
+                                                              self.wn, pq.data_ptr(), ps.data_ptr(), n_pairs, self.nq, int(subject_base),
+                                                              max_distance, distance.data_ptr(), span.data_ptr(), n_ops.data_ptr(),
+                                                              cigar.data_ptr(), cap, work, work_bytes, self._stream()),
+                  "myers_place_pairs_banded_dev")
+        if workspace_bytes is None:
+            call(0, None, 0)   # an empty list runs the C call's checks alone: a window too wide is refused before a workspace is allocated for it
+            workspace_bytes = int(lib().bgsa_hip_place_pairs_banded_workspace_bytes(self.qlen, self.slen, max_distance, n))
+        call(n, *self._align_workspace(workspace_bytes))
+        return distance, span, n_ops, cigar
+
+    def place_hits_banded(self, hit_subjects, max_distance: int, cigar_cap=None, subject_base: int = 0, into=None, workspace_bytes=None):
+        """place_pairs_banded for the subjects[nq, K] tensor of top_hits / threshold_hits, as trace_hits is for trace_pairs:
+        (distance[nq, K], span[nq, K, 4], n_ops[nq, K], cigar[nq, K, cap]); unused slots (subject -1) keep distance -1, span -1,
+        n_ops 0.  into= the quadruple of an earlier call, for walking buckets."""
+        torch = self.torch
+        hs = torch.as_tensor(hit_subjects).to(device=self.device, dtype=torch.int64)
+        if hs.dim() != 2 or hs.shape[0] != self.nq:
+            raise BgsaHipError(f"place_hits_banded: hit_subjects must be [nq = {self.nq}, K]")
+        nq, k = hs.shape
+        pq = torch.arange(nq, dtype=torch.int32, device=self.device).repeat_interleave(k)
+        if into is not None:
+            into = list(into)
+            if len(into) != 4 or any(not t.is_contiguous() for t in into) or tuple(into[0].shape) != (nq, k) or \
+                    tuple(into[1].shape) != (nq, k, 4) or tuple(into[2].shape) != (nq, k) or into[3].dim() != 3 or \
+                    tuple(into[3].shape[:2]) != (nq, k):
+                raise BgsaHipError(f"place_hits_banded: into= needs contiguous tensors of shape ({nq}, {k}), ({nq}, {k}, 4), ({nq}, {k}), ({nq}, {k}, cap)")
+            if cigar_cap is None:
+                cigar_cap = into[3].shape[2]
+            into = (into[0].view(-1), into[1].view(nq * k, 4), into[2].view(-1), into[3].view(nq * k, -1))
+        distance, span, n_ops, cigar = self.place_pairs_banded(pq, hs.contiguous().view(-1), max_distance, cigar_cap, subject_base, into,
+                                                               workspace_bytes)
+        return distance.view(nq, k), span.view(nq, k, 4), n_ops.view(nq, k), cigar.view(nq, k, -1)
+
     def check_faults(self) -> None:
         """Synchronises and raises if a kernel reported a stream fault (bgsa_hip_stream_faults)."""
         self.torch.cuda.synchronize(self.device)
@@ -949,3 +1032,28 @@ def trace_top_queries(queries: np.ndarray, subjects: np.ndarray, k_best: int, al
     ns, kk = ids.shape
     cigars = [[text[c * kk + r] if ids[c, r] >= 0 else None for r in range(kk)] for c in range(ns)]
     return hit_scores.cpu().numpy(), ids, span.cpu().numpy().reshape(ns, kk, 4), cigars
+
+
+def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: int, max_distance=None, device: str = "cuda:0",
+                             block_rows: int = 1000, cigar_cap=None):
+    """Read placement for reads of any length, beside trace_top_queries (which stops at 1,024 bp): windows of a reference as
+    queries, reads as subjects, Myers semi-global.  The k_best best windows of every read AND where and how the read aligns
+    inside them, within max_distance, as (scores[ns, K] int32, queries[ns, K] int32, spans[ns, K, 4] int32 = (q_begin, q_end, 0,
+    slen), cigars); cigars[c][r] is None for an unused slot (its span is -1) and for a hit beyond max_distance (its span keeps
+    q_begin -1).  max_distance=None: the worst distance in the hit lists, so that every hit is placed — one scalar read back
+    from the device.  Selected, located and traced back on the device (top_queries, query_hits_as_pairs, place_pairs_banded)."""
+    a = DeviceAligner(ALGO_MYERS, device, semi_global=True)
+    a.set_queries(queries)
+    a.set_subjects(subjects)
+    hit_scores, hit_queries = a.top_queries(k_best, block_rows=block_rows)
+    if max_distance is None:
+        max_distance = -int(a.torch.where(hit_queries >= 0, hit_scores, a.torch.zeros_like(hit_scores)).min().item())
+    pair_queries, pair_subjects = a.query_hits_as_pairs(hit_queries)
+    _, span, n_ops, cigar = a.place_pairs_banded(pair_queries, pair_subjects, max_distance, cigar_cap=cigar_cap)
+    a.check_faults()
+    ids = hit_queries.cpu().numpy()
+    ns, kk = ids.shape
+    spans = span.cpu().numpy().reshape(ns, kk, 4)
+    text = cigar_strings(n_ops, cigar)
+    cigars = [[text[c * kk + r] if ids[c, r] >= 0 and spans[c, r, 0] >= 0 else None for r in range(kk)] for c in range(ns)]
+    return hit_scores.cpu().numpy(), ids, spans, cigars

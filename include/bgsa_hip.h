@@ -549,6 +549,64 @@ int bgsa_hip_trace_pairs_lens_dev(const bgsa_hip_params_t *params, const char *d
                                   int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
                                   void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- band-limited semi-global placement: where a read of ANY length lies inside its window, and how it aligns ----
+ * bgsa_hip_trace_pairs_dev keeps a 16-bit DP row of the whole subject in LDS: it stops at 1,024 bp.  This call reports the
+ * same four outputs for the "Myers, semi-global" model above (the subject, n = read_len columns, end to end inside the query,
+ * m = ref_len rows; D[0][j] = j, D[i][0] = 0; unit costs) for every subject length the semi-global scoring call takes, with the
+ * history limited by a caller-given bound on the distance, as bgsa_hip_myers_align_pairs_banded_dev does in global mode.  Short
+ * reads too: there it is bit-parallel where bgsa_hip_trace_pairs_dev runs a scalar DP.  No mixed-length variant.
+ * LOCATE (exact, independent of the bound).  D* = min over i in [0, m] of D[i][n], e = the SMALLEST such i: the bit-parallel
+ * Myers semi-global row on all word_num words of the subject (natural bit positions), the row edge feeding hp_in = 0, the query
+ * character per lane; run starts at n (row 0) and moves by Hp - Hn at column n per row, a strictly smaller run moves e.
+ * THE BOUND.  B = min(max_distance, n) — D* <= n always.  A pair with D* > B is beyond the bound.
+ * THE RULE for a pair with D* <= B, in VIRTUAL rows: o = e - n - B (per pair, may be negative), M' = n + B; virtual row
+ * i' = 1 .. M' is query row i = i' + o, so the end cell (e, n) is (M', n) for every pair.  Rows run in blocks of 32 virtual
+ * rows: the block of 0-based virtual rows i0 .. last - 1, i0 % 32 == 0, last = min(i0 + 32, M'), has the WINDOW of words [a, b],
+ * a = (max(1, i0 + 1 - 2B) - 1) / 32, b = (min(n, last) - 1) / 32 — the diagonals j - i' in [-2B, 0]: a path that ends on -B
+ * and costs <= B moves at most B either way.  The windows depend on (n, B) only.  Every row of a block is the Myers row on
+ * exactly its window's words: the lowest window word takes hp_in = 0 when a == 0 (the free column 0 of the mode) and hp_in = 1
+ * otherwise, hn_in = 0, add-carry 0; words left of the window keep their last deltas, words right of it their initial state
+ * (pv = ~0, mv = 0).  A virtual row whose query row does not exist (i < 1, only when o < 0, only in blocks with a == 0 because
+ * -o <= 2B) runs with an all-zero match mask, which with hp_in = 0 leaves the state at row 0's.
+ * CERTIFICATION.  D' = (the number of rows run with hp_in = 1) + the sum over all word_num words of popc(pv & mask) -
+ * popc(mv & mask) is the cost of a real path ending at (e, n), so D' >= D*, and for D* <= B the two are equal.  D' != D*
+ * raises the sticky BGSA_HIP_FAULT_BAND and leaves n_ops = 0: the bit means a bug, never an input.
+ * TRACEBACK from (e, n) through the window words' history (the two vectors of bgsa_hip_myers_align_pairs_dev) with the
+ * preference of every pair call — diagonal, then up 'I', then left 'D' —, stopped at the first cell with j = 0, whose row is
+ * q_begin; on query row 0 with j > 0 the remaining j steps are 'D'.  A step that asks for a cell outside its block's window
+ * raises BGSA_HIP_FAULT_BAND as in the global call.
+ * bgsa_hip_place_pairs_band_words: the widest window of (read_len, max_distance) in words, 1 .. word_num; 0 for a non-positive
+ * length or a negative bound.  A window of w >= 2 words first appears at B = 16 (w - 2) + 1.
+ * Arguments, pair ownership (subject_base, the slot -1, pairs of other buckets untouched in all four outputs),
+ * BGSA_HIP_FAULT_PAIR, the cigar format and the chunking (any workspace from the minimum up, whole waves per chunk, the locate,
+ * forward and traceback kernels one after the other on `stream`; with a caller workspace only kernel launches: capture safe)
+ * are those of bgsa_hip_myers_align_pairs_banded_dev.  Per owned pair, whatever the bound: d_distance[p] = D* (exact; minus the
+ * score the semi-global scoring call reports) and d_span[4p .. 4p+3] = (q_begin, e, 0, n).
+ *   D* <= B: d_n_ops[p] = the TRUE number of runs even beyond cigar_cap, d_cigar[p * cigar_cap ...] = the first
+ *     min(n_ops, cigar_cap) runs; distance = -score, span, n_ops and runs are bit for bit what bgsa_hip_trace_pairs_dev writes
+ *     for the pair where that call applies;
+ *   D* >  B: q_begin = -1, d_n_ops[p] = 0, the cigar row untouched.
+ * The workspace: one wave's slice = history ((n + B) x 2 x band_words x 256 B) + state ((2 x word_num + 1) x 256 B) + locate's
+ * carries (ceil(m / 32) x 3 x 256 B) + op bytes ((n + min(m, n + B)) x 64), rounded up to 256 =
+ * ..._banded_min_workspace_bytes(); ..._banded_workspace_bytes() = what all n_pairs need in one pass, at most
+ * BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE, never below one wave; NULL = the library's own grow-only scratch (not capture safe).
+ * BGSA_HIP_EINVAL, checked in this order before the first HIP call: a NULL pointer (workspace and stream excepted), negative
+ * n_pairs, non-positive lengths / n_queries / cigar_cap, read_count not a positive multiple of 64, word_num other than
+ * bgsa_hip_word_num(BGSA_ALGO_MYERS, ...), a negative max_distance; then BGSA_HIP_EUNSUPPORTED: ref_len + read_len + B or
+ * 2 read_len + B beyond 2^31 - 1 (B as above: rows and op bytes are counted in int), a window wider than the 32 words the
+ * kernels hold (bgsa_hip_last_error() names the largest max_distance the read takes: 496 beyond 1,024 bp; a read of up to
+ * 1,024 bp takes any bound); then BGSA_HIP_EINVAL: a workspace below the minimum.  n_pairs == 0 is BGSA_HIP_OK once the checks
+ * pass and launches nothing. */
+int bgsa_hip_place_pairs_band_words(int read_len, int max_distance);
+size_t bgsa_hip_place_pairs_banded_min_workspace_bytes(int ref_len, int read_len, int max_distance);
+size_t bgsa_hip_place_pairs_banded_workspace_bytes(int ref_len, int read_len, int max_distance, int64_t n_pairs);
+int bgsa_hip_myers_place_pairs_banded_dev(const char *d_content, const hip_read_t *d_peq,
+                                          int ref_len, int read_len, int64_t read_count, int word_num,
+                                          const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs,
+                                          int n_queries, int64_t subject_base, int max_distance,
+                                          int32_t *d_distance, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
+                                          void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
@@ -563,7 +621,8 @@ int bgsa_hip_trace_pairs_lens_dev(const bgsa_hip_params_t *params, const char *d
 /* bgsa_hip_myers_align_pairs_dev / bgsa_hip_trace_pairs_dev: a pair this call owned named a query outside [0, n_queries); that pair was skipped (an
  * argument check inside the kernel, not a damaged stream — the other pairs of the call are good). */
 #define BGSA_HIP_FAULT_PAIR 4
-/* bgsa_hip_myers_align_pairs_banded_dev: a traceback step left its block's window (a bug guard, see there). */
+/* bgsa_hip_myers_align_pairs_banded_dev, bgsa_hip_myers_place_pairs_banded_dev: a traceback step left its block's window, or the
+ * placement's certified distance differs from the located one (bug guards, see there). */
 #define BGSA_HIP_FAULT_BAND 8
 int bgsa_hip_stream_faults(int clear);
 int bgsa_hip_debug_inject_stream_fault(int kind);
