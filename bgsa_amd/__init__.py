@@ -132,6 +132,15 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
+    # a reference as the query set (the same: an older build lacks them)
+    for name, types, restype in (("bgsa_hip_reference_window_count", [i64, i32, i32], i64),
+                                 ("bgsa_hip_reference_window_start", [i64, i32, i32, i64], i64),
+                                 ("bgsa_hip_reference_windows_dev", [vp, i64, i32, i32, vp, i64, i64, vp, vp], i32),
+                                 ("bgsa_hip_reference_placements_dev",
+                                  [i64, i32, i32, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp], i32)):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = restype
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -315,6 +324,21 @@ class DeviceAligner:
         self.d_content = torch.zeros(buf.size + 8, dtype=torch.uint8, device=self.device)
         self.d_content[: buf.size].copy_(torch.from_numpy(buf))
         check(lib().bgsa_hip_map_queries_dev(self.d_content.data_ptr(), buf.size, self._stream()), "map_queries")
+
+    def set_query_rows_device(self, d_content, nq: int, qlen: int) -> None:
+        """The counterpart of set_subject_rows_device for queries: d_content is a contiguous uint8 device tensor that already
+        holds nq MAPPED rows (codes 0..4) of qlen + 1 bytes each ('\\n' last), followed by at least 8 spare bytes (the kernels'
+        scalar dword fetch of the last characters stays in bounds).  Nothing is copied or launched: the tensor is the aligner's
+        query buffer from here on (bgsa_hip_reference_windows_dev writes such rows; bgsa_amd.reference.ReferenceMapper)."""
+        torch = self.torch
+        nq, qlen = int(nq), int(qlen)
+        if nq < 1 or qlen < 1:
+            raise BgsaHipError("set_query_rows_device: rc=-1: nq and qlen must be positive")
+        if not isinstance(d_content, torch.Tensor) or d_content.dtype != torch.uint8 or d_content.device != self.device or \
+                d_content.dim() != 1 or not d_content.is_contiguous() or d_content.numel() < nq * (qlen + 1) + 8:
+            raise BgsaHipError(f"set_query_rows_device: rc=-1: d_content must be a contiguous 1-D uint8 tensor on {self.device} of at "
+                               f"least nq * (qlen + 1) + 8 = {nq * (qlen + 1) + 8} bytes")
+        self.nq, self.qlen, self.d_content = nq, qlen, d_content
 
     def set_subjects(self, subjects: np.ndarray, qlen: int | None = None) -> None:
         """subjects: [ns, slen] uint8 ASCII (padded here to a multiple of 64 with 'N' reads)."""
@@ -1057,3 +1081,7 @@ def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: 
     text = cigar_strings(n_ops, cigar)
     cigars = [[text[c * kk + r] if ids[c, r] >= 0 and spans[c, r, 0] >= 0 else None for r in range(kk)] for c in range(ns)]
     return hit_scores.cpu().numpy(), ids, spans, cigars
+
+
+# reads mapped onto one reference: windows cut on the device, both strands, reference coordinates (bgsa_amd/reference.py)
+from .reference import Placement, ReferenceHits, ReferenceMapper, max_stride, window_plan  # noqa: E402

@@ -1,0 +1,217 @@
+"""Reads mapped onto ONE reference sequence: the windows are cut on the device, on both strands, and the hits come back in
+reference coordinates (include/bgsa_hip.h "a reference as the query set").
+
+The geometry is stated once in the header and restated here (window_plan, max_stride): L mapped bytes, 1 <= S <= W <= L,
+n_windows = 1 + ceil((L - W) / S), start(w) = min(w * S, L - W); forward window w has id w, its reverse complement id
+n_windows + w.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
+
+import bgsa_amd as B
+
+INT32_MAX = 2 ** 31 - 1
+
+
+def window_plan(ref_len: int, window_len: int, stride: int) -> tuple[int, np.ndarray]:
+    """(n_windows, starts int64[n_windows]) of a reference of ref_len bases cut into windows of window_len every stride bases,
+    the last one anchored at the reference's end.  Pure Python: no device, no library."""
+    L, W, S = int(ref_len), int(window_len), int(stride)
+    if not 1 <= S <= W <= L:
+        raise B.BgsaHipError(f"window_plan: rc=-1: needs 1 <= stride <= window_len <= ref_len, got stride {S}, window_len {W}, ref_len {L}")
+    n = 1 + -(-(L - W) // S)
+    return n, np.minimum(np.arange(n, dtype=np.int64) * S, L - W)
+
+
+def max_stride(window_len: int, read_len: int, max_distance: int) -> int:
+    """The largest stride at which every placement of a read_len bp read within max_distance lies wholly inside at least one
+    window: such a placement spans at most read_len + B reference bases, B = min(max_distance, read_len), and every interval of
+    that length is inside a window exactly when stride <= window_len - (read_len + B) + 1.  Below 1: no stride does."""
+    n = int(read_len)
+    return int(window_len) - (n + min(int(max_distance), n)) + 1
+
+
+class ReferenceHits(NamedTuple):
+    """What ReferenceMapper.map_reads returns, numpy, one row per read and one column per selected hit, best first."""
+    scores: np.ndarray      # [ns, k_sel] int32: minus the distance of the read inside its r-th best window; INT32_MIN = unused slot
+    strand: np.ndarray      # [ns, k_sel] int32: 0 forward, 1 reverse, -1 unused slot
+    ref_begin: np.ndarray   # [ns, k_sel] int64: half-open interval on the forward reference, -1 where the hit is not placed
+    ref_end: np.ndarray     # [ns, k_sel] int64
+    keep: np.ndarray        # [ns, k_sel] int32: 1 = the best view of its locus, 0 = unplaced, or a locus already reported
+    cigars: list            # cigars[c][r]: the edit script along the forward reference, or None where keep is 0
+    windows: np.ndarray     # [ns, k_sel] int32: the window ids behind the hits (reverse ones from n_windows on), -1 = unused
+
+
+class Placement(NamedTuple):
+    strand: int
+    ref_begin: int
+    ref_end: int
+    distance: int
+    cigar: str
+
+
+class ReferenceMapper:
+    """One reference, resident on the device as mapped codes, and a Myers semi-global aligner over its windows.
+
+    reference: bytes, str or a 1-D uint8 array of ASCII bases (a '\\n' in it raises: it is one sequence, not a file).  It is
+    uploaded and mapped once; the windows of window_len every stride bases exist only as query rows built on the device, a
+    segment of segment_windows ids at a time.  both_strands=False leaves the reverse-complemented windows out.
+
+    Limits: one read length per map_reads call, Myers unit-cost distance, one GPU.  The r-th distinct locus of a read is
+    reported if its best window is among the read's k_sel best windows; for k_best = 1 that always holds."""
+
+    def __init__(self, reference, window_len: int, stride: int, device: str = "cuda:0", both_strands: bool = True,
+                 segment_windows: int = 65536):
+        if isinstance(reference, str):
+            reference = reference.encode("ascii")
+        if isinstance(reference, (bytes, bytearray, memoryview)):
+            ref = np.frombuffer(reference, dtype=np.uint8)
+        else:
+            ref = np.ascontiguousarray(reference, dtype=np.uint8)
+        if ref.ndim != 1:
+            raise B.BgsaHipError("ReferenceMapper: rc=-1: the reference is one sequence (1-D)")
+        if (ref == ord("\n")).any():
+            raise B.BgsaHipError("ReferenceMapper: rc=-1: the reference holds a newline: pass the bases of ONE sequence, not a file's lines")
+        self.ref_len, self.window_len, self.stride = int(ref.size), int(window_len), int(stride)
+        self.n_windows, self.starts = window_plan(self.ref_len, self.window_len, self.stride)
+        if 2 * self.n_windows > INT32_MAX:
+            raise B.BgsaHipError(f"ReferenceMapper: rc=-1: {self.n_windows} windows on two strands do not fit int32 window ids")
+        self.both_strands = bool(both_strands)
+        self.n_ids = self.n_windows * (2 if self.both_strands else 1)
+        self.segment_windows = int(segment_windows)
+        if self.segment_windows < 1:
+            raise B.BgsaHipError("ReferenceMapper: rc=-1: segment_windows is not positive")
+        self.aligner = a = B.DeviceAligner(B.ALGO_MYERS, device, semi_global=True)
+        torch = a.torch
+        self.d_reference = torch.zeros(self.ref_len + 8, dtype=torch.uint8, device=a.device)
+        self.d_reference[: self.ref_len].copy_(torch.from_numpy(ref))
+        B.check(B.lib().bgsa_hip_map_queries_dev(self.d_reference.data_ptr(), self.ref_len, a._stream()), "map_queries")
+        self.d_rows = None      # the query rows of one segment / of one block's hit windows, grown on demand
+
+    def _rows_buffer(self, n_rows: int):
+        need = n_rows * (self.window_len + 1) + 8
+        if self.d_rows is None or self.d_rows.numel() < need:
+            self.d_rows = self.aligner.torch.zeros(need, dtype=self.aligner.torch.uint8, device=self.aligner.device)
+        return self.d_rows
+
+    def _build_rows(self, d_ids, first_id: int, n_rows: int):
+        """n_rows window rows as the aligner's query set: the ids first_id + r (d_ids None), or d_ids[r]."""
+        a = self.aligner
+        rows = self._rows_buffer(n_rows)
+        B.check(B.lib().bgsa_hip_reference_windows_dev(self.d_reference.data_ptr(), self.ref_len, self.window_len, self.stride,
+                                                       None if d_ids is None else d_ids.data_ptr(), int(first_id), n_rows,
+                                                       rows.data_ptr(), a._stream()), "reference_windows_dev")
+        a.set_query_rows_device(rows, n_rows, self.window_len)
+
+    def k_selected(self, k_best: int) -> int:
+        """Windows selected per read for k_best loci: a locus shows in up to ceil(W / S) overlapping windows, and one more
+        holds a clipped copy at an edge."""
+        return min(B.V_NUM, int(k_best) * (-(-self.window_len // self.stride) + 1))
+
+    def select_windows(self, k_sel: int, block_rows: int = 1000):
+        """The device half of map_reads' selection, for the reads the aligner holds (aligner.set_subjects(reads, qlen=window_len)):
+        the ids in segments, every segment's rows built straight into the aligner's content buffer and joined to the lists by
+        top_queries.  Returns device tensors (scores[ns, k_sel] int32, window ids[ns, k_sel] int32)."""
+        a = self.aligner
+        segment = min(self.segment_windows, self.n_ids)
+        into = None
+        for lo in range(0, self.n_ids, segment):
+            self._build_rows(None, lo, min(segment, self.n_ids - lo))
+            into = a.top_queries(k_sel, block_rows=block_rows, query_base=lo, into=into)
+        return into
+
+    def place_hits(self, ids, max_distance: int, cap: int, block_rows: int = 1000):
+        """The device half of map_reads' placement: block_rows reads at a time, the hit windows ids[ns, k_sel] gathered by id,
+        placed within max_distance and turned into reference coordinates.  Returns device tensors (strand, ref_begin, ref_end,
+        keep, n_ops — all [ns, k_sel] —, cigar[ns, k_sel, cap])."""
+        a, L = self.aligner, B.lib()
+        torch, dev, W = a.torch, a.device, self.window_len
+        ns, k_sel = ids.shape
+        span = torch.full((ns, k_sel, 4), -1, dtype=torch.int32, device=dev)
+        distance = torch.full((ns, k_sel), -1, dtype=torch.int32, device=dev)
+        n_ops = torch.zeros((ns, k_sel), dtype=torch.int32, device=dev)
+        cigar = torch.zeros((ns, k_sel, cap), dtype=torch.int32, device=dev)
+        strand = torch.empty((ns, k_sel), dtype=torch.int32, device=dev)
+        ref_begin = torch.empty((ns, k_sel), dtype=torch.int64, device=dev)
+        ref_end = torch.empty((ns, k_sel), dtype=torch.int64, device=dev)
+        keep = torch.empty((ns, k_sel), dtype=torch.int32, device=dev)
+        block = max(1, min(int(block_rows), ns))
+        for lo in range(0, ns, block):
+            hi = min(lo + block, ns)
+            hit = ids[lo:hi]
+            n_rows = (hi - lo) * k_sel
+            self._build_rows(hit, 0, n_rows)
+            pair_queries = torch.arange(n_rows, dtype=torch.int32, device=dev)
+            columns = torch.arange(lo, hi, dtype=torch.int64, device=dev).repeat_interleave(k_sel)
+            pair_subjects = torch.where(hit.reshape(-1) >= 0, columns, torch.full_like(columns, -1))
+            a.place_pairs_banded(pair_queries, pair_subjects, max_distance, cigar_cap=cap,
+                                 into=(distance[lo:hi].view(-1), span[lo:hi].view(-1, 4), n_ops[lo:hi].view(-1), cigar[lo:hi].view(-1, cap)))
+            B.check(L.bgsa_hip_reference_placements_dev(self.ref_len, W, self.stride, hit.data_ptr(), hi - lo, k_sel,
+                                                        span[lo:hi].data_ptr(), n_ops[lo:hi].data_ptr(), cigar[lo:hi].data_ptr(), cap,
+                                                        strand[lo:hi].data_ptr(), ref_begin[lo:hi].data_ptr(), ref_end[lo:hi].data_ptr(),
+                                                        keep[lo:hi].data_ptr(), a._stream()), "reference_placements_dev")
+        return strand, ref_begin, ref_end, keep, n_ops, cigar
+
+    def map_reads(self, reads: np.ndarray, k_best: int = 1, max_distance=None, block_rows: int = 1000, cigar_cap=None) -> ReferenceHits:
+        """reads: [ns, n] uint8 ASCII, one length.  Selects every read's k_sel = k_selected(k_best) best windows over both
+        strands (top_queries, segment by segment: the number of segments never changes a result), places the read inside
+        each within max_distance (place_pairs_banded on the hit windows, gathered on the device block_rows reads at a time) and
+        reports reference coordinates, with the copies of one locus marked (keep).  max_distance=None: the worst selected
+        distance, one scalar read back, so that every hit is placed.
+        A stride above max_stride(window_len, n, max_distance) — with max_distance=None: above window_len - n + 1, where not even
+        an exact placement is sure of a window — is refused before anything is launched: some placement within the bound would
+        lie in no window, and the best window's distance would not be the reference's optimum.
+        cigar_cap=None: window_len + n runs per hit, which cannot overflow (4 bytes each: pass a smaller cap for many reads)."""
+        a = self.aligner
+        torch = a.torch
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        if reads.ndim != 2 or reads.shape[0] < 1 or reads.shape[1] < 1:
+            raise B.BgsaHipError("map_reads: rc=-1: reads must be [ns, n] with ns, n >= 1 (one read length per call)")
+        ns, n = reads.shape
+        k_best = int(k_best)
+        if not 1 <= k_best <= B.V_NUM:
+            raise B.BgsaHipError(f"map_reads: rc=-1: k_best must lie in 1..{B.V_NUM}")
+        if max_distance is not None and int(max_distance) < 0:
+            raise B.BgsaHipError("map_reads: rc=-1: max_distance is negative")
+        bound = 0 if max_distance is None else min(int(max_distance), n)
+        largest = max_stride(self.window_len, n, bound)
+        if self.stride > largest:
+            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
+            raise B.BgsaHipError(f"map_reads: rc=-1: at stride {self.stride} a placement of a {n} bp read within distance {bound} can lie in "
+                                 f"no window of {self.window_len} bp: {allowed}")
+        k_sel = self.k_selected(k_best)
+        W = self.window_len
+        cap = W + n if cigar_cap is None else int(cigar_cap)
+        if cap < 1:
+            raise B.BgsaHipError("map_reads: rc=-1: cigar_cap is not positive")
+
+        a.set_subjects(reads, qlen=W)
+        scores, ids = self.select_windows(k_sel, block_rows)
+        if max_distance is None:
+            max_distance = -int(torch.where(ids >= 0, scores, torch.zeros_like(scores)).min().item())
+        strand, ref_begin, ref_end, keep, n_ops, cigar = self.place_hits(ids, int(max_distance), cap, block_rows)
+        a.check_faults()
+
+        kept = keep.cpu().numpy()
+        counts, runs = n_ops.cpu().numpy(), cigar.cpu().numpy().view(np.uint32)
+        cigars = [[None] * k_sel for _ in range(ns)]
+        for c, r in zip(*np.nonzero(kept)):
+            if counts[c, r] > cap:
+                raise B.BgsaHipError(f"map_reads: hit {r} of read {c} has {counts[c, r]} runs, its row holds {cap} (raise cigar_cap)")
+            cigars[c][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : counts[c, r]].tolist())
+        return ReferenceHits(scores.cpu().numpy(), strand.cpu().numpy(), ref_begin.cpu().numpy(), ref_end.cpu().numpy(), kept, cigars,
+                             ids.cpu().numpy())
+
+    @staticmethod
+    def placements_of(hits: ReferenceHits, k_best: int = 1) -> list:
+        """Per read the first k_best kept hits of map_reads' result, best first, as Placement(strand, ref_begin, ref_end,
+        distance, cigar) — for callers who want no more than that."""
+        out = []
+        for c in range(hits.keep.shape[0]):
+            rows = np.flatnonzero(hits.keep[c])[: int(k_best)]
+            out.append([Placement(int(hits.strand[c, r]), int(hits.ref_begin[c, r]), int(hits.ref_end[c, r]), -int(hits.scores[c, r]),
+                                  hits.cigars[c][r]) for r in rows])
+        return out

@@ -607,6 +607,60 @@ int bgsa_hip_myers_place_pairs_banded_dev(const char *d_content, const hip_read_
                                           int32_t *d_distance, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
                                           void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- a reference as the query set: its windows cut on the device, both strands, placements in reference coordinates ----
+ * The placement calls above take windows of a reference as queries and reads as the resident subjects.  These calls know that
+ * the queries are ONE sequence: the reference crosses to the device once, its overlapping windows are written as query rows
+ * there — forward and reverse-complemented —, and the spans of the pair calls become (strand, reference begin, reference end)
+ * with the copies of one locus seen through overlapping windows marked.  No scoring, selection or pair call changes.
+ * GEOMETRY (the one rule; bgsa_amd/reference.py: window_plan restates it).  The reference is ref_len = L mapped bytes (codes
+ * 0..4 as bgsa_hip_map_queries_dev writes them, no newlines).  Window length W and stride S satisfy 1 <= S <= W <= L.
+ *   n_windows = 1 + ceil((L - W) / S);  start(w) = min(w * S, L - W) — the last window is anchored at the reference's end, so
+ *   every window is W long.
+ * Window ids are int32: forward window w has id w, reverse window w has id n_windows + w; row i of the reverse window is
+ * comp(reference[start(w) + W - 1 - i]), comp(c) = 3 - c for c < 4 and 4 ('N') otherwise — on codes, so a byte outside the
+ * alphabet, which maps to 0 like 'A', complements to 'T'.  2 * n_windows beyond INT32_MAX is BGSA_HIP_EINVAL in the device calls.
+ * COMPLETENESS.  B = min(max_distance, n) for a read of n bp: a placement within the bound spans at most n + B reference
+ * bases, and such a span lies wholly inside at least one window exactly when S <= W - (n + B) + 1.  Under that condition the
+ * best distance over all windows IS the semi-global optimum over the whole reference for every read whose optimum is <= B (the
+ * optimal span fits a window; no window can beat a superstring of it).
+ * bgsa_hip_reference_window_count / _window_start: host only, no device — n_windows (whatever its size) and start(window);
+ * -1 with bgsa_hip_last_error() set for a shape outside 1 <= S <= W <= L or a window outside [0, n_windows).
+ * bgsa_hip_reference_windows_dev writes n_rows query rows of window_len codes + '\n' (stride window_len + 1) to d_content —
+ * the buffer the scoring and pair calls take as d_content; it may start at any byte address, and nothing is written at or
+ * beyond n_rows * (window_len + 1).  d_window_ids == NULL: row r is window id first_id + r, and [first_id, first_id + n_rows)
+ * must lie in [0, 2 * n_windows).  Otherwise row r is window d_window_ids[r] (first_id is ignored); an id outside
+ * [0, 2 * n_windows) — the -1 of an unused hit slot — writes a row of code 4: such an id forms a value, never an address.
+ * n_rows in [0, 2^31 - 1]; n_rows == 0 is BGSA_HIP_OK and launches nothing.  Only a launch on `stream`: no allocation, no
+ * synchronisation (capture safe).
+ * bgsa_hip_reference_placements_dev turns the outputs of bgsa_hip_myers_place_pairs_banded_dev (or bgsa_hip_trace_pairs_dev) for
+ * the hit lists d_hit_windows[n_reads][k] (bgsa_hip_top_queries_dev's ids, best first; pair p = c * k + r) into one list per
+ * read.  Hit (c, r) with window id g, w = g mod n_windows, span (qb, qe, ., .) = d_span[4p], d_span[4p + 1]:
+ *   unused slot (g < 0, or g >= 2 * n_windows): strand -1, begin -1, end -1, keep 0;
+ *   beyond the bound (qb < 0):   the strand its id says, begin -1, end -1, keep 0;
+ *   forward (g < n_windows):     strand 0, ref_begin = start(w) + qb, ref_end = start(w) + qe;
+ *   reverse:                     strand 1, ref_begin = start(w) + W - qe, ref_end = start(w) + W - qb, and the first d_n_ops[p]
+ *                                runs of its row d_cigar[p * cigar_cap ...] are reversed in place: they then read along the
+ *                                forward reference against the reverse-complemented read ('I' and 'D' keep their meaning); a
+ *                                row whose n_ops exceeds cigar_cap is left untouched.  d_n_ops == d_cigar == NULL: nothing to
+ *                                reverse.
+ *   keep: walking r = 0 .. k - 1, hit r is kept if it is placed and no kept r' < r of the same read has the same strand and a
+ *         reference interval with begin' < end and begin < end' — so one locus seen through two overlapping windows, or a
+ *         clipped copy of it at a window's edge, keeps only its best view.
+ * k in 1..64; n_reads == 0 is BGSA_HIP_OK and launches nothing.  Only a launch on `stream`.
+ * BGSA_HIP_EINVAL, all checked before the first HIP call: a NULL pointer (stream, d_window_ids and the d_n_ops / d_cigar pair
+ * excepted), a shape outside 1 <= S <= W <= L, 2 * n_windows > INT32_MAX, negative n_rows / n_reads, an id range outside
+ * [0, 2 * n_windows), k outside 1..64, d_cigar without d_n_ops or with a non-positive cigar_cap. */
+int64_t bgsa_hip_reference_window_count(int64_t ref_len, int window_len, int stride);
+int64_t bgsa_hip_reference_window_start(int64_t ref_len, int window_len, int stride, int64_t window);
+int bgsa_hip_reference_windows_dev(const char *d_reference, int64_t ref_len, int window_len, int stride,
+                                   const int32_t *d_window_ids, int64_t first_id, int64_t n_rows,
+                                   char *d_content, void *stream);
+int bgsa_hip_reference_placements_dev(int64_t ref_len, int window_len, int stride,
+                                      const int32_t *d_hit_windows, int64_t n_reads, int k,
+                                      const int32_t *d_span, const int32_t *d_n_ops, int32_t *d_cigar, int cigar_cap,
+                                      int32_t *d_strand, int64_t *d_ref_begin, int64_t *d_ref_end, int32_t *d_keep,
+                                      void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
