@@ -102,6 +102,10 @@ int launch_myers(const ScoreArgs &a, int semi_global = 0);
 const char *myers_kernel_name(int word_num, int semi_global = 0);
 // Subject groups per wave (1 | 2) of a global Myers launch on the certified band: myers_select's answer for this bucket (host only).
 int myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_len, int mixed_lengths);
+// The snapshot depths of prefix sharing (myers_band.h) in such a launch of n_queries queries, written to depths[0 .. kPrefixMaxDepths);
+// returns their number, 0 where the launch does not share.  Launches nothing; the tile it assumes is plan_tasks', which asks the
+// runtime for the device's CU count once (256 where there is no device).
+int myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_len, int n_queries, int mixed_lengths, int *depths);
 
 // Packed query stream (one per query, 8-byte windows): codes 0..4 = A C G T N row, 5 = END,
 // 6 = REFILL.  Window i < n_windows-1 holds characters 7i..7i+6 and a REFILL; the last window

@@ -255,7 +255,8 @@ static size_t plan_workspace_bytes(const Plan &plan, int ref_len, int read_len, 
         return banded_stream_bound(ref_len) * n_queries + kTaskCounterBytes;
     // the longer of the plain stream and the Myers band stream (myers_band.h), whichever kernel the plan picks: one size for
     // every plain plan, as the score sets that reduce to edit distance run the Myers kernels
-    return band_stream_stride(ref_len) * static_cast<size_t>(n_queries) + kTaskCounterBytes;   // bgsa_common.h "dynamic task handout"
+    // ... in segments (prefix sharing), with the sorted order of the launch's queries behind the task counter
+    return band_segments_stride_bound(ref_len) * static_cast<size_t>(n_queries) + kTaskCounterBytes + prefix_order_bytes(n_queries);   // bgsa_common.h "dynamic task handout"
 }
 
 int ab_knob_refused(const char *what)
@@ -611,6 +612,40 @@ int bgsa_hip_myers_band_groups(int word_num, int64_t read_count, int ref_len, in
 {
     if (word_num <= 0 || read_count < 0 || ref_len <= 0 || read_len <= 0) return BGSA_HIP_EINVAL;
     return myers_band_groups(word_num, read_count, ref_len, read_len, mixed_lengths);
+}
+
+int bgsa_hip_myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_len, int n_queries, int mixed_lengths,
+                                 int *depths, int cap)
+{
+    if (word_num <= 0 || read_count < 0 || ref_len <= 0 || read_len <= 0 || n_queries < 0 || cap < 0 || (cap > 0 && !depths)) return BGSA_HIP_EINVAL;
+    int d[kPrefixMaxDepths] = {};
+    const int n = myers_prefix_depths(word_num, read_count, ref_len, read_len, n_queries, mixed_lengths, d);
+    for (int j = 0; j < n && j < cap; j++) depths[j] = d[j];
+    return n;
+}
+
+int bgsa_hip_myers_band_segments(const char *mapped_row, int ref_len, int read_len, const int *depths, int n_depths,
+                                 unsigned char *dst, int cap, int *offsets)
+{
+    if (!mapped_row || ref_len <= 0 || read_len <= 0 || !depths || n_depths < 1 || n_depths > kPrefixMaxDepths) return 0;
+    BandSchedule s;
+    if (!band_schedule(ref_len, read_len, band_half(ref_len, read_len), (read_len + 31) / 32, &s)) return 0;
+    PrefixPlan p;
+    p.n = n_depths;
+    for (int j = 0; j < n_depths; j++) p.depth[j] = depths[j];
+    if (!prefix_plan_layout(ref_len, (read_len + 31) / 32, s, &p)) return 0;
+    const int n = p.off[p.n + 1];
+    if (offsets)
+        for (int j = 0; j <= p.n + 1; j++) offsets[j] = p.off[j];
+    if (dst && cap >= n)   // window by window, as pack_band_segments_kernel writes it
+        for (int i = 0; i < n / 8; i++) {
+            int seg = 0;
+            while (seg < p.n && p.off[seg + 1] <= 8 * i) seg++;
+            for (int j = 0; j < 8; j++) dst[8 * i + j] = kCodeEnd;
+            band_rows_layout(s, seg ? p.depth[seg - 1] : 0, seg < p.n ? p.depth[seg] : ref_len, seg == p.n, mapped_row, dst + 8 * i,
+                             8 * i - p.off[seg], 8);
+        }
+    return n;
 }
 
 int bgsa_hip_myers_band_stream(const char *mapped_row, int ref_len, int read_len, unsigned char *dst, int cap)

@@ -88,13 +88,15 @@ inline bool band_schedule(int m, int n, int h, int nw, BandSchedule *s)
 // byte 7 skipped by an early REFILL), END, the spare window.
 inline size_t band_stream_stride(int ref_len) { return stream_stride(ref_len + 3 * kBandMaxSwitches); }
 
-// Writes bytes [first, first + count) of the band stream of one query (row = its mapped characters) to dst[0 .. count) when
-// dst != nullptr and returns the stream's length in bytes (<= band_stream_stride) — or, once the range is written, the position
-// after it.  Where the SETWIN and REFILL bytes go depends on the schedule only, so the packer gives every 8-byte window a
-// thread of its own, which reads the (at most seven) characters of its window and no others.  Shared by the packer kernel
-// and bgsa_hip_myers_band_stream.
-__host__ __device__ inline int band_stream_layout(int len, const BandSchedule &s, const char *row, unsigned char *dst,
-                                                  int first = 0, int count = 0x7fffffff)
+// Writes bytes [first, first + count) of the stream of rows r0 .. r1 - 1 of one query (row = its mapped characters) to
+// dst[0 .. count) when dst != nullptr and returns the length in bytes — or, once the range is written, the position after
+// it.  The stream begins with the SETWIN of row r0's window, ends with END padded to its 8-byte window and, if `spare`, the
+// all-END window that the loops fetch ahead.  Where the SETWIN and REFILL bytes go depends on the schedule only, so the
+// packers give every 8-byte window a thread of its own, which reads the (at most seven) characters of its window and no
+// others.  Rows 0 .. len - 1 with the spare window are the band stream of a query (band_stream_layout); a query's stream in
+// segments (prefix sharing, below) is one such stream per segment.
+__host__ __device__ inline int band_rows_layout(const BandSchedule &s, int r0, int r1, bool spare, const char *row, unsigned char *dst,
+                                                int first = 0, int count = 0x7fffffff)
 {
     int pos = 0, sw = 0;
     auto in = [&]() { return dst && pos >= first && pos - first < count; };
@@ -106,9 +108,10 @@ __host__ __device__ inline int band_stream_layout(int len, const BandSchedule &s
         put(kCodeRefill);
         while (pos & 7) put(kCodeEnd);
     };
-    for (int r = 0; r < len; r++) {
+    while (sw + 1 < s.n && s.row[sw + 1] <= r0) sw++;   // the window row r0 runs on (s.row[0] = 0)
+    for (int r = r0; r < r1; r++) {
         if (dst && pos - first >= count) return pos;
-        if (sw < s.n && s.row[sw] == r) {
+        if (sw < s.n && (s.row[sw] == r || r == r0)) {
             if ((pos & 7) >= 6) refill();
             put(kCodeSetWin);
             put(s.win[sw]);
@@ -124,9 +127,85 @@ __host__ __device__ inline int band_stream_layout(int len, const BandSchedule &s
     if ((pos & 7) == 7) refill();
     put(kCodeEnd);
     while (pos & 7) put(kCodeEnd);
-    for (int j = 0; j < 8; j++) put(kCodeEnd);
+    for (int j = 0; spare && j < 8; j++) put(kCodeEnd);
     return pos;
 }
+
+// ... of the whole query: the band stream (<= band_stream_stride bytes).  Shared by the packer kernel and bgsa_hip_myers_band_stream.
+__host__ __device__ inline int band_stream_layout(int len, const BandSchedule &s, const char *row, unsigned char *dst,
+                                                  int first = 0, int count = 0x7fffffff)
+{
+    return band_rows_layout(s, 0, len, true, row, dst, first, count);
+}
+
+// ---- prefix sharing ------------------------------------------------------------------------------------------
+// The state after query row r depends on the subjects and on the query's first r characters only.  A wave walks a tile of
+// queries over the same subjects, so with the tile's queries in sorted order a query that begins like its predecessor need
+// not run the rows they share: the wave keeps the state after rows d_1 < d_2 < ... (the DEPTHS, launch constants) of the
+// current query's prefix in LDS and a query resumes behind the deepest depth <= its common prefix with the predecessor.
+// The packer writes each query's stream in segments — rows 1..d_1, d_1+1..d_2, ..., d_n+1..m, each a stream of its own
+// (band_rows_layout) at an offset that depends on the schedule only.  Only where rows 1..d_n run on words 0..1: the snapshot
+// is those two words of each group, the other words still hold their initial state.
+constexpr int kPrefixMaxDepths = 5;
+constexpr int kPrefixKeyChars = 10;                     // characters of the sort key, 3 bits each; also the deepest depth
+struct PrefixPlan {
+    int n = 0;                                // depths (0: no sharing — one segment, the band stream as ever)
+    int depth[kPrefixMaxDepths] = {};         // ascending, 1 .. kPrefixKeyChars
+    int off[kPrefixMaxDepths + 2] = {};       // byte offset of segment j in a query's stream, j = 0 .. n; off[n + 1] = the stride
+};
+// Bytes per query that n_depths more segments add at most: per cut the SETWIN and its byte, the END and its padding.
+inline size_t band_segments_stride_bound(int ref_len) { return band_stream_stride(ref_len) + 16 * kPrefixMaxDepths; }
+
+// Fills the segment offsets for depths p->depth[0 .. n); false (p->n = 0) where the shape does not qualify: a depth outside
+// 1 .. min(kPrefixKeyChars, m - 1), depths not ascending, or a row up to the deepest depth whose window leaves words 0..1.
+inline bool prefix_plan_layout(int m, int nw, const BandSchedule &s, PrefixPlan *p)
+{
+    const int n = p->n;
+    p->n = 0;
+    if (n < 1 || n > kPrefixMaxDepths || s.n < 1) return false;
+    for (int j = 0; j < n; j++)
+        if (p->depth[j] < 1 || p->depth[j] > kPrefixKeyChars || p->depth[j] >= m || (j && p->depth[j] <= p->depth[j - 1])) return false;
+    for (int i = 0; i < s.n && s.row[i] < p->depth[n - 1]; i++)   // windows (0, 0) and (0, 1) are slot groups 0 and 1
+        if (s.win[i] != band_window_index(nw, 0, 0) && s.win[i] != band_window_index(nw, 0, 1)) return false;
+    int pos = 0;
+    for (int j = 0; j <= n; j++) {
+        p->off[j] = pos;
+        pos += band_rows_layout(s, j ? p->depth[j - 1] : 0, j < n ? p->depth[j] : m, j == n, nullptr, nullptr);
+    }
+    p->off[n + 1] = pos;
+    if (static_cast<size_t>(pos) > band_segments_stride_bound(m) || pos / 8 > 255) return false;   // (prefix_segments_word: a byte per offset)
+    p->n = n;
+    return true;
+}
+
+// One entry per query of a sharing launch, in sorted order, behind the streams and the task counter's kTaskCounterBytes:
+// q = the query (relative to ref_start), lcp = its common prefix with the sorted predecessor, capped at the deepest depth and
+// 0 for the first query of every tile, seg = the segment it may start at (the depths <= lcp).  The sort keys follow the entries
+// (scratch of the launch).
+struct PrefixEntry {
+    int q;
+    short lcp, seg;
+};
+inline size_t prefix_order_bytes(int n_queries) { return static_cast<size_t>(n_queries) * (sizeof(PrefixEntry) + sizeof(uint32_t)) + 256; }
+__host__ __device__ inline PrefixEntry *prefix_entries(unsigned *task_counter)
+{
+    return reinterpret_cast<PrefixEntry *>(reinterpret_cast<unsigned char *>(task_counter) + kTaskCounterBytes);
+}
+// What the kernel gets of a plan, one word: byte j <= n = off[j] / 8, the top byte = n (0: no sharing).
+inline unsigned long long prefix_segments_word(const PrefixPlan &p)
+{
+    unsigned long long w = static_cast<unsigned long long>(p.n) << 56;
+    for (int j = 0; j <= p.n && p.n; j++) w |= static_cast<unsigned long long>(p.off[j] / 8) << (8 * j);
+    return w;
+}
+
+// Sorts queries ref_start .. ref_end - 1 by their first kPrefixKeyChars class codes and writes the entries (q_tile: the
+// launch's queries per task); then packs their streams in the segments of `p` and zeroes the task counter and the guard's
+// pair, as launch_pack_band does.  All on `stream`, nothing read back.
+int launch_prefix_order(const char *d_content, int ref_len, int ref_start, int ref_end, int q_tile, const PrefixPlan &p,
+                        unsigned *d_words, hipStream_t stream);   // preprocess.hip
+int launch_pack_band_segments(const char *d_content, int ref_len, const BandSchedule &s, const PrefixPlan &p, int ref_start,
+                              int ref_end, void *d_streams, hipStream_t stream, unsigned *d_words);   // preprocess.hip
 
 // The guard's pair of one launch, {queries redone, queries banded} (myers_global_asm_kernel<NW, 1, *, true>): 64 bytes behind
 // the task counter, inside the kTaskCounterBytes behind the streams; zeroed by the packer with the counter.

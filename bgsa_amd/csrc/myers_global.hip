@@ -27,7 +27,8 @@
 //   myers_blocked_kernel<NW>        > 1024 bp    column blocks of the planes body, carries between
 //                                                blocks through per-wave carry words
 //
-// Integer/bitwise only; no LDS, no MFMA.  The kernels are VALU-issue bound.
+// Integer/bitwise only; no MFMA, and no LDS but the band kernels' snapshots of a prefix-sharing launch.  The kernels are
+// VALU-issue bound.
 #include <stdlib.h>
 #include <string.h>
 
@@ -191,17 +192,37 @@ constexpr int kBandPairMaxWords = 5;  // widest band loop with two subject group
 // length read_lens[column] — per lane instead of wave-uniform, once per query.  What lies behind a subject's end never enters.
 // A separate instantiation: the equal-length kernels keep their code and their register counts.  Never with BAND: the window
 // schedule and the limit certify one (m, n), DESIGN §4.2.
-template <int NW, int G, bool DYN = false, bool BAND = false, bool LENS = false>
-__global__ __launch_bounds__(256) void myers_global_asm_kernel(
+// the band kernels' snapshots of a sharing launch (dynamic LDS: launch_asm sizes it by the launch's depths; none without sharing)
+extern __shared__ uint4 prefix_slots[];
+// SHARE (prefix sharing, myers_band.h) is a separate instantiation of the band kernels: a launch that does not share runs a
+// kernel without the segment loop, the entry load and the slots (within one VGPR and two SGPRs of what it was before; the
+// loop cost such a launch about 0.4 % while every band kernel carried it, LABNOTES §24.4).
+// Waves per SIMD the SHARING kernels are held to — those of the same kernel without sharing, as the resource report gives them
+// (3..8 words: 8, 8, 8, 8 | 7, 7 | 6, 6 | 5, the counter kernels from 6 words on one fewer; two groups: 8, 7 | 6, 5).  The segment
+// loop put the counter kernels of 3..5 words a few scalar registers above the 100 that eight waves leave each; asked for, the
+// compiler parks those in vector-register lanes outside the row loop.  The figure is a MINIMUM the compiler is forced under:
+// a later change that needs more registers will not show up as a lost wave but as scratch, so whoever changes these kernels
+// runs -Rpass-analysis=kernel-resource-usage again and looks at ScratchSize (0 everywhere today) as well as at the waves.
+// 1 (every other kernel) asks for nothing.
+constexpr int band_kernel_waves(int nw, int g, bool dyn, bool share)
+{
+    if (!share) return 1;
+    if (g == 2) return nw == 3 ? 8 : (nw == 4 ? (dyn ? 6 : 7) : 5);
+    return nw <= 5 ? 8 : (nw == 6 ? (dyn ? 7 : 8) : (nw == 7 ? (dyn ? 6 : 7) : (dyn ? 5 : 6)));
+}
+template <int NW, int G, bool DYN = false, bool BAND = false, bool LENS = false, bool SHARE = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel_waves(NW, G, DYN, SHARE)))) void myers_global_asm_kernel(
     const unsigned char *__restrict__ streams, const uint32_t *__restrict__ peq,
     int16_t *__restrict__ out, int ref_len, int read_len, long long ld, int n_groups, int word_num,
     int n_queries, int q_tile, int stream_stride_bytes, unsigned *__restrict__ fault_word,
     unsigned *__restrict__ task_counter, int band_limit = 0, unsigned long long *__restrict__ band_launch = nullptr,
-    const int32_t *__restrict__ read_lens = nullptr)
+    const int32_t *__restrict__ read_lens = nullptr, unsigned long long prefix_segments = 0,
+    const PrefixEntry *__restrict__ order = nullptr)
 {
     static_assert(!BAND || (NW >= kBandMinWords && NW <= kBandMaxWords && (G == 1 || (G == 2 && NW <= kBandPairMaxWords))),
                   "band: 3..8 words, one subject group per wave — or two up to 5 words");
     static_assert(!(LENS && BAND), "the certified band is derived from one (m, n): a length-aware launch runs full rows");
+    static_assert(!SHARE || BAND, "prefix sharing: the band kernels only");
     // LENS: the lane's length is loaded once per task and kept across the row loops, one VGPR per group — except beyond 8 words,
     // where the widths sit at their occupancy steps (20 words 238, 28 and 32 words 255 VGPRs): there the epilogue loads it again
     // per query, one dword per lane against >= 10 words x ref_len rows.
@@ -253,9 +274,17 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
         const int q1 = (q0 + q_tile < n_queries) ? q0 + q_tile : n_queries;
         int16_t *dst = out + static_cast<size_t>(group0) * kLanes + lane;
 
-        for (int q = q0; q < q1; q++) {
+        for (int k = q0; k < q1; k++) {
             if constexpr (DYN) {   // the next task, asked for under this one's last query: late enough that the tail of a
-                if (q == q1 - 1) task_issued = issue_wave_task(task_counter);   // launch is handed out as waves free up, early enough that the round trip is hidden
+                if (k == q1 - 1) task_issued = issue_wave_task(task_counter);   // launch is handed out as waves free up, early enough that the round trip is hidden
+            }
+            // SHARE: the tile is walked in sorted order, k is a sorted position, and its entry names the query and the segment it may
+            // start at (a pointer of its own, read-only: a scalar load)
+            int q = k, seg = 0;
+            if constexpr (SHARE) {
+                const int2 e = *reinterpret_cast<const int2 *>(order + k);   // {q, lcp | seg << 16}
+                q = __builtin_amdgcn_readfirstlane(e.x);
+                seg = __builtin_amdgcn_readfirstlane(e.y >> 16);
             }
             uint32_t st[2 * G * NW];  // {VP, VN} per word
 #pragma unroll
@@ -273,11 +302,39 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
                 const int n_live = G == 1 ? 1 : (group0 + 1 < n_groups ? 2 : 1);
                 const int tried = band_on * n_live;
                 int band = band_on, score[G];
+                // Prefix sharing: the stream is n_depths + 1 segments, and behind segment j < n_depths the banded pass leaves words
+                // 0..1 of each group in this wave's slot j.  A slot then holds the state of the CURRENT query's first depth[j] rows:
+                // either this query ran them and wrote the slot, or it resumed at or behind that depth — it shares those rows with
+                // whoever wrote it.  The full-row pass starts at row 0 and stores nothing (a banded snapshot is no full-row state);
+                // a wave whose guard is off shares nothing.  Without SHARE: one segment, the band stream as ever.
+                const int n_depths = SHARE ? static_cast<int>(prefix_segments >> 56) : 0;   // wave-uniform: a kernel argument
+                const bool sharing = SHARE && band_on;
+                [[maybe_unused]] uint4 *const slots = prefix_slots + ((threadIdx.x >> 6) * G) * kLanes + lane;   // [depth][wave][group][lane]
+                if (!sharing) seg = 0;
+                if (SHARE && seg) {
+#pragma unroll
+                    for (int gi = 0; gi < G; gi++) {
+                        const uint4 v = slots[((seg - 1) * kWavesPerBlock * G + gi) * kLanes];
+                        st[2 * gi * NW] = v.x;
+                        st[2 * gi * NW + 1] = v.y;
+                        st[2 * gi * NW + 2] = v.z;
+                        st[2 * gi * NW + 3] = v.w;
+                    }
+                }
                 for (;;) {
-                    const int left = myers_band_rows_asm<NW, G>(st, P, uniform_u64(s),
-                                                                __builtin_amdgcn_readfirstlane(stream_stride_bytes / 8 - 2),
-                                                                __builtin_amdgcn_readfirstlane(band));
-                    note_stream_fault(fault_word, left);
+                    for (; seg <= n_depths; seg++) {
+                        const int at = SHARE ? static_cast<int>((prefix_segments >> (8 * seg)) & 0xffu) * 8 : 0;   // the segment's offset in the stream
+                        const int left = myers_band_rows_asm<NW, G>(st, P, uniform_u64(s + static_cast<unsigned>(at)),
+                                                                    __builtin_amdgcn_readfirstlane((stream_stride_bytes - at) / 8 - 2),
+                                                                    __builtin_amdgcn_readfirstlane(band));
+                        note_stream_fault(fault_word, left);
+                        if (SHARE && sharing && band && seg < n_depths) {
+#pragma unroll
+                            for (int gi = 0; gi < G; gi++)
+                                slots[(seg * kWavesPerBlock * G + gi) * kLanes] =
+                                    make_uint4(st[2 * gi * NW], st[2 * gi * NW + 1], st[2 * gi * NW + 2], st[2 * gi * NW + 3]);
+                        }
+                    }
 #pragma unroll
                     for (int gi = 0; gi < G; gi++) {
                         score[gi] = ref_len;
@@ -296,6 +353,7 @@ __global__ __launch_bounds__(256) void myers_global_asm_kernel(
                     if (n_over == 0) break;
                     if constexpr (G == 1) n_over = 1;   // (what it is: said so that the one-group kernels keep their code)
                     band = 0;   // a lane is not certified: the whole wave runs the query again with full rows
+                    seg = 0;    // ... from row 0
                     unsigned long long r = static_cast<unsigned long long>(n_over),
                                        b = static_cast<unsigned long long>(unreported) + n_live;
                     if (lane == 0) {
@@ -801,6 +859,75 @@ bool peq_blocks()
     return on;
 }
 
+// ---- prefix sharing of the band kernels (myers_band.h) ----
+// BGSA_MYERS_PREFIX_SHARE (read once): 0 = off; 1 = the default depths under the default rule; a list a,b,c of one to
+// kPrefixMaxDepths depths (a single number from 2 up is a list of one) = these depths for every banded launch whose shape
+// and tile qualify, whatever its query count (tests, A/B); unset = kPrefixShareDefault.  A list that is too long, not
+// ascending, outside 1 .. kPrefixKeyChars or reaching rows that leave words 0..1 turns sharing OFF for the launch — it is
+// never cut to fit —, and bgsa_hip_myers_prefix_depths then answers 0.
+constexpr bool kPrefixShareDefault = true;
+// The fewest queries of a launch that shares by default.  The order costs three small kernels and the segments a few hundred
+// cycles per (query, wave); a block of 100 queries shares about two rows.
+constexpr int kPrefixMinQueries = 2000;
+constexpr int kPrefixMinTile = 16;      // a tile's first query shares nothing
+struct PrefixKnob {
+    int mode;   // 0 off, 1 default depths, 2 the listed depths
+    int n, depth[kPrefixMaxDepths];
+};
+static const PrefixKnob &prefix_knob()
+{
+    static const PrefixKnob k = [] {
+        PrefixKnob v = {kPrefixShareDefault ? 1 : 0, 0, {}};
+        const char *e = getenv("BGSA_MYERS_PREFIX_SHARE");
+        if (!e || !*e) return v;
+        if (!strchr(e, ',')) {
+            const int d = atoi(e);
+            if (d <= 0) v.mode = 0;
+            else if (d == 1) v.mode = 1;
+            else v = {2, 1, {d}};
+            return v;
+        }
+        v = {2, 0, {}};
+        for (const char *c = e; c; c = strchr(c, ',') ? strchr(c, ',') + 1 : nullptr) {
+            if (v.n == kPrefixMaxDepths) return PrefixKnob{0, 0, {}};   // more depths than slots: off, not cut
+            v.depth[v.n++] = atoi(c);
+        }
+        return v;
+    }();
+    return k;
+}
+
+// The depths of a banded launch of nq queries in tiles of q_tile against read_count subjects (s: its schedule), and its
+// segment offsets: p->n = 0 where the launch does not share.  Default depths: d0 - 1, d0, d0 + 1 around d0 = floor(log4 nq), the
+// prefix that consecutive queries of a sorted uniform set share, clipped to 1 .. kPrefixKeyChars and to the shape.
+void prefix_select(int ref_len, int nw, const BandSchedule &s, int nq, int q_tile, int64_t read_count, PrefixPlan *p)
+{
+    *p = PrefixPlan{};
+    const PrefixKnob &knob = prefix_knob();
+    // the order is n^2 comparisons: not where the queries outnumber the subjects many times
+    if (knob.mode == 0 || q_tile < kPrefixMinTile || nq < kPrefixMinTile || nq > 8 * read_count) return;
+    PrefixPlan want;
+    if (knob.mode == 2) {
+        want.n = knob.n;
+        for (int j = 0; j < knob.n; j++) want.depth[j] = knob.depth[j];
+    } else {
+        if (nq < kPrefixMinQueries) return;
+        int d0 = 0;
+        for (long long v = nq; v >= 4; v /= 4) d0++;
+        for (int d = d0 - 1; d <= d0 + 1; d++)
+            if (d >= 1 && d <= kPrefixKeyChars && d < ref_len) want.depth[want.n++] = d;
+        // clipped to the rows on words 0..1: drop the depths behind the first window that leaves them
+        while (want.n > 0) {
+            PrefixPlan probe = want;
+            if (prefix_plan_layout(ref_len, nw, s, &probe)) break;
+            want.n--;
+        }
+    }
+    if (prefix_plan_layout(ref_len, nw, s, &want)) *p = want;
+}
+// LDS of a sharing launch: per workgroup its waves' slots of two words {VP, VN} per group and lane
+size_t prefix_lds_bytes(const PrefixPlan &p, int groups) { return static_cast<size_t>(p.n) * kWavesPerBlock * groups * kLanes * sizeof(uint4); }
+
 // The certificate statistics of one band launch into the device's sticky counts (myers_band.h: band_stats_words).
 __global__ void band_stats_add_kernel(const unsigned long long *__restrict__ launch, unsigned long long *__restrict__ stats)
 {
@@ -811,7 +938,7 @@ __global__ void band_stats_add_kernel(const unsigned long long *__restrict__ lau
 // Every instantiation of myers_global_asm_kernel through one pointer type (a function pointer has no default arguments: the
 // plain kernels get their two band parameters passed as 0 / nullptr).
 using AsmKernel = void (*)(const unsigned char *, const uint32_t *, int16_t *, int, int, long long, int, int, int, int, int,
-                           unsigned *, unsigned *, int, unsigned long long *, const int32_t *);
+                           unsigned *, unsigned *, int, unsigned long long *, const int32_t *, unsigned long long, const PrefixEntry *);
 
 template <int NW, int G>
 int launch_asm(const ScoreArgs &a)
@@ -847,6 +974,7 @@ int launch_asm(const ScoreArgs &a)
         }
     }
     BandSchedule sched;
+    PrefixPlan prefix;   // n = 0: the launch packs and runs as ever, on the kernel it ran on before
     int h = 0;
     bool band = false;
     if constexpr ((G == 1 || kBandPair) && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
@@ -855,21 +983,34 @@ int launch_asm(const ScoreArgs &a)
         if (band) {
             on_grid = myers_global_asm_kernel<NW, G, false, true>;
             on_counter = myers_global_asm_kernel<NW, G, true, true>;
+            prefix_select(a.ref_len, NW, sched, nq, plan.q_tile, a.read_count, &prefix);
+            if (prefix.n) {
+                on_grid = myers_global_asm_kernel<NW, G, false, true, false, true>;
+                on_counter = myers_global_asm_kernel<NW, G, true, true, false, true>;
+            }
         }
     }
     if (kBandPair && !band) {   // myers_band_groups answers 2 for banded launches only
         set_error_text("myers: two subject groups per wave selected for a launch without the certified band");
         return BGSA_HIP_EUNSUPPORTED;
     }
-    const int stride = static_cast<int>(band ? band_stream_stride(a.ref_len) : kPairs ? pair_stream_stride(a.ref_len) : stream_stride(a.ref_len));
+    const unsigned lds = (plan.dynamic ? myers_lds_pad() : 0u) + static_cast<unsigned>(prefix_lds_bytes(prefix, G));
+    const int stride = static_cast<int>(prefix.n  ? static_cast<size_t>(prefix.off[prefix.n + 1])
+                                        : band    ? band_stream_stride(a.ref_len)
+                                        : kPairs  ? pair_stream_stride(a.ref_len)
+                                                  : stream_stride(a.ref_len));
     // the task counter sits behind the streams, and the band's guard pair 64 bytes further (both inside the kTaskCounterBytes
     // the workspace reserves); the packer zeroes them
     unsigned *words = task_counter_in(a.d_workspace, static_cast<size_t>(stride) * nq);
     LaunchGrid lg;
     if (int rc = plan_grid(plan, n_waves, nq, words,
-                           [&] { return on_counter ? persistent_blocks_for(on_counter, myers_lds_pad()) : persistent_blocks(); }, "myers", &lg))
+                           [&] { return on_counter ? persistent_blocks_for(on_counter, lds) : persistent_blocks(); }, "myers", &lg))
         return rc;
-    if (int rc = band     ? launch_pack_band(a.d_content, a.ref_len, sched, a.ref_start, a.ref_end, a.d_workspace, a.stream, words)
+    if (prefix.n)
+        if (int rc = launch_prefix_order(a.d_content, a.ref_len, a.ref_start, a.ref_end, plan.q_tile, prefix, words, a.stream))
+            return rc;
+    if (int rc = prefix.n ? launch_pack_band_segments(a.d_content, a.ref_len, sched, prefix, a.ref_start, a.ref_end, a.d_workspace, a.stream, words)
+                 : band   ? launch_pack_band(a.d_content, a.ref_len, sched, a.ref_start, a.ref_end, a.d_workspace, a.stream, words)
                  : kPairs ? launch_pack_query_pairs(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter)
                           : launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter))
         return rc;
@@ -878,10 +1019,11 @@ int launch_asm(const ScoreArgs &a)
         return rc;
     unsigned long long *guard = band ? band_launch_words(words) : nullptr;
     const AsmKernel kernel = lg.counter ? on_counter : on_grid;
-    hipLaunchKernelGGL(kernel, lg.grid, dim3(256), lg.counter ? myers_lds_pad() : 0u, a.stream,
+    hipLaunchKernelGGL(kernel, lg.grid, dim3(256), lds, a.stream,
                        static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len, a.read_len,
                        static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq, plan.q_tile, stride,
-                       fault, lg.counter, band ? 2 * h + 1 : 0, guard, a.d_read_lens);
+                       fault, lg.counter, band ? 2 * h + 1 : 0, guard, a.d_read_lens, prefix_segments_word(prefix),
+                       static_cast<const PrefixEntry *>(prefix_entries(words)));
     BGSA_HIP_TRY(hipGetLastError());
     if (band) {
         hipLaunchKernelGGL(band_stats_add_kernel, dim3(1), dim3(1), 0, a.stream, static_cast<const unsigned long long *>(guard),
@@ -1098,6 +1240,22 @@ int myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_le
     if (word_num < 1 || word_num > kMaxWords) return 1;
     const MyersChoice c = myers_select(word_num, 0, read_count, ref_len, read_len, mixed_lengths != 0);
     return c.family == MyersFamily::kAsmBandPairs ? 2 : 1;
+}
+
+int myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_len, int n_queries, int mixed_lengths, int *depths)
+{
+    if (word_num < 1 || word_num > kMaxWords || n_queries < 1) return 0;
+    const MyersChoice c = myers_select(word_num, 0, read_count, ref_len, read_len, mixed_lengths != 0);
+    if ((c.family != MyersFamily::kAsm && c.family != MyersFamily::kAsmBandPairs) || mixed_lengths) return 0;
+    BandSchedule sched;
+    if (!band_schedule(ref_len, read_len, band_half(ref_len, read_len), c.nw, &sched)) return 0;
+    // the tile launch_asm picks for the band widths (3..8 words: a counter kernel, tiles up to query_tile_max())
+    const int64_t n_waves = (read_count / kLanes + c.G - 1) / c.G;
+    const TaskPlan plan = plan_tasks(n_queries, n_waves, static_cast<long long>(ref_len) * c.nw * c.G, 32, true, query_tile_max());
+    PrefixPlan p;
+    prefix_select(ref_len, c.nw, sched, n_queries, plan.q_tile, read_count, &p);
+    for (int j = 0; j < p.n; j++) depths[j] = p.depth[j];
+    return p.n;
 }
 
 const char *myers_kernel_name(int word_num, int semi_global)

@@ -271,6 +271,119 @@ int launch_pack_band(const char *d_content, int ref_len, const BandSchedule &s, 
     return BGSA_HIP_OK;
 }
 
+// ---- prefix sharing (myers_band.h): the launch's queries in sorted order, and their streams in segments ----
+// The key of a query: its first kPrefixKeyChars class codes as the streams carry them (out-of-alphabet bytes behave as 'A'),
+// three bits each, the first character on top; a query shorter than that is padded with code 0.
+__global__ __launch_bounds__(256) void prefix_key_kernel(const char *__restrict__ content, int len, int ref_start, int n_queries,
+                                                         uint32_t *__restrict__ keys)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_queries) return;
+    const char *row = content + static_cast<size_t>(ref_start + q) * (len + 1);
+    uint32_t key = 0;
+    for (int j = 0; j < kPrefixKeyChars; j++) {
+        const unsigned c = j < len ? static_cast<unsigned char>(row[j]) : 0u;
+        key = (key << 3) | (c > 4 ? 0u : c);
+    }
+    keys[q] = key;
+}
+// A query's position in the sorted order = the queries with a smaller key, or the same key and a smaller number: every
+// thread counts them over the keys, which pass through LDS a block at a time.  n^2 comparisons — four instructions each
+// against the some thousand per (query, subject) of the scoring launch that follows, which is why launch_asm asks for no
+// more queries than a few times the subjects.
+__global__ __launch_bounds__(256) void prefix_rank_kernel(const uint32_t *__restrict__ keys, int n_queries,
+                                                          PrefixEntry *__restrict__ entries)
+{
+    __shared__ uint32_t block_keys[256];
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t own = q < n_queries ? keys[q] : 0u;
+    int rank = 0;
+    for (int base = 0; base < n_queries; base += 256) {
+        block_keys[threadIdx.x] = base + static_cast<int>(threadIdx.x) < n_queries ? keys[base + threadIdx.x] : ~0u;   // above every 30-bit key
+        __syncthreads();
+        for (int j = 0; j < 256; j++) {
+            const uint32_t other = block_keys[j];
+            rank += (other < own || (other == own && base + j < q)) ? 1 : 0;
+        }
+        __syncthreads();
+    }
+    if (q < n_queries) entries[rank].q = q;
+}
+// lcp of sorted position k with k - 1, from the keys: capped at the deepest depth, 0 for the first query of every tile.
+__global__ __launch_bounds__(256) void prefix_lcp_kernel(const uint32_t *__restrict__ keys, int n_queries, int q_tile, PrefixPlan plan,
+                                                         PrefixEntry *__restrict__ entries)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_queries) return;
+    int lcp = 0;
+    if (k % q_tile) {
+        const uint32_t diff = keys[entries[k].q] ^ keys[entries[k - 1].q];
+        lcp = diff ? (3 * kPrefixKeyChars - 1 - (31 - __clz(diff))) / 3 : kPrefixKeyChars;
+        if (lcp > plan.depth[plan.n - 1]) lcp = plan.depth[plan.n - 1];
+    }
+    int seg = 0;
+    while (seg < plan.n && plan.depth[seg] <= lcp) seg++;
+    entries[k].lcp = static_cast<short>(lcp);
+    entries[k].seg = static_cast<short>(seg);
+}
+
+int launch_prefix_order(const char *d_content, int ref_len, int ref_start, int ref_end, int q_tile, const PrefixPlan &p,
+                        unsigned *d_words, hipStream_t stream)
+{
+    const int nq = ref_end - ref_start;
+    if (nq <= 0 || p.n < 1) return BGSA_HIP_OK;
+    PrefixEntry *entries = prefix_entries(d_words);
+    uint32_t *keys = reinterpret_cast<uint32_t *>(entries + nq);
+    const dim3 grid((nq + 255) / 256), block(256);
+    hipLaunchKernelGGL(prefix_key_kernel, grid, block, 0, stream, d_content, ref_len, ref_start, nq, keys);
+    BGSA_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prefix_rank_kernel, grid, block, 0, stream, static_cast<const uint32_t *>(keys), nq, entries);
+    BGSA_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prefix_lcp_kernel, grid, block, 0, stream, static_cast<const uint32_t *>(keys), nq, q_tile, p, entries);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+// One thread per 8-byte window of a query's segments: the segment that holds the window, then band_rows_layout on it.
+__global__ __launch_bounds__(256) void pack_band_segments_kernel(const char *__restrict__ content, unsigned long long *__restrict__ streams,
+                                                                 int len, BandSchedule sched, PrefixPlan plan, int ref_start,
+                                                                 int n_queries, int per, unsigned *__restrict__ words)
+{
+    const long long tid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (tid == 0) {   // as pack_band_kernel
+        words[0] = 0u;
+        band_launch_words(words)[0] = band_launch_words(words)[1] = 0ull;
+    }
+    if (tid >= static_cast<long long>(n_queries) * per) return;
+    const int q = static_cast<int>(tid / per), i = static_cast<int>(tid % per);
+    int seg = 0;
+    while (seg < plan.n && plan.off[seg + 1] <= 8 * i) seg++;
+    unsigned char win[8];
+    for (int j = 0; j < 8; j++) win[j] = kCodeEnd;
+    band_rows_layout(sched, seg ? plan.depth[seg - 1] : 0, seg < plan.n ? plan.depth[seg] : len, seg == plan.n,
+                     content + static_cast<size_t>(ref_start + q) * (len + 1), win, 8 * i - plan.off[seg], 8);
+    unsigned long long w = 0;
+    for (int j = 0; j < 8; j++) w |= static_cast<unsigned long long>(win[j]) << (8 * j);
+    streams[tid] = w;
+}
+
+int launch_pack_band_segments(const char *d_content, int ref_len, const BandSchedule &s, const PrefixPlan &p, int ref_start,
+                              int ref_end, void *d_streams, hipStream_t stream, unsigned *d_words)
+{
+    const int nq = ref_end - ref_start;
+    if (nq <= 0) return BGSA_HIP_OK;
+    const int stride = p.off[p.n + 1];
+    if (p.n < 1 || stride <= 0 || (stride & 7) || static_cast<size_t>(stride) > band_segments_stride_bound(ref_len)) {
+        set_error_text("myers band: segmented stream longer than its stride");
+        return BGSA_HIP_EINVAL;
+    }
+    const long long total = static_cast<long long>(nq) * (stride / 8);
+    hipLaunchKernelGGL(pack_band_segments_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, d_content,
+                       static_cast<unsigned long long *>(d_streams), ref_len, s, p, ref_start, nq, stride / 8, d_words);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
 __global__ __launch_bounds__(64) void pack_blocked_kernel(const char *__restrict__ content,
                                                           unsigned char *__restrict__ streams, int len,
                                                           int ref_start, int n_queries, int stride)

@@ -689,6 +689,44 @@ def myers_band_stream(codes, m: int, n: int, h: int, nw: int) -> bytes | None:
     return bytes(out)
 
 
+def myers_band_segments(codes, m: int, n: int, h: int, nw: int, depths) -> tuple[bytes, list] | None:
+    """The stream of one query cut behind rows depths[0] < depths[1] < ... (prefix sharing): one band stream per
+    segment — it begins with the SETWIN of its first row's window whether or not the window changes there, ends with END
+    padded to its 8-byte window, and only the last one carries the spare all-END window.  Returns the bytes and the offsets
+    of the segments followed by the total length.  None where the band is off or a row up to the deepest depth leaves
+    words 0..1.  Restates myers_band.h: band_rows_layout / prefix_plan_layout."""
+    win = myers_band_windows(m, n, h, nw)
+    depths = list(depths)
+    if win is None or not depths or depths != sorted(set(depths)) or depths[0] < 1 or depths[-1] >= m:
+        return None
+    if any(w not in ((0, 0), (0, 1)) for w in win[:depths[-1]]):
+        return None
+    out, offsets = bytearray(), []
+    cuts = [0] + depths + [m]
+    for j in range(len(cuts) - 1):
+        offsets.append(len(out))
+        seg = bytearray()
+        cur = None
+        for i in range(cuts[j], cuts[j + 1]):
+            if win[i] != cur:
+                if len(seg) % 8 >= 6:
+                    seg += bytes([6] + [5] * (7 - len(seg) % 8))
+                seg += bytes([7, myers_window_index(nw, *win[i])])
+                cur = win[i]
+            if len(seg) % 8 == 7:
+                seg.append(6)
+            seg.append(int(codes[i]))
+        if len(seg) % 8 == 7:
+            seg.append(6)
+        seg.append(5)
+        seg += bytes([5] * (-len(seg) % 8))
+        if j == len(cuts) - 2:
+            seg += bytes([5] * 8)
+        out += seg
+    offsets.append(len(out))
+    return bytes(out), offsets
+
+
 def run_band_stream(nw: int, state: list, peq: np.ndarray, stream: bytes, band: bool = True, balanced: bool = False,
                     schedule=None, groups: int = 1) -> int:
     """Interpret a band stream the way myers_band_rows_asm walks it (band = False: SETWIN keeps the full window; schedule:

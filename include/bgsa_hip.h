@@ -716,7 +716,21 @@ int bgsa_hip_query_stream(int algo, const char *mapped_row, int ref_len, int k, 
  * bgsa_hip_myers_band_groups: the subject groups a wave carries (1 | 2) in a global launch of word_num-word subjects, this bucket
  * size and these lengths (mixed_lengths != 0: a bucket with per-subject lengths) — 2 only where the band applies, word_num <= 5
  * and the bucket is large, or BGSA_MYERS_BAND_GROUPS=1|2 forces it (host only, no GPU).  bgsa_hip_kernel_name names the
- * one-group kernel, the small bucket's. */
+ * one-group kernel, the small bucket's.
+ * bgsa_hip_myers_prefix_depths: prefix sharing of the band kernels — a wave walks its tile of queries in sorted order and
+ * resumes each behind the rows it shares with its predecessor, from snapshots at a few fixed depths.  Writes the depths
+ * such a launch of n_queries queries would use to depths[0 .. cap) and returns their number, 0 where the launch does not
+ * share.  It launches nothing; the query tile it assumes depends on the device's CU count, which it asks the runtime for once
+ * (256 where there is no device).  BGSA_MYERS_PREFIX_SHARE (read once): 0 = off, 1 = on, a list of one to five ascending
+ * depths in 1 .. 10 (a,b,c; a single number from 2 up is a list of one) = these depths whatever the query count.  A list that
+ * is longer, out of order, out of range or reaches rows beyond the first two words turns sharing off: the answer is then 0.
+ * bgsa_hip_myers_band_segments: the stream of one mapped query row cut at these depths, as a sharing launch packs it — one
+ * band stream per segment, each beginning with its SETWIN; offsets[0 .. n_depths + 1] = where each begins, and the length.
+ * Returns the length (<= cap bytes written), or 0 when the shape does not qualify (host only, no GPU). */
+int bgsa_hip_myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_len, int n_queries, int mixed_lengths,
+                                 int *depths, int cap);
+int bgsa_hip_myers_band_segments(const char *mapped_row, int ref_len, int read_len, const int *depths, int n_depths,
+                                 unsigned char *dst, int cap, int *offsets);
 int bgsa_hip_myers_band_stream(const char *mapped_row, int ref_len, int read_len, unsigned char *dst, int cap);
 int bgsa_hip_myers_band_half(int ref_len, int read_len);
 int bgsa_hip_myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_len, int mixed_lengths);
