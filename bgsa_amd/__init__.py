@@ -106,6 +106,12 @@ def lib() -> ctypes.CDLL:
                         ("bgsa_hip_trace_pairs_lens_dev", [pp, vp, vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, sz, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = types
+    # read placement on mixed-length buckets, Myers semi-global with per-lane lengths (the same: an older build lacks them)
+    for name, types in (("bgsa_hip_myers_place_score_lens_dev", [vp, vp, vp, vp, i32, i32, i64, i32, i32, i32, vp, sz, vp]),
+                        ("bgsa_hip_myers_place_trace_pairs_lens_dev",
+                         [vp, vp, vp, i32, i32, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, sz, vp])):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
     # band-limited pair alignment (the same: an older build lacks it)
     for name, types, restype in (("bgsa_hip_align_pairs_band_words", [i32, i32, i32], i32),
                                  ("bgsa_hip_align_pairs_banded_min_workspace_bytes", [i32, i32, i32], sz),
@@ -312,7 +318,8 @@ class DeviceAligner:
         torch.cuda.set_device(self.device)
         check(lib().bgsa_hip_set_device(self.device.index or 0), "set_device")
         self.out_dtype = torch.int8 if algo == ALGO_BANDED else torch.int16
-        self.d_lens = None    # per-column subject lengths of a mixed-length bucket (set_subjects_ragged)
+        self.d_lens = None    # per-column subject lengths of a mixed-length bucket (set_subjects_ragged, set_reads_ragged)
+        self.reads_ragged = False   # the bucket is one of set_reads_ragged: Myers semi-global with every read's own length
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -372,6 +379,43 @@ class DeviceAligner:
         d_rows = torch.from_numpy(rows_to_buffer(s)).to(self.device)
         self.set_subject_rows_device(d_rows, s.shape[0], s.shape[1], qlen, d_lens=torch.from_numpy(lens).to(self.device))
 
+    def _reads_ragged_refusals(self, what: str) -> None:
+        if self.algo != ALGO_MYERS or not self.semi_global or self.scores == (0, 1, 1):
+            raise BgsaHipError(f"{what}: rc=-2: reads of mixed lengths are placed by the Myers unit-cost semi-global aligner only "
+                               "(ALGO_MYERS, semi_global=True, not +distance; global modes: set_subjects_ragged)")
+
+    def set_reads_ragged(self, reads, qlen: int | None = None) -> None:
+        """reads: byte strings or 1-D uint8 arrays of MIXED lengths, up to 1,024 bp, as one bucket of the Myers semi-global aligner
+        (the read end to end inside the query): packed as set_subjects_ragged packs (pad_ragged, then pad_rows; pad columns get the
+        longest length).  From here on score() — and with it top_hits, threshold_hits, top_queries, threshold_queries — and
+        trace_pairs / trace_hits treat column c as the read's own first lens[c] characters, bit for bit what a bucket of that one
+        length reports (bgsa_hip_myers_place_score_lens_dev, bgsa_hip_myers_place_trace_pairs_lens_dev).  Only ALGO_MYERS with
+        semi_global=True and not +distance: anything else raises rc=-2 before anything is allocated.  If all lengths are equal this
+        IS set_subjects.  place_pairs_banded keeps refusing a mixed-length bucket.  To keep a short read from being scored at the
+        width of the longest, bin the reads first (bin_by_words; ReferenceMapper.map_reads_ragged does)."""
+        torch = self.torch
+        self._reads_ragged_refusals("set_reads_ragged")
+        rows, lens = pad_ragged(reads)
+        if (lens == lens[0]).all():
+            return self.set_subjects(rows, qlen)
+        if rows.shape[1] > 1024:
+            raise BgsaHipError("set_reads_ragged: rc=-2: reads beyond 1,024 bp (word_num > 32) run as column blocks, which have no "
+                               "per-lane form")
+        s, self.extra = pad_rows(rows)
+        self.ns_real = rows.shape[0]
+        lens = np.concatenate([lens, np.full(self.extra, rows.shape[1], dtype=np.int32)])
+        d_rows = torch.from_numpy(rows_to_buffer(s)).to(self.device)
+        self.set_subject_rows_device(d_rows, s.shape[0], s.shape[1], qlen, d_lens=torch.from_numpy(lens).to(self.device))
+        self.mark_reads_ragged()
+
+    def mark_reads_ragged(self) -> None:
+        """Marks the bucket set_subject_rows_device(..., d_lens=) has just set as one of set_reads_ragged: its lengths are reads' own
+        lengths under the Myers semi-global aligner.  Every later set_subject* call clears the mark."""
+        self._reads_ragged_refusals("mark_reads_ragged")
+        if self.d_lens is None:
+            raise BgsaHipError("mark_reads_ragged: rc=-1: the bucket has no lengths (set_subject_rows_device(..., d_lens=))")
+        self.reads_ragged = True
+
     def set_subject_rows_device(self, d_rows, ns: int, slen: int, qlen: int | None = None, d_lens=None) -> None:
         """d_rows: uint8 device tensor holding ns rows of slen+1 bytes; ns % 64 == 0.  d_lens: None (every subject is slen long), or
         an int32 device tensor of ns subject lengths (a mixed-length bucket, slen the longest: set_subjects_ragged)."""
@@ -379,6 +423,7 @@ class DeviceAligner:
         if d_lens is not None and (d_lens.dtype != torch.int32 or d_lens.numel() != int(ns) or not d_lens.is_contiguous()):
             raise BgsaHipError("set_subject_rows_device: d_lens must be a contiguous int32 tensor of ns entries")
         self.d_lens = d_lens
+        self.reads_ragged = False
         self.ns, self.slen = int(ns), int(slen)
         qlen = self.qlen if qlen is None else qlen
         self.wn = word_num(self.algo, qlen, self.slen, self.k)
@@ -409,6 +454,12 @@ class DeviceAligner:
         need = int(lib().bgsa_hip_workspace_bytes_ex(ctypes.byref(p), self.qlen, self.slen, ref_end - ref_start))
         if getattr(self, "d_work", None) is None or self.d_work.numel() < need:
             self.d_work = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        if self.d_lens is not None and self.reads_ragged:
+            check(lib().bgsa_hip_myers_place_score_lens_dev(self.d_content.data_ptr(), self.d_peq.data_ptr(), out.data_ptr(),
+                                                            self.d_lens.data_ptr(), self.qlen, self.slen, self.ns, ref_start, ref_end,
+                                                            self.wn, self.d_work.data_ptr(), self.d_work.numel(), self._stream()),
+                  "myers_place_score_lens_dev")
+            return out
         if self.d_lens is not None:
             check(lib().bgsa_hip_cal_align_score_lens_ex(ctypes.byref(p), self.d_content.data_ptr(), self.d_peq.data_ptr(),
                                                          out.data_ptr(), self.d_lens.data_ptr(), self.qlen, self.slen, self.ns,
@@ -728,6 +779,13 @@ class DeviceAligner:
                 self.d_align_work = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
             work, work_bytes = self.d_align_work.data_ptr(), int(workspace_bytes)
         p = self.params()
+        if self.d_lens is not None and self.reads_ragged:
+            check(lib().bgsa_hip_myers_place_trace_pairs_lens_dev(self.d_content.data_ptr(), self.d_peq.data_ptr(), self.d_lens.data_ptr(),
+                                                                  self.qlen, self.slen, self.ns, self.wn, pq.data_ptr(), ps.data_ptr(), n,
+                                                                  self.nq, int(subject_base), score.data_ptr(), span.data_ptr(),
+                                                                  n_ops.data_ptr(), cigar.data_ptr(), cap, work, work_bytes,
+                                                                  self._stream()), "myers_place_trace_pairs_lens_dev")
+            return score, span, n_ops, cigar
         if self.d_lens is not None:
             check(lib().bgsa_hip_trace_pairs_lens_dev(ctypes.byref(p), self.d_content.data_ptr(), self.d_peq.data_ptr(),
                                                       self.d_lens.data_ptr(), self.qlen, self.slen, self.ns, self.wn, pq.data_ptr(),

@@ -97,6 +97,9 @@ template <typename A, typename B> using Join = typename JoinWidths<A, B>::type;
 // Launchers implemented in the per-algorithm .hip files.  Which kernel a launch runs is decided by ONE function per algorithm
 // (myers_select, banded_select, the per-set bitpal_select); the launcher switches on its answer and *_kernel_name formats it.
 int launch_myers(const ScoreArgs &a, int semi_global = 0);
+// Semi-global Myers on a bucket of mixed read lengths (a.d_read_lens set): myers_semi_asm_kernel<NW, true>, every lane right-aligned
+// by its own length (bgsa_hip_myers_place_score_lens_dev).  Up to 32 words; anything else is BGSA_HIP_EUNSUPPORTED.
+int launch_myers_place_lens(const ScoreArgs &a);
 // The name of the kernel the knobs select for a launch with at least two subject groups (no read count here: a bucket of
 // ONE group of <= 64 bp subjects runs <NW, 1> where this says <NW, 2>).
 const char *myers_kernel_name(int word_num, int semi_global = 0);

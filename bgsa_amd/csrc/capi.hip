@@ -756,10 +756,26 @@ static int lens_refused(const Plan &plan, int word_num)
     return BGSA_HIP_EUNSUPPORTED;
 }
 
+// The entry of the scoring calls.  place_lens: the caller is bgsa_hip_myers_place_score_lens_dev — semi-global Myers params whose
+// bucket carries the reads' own lengths.
+static int score_entry(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                       void *d_results, const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count,
+                       int ref_start, int ref_end, int word_num,
+                       void *d_workspace, size_t workspace_bytes, void *stream, bool place_lens);
+
 int bgsa_hip_cal_align_score_lens_ex(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
                                      void *d_results, const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count,
                                      int ref_start, int ref_end, int word_num,
                                      void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return score_entry(params, d_content, d_peq, d_results, d_read_lens, ref_len, read_len, read_count, ref_start, ref_end, word_num,
+                       d_workspace, workspace_bytes, stream, false);
+}
+
+static int score_entry(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                       void *d_results, const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count,
+                       int ref_start, int ref_end, int word_num,
+                       void *d_workspace, size_t workspace_bytes, void *stream, bool place_lens)
 {
     if (!params) {
         set_error_text("cal_align_score: params is NULL");
@@ -772,6 +788,10 @@ int bgsa_hip_cal_align_score_lens_ex(const bgsa_hip_params_t *params, const char
         set_error_text("cal_align_score_dev: bad argument (read_count must be a multiple of 64)");
         return BGSA_HIP_EINVAL;
     }
+    if (place_lens && !d_read_lens) {
+        set_error_text("myers_place_score_lens_dev: d_read_lens is NULL (equal lengths: bgsa_hip_cal_align_score_ex)");
+        return BGSA_HIP_EINVAL;
+    }
     Plan plan;
     if (int rc = make_plan(*params, &plan)) return rc;
     // the kernels index the Peq / Mext blocks with the caller's word_num: it must be the layout's
@@ -782,8 +802,15 @@ int bgsa_hip_cal_align_score_lens_ex(const bgsa_hip_params_t *params, const char
                            : "cal_align_score_dev: word_num does not match read_len");
         return BGSA_HIP_EINVAL;
     }
-    if (d_read_lens)
+    if (place_lens) {
+        if (word_num > kMaxWords) {
+            set_error_text("myers_place_score_lens_dev: per-read lengths: reads beyond 1,024 bp (word_num > 32) run as column blocks, "
+                           "which have no per-lane form");
+            return BGSA_HIP_EUNSUPPORTED;
+        }
+    } else if (d_read_lens) {
         if (int rc = lens_refused(plan, word_num)) return rc;
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t need = plan_workspace_bytes(plan, ref_len, read_len, ref_end - ref_start);
     std::unique_lock<std::mutex> own_scratch(g_scratch_mu, std::defer_lock);
@@ -800,7 +827,7 @@ int bgsa_hip_cal_align_score_lens_ex(const bgsa_hip_params_t *params, const char
     const ScoreArgs args = {d_content, d_peq, d_results, ref_len, read_len, read_count, ref_start, ref_end, word_num, d_workspace, s, d_read_lens};
     switch (plan.kernel) {
     case BGSA_ALGO_MYERS:
-        if (int rc = launch_myers(args, plan.semi)) return rc;
+        if (int rc = place_lens ? launch_myers_place_lens(args) : launch_myers(args, plan.semi)) return rc;
         return launch_scale_scores(static_cast<int16_t *>(d_results), n_scores, plan.factor, s);
     case BGSA_ALGO_BANDED:
         return launch_banded(args, params->k);
@@ -811,6 +838,18 @@ int bgsa_hip_cal_align_score_lens_ex(const bgsa_hip_params_t *params, const char
         set_error_text("cal_align_score_dev: unknown algorithm");
         return BGSA_HIP_EINVAL;
     }
+}
+
+// Myers semi-global (0 / -1 / -1) on a bucket of mixed read lengths: the entry above with the lengths REQUIRED and the launch
+// myers_semi_asm_kernel<NW, true> (every lane right-aligned by its own length).
+int bgsa_hip_myers_place_score_lens_dev(const char *d_content, const hip_read_t *d_peq, void *d_results,
+                                        const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count,
+                                        int ref_start, int ref_end, int word_num,
+                                        void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    const bgsa_hip_params_t params = {BGSA_ALGO_MYERS, BGSA_ALIGN_SEMIGLOBAL, 0, -1, -1, 0};
+    return score_entry(&params, d_content, d_peq, d_results, d_read_lens, ref_len, read_len, read_count, ref_start, ref_end, word_num,
+                       d_workspace, workspace_bytes, stream, true);
 }
 
 int bgsa_hip_cal_align_score_dev(int algo, const char *d_content, const hip_read_t *d_peq,

@@ -444,16 +444,29 @@ __device__ __forceinline__ uint32_t semi_dummy_mask(int aw, int s)
 
 // Subjects up to 1024 bp (resident Peq planes at every width; 26..32 words with the two carry chains in turns): generated asm row loop of
 // myers_semi_body, 8 VALU per word + 3 per row.
-template <int NW>
+// LENS (a bucket of mixed read lengths, bgsa_hip_myers_place_score_lens_dev): nothing in the row loop depends on the length — the subject
+// is right-aligned once per task, and from then on the carries that leave the top word are D[i][n] - D[i-1][n] whatever n is.  So every
+// lane right-aligns by its OWN n = read_lens[column]: shift, source word indices (per-lane addresses; the loads stay unconditional),
+// dummy mask and start score are per lane instead of wave-uniform, and the generated rows run unchanged.  Column n of every lane is
+// bit 31 of the last word; what lies behind a read's end is shifted out of the top word and never enters.  n = 0 (a clamped length):
+// all columns dummy, VP = 0, score 0.  A separate instantiation: the equal-length kernels keep their code and their register counts.
+// The lane keeps n across the row loop (one VGPR) except where the width sits at the register limit (semi_len_per_query): there the
+// per-query set-up loads it again, one dword per lane against NW x ref_len rows.
+constexpr bool semi_len_per_query(int nw) { return nw >= 32; }
+template <int NW, bool LENS = false>
 __global__ __launch_bounds__(256) void myers_semi_asm_kernel(
     const unsigned char *__restrict__ streams, const uint32_t *__restrict__ peq,
     int16_t *__restrict__ out, int ref_len, int read_len, long long ld, int n_groups, int word_num,
-    int n_queries, int q_tile, int stream_stride_bytes, unsigned *__restrict__ fault_word)
+    int n_queries, int q_tile, int stream_stride_bytes, unsigned *__restrict__ fault_word,
+    const int32_t *__restrict__ read_lens = nullptr)
 {
+    constexpr bool kLenPerQuery = LENS && semi_len_per_query(NW);
     const int lane = threadIdx.x & (kLanes - 1);
     const int group = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
     if (group >= n_groups) return;
-    const int s_cols = 32 * NW - read_len, sq = s_cols >> 5, sr = s_cols & 31;
+    int own_len = read_len;   // LENS: per lane; else wave-uniform, and everything derived from it stays scalar
+    if constexpr (LENS) own_len = lane_read_len(read_lens, static_cast<size_t>(group) * kLanes + lane, read_len);
+    const int s_cols = 32 * NW - own_len, sq = s_cols >> 5, sr = s_cols & 31;
 
     uint32_t P[kChars][NW];
     const uint32_t *g = peq + static_cast<size_t>(group) * kChars * word_num * kLanes + lane;
@@ -473,12 +486,23 @@ __global__ __launch_bounds__(256) void myers_semi_asm_kernel(
 
     for (int q = q0; q < q1; q++) {
         uint32_t st[2 * NW + 2];
+        int n_cols = own_len;
+        if constexpr (kLenPerQuery) {
+            // (the lane number formed here: an address kept per lane across the row loop is two VGPRs this width lacks)
+            unsigned lane_e;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+            n_cols = lane_read_len(read_lens, static_cast<size_t>(group) * kLanes + lane_e, read_len);
+        }
+        // (LENS: the NW masks depend on the task only: laundered, or the compiler forms them once per task and keeps NW more VGPRs
+        // across the row loop)
+        if constexpr (LENS) asm volatile("" : "+v"(n_cols));
+        const int dummy_cols = 32 * NW - n_cols;
 #pragma unroll
         for (int w = 0; w < NW; w++) {
-            st[2 * w] = ~semi_dummy_mask(w, s_cols);
+            st[2 * w] = ~semi_dummy_mask(w, dummy_cols);
             st[2 * w + 1] = 0u;
         }
-        st[2 * NW] = st[2 * NW + 1] = static_cast<uint32_t>(read_len);   // D[0][n] = n (genSemiGlobal: min_score = score = read_len)
+        st[2 * NW] = st[2 * NW + 1] = static_cast<uint32_t>(n_cols);   // D[0][n] = n (genSemiGlobal: min_score = score = read_len), LENS: the lane's own
         const unsigned long long s =
             reinterpret_cast<unsigned long long>(streams) + static_cast<unsigned long long>(q) * stream_stride_bytes;
         note_stream_fault(fault_word, myers_semi_rows_asm<NW>(st, P, uniform_u64(s),
@@ -1033,7 +1057,8 @@ int launch_asm(const ScoreArgs &a)
     return BGSA_HIP_OK;
 }
 
-template <int NW>
+// LENS: the bucket's per-column lengths go to the kernel (launch_myers_place_lens); tile and grid are planned as without them.
+template <int NW, bool LENS = false>
 int launch_semi_asm(const ScoreArgs &a)
 {
     const int nq = a.nq(), stride = static_cast<int>(stream_stride(a.ref_len));
@@ -1044,10 +1069,10 @@ int launch_semi_asm(const ScoreArgs &a)
     if (int rc = launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream)) return rc;
     unsigned *fault = nullptr;
     if (int rc = stream_guard(a.d_workspace, stride, kCodeRefill, 7, a.stream, &fault)) return rc;
-    hipLaunchKernelGGL((myers_semi_asm_kernel<NW>), lg.grid, dim3(256), 0, a.stream,
+    hipLaunchKernelGGL((myers_semi_asm_kernel<NW, LENS>), lg.grid, dim3(256), 0, a.stream,
                        static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len,
                        a.read_len, static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num,
-                       nq, q_tile, stride, fault);
+                       nq, q_tile, stride, fault, LENS ? a.d_read_lens : nullptr);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
@@ -1325,6 +1350,19 @@ int launch_myers(const ScoreArgs &a, int semi_global)
     }
     set_error_text("myers: no kernel for this word count");
     return BGSA_HIP_EUNSUPPORTED;
+}
+
+int launch_myers_place_lens(const ScoreArgs &a)
+{
+    if (a.ref_end <= a.ref_start || a.read_count == 0) return BGSA_HIP_OK;
+    const MyersChoice c = myers_select(a.word_num, 1, a.read_count, a.ref_len, a.read_len, true);
+    if (!a.d_read_lens || c.family != MyersFamily::kSemiAsm) {
+        set_error_text("myers: per-read lengths in semi-global mode are scored by myers_semi_asm_kernel only (word_num <= 32, no "
+                       "BGSA_MYERS_IMPL / BGSA_MYERS_PEQ_MAX_WORDS alternative)");
+        return BGSA_HIP_EUNSUPPORTED;
+    }
+    return PeqWidths::dispatch(c.nw, "myers_semi_asm_kernel (per-lane lengths)",
+                               [&](auto nw) { return launch_semi_asm<decltype(nw)::value, true>(a); });
 }
 
 }  // namespace bgsa

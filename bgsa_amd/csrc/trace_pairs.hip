@@ -263,11 +263,45 @@ int bgsa_hip_trace_pairs_dev(const bgsa_hip_params_t *params, const char *d_cont
                                          d_workspace, workspace_bytes, stream);
 }
 
+// The entry shared by the three calls.  semi_lens: the caller is bgsa_hip_myers_place_trace_pairs_lens_dev, whose semi-global
+// pairs carry lengths of their own (the forward kernel takes pair_read_len whatever the mode).
+static int trace_pairs_entry(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                             const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count, int word_num,
+                             const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs, int n_queries,
+                             int64_t subject_base, int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar,
+                             int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream, bool semi_lens);
+
 int bgsa_hip_trace_pairs_lens_dev(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
                                   const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count, int word_num,
                                   const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs, int n_queries,
                                   int64_t subject_base, int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar,
                                   int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return trace_pairs_entry(params, d_content, d_peq, d_read_lens, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject,
+                             n_pairs, n_queries, subject_base, d_score, d_span, d_n_ops, d_cigar, cigar_cap, d_workspace, workspace_bytes,
+                             stream, false);
+}
+
+int bgsa_hip_myers_place_trace_pairs_lens_dev(const char *d_content, const hip_read_t *d_peq, const int32_t *d_read_lens, int ref_len,
+                                              int read_len, int64_t read_count, int word_num, const int32_t *d_pair_query,
+                                              const int64_t *d_pair_subject, int64_t n_pairs, int n_queries, int64_t subject_base,
+                                              int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
+                                              void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    const bgsa_hip_params_t params = {BGSA_ALGO_MYERS, BGSA_ALIGN_SEMIGLOBAL, 0, -1, -1, 0};
+    if (!d_read_lens)
+        return refuse(BGSA_HIP_EINVAL, "d_read_lens is NULL (bgsa_hip_myers_place_trace_pairs_lens_dev takes the bucket's lengths; "
+                                       "equal lengths: bgsa_hip_trace_pairs_dev)");
+    return trace_pairs_entry(&params, d_content, d_peq, d_read_lens, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject,
+                             n_pairs, n_queries, subject_base, d_score, d_span, d_n_ops, d_cigar, cigar_cap, d_workspace, workspace_bytes,
+                             stream, true);
+}
+
+static int trace_pairs_entry(const bgsa_hip_params_t *params, const char *d_content, const hip_read_t *d_peq,
+                             const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count, int word_num,
+                             const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs, int n_queries,
+                             int64_t subject_base, int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar,
+                             int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream, bool semi_lens)
 {
     if (!params || !d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_score || !d_span || !d_n_ops || !d_cigar)
         return refuse(BGSA_HIP_EINVAL, "a NULL pointer (only the workspace and the stream may be NULL)");
@@ -287,7 +321,7 @@ int bgsa_hip_trace_pairs_lens_dev(const bgsa_hip_params_t *params, const char *d
     if (word_num != bgsa_hip_word_num(params->algo, ref_len, read_len, params->k))
         return refuse(BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(params->algo, ...)");
     if (word_num > kMaxWords) return refuse(BGSA_HIP_EUNSUPPORTED, "subjects beyond 1,024 bp (word_num > 32) are not covered");
-    if (d_read_lens && params->alignment != BGSA_ALIGN_GLOBAL)
+    if (d_read_lens && params->alignment != BGSA_ALIGN_GLOBAL && !semi_lens)
         return refuse(BGSA_HIP_EUNSUPPORTED, "per-subject lengths are traced in global mode only (semi-global buckets take subjects of one length)");
     // Myers scores -distance whatever the three ints hold (as the scoring calls: make_plan)
     const bool myers = params->algo == BGSA_ALGO_MYERS;

@@ -60,8 +60,9 @@ class ReferenceMapper:
     uploaded and mapped once; the windows of window_len every stride bases exist only as query rows built on the device, a
     segment of segment_windows ids at a time.  both_strands=False leaves the reverse-complemented windows out.
 
-    Limits: one read length per map_reads call, Myers unit-cost distance, one GPU.  The r-th distinct locus of a read is
-    reported if its best window is among the read's k_sel best windows; for k_best = 1 that always holds."""
+    Limits: one read length per map_reads call (map_reads_ragged takes reads of mixed lengths up to 1,024 bp), Myers unit-cost
+    distance, one GPU.  The r-th distinct locus of a read is reported if its best window is among the read's k_sel best
+    windows; for k_best = 1 that always holds."""
 
     def __init__(self, reference, window_len: int, stride: int, device: str = "cuda:0", both_strands: bool = True,
                  segment_windows: int = 65536):
@@ -123,10 +124,13 @@ class ReferenceMapper:
             into = a.top_queries(k_sel, block_rows=block_rows, query_base=lo, into=into)
         return into
 
-    def place_hits(self, ids, max_distance: int, cap: int, block_rows: int = 1000):
+    def place_hits(self, ids, max_distance, cap: int, block_rows: int = 1000, ragged: bool = False):
         """The device half of map_reads' placement: block_rows reads at a time, the hit windows ids[ns, k_sel] gathered by id,
         placed within max_distance and turned into reference coordinates.  Returns device tensors (strand, ref_begin, ref_end,
-        keep, n_ops — all [ns, k_sel] —, cigar[ns, k_sel, cap])."""
+        keep, n_ops — all [ns, k_sel] —, cigar[ns, k_sel, cap]).
+        ragged (the aligner holds a bucket of set_reads_ragged, which place_pairs_banded refuses): the hits are traced with
+        trace_pairs, every read at its own length, and a hit beyond max_distance (None: no bound) is then marked as
+        place_pairs_banded leaves it — q_begin -1, n_ops 0 — so that it is reported unplaced."""
         a, L = self.aligner, B.lib()
         torch, dev, W = a.torch, a.device, self.window_len
         ns, k_sel = ids.shape
@@ -147,8 +151,16 @@ class ReferenceMapper:
             pair_queries = torch.arange(n_rows, dtype=torch.int32, device=dev)
             columns = torch.arange(lo, hi, dtype=torch.int64, device=dev).repeat_interleave(k_sel)
             pair_subjects = torch.where(hit.reshape(-1) >= 0, columns, torch.full_like(columns, -1))
-            a.place_pairs_banded(pair_queries, pair_subjects, max_distance, cigar_cap=cap,
-                                 into=(distance[lo:hi].view(-1), span[lo:hi].view(-1, 4), n_ops[lo:hi].view(-1), cigar[lo:hi].view(-1, cap)))
+            into = (distance[lo:hi].view(-1), span[lo:hi].view(-1, 4), n_ops[lo:hi].view(-1), cigar[lo:hi].view(-1, cap))
+            if ragged:
+                distance[lo:hi] = 0    # trace_pairs reports scores: minus the distance, 0 where nobody owns the pair
+                a.trace_pairs(pair_queries, pair_subjects, cigar_cap=cap, into=into)
+                if max_distance is not None:
+                    beyond = -distance[lo:hi] > int(max_distance)
+                    span[lo:hi, :, 0].masked_fill_(beyond, -1)
+                    n_ops[lo:hi].masked_fill_(beyond, 0)
+            else:
+                a.place_pairs_banded(pair_queries, pair_subjects, max_distance, cigar_cap=cap, into=into)
             B.check(L.bgsa_hip_reference_placements_dev(self.ref_len, W, self.stride, hit.data_ptr(), hi - lo, k_sel,
                                                         span[lo:hi].data_ptr(), n_ops[lo:hi].data_ptr(), cigar[lo:hi].data_ptr(), cap,
                                                         strand[lo:hi].data_ptr(), ref_begin[lo:hi].data_ptr(), ref_end[lo:hi].data_ptr(),
@@ -204,6 +216,62 @@ class ReferenceMapper:
             cigars[c][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : counts[c, r]].tolist())
         return ReferenceHits(scores.cpu().numpy(), strand.cpu().numpy(), ref_begin.cpu().numpy(), ref_end.cpu().numpy(), kept, cigars,
                              ids.cpu().numpy())
+
+    def map_reads_ragged(self, reads, k_best: int = 1, max_distance=None, block_rows: int = 1000, cigar_cap=None) -> ReferenceHits:
+        """map_reads for reads of MIXED lengths: a list of byte strings or 1-D uint8 arrays, 1..1,024 bp each.  The reads are binned by
+        the 32-bit words they occupy (bin_by_words), so that a short read is not scored at the longest one's width; every bin is ONE
+        bucket of the aligner (set_reads_ragged(bin, qlen=window_len): every read scored and traced at its own length) and makes
+        one pass over the reference — select_windows, then the hit windows gathered by id block_rows reads at a time, traced
+        (trace_pairs) and turned into reference coordinates.  A hit whose distance exceeds max_distance is reported unplaced
+        (ref_begin -1, keep 0, cigar None), as map_reads does; max_distance=None places every hit.  The result is in the caller's
+        order and equals, read by read, map_reads called once per exact length.
+        The stride check is map_reads' rule applied with the LONGEST read (shorter reads span less); it is made before anything
+        is launched.  cigar_cap=None: window_len + the longest read."""
+        a = self.aligner
+        rows, lens = B.pad_ragged(reads)
+        ns, longest = rows.shape
+        if longest > 1024:
+            raise B.BgsaHipError("map_reads_ragged: rc=-2: reads beyond 1,024 bp have no per-lane form (one length per call: map_reads)")
+        k_best = int(k_best)
+        if not 1 <= k_best <= B.V_NUM:
+            raise B.BgsaHipError(f"map_reads_ragged: rc=-1: k_best must lie in 1..{B.V_NUM}")
+        if max_distance is not None and int(max_distance) < 0:
+            raise B.BgsaHipError("map_reads_ragged: rc=-1: max_distance is negative")
+        bound = 0 if max_distance is None else min(int(max_distance), longest)
+        largest = max_stride(self.window_len, longest, bound)
+        if self.stride > largest:
+            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
+            raise B.BgsaHipError(f"map_reads_ragged: rc=-1: at stride {self.stride} a placement of the longest read ({longest} bp) within "
+                                 f"distance {bound} can lie in no window of {self.window_len} bp: {allowed}")
+        k_sel = self.k_selected(k_best)
+        cap = self.window_len + longest if cigar_cap is None else int(cigar_cap)
+        if cap < 1:
+            raise B.BgsaHipError("map_reads_ragged: rc=-1: cigar_cap is not positive")
+
+        scores = np.empty((ns, k_sel), dtype=np.int32)
+        strand, keep, windows = np.empty_like(scores), np.empty_like(scores), np.empty_like(scores)
+        ref_begin, ref_end = np.empty((ns, k_sel), dtype=np.int64), np.empty((ns, k_sel), dtype=np.int64)
+        cigars = [[None] * k_sel for _ in range(ns)]
+        for idx in B.bin_by_words(lens):
+            a.set_reads_ragged([rows[i, : lens[i]] for i in idx], qlen=self.window_len)
+            d_scores, d_ids = self.select_windows(k_sel, block_rows)
+            limit = None if max_distance is None else int(max_distance)
+            if a.reads_ragged:
+                d_strand, d_begin, d_end, d_keep, d_n_ops, d_cigar = self.place_hits(d_ids, limit, cap, block_rows, ragged=True)
+            else:   # a bin of one length: map_reads' own placement
+                if limit is None:
+                    limit = -int(a.torch.where(d_ids >= 0, d_scores, a.torch.zeros_like(d_scores)).min().item())
+                d_strand, d_begin, d_end, d_keep, d_n_ops, d_cigar = self.place_hits(d_ids, limit, cap, block_rows)
+            a.check_faults()
+            kept = d_keep.cpu().numpy()
+            scores[idx], strand[idx], keep[idx], windows[idx] = d_scores.cpu().numpy(), d_strand.cpu().numpy(), kept, d_ids.cpu().numpy()
+            ref_begin[idx], ref_end[idx] = d_begin.cpu().numpy(), d_end.cpu().numpy()
+            counts, runs = d_n_ops.cpu().numpy(), d_cigar.cpu().numpy().view(np.uint32)
+            for c, r in zip(*np.nonzero(kept)):
+                if counts[c, r] > cap:
+                    raise B.BgsaHipError(f"map_reads_ragged: hit {r} of read {idx[c]} has {counts[c, r]} runs, its row holds {cap} (raise cigar_cap)")
+                cigars[idx[c]][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : counts[c, r]].tolist())
+        return ReferenceHits(scores, strand, ref_begin, ref_end, keep, cigars, windows)
 
     @staticmethod
     def placements_of(hits: ReferenceHits, k_best: int = 1) -> list:

@@ -549,6 +549,35 @@ int bgsa_hip_trace_pairs_lens_dev(const bgsa_hip_params_t *params, const char *d
                                   int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
                                   void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- read placement on a bucket of MIXED read lengths: Myers semi-global with every read's own n ----
+ * The two calls above refuse semi-global params together with lengths; these two are the Myers semi-global mode (the read —
+ * the subject — end to end inside the query, unit costs: params 0 / -1 / -1, BGSA_ALIGN_SEMIGLOBAL) for a bucket built as
+ * bgsa_hip_cal_align_score_lens_ex takes it: rows of read_len bytes, d_peq from bgsa_hip_handle_reads_dev at read_len,
+ * d_read_lens[column] = the read's own length for all read_count columns, padding columns included.  A length is clamped to
+ * [0, read_len]; it forms shifts, masks and start scores and, as an index, is clamped again: no value takes an access out of
+ * bounds.  Column c is scored and traced as the first d_read_lens[c] characters of its row, bit for bit what the equal-length
+ * calls report for a bucket of those prefixes; the bytes behind a read's end never enter.  A length of 0 scores 0.
+ * bgsa_hip_myers_place_score_lens_dev: bgsa_hip_cal_align_score_ex with those params, int16 results [query][column], the same
+ * argument checks, the same empty-window shortcut (ref_end == ref_start or read_count == 0: BGSA_HIP_OK, nothing touched) and
+ * the same workspace (bgsa_hip_workspace_bytes_ex of those params; NULL = the library's own scratch).  Every lane of the
+ * scoring kernel right-aligns its read by its own length; the row loop is the equal-length kernel's.  BGSA_HIP_EINVAL:
+ * d_read_lens == NULL (equal lengths: bgsa_hip_cal_align_score_ex) and what that call answers EINVAL to.
+ * BGSA_HIP_EUNSUPPORTED: word_num > 32 — reads beyond 1,024 bp run as column blocks, which have no per-lane form — and a
+ * measurement knob that selects another semi-global kernel (BGSA_MYERS_IMPL, BGSA_MYERS_PEQ_MAX_WORDS).
+ * bgsa_hip_myers_place_trace_pairs_lens_dev: bgsa_hip_trace_pairs_dev's "Myers, semi-global" model with n = d_read_lens[column]
+ * per pair: the outputs, ownership, cigar format, workspace rules and checks are that call's, span[3] = the pair's own length.
+ * BGSA_HIP_EINVAL also for d_read_lens == NULL. */
+int bgsa_hip_myers_place_score_lens_dev(const char *d_content, const hip_read_t *d_peq, void *d_results,
+                                        const int32_t *d_read_lens, int ref_len, int read_len, int64_t read_count,
+                                        int ref_start, int ref_end, int word_num,
+                                        void *d_workspace, size_t workspace_bytes, void *stream);
+int bgsa_hip_myers_place_trace_pairs_lens_dev(const char *d_content, const hip_read_t *d_peq, const int32_t *d_read_lens,
+                                              int ref_len, int read_len, int64_t read_count, int word_num,
+                                              const int32_t *d_pair_query, const int64_t *d_pair_subject, int64_t n_pairs,
+                                              int n_queries, int64_t subject_base,
+                                              int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap,
+                                              void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- band-limited semi-global placement: where a read of ANY length lies inside its window, and how it aligns ----
  * bgsa_hip_trace_pairs_dev keeps a 16-bit DP row of the whole subject in LDS: it stops at 1,024 bp.  This call reports the
  * same four outputs for the "Myers, semi-global" model above (the subject, n = read_len columns, end to end inside the query,
