@@ -147,6 +147,20 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
+    # seeded read mapping (the same: an older build lacks them)
+    seed = [i64, i32, i32, vp, vp, i32, vp, i32, i64, i32, i32]   # the shape, the index, the reads, the bound, both_strands
+    for name, types, restype in (("bgsa_hip_seed_index_offsets", [i32], i64),
+                                 ("bgsa_hip_seed_index_workspace_bytes", [i64, i32], sz),
+                                 ("bgsa_hip_seed_index_build_dev", [vp, i64, i32, vp, vp, vp, sz, vp], i32),
+                                 ("bgsa_hip_seed_count_candidates_dev", seed + [i64, vp, vp], i32),
+                                 ("bgsa_hip_seed_emit_candidates_dev", seed + [vp, vp, i64, vp, vp, vp], i32),
+                                 ("bgsa_hip_reference_verify_workspace_bytes", [i32, i32, i64], sz),
+                                 ("bgsa_hip_reference_verify_pairs_dev",
+                                  [vp, i64, i32, i32, vp, i32, i64, i32, vp, vp, i64, i64, vp, vp, sz, vp], i32),
+                                 ("bgsa_hip_seed_select_dev", [vp, vp, vp, i64, i32, i32, vp, vp, vp], i32)):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = restype
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -1145,4 +1159,4 @@ def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: 
 
 
 # reads mapped onto one reference: windows cut on the device, both strands, reference coordinates (bgsa_amd/reference.py)
-from .reference import Placement, ReferenceHits, ReferenceMapper, max_stride, window_plan  # noqa: E402
+from .reference import Placement, ReferenceHits, ReferenceMapper, blank_beyond, max_stride, seed_plan, window_plan  # noqa: E402

@@ -34,6 +34,49 @@ def max_stride(window_len: int, read_len: int, max_distance: int) -> int:
     return int(window_len) - (n + min(int(max_distance), n)) + 1
 
 
+SEED_LEN_MAX = 13      # 4^13 + 1 index offsets; include/bgsa_hip.h "seeded read mapping"
+INT32_MIN = -2 ** 31
+# map_reads_seeded's default max_candidates is max(n_ids // SEED_CAP_FRACTION, SEED_MIN_CANDIDATES).  The fraction is measured
+# (profiles/seeded_map.txt, LABNOTES.md §27.3): at 83,682 ids, sort + verify + select of C candidates per read meet the exhaustive
+# selection between C = 16,384 and 32,768; n_ids / 8 is the largest power-of-two fraction below that.  The floor: on a small
+# reference n_ids / 8 is a handful, fewer than the (B + 1) * ceil(W / S) candidates a read's own locus emits, and every read would
+# take the exhaustive path; 256 candidates per read cost a third of the exhaustive selection even at 8,368 ids.
+SEED_CAP_FRACTION = 8
+SEED_MIN_CANDIDATES = 256
+
+
+def seed_plan(read_len: int, max_distance: int, seed_len=None) -> tuple[int, int, int]:
+    """(B, step, q) of the pigeonhole filter for reads of read_len bp within max_distance: B = min(max_distance, n), the B + 1
+    pieces start step = n // (B + 1) apart (piece j at j * step) and are q = seed_len long; seed_len=None: min(12, step).
+    step < q — the pieces would overlap, and B edits could then touch all of them — raises, naming the largest bound this
+    seed_len allows and the largest seed_len this bound allows.  Pure Python: no device, no library."""
+    n = int(read_len)
+    if n < 1 or int(max_distance) < 0:
+        raise B.BgsaHipError("seed_plan: rc=-1: read_len must be positive and max_distance not negative")
+    bound = min(int(max_distance), n)
+    step = n // (bound + 1)
+    q = min(12, step) if seed_len is None else int(seed_len)
+    if seed_len is not None and not 1 <= q <= SEED_LEN_MAX:
+        raise B.BgsaHipError(f"seed_plan: rc=-1: seed_len must lie in 1..{SEED_LEN_MAX}")
+    if step < q or q < 1:
+        longest = min(step, SEED_LEN_MAX)
+        by_len = f"seed_len {q} allows max_distance <= {n // q - 1}" if 1 <= q <= n else f"no bound allows seed_len {q}"
+        by_bound = f"max_distance {bound} allows seed_len <= {longest}" if longest >= 1 else f"max_distance {bound} allows no seed"
+        raise B.BgsaHipError(f"seed_plan: rc=-1: the {bound + 1} pieces of a {n} bp read within distance {bound} start {step} bp apart, "
+                             f"too close for seeds of {q} bp: {by_len}; {by_bound}")
+    return bound, step, q
+
+
+def blank_beyond(hits: "ReferenceHits", bound: int) -> "ReferenceHits":
+    """map_reads' result with every slot whose distance exceeds `bound` (and every unused slot) blanked: scores INT32_MIN, windows,
+    strand, ref_begin and ref_end -1, keep 0, cigar None.  This is what map_reads_seeded returns, bit for bit."""
+    gone = (hits.windows < 0) | (-hits.scores.astype(np.int64) > int(bound))
+    cigars = [[None if gone[c, r] else text for r, text in enumerate(row)] for c, row in enumerate(hits.cigars)]
+    return ReferenceHits(np.where(gone, INT32_MIN, hits.scores).astype(np.int32), np.where(gone, -1, hits.strand).astype(np.int32),
+                         np.where(gone, -1, hits.ref_begin).astype(np.int64), np.where(gone, -1, hits.ref_end).astype(np.int64),
+                         np.where(gone, 0, hits.keep).astype(np.int32), cigars, np.where(gone, -1, hits.windows).astype(np.int32))
+
+
 class ReferenceHits(NamedTuple):
     """What ReferenceMapper.map_reads returns, numpy, one row per read and one column per selected hit, best first."""
     scores: np.ndarray      # [ns, k_sel] int32: minus the distance of the read inside its r-th best window; INT32_MIN = unused slot
@@ -91,6 +134,8 @@ class ReferenceMapper:
         self.d_reference[: self.ref_len].copy_(torch.from_numpy(ref))
         B.check(B.lib().bgsa_hip_map_queries_dev(self.d_reference.data_ptr(), self.ref_len, a._stream()), "map_queries")
         self.d_rows = None      # the query rows of one segment / of one block's hit windows, grown on demand
+        self.seed_indexes = {}  # seed_len -> (offsets, positions) device tensors (map_reads_seeded builds them on first use)
+        self.last_seed_stats = None
 
     def _rows_buffer(self, n_rows: int):
         need = n_rows * (self.window_len + 1) + 8
@@ -216,6 +261,159 @@ class ReferenceMapper:
             cigars[c][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : counts[c, r]].tolist())
         return ReferenceHits(scores.cpu().numpy(), strand.cpu().numpy(), ref_begin.cpu().numpy(), ref_end.cpu().numpy(), kept, cigars,
                              ids.cpu().numpy())
+
+    # ---- seeded mapping: include/bgsa_hip.h "seeded read mapping" -----------------------------------------------------------
+    def seed_index(self, seed_len: int):
+        """The k-mer index of the forward reference for seeds of seed_len bp, built on the device on first use and kept:
+        (offsets int32[4^q + 1], positions int32[max(L - q + 1, 1)]) device tensors; bucket c is positions[offsets[c] : offsets[c + 1]]."""
+        q = int(seed_len)
+        if q not in self.seed_indexes:
+            a, L = self.aligner, B.lib()
+            torch = a.torch
+            n_offsets = int(L.bgsa_hip_seed_index_offsets(q))
+            if n_offsets < 0 or self.ref_len > INT32_MAX:
+                raise B.BgsaHipError(f"seed_index: rc=-1: seed_len must lie in 1..{SEED_LEN_MAX} and the reference within 2^31 - 1 bases")
+            offsets = torch.empty(n_offsets, dtype=torch.int32, device=a.device)
+            positions = torch.empty(max(self.ref_len - q + 1, 1), dtype=torch.int32, device=a.device)
+            work = torch.empty(max(int(L.bgsa_hip_seed_index_workspace_bytes(self.ref_len, q)), 8), dtype=torch.uint8, device=a.device)
+            B.check(L.bgsa_hip_seed_index_build_dev(self.d_reference.data_ptr(), self.ref_len, q, offsets.data_ptr(), positions.data_ptr(),
+                                                    work.data_ptr(), work.numel(), a._stream()), "seed_index_build_dev")
+            torch.cuda.current_stream(a.device).synchronize()      # the workspace goes away with this frame
+            self.seed_indexes[q] = (offsets, positions)
+        return self.seed_indexes[q]
+
+    def select_seeded(self, d_rows, n_reads: int, read_len: int, bound: int, seed_len: int, k_sel: int, max_candidates: int,
+                      block_rows: int = 1000):
+        """The device half of map_reads_seeded's selection, for the reads the aligner holds AND whose ASCII rows d_rows (stride
+        read_len + 1) are on the device: block_rows reads at a time count -> emit -> sort and deduplicate (torch) -> verify ->
+        select.  Returns (scores[n_reads, k_sel] int32, window ids[n_reads, k_sel] int32, counts[n_reads] int32: the candidates
+        of every read or its flag -1 / -2, stats: three device scalars emitted / unique / within the bound).  A flagged read
+        gets a list of unused slots."""
+        a, L = self.aligner, B.lib()
+        torch, dev, W, S = a.torch, a.device, self.window_len, self.stride
+        offsets, positions = self.seed_index(seed_len)
+        n_ids2 = 2 * self.n_windows
+        scores = torch.empty((n_reads, k_sel), dtype=torch.int32, device=dev)
+        ids = torch.empty((n_reads, k_sel), dtype=torch.int32, device=dev)
+        counts = torch.empty(n_reads, dtype=torch.int32, device=dev)
+        emitted = torch.zeros((), dtype=torch.int64, device=dev)
+        unique, within = torch.zeros_like(emitted), torch.zeros_like(emitted)
+        shape = (self.ref_len, W, S, offsets.data_ptr(), positions.data_ptr(), int(seed_len))
+        block = max(1, min(int(block_rows), n_reads))
+        for lo in range(0, n_reads, block):
+            hi = min(lo + block, n_reads)
+            rows = d_rows.data_ptr() + lo * (read_len + 1)
+            reads = (rows, read_len, hi - lo, bound, int(self.both_strands))
+            B.check(L.bgsa_hip_seed_count_candidates_dev(*shape, *reads, int(max_candidates), counts[lo:hi].data_ptr(), a._stream()),
+                    "seed_count_candidates_dev")
+            ends = counts[lo:hi].clamp(min=0).to(torch.int64).cumsum(0)
+            total = int(ends[-1].item())                    # the one scalar read back per block: it sizes the candidate arrays
+            prefix = (ends - counts[lo:hi].clamp(min=0)).contiguous()
+            cand_read = torch.empty(total, dtype=torch.int32, device=dev)
+            cand_window = torch.empty(total, dtype=torch.int32, device=dev)
+            if total:
+                B.check(L.bgsa_hip_seed_emit_candidates_dev(*shape, *reads, counts[lo:hi].data_ptr(), prefix.data_ptr(), 0,
+                                                            cand_read.data_ptr(), cand_window.data_ptr(), a._stream()),
+                        "seed_emit_candidates_dev")
+            keys = torch.unique(cand_read.to(torch.int64) * n_ids2 + cand_window)      # sorted by (read, id), every pair once
+            pair_read = keys // n_ids2
+            pair_window = (keys - pair_read * n_ids2).to(torch.int32)
+            distance = torch.full((keys.numel(),), -1, dtype=torch.int32, device=dev)
+            pair_subject = pair_read + lo
+            if keys.numel():
+                need = int(L.bgsa_hip_reference_verify_workspace_bytes(W, read_len, keys.numel()))
+                if need and (getattr(self, "d_verify_work", None) is None or self.d_verify_work.numel() < need):
+                    self.d_verify_work = torch.empty(need, dtype=torch.uint8, device=dev)
+                work = self.d_verify_work if need else None
+                B.check(L.bgsa_hip_reference_verify_pairs_dev(self.d_reference.data_ptr(), self.ref_len, W, S, a.d_peq.data_ptr(), read_len,
+                                                              a.ns, a.wn, pair_window.data_ptr(), pair_subject.data_ptr(), keys.numel(), 0,
+                                                              distance.data_ptr(), None if work is None else work.data_ptr(),
+                                                              0 if work is None else work.numel(), a._stream()),
+                        "reference_verify_pairs_dev")
+            segments = torch.searchsorted(pair_read, torch.arange(hi - lo + 1, dtype=torch.int64, device=dev)).contiguous()
+            B.check(L.bgsa_hip_seed_select_dev(pair_window.data_ptr() if keys.numel() else None, distance.data_ptr() if keys.numel() else None,
+                                               segments.data_ptr(), hi - lo, bound, k_sel, scores[lo:hi].data_ptr(), ids[lo:hi].data_ptr(),
+                                               a._stream()), "seed_select_dev")
+            emitted += total
+            unique += keys.numel()
+            within += ((distance >= 0) & (distance <= bound)).sum()
+        return scores, ids, counts, (emitted, unique, within)
+
+    def map_reads_seeded(self, reads: np.ndarray, k_best: int = 1, max_distance=None, seed_len=None, max_candidates=None,
+                         block_rows: int = 1000, cigar_cap=None) -> ReferenceHits:
+        """map_reads without the pass over every window: an exact pigeonhole k-mer filter names, per read, the windows that can hold
+        it within max_distance, and only those are verified (include/bgsa_hip.h "seeded read mapping").  max_distance is required: the
+        filter is derived from it.  With B = min(max_distance, n) the result equals blank_beyond(map_reads(reads, k_best,
+        max_distance), B) field by field and bit for bit: every window within B is a candidate, the slots beyond B are a suffix
+        of map_reads' lists and unplaced there too.
+        seed_len=None: min(12, n // (B + 1)); seeds that would overlap (seed_plan) are refused before anything is launched, as are
+        map_reads' own refusals (the stride rule, k_best, cigar_cap) and reads beyond 1,024 bp.  One read length per call.
+        A read with an 'N' in one of its pieces, or with more than max_candidates candidates (default max(n_ids // 8, 256): the measured break-even), is not answered
+        from candidates: those reads, and only those, go through map_reads as a sub-batch.  max_candidates never changes a result,
+        only the time.  last_seed_stats says what happened."""
+        a = self.aligner
+        torch = a.torch
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        if reads.ndim != 2 or reads.shape[0] < 1 or reads.shape[1] < 1:
+            raise B.BgsaHipError("map_reads_seeded: rc=-1: reads must be [ns, n] with ns, n >= 1 (one read length per call)")
+        ns, n = reads.shape
+        if n > 1024:
+            raise B.BgsaHipError("map_reads_seeded: rc=-2: reads beyond 1,024 bp have no verify kernel (map_reads takes them)")
+        k_best = int(k_best)
+        if not 1 <= k_best <= B.V_NUM:
+            raise B.BgsaHipError(f"map_reads_seeded: rc=-1: k_best must lie in 1..{B.V_NUM}")
+        if max_distance is None:
+            raise B.BgsaHipError("map_reads_seeded: rc=-1: max_distance is required: the seed filter is derived from it (map_reads "
+                                 "takes max_distance=None)")
+        if int(max_distance) < 0:
+            raise B.BgsaHipError("map_reads_seeded: rc=-1: max_distance is negative")
+        bound, _, q = seed_plan(n, int(max_distance), seed_len)
+        largest = max_stride(self.window_len, n, bound)
+        if self.stride > largest:
+            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
+            raise B.BgsaHipError(f"map_reads_seeded: rc=-1: at stride {self.stride} a placement of a {n} bp read within distance {bound} can "
+                                 f"lie in no window of {self.window_len} bp: {allowed}")
+        if self.ref_len > INT32_MAX:
+            raise B.BgsaHipError("map_reads_seeded: rc=-1: the index holds int32 positions: a reference beyond 2^31 - 1 bases goes in parts")
+        k_sel = self.k_selected(k_best)
+        cap = self.window_len + n if cigar_cap is None else int(cigar_cap)
+        if cap < 1:
+            raise B.BgsaHipError("map_reads_seeded: rc=-1: cigar_cap is not positive")
+        max_candidates = max(self.n_ids // SEED_CAP_FRACTION, SEED_MIN_CANDIDATES) if max_candidates is None else int(max_candidates)
+        if max_candidates < 0:
+            raise B.BgsaHipError("map_reads_seeded: rc=-1: max_candidates is negative")
+
+        # set_subjects(reads, qlen=W), keeping the ASCII rows: the candidate kernels read them
+        padded, a.extra = B.pad_rows(reads)
+        a.ns_real = ns
+        d_rows = torch.from_numpy(B.rows_to_buffer(padded)).to(a.device)
+        a.set_subject_rows_device(d_rows, padded.shape[0], n, self.window_len)
+        scores, ids, counts, totals = self.select_seeded(d_rows, ns, n, bound, q, k_sel, max_candidates, block_rows)
+        strand, ref_begin, ref_end, keep, n_ops, cigar = self.place_hits(ids, bound, cap, block_rows)
+        a.check_faults()
+
+        flags = counts.cpu().numpy()
+        self.last_seed_stats = dict(reads_seeded=int((flags >= 0).sum()), reads_fallback_n=int((flags == -1).sum()),
+                                    reads_fallback_cap=int((flags == -2).sum()), candidates_emitted=int(totals[0].item()),
+                                    candidates_unique=int(totals[1].item()), candidates_within_bound=int(totals[2].item()),
+                                    seed_len=q, max_candidates=max_candidates)
+        kept = keep.cpu().numpy()
+        runs_n, runs = n_ops.cpu().numpy(), cigar.cpu().numpy().view(np.uint32)
+        cigars = [[None] * k_sel for _ in range(ns)]
+        for c, r in zip(*np.nonzero(kept)):
+            if runs_n[c, r] > cap:
+                raise B.BgsaHipError(f"map_reads_seeded: hit {r} of read {c} has {runs_n[c, r]} runs, its row holds {cap} (raise cigar_cap)")
+            cigars[c][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : runs_n[c, r]].tolist())
+        out = ReferenceHits(scores.cpu().numpy(), strand.cpu().numpy(), ref_begin.cpu().numpy(), ref_end.cpu().numpy(), kept, cigars,
+                            ids.cpu().numpy())
+        rest = np.flatnonzero(flags < 0)
+        if rest.size:        # the reads the filter does not cover: the exhaustive path, blanked, into the caller's order
+            full = blank_beyond(self.map_reads(reads[rest], k_best, int(max_distance), block_rows, cigar_cap), bound)
+            for mine, theirs in zip(out[:5] + (out.windows,), full[:5] + (full.windows,)):
+                mine[rest] = theirs
+            for at, row in zip(rest.tolist(), full.cigars):
+                out.cigars[at] = row
+        return out
 
     def map_reads_ragged(self, reads, k_best: int = 1, max_distance=None, block_rows: int = 1000, cigar_cap=None) -> ReferenceHits:
         """map_reads for reads of MIXED lengths: a list of byte strings or 1-D uint8 arrays, 1..1,024 bp each.  The reads are binned by

@@ -690,6 +690,74 @@ int bgsa_hip_reference_placements_dev(int64_t ref_len, int window_len, int strid
                                       int32_t *d_strand, int64_t *d_ref_begin, int64_t *d_ref_end, int32_t *d_keep,
                                       void *stream);
 
+/* ---- seeded read mapping: an exact pigeonhole k-mer filter that names the windows worth verifying ----
+ * The calls above choose a read's windows by scoring EVERY window.  These calls name, per read, the windows that CAN hold it
+ * within a distance bound, verify exactly those, and leave hit lists in the format bgsa_hip_top_queries_dev leaves — so that
+ * bgsa_hip_myers_place_pairs_banded_dev and bgsa_hip_reference_placements_dev finish the job unchanged.  Every result is exact:
+ * the lists equal the exhaustive ones with the hits beyond the bound left out.
+ * PIGEONHOLE.  A read of n bp placed with at most B = min(max_distance, n) unit-cost edits, cut into B + 1 disjoint pieces: an
+ * edit touches at most one piece, so one piece lies on the reference unedited, on a diagonal within B of the placement's.
+ * GEOMETRY (normative; bgsa_amd/reference.py: seed_plan, and tests/seed_map_reference.py restate it).  Windows, ids and strands
+ * are those of "a reference as the query set" above: L mapped bytes, 1 <= S <= W <= L, start(w) = min(w * S, L - W).
+ *   index       the forward reference only.  q = seed_len, 1 <= q <= 13.  Position p is indexed when ref[p .. p + q) are all
+ *               below 4 (no k-mer with an 'N'); its value is sum over i of ref[p + i] * 4^(q - 1 - i).  d_offsets: int32,
+ *               bgsa_hip_seed_index_offsets(q) = 4^q + 1 entries; d_positions: int32, at least max(L - q + 1, 1) entries; bucket
+ *               c is d_positions[d_offsets[c] .. d_offsets[c + 1]), in no particular order.  ref_len above INT32_MAX is refused;
+ *               ref_len < q gives an empty index (every offset 0).
+ *   pieces      step = n / (B + 1) (integer division); piece j = 0 .. B starts at o_j = j * step and is q long.  step < q is
+ *               BGSA_HIP_EINVAL: the pieces would overlap.  Forward strand: the pieces of the read.  Reverse strand: the pieces
+ *               of the read's reverse complement, looked up in the same forward index; a window w found that way has id
+ *               n_windows + w.  Read bytes get the classes of the subject preprocess: A C G T N = 0..4, any other byte 0.
+ *   candidates  an occurrence at p of the piece at o makes window w a candidate when all four hold:
+ *                 start(w) <= p;  p + q <= start(w) + W      (the seed lies inside the window)
+ *                 start(w) <= p - o + B;  p - o + n - B <= start(w) + W      (so do both ends of any placement within B through it)
+ *               Every window whose semi-global distance to the read is <= B is a candidate of a read that is not flagged.
+ *   flags       -1: one of the read's pieces (both strands' pieces with both_strands != 0) holds class 4 — 'N' matches 'N' in
+ *               the scorer and the index has no 'N', so the pigeonhole count does not hold; -2: the read has more than
+ *               max_candidates candidates (counted with repetitions).  A flagged read is answered by the exhaustive calls.
+ * bgsa_hip_seed_index_offsets / _workspace_bytes: host only.  -1 / 0 for a seed_len outside 1..13 (or ref_len outside int32).
+ * bgsa_hip_seed_index_build_dev: a rolling-code count, an inclusive scan over the 4^q counts and a fill, all on `stream`.
+ * bgsa_hip_seed_count_candidates_dev: d_counts[r], r < n_reads = the candidates of read r over the strands asked for, or a flag.
+ * d_reads: ASCII rows, stride read_len + 1 (the rows bgsa_hip_handle_reads_dev takes).
+ * bgsa_hip_seed_emit_candidates_dev: with d_prefix[r] int64 = the sum of the non-negative d_counts in front of r (the caller's
+ * scan), read r with d_counts[r] >= 0 writes (read_base + r, window id) to d_cand_read / d_cand_window [d_prefix[r] ..
+ * d_prefix[r] + d_counts[r]), in no particular order and with repetitions; the caller sorts and deduplicates.
+ * bgsa_hip_reference_verify_pairs_dev: for every owned pair p, d_distance[p] = the exact Myers semi-global distance of read
+ * d_pair_subject[p] - subject_base inside window d_pair_window[p]: minus the entry the scoring call puts in the tile for that
+ * window row and read.  One pair per lane; the window's characters are read straight from d_reference (forward ids forwards,
+ * reverse ids complemented from the window's end backwards): no window row is written anywhere.  d_peq, read_count and
+ * word_num are the resident bucket's.  A pair is owned when its subject lies in [subject_base, subject_base + read_count); an
+ * owned pair whose window id lies outside [0, 2 * n_windows) forms no address; neither kind has its d_distance entry touched.
+ * word_num 1..32 (BGSA_HIP_EUNSUPPORTED beyond); reads beyond 16 words run as column blocks and need a workspace of
+ * bgsa_hip_reference_verify_workspace_bytes(W, read_len, n_pairs) (at least that of one wave: n_pairs = 0), narrower ones none.
+ * bgsa_hip_seed_select_dev: the candidates of read r are entries [d_segments[r], d_segments[r + 1]) (int64, n_reads + 1
+ * entries) of d_cand_window / d_cand_distance, window ids ascending and distinct within a read.  Fills d_hit_scores[r][k] (minus
+ * the distance; INT32_MIN = unused) and d_hit_windows[r][k] (-1 = unused) with the read's k best candidates of distance in
+ * [0, max_distance], best first by (distance ascending, id ascending).  k in 1..64.  One wave per read.
+ * All device calls only launch on `stream`: no allocation, no synchronisation.  A zero count is BGSA_HIP_OK and launches
+ * nothing.  BGSA_HIP_EINVAL, checked before the first HIP call: a NULL pointer (the stream, the workspace of a narrow verify and
+ * the candidate arrays of an empty select excepted), seed_len outside 1..13, a shape outside 1 <= S <= W <= L, ref_len above
+ * INT32_MAX, 2 * n_windows above INT32_MAX, a negative count, step < seed_len, a workspace too small, a word_num that is not
+ * ceil(read_len / 32), read_count no positive multiple of 64, k outside 1..64. */
+int64_t bgsa_hip_seed_index_offsets(int seed_len);
+size_t bgsa_hip_seed_index_workspace_bytes(int64_t ref_len, int seed_len);
+int bgsa_hip_seed_index_build_dev(const char *d_reference, int64_t ref_len, int seed_len, int32_t *d_offsets, int32_t *d_positions,
+                                  void *d_workspace, size_t workspace_bytes, void *stream);
+int bgsa_hip_seed_count_candidates_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_offsets,
+                                       const int32_t *d_positions, int seed_len, const char *d_reads, int read_len, int64_t n_reads,
+                                       int max_distance, int both_strands, int64_t max_candidates, int32_t *d_counts, void *stream);
+int bgsa_hip_seed_emit_candidates_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_offsets,
+                                      const int32_t *d_positions, int seed_len, const char *d_reads, int read_len, int64_t n_reads,
+                                      int max_distance, int both_strands, const int32_t *d_counts, const int64_t *d_prefix,
+                                      int64_t read_base, int32_t *d_cand_read, int32_t *d_cand_window, void *stream);
+size_t bgsa_hip_reference_verify_workspace_bytes(int window_len, int read_len, int64_t n_pairs);
+int bgsa_hip_reference_verify_pairs_dev(const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,
+                                        int read_len, int64_t read_count, int word_num, const int32_t *d_pair_window,
+                                        const int64_t *d_pair_subject, int64_t n_pairs, int64_t subject_base, int32_t *d_distance,
+                                        void *d_workspace, size_t workspace_bytes, void *stream);
+int bgsa_hip_seed_select_dev(const int32_t *d_cand_window, const int32_t *d_cand_distance, const int64_t *d_segments, int64_t n_reads,
+                             int max_distance, int k, int32_t *d_hit_scores, int32_t *d_hit_windows, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
