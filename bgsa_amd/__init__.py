@@ -157,7 +157,12 @@ def lib() -> ctypes.CDLL:
                                  ("bgsa_hip_reference_verify_workspace_bytes", [i32, i32, i64], sz),
                                  ("bgsa_hip_reference_verify_pairs_dev",
                                   [vp, i64, i32, i32, vp, i32, i64, i32, vp, vp, i64, i64, vp, vp, sz, vp], i32),
-                                 ("bgsa_hip_seed_select_dev", [vp, vp, vp, i64, i32, i32, vp, vp, vp], i32)):
+                                 ("bgsa_hip_seed_select_dev", [vp, vp, vp, i64, i32, i32, vp, vp, vp], i32),
+                                 # every read at its own length: d_read_lens follows the reads / the planes
+                                 ("bgsa_hip_seed_count_candidates_lens_dev", seed[:7] + [vp] + seed[7:] + [i64, vp, vp], i32),
+                                 ("bgsa_hip_seed_emit_candidates_lens_dev", seed[:7] + [vp] + seed[7:] + [vp, vp, i64, vp, vp, vp], i32),
+                                 ("bgsa_hip_reference_verify_pairs_lens_dev",
+                                  [vp, i64, i32, i32, vp, vp, i32, i64, i32, vp, vp, i64, i64, vp, vp, sz, vp], i32)):
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
@@ -1159,4 +1164,4 @@ def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: 
 
 
 # reads mapped onto one reference: windows cut on the device, both strands, reference coordinates (bgsa_amd/reference.py)
-from .reference import Placement, ReferenceHits, ReferenceMapper, blank_beyond, max_stride, seed_plan, window_plan  # noqa: E402
+from .reference import Placement, ReferenceHits, ReferenceMapper, blank_beyond, max_stride, seed_plan, seed_plan_ragged, window_plan  # noqa: E402

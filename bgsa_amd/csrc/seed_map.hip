@@ -15,6 +15,9 @@
 //               start(w) <= p - o + B and p - o + n - B <= start(w) + W.
 //   flags       a read with a class-4 character in any piece of the strands asked for is -1 (N matches N in the scorer, the index
 //               has no N: the pigeonhole count does not hold); a read with more than max_candidates candidates is -2.
+//   lengths     the *_lens_dev calls: read r is its row's first n_r = lens[r] characters, B_r = min(max_distance, n_r), step_r =
+//               n_r / (B_r + 1); the rules above hold with n_r and B_r, and step_r < q (n_r == 0 among them) is flag -3.  The
+//               verify kernel's Lens instances take a lane's score column from the lane's own word (LABNOTES §28).
 //
 // Five steps, each a launch on the caller's stream and nothing else:
 //   index build  rolling codes counted with atomics into offsets[c + 1], an inclusive scan over the 4^q counts in three kernels
@@ -167,6 +170,7 @@ struct SeedArgs {
     int64_t n_reads;
     int bound, step, strands;
     int64_t cap;
+    const int32_t *lens;             // the *_lens calls: every read's own length (n is then the rows' width), else NULL
 };
 
 __device__ __forceinline__ uint32_t map_char(uint32_t ch)   // the subject preprocess's classes (preprocess.hip)
@@ -196,7 +200,10 @@ __device__ __forceinline__ int candidate_windows(const Geometry &g, int64_t lo, 
 
 // Emit == false: counts[r] = the read's candidates, -1 (an N in a piece) or -2 (above the cap).  Emit == true: a read with a
 // non-negative count writes its candidates from prefix[r] on.
-template <bool Emit>
+// Lens == true: read r is its row's first n_r = lens[r] characters (clamped to [0, a.n]) with B_r = min(a.bound, n_r) and step_r =
+// n_r / (B_r + 1); step_r < q (n_r == 0 among them) is flag -3 and nothing of the row is read.  Every piece ends at or before
+// (B_r + 1) * step_r <= n_r, and the reverse strand counts back from n_r - 1: the pad behind a read's end is never looked at.
+template <bool Emit, bool Lens>
 __global__ __launch_bounds__(256) void seed_candidates_kernel(SeedArgs a, int32_t *__restrict__ counts, const int64_t *__restrict__ prefix,
                                                               int64_t read_base, int32_t *__restrict__ out_read,
                                                               int32_t *__restrict__ out_window)
@@ -205,23 +212,34 @@ __global__ __launch_bounds__(256) void seed_candidates_kernel(SeedArgs a, int32_
     if (r >= a.n_reads) return;
     const unsigned char *row = a.reads + r * (a.n + 1);
     int64_t at = 0;
+    if (Emit && counts[r] < 0) return;
+    int n = a.n, B = a.bound, step = a.step;
+    if (Lens) {
+        n = a.lens[r];
+        n = n < 0 ? 0 : n > a.n ? a.n : n;
+        B = a.bound < n ? a.bound : n;
+        step = n / (B + 1);
+        if (step < a.q) {                         // too short for this seed and bound (n == 0: step 0)
+            if (!Emit) counts[r] = -3;
+            return;
+        }
+    }
     if (Emit) {
-        if (counts[r] < 0) return;
         at = prefix[r];
     } else {
         for (int s = 0; s < a.strands; s++)
-            for (int j = 0; j <= a.bound; j++)
+            for (int j = 0; j <= B; j++)
                 for (int t = 0; t < a.q; t++)
-                    if (strand_class(row, a.n, s, j * a.step + t) == 4u) {
+                    if (strand_class(row, n, s, j * step + t) == 4u) {
                         counts[r] = -1;
                         return;
                     }
     }
-    const int W = a.g.window_len, n = a.n, B = a.bound, q = a.q;
+    const int W = a.g.window_len, q = a.q;
     int64_t count = 0;
     for (int s = 0; s < a.strands; s++) {
         for (int j = 0; j <= B; j++) {
-            const int o = j * a.step;
+            const int o = j * step;
             uint32_t code = 0;
             for (int t = 0; t < q; t++) code = (code << 2) | (strand_class(row, n, s, o + t) & 3u);
             const int32_t end = a.offsets[code + 1];
@@ -267,6 +285,7 @@ struct VerifyArgs {
     const int32_t *pair_window;
     const int64_t *pair_subject;
     int64_t n_pairs, subject_base;
+    const int32_t *read_lens;        // the *_lens call: one length per column of the bucket, else NULL
     int32_t *distance;
     unsigned char *workspace;        // [wave][block of 32 rows][Hp | Hn | add][lane] uint32: only for word_num > kVerifyWords
     size_t wave_bytes;
@@ -322,7 +341,12 @@ __device__ __forceinline__ void window_block(const unsigned char *reference, int
 }
 
 // WB words per column block; Blocks == false: the read is one block (word_num <= WB), no carries leave the registers.
-template <int WB, bool Blocks>
+// Lens == true: lane p verifies its column's first n = read_lens[col] characters (clamped to [0, read_len]).  The planes stay
+// where the bucket's preprocess put them; the lane takes its score column from its OWN word (n - 1) >> 5 at bit (n - 1) & 31 —
+// a compare (hoisted out of the row loop) and two selects per word and row.  Carries and shifts travel upward only, so the
+// columns above n (the pad, and with column blocks every later block) are computed and never looked at; the block that holds
+// the lane's word sees every row, so `run` and `best` are complete when that block ends.  n == 0: distance 0.
+template <int WB, bool Blocks, bool Lens>
 __global__ __launch_bounds__(kLanes) void reference_verify_pairs_kernel(VerifyArgs a, int64_t first)
 {
     const int lane = threadIdx.x;
@@ -335,18 +359,29 @@ __global__ __launch_bounds__(kLanes) void reference_verify_pairs_kernel(VerifyAr
     const int64_t id = a.pair_window[p];
     if (id < 0 || id >= 2 * a.g.n_windows) return;   // no window: the id forms no address
     const int64_t col = s - a.subject_base;
-    const int wn = a.word_num, m = a.g.window_len, n = a.read_len;
+    const int wn = a.word_num, m = a.g.window_len;
+    int n = a.read_len;
+    if (Lens) {
+        n = a.read_lens[col];
+        n = n < 0 ? 0 : n > a.read_len ? a.read_len : n;
+        if (n == 0) {
+            a.distance[p] = 0;
+            return;
+        }
+    }
     const bool reverse = id >= a.g.n_windows;
     const int64_t at = window_start(a.g, reverse ? id - a.g.n_windows : id);
 
     const uint32_t *planes = a.peq + static_cast<size_t>(col >> 6) * kChars * wn * kLanes + (col & (kLanes - 1));
     uint32_t *carries = Blocks ? reinterpret_cast<uint32_t *>(a.workspace + static_cast<size_t>(blockIdx.x) * a.wave_bytes) + lane : nullptr;
-    const int top = (n - 1) & 31;   // column n inside the last word
+    const int top = (n - 1) & 31;   // column n inside the last word (Lens: inside the lane's own word)
+    const int own = Lens ? (n - 1) >> 5 : 0;
 
     int run = n, best = n;
     for (int w0 = 0; w0 < (Blocks ? wn : 1); w0 += WB) {
         const int wb = wn - w0 < WB ? wn - w0 : WB;   // wave-uniform
         const bool leftmost = w0 == 0, rightmost = !Blocks || w0 + WB >= wn;
+        const int own_w = own - w0;                   // Lens: the lane's word inside this block, or outside [0, WB)
         uint32_t peq[kChars][WB], pv[WB], mv[WB];
 #pragma unroll
         for (int w = 0; w < WB; w++) {
@@ -394,8 +429,13 @@ __global__ __launch_bounds__(kLanes) void reference_verify_pairs_kernel(VerifyAr
                         hn_in = hn >> 31;
                         pv[w] = ~(d0 | hps) | hns;
                         mv[w] = d0 & hps;
-                        top_hp = hp;
-                        top_hn = hn;
+                        if (Lens) {
+                            top_hp = w == own_w ? hp : top_hp;
+                            top_hn = w == own_w ? hn : top_hn;
+                        } else {
+                            top_hp = hp;
+                            top_hn = hn;
+                        }
                     }
                 }
                 if (Blocks) {
@@ -403,7 +443,7 @@ __global__ __launch_bounds__(kLanes) void reference_verify_pairs_kernel(VerifyAr
                     out_hn |= hn_in << r;
                     out_add |= carry << r;
                 }
-                if (rightmost) {
+                if (Lens || rightmost) {             // Lens: a block without the lane's word adds 0
                     run += static_cast<int>((top_hp >> top) & 1u) - static_cast<int>((top_hn >> top) & 1u);
                     best = run < best ? run : best;
                 }
@@ -421,7 +461,8 @@ __global__ __launch_bounds__(kLanes) void reference_verify_pairs_kernel(VerifyAr
 template <int WB, bool Blocks>
 int launch_verify(const VerifyArgs &a, dim3 grid, int64_t first, hipStream_t stream)
 {
-    hipLaunchKernelGGL((reference_verify_pairs_kernel<WB, Blocks>), grid, dim3(kLanes), 0, stream, a, first);
+    if (a.read_lens) hipLaunchKernelGGL((reference_verify_pairs_kernel<WB, Blocks, true>), grid, dim3(kLanes), 0, stream, a, first);
+    else hipLaunchKernelGGL((reference_verify_pairs_kernel<WB, Blocks, false>), grid, dim3(kLanes), 0, stream, a, first);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
@@ -569,10 +610,12 @@ int bgsa_hip_seed_index_build_dev(const char *d_reference, int64_t ref_len, int 
     return BGSA_HIP_OK;
 }
 
+// per_read: the *_lens calls — d_read_lens is required, and step < seed_len is every read's own flag -3, not a refusal.
 static int seed_args(const char *who, int64_t ref_len, int window_len, int stride, const int32_t *d_offsets, const int32_t *d_positions,
-                     int seed_len, const char *d_reads, int read_len, int64_t n_reads, int max_distance, int both_strands, SeedArgs *out)
+                     int seed_len, const char *d_reads, int read_len, int64_t n_reads, int max_distance, int both_strands, SeedArgs *out,
+                     bool per_read = false, const int32_t *d_read_lens = nullptr)
 {
-    if (!d_offsets || !d_positions || !d_reads) return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
+    if (!d_offsets || !d_positions || !d_reads || (per_read && !d_read_lens)) return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
     if (!seed_len_ok(seed_len)) return refuse(who, BGSA_HIP_EINVAL, "seed_len must lie in 1..13");
     Geometry g;
     if (int rc = make_geometry(who, ref_len, window_len, stride, &g)) return rc;
@@ -580,14 +623,60 @@ static int seed_args(const char *who, int64_t ref_len, int window_len, int strid
     if (n_reads < 0 || n_reads > static_cast<int64_t>(INT32_MAX)) return refuse(who, BGSA_HIP_EINVAL, "n_reads must lie in [0, 2^31 - 1]");
     const int bound = max_distance < read_len ? max_distance : read_len;
     const int step = read_len / (bound + 1);
-    if (step < seed_len) {
+    if (!per_read && step < seed_len) {
         char why[200];
         snprintf(why, sizeof why, "the %d pieces of a %d bp read within distance %d are %d bp apart, shorter than seed_len %d", bound + 1,
                  read_len, bound, step, seed_len);
         return refuse(who, BGSA_HIP_EINVAL, why);
     }
     *out = SeedArgs{g, d_offsets, d_positions, seed_len, reinterpret_cast<const unsigned char *>(d_reads), read_len, n_reads, bound, step,
-                    both_strands ? 2 : 1, 0};
+                    both_strands ? 2 : 1, 0, per_read ? d_read_lens : nullptr};
+    return BGSA_HIP_OK;
+}
+
+static int count_candidates(const char *who, int64_t ref_len, int window_len, int stride, const int32_t *d_offsets,
+                            const int32_t *d_positions, int seed_len, const char *d_reads, const int32_t *d_read_lens, bool per_read,
+                            int read_len, int64_t n_reads, int max_distance, int both_strands, int64_t max_candidates, int32_t *d_counts,
+                            void *stream)
+{
+    SeedArgs a;
+    if (!d_counts) return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
+    if (int rc = seed_args(who, ref_len, window_len, stride, d_offsets, d_positions, seed_len, d_reads, read_len, n_reads, max_distance,
+                           both_strands, &a, per_read, d_read_lens))
+        return rc;
+    if (max_candidates < 0) return refuse(who, BGSA_HIP_EINVAL, "max_candidates is negative");
+    a.cap = max_candidates < (1ll << 30) ? max_candidates : (1ll << 30);   // a count stays an int32
+    if (n_reads == 0) return BGSA_HIP_OK;
+    const dim3 grid(static_cast<unsigned>((n_reads + 255) / 256));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (per_read) hipLaunchKernelGGL((seed_candidates_kernel<false, true>), grid, dim3(256), 0, s, a, d_counts, nullptr, 0, nullptr, nullptr);
+    else hipLaunchKernelGGL((seed_candidates_kernel<false, false>), grid, dim3(256), 0, s, a, d_counts, nullptr, 0, nullptr, nullptr);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+static int emit_candidates(const char *who, int64_t ref_len, int window_len, int stride, const int32_t *d_offsets,
+                           const int32_t *d_positions, int seed_len, const char *d_reads, const int32_t *d_read_lens, bool per_read,
+                           int read_len, int64_t n_reads, int max_distance, int both_strands, const int32_t *d_counts,
+                           const int64_t *d_prefix, int64_t read_base, int32_t *d_cand_read, int32_t *d_cand_window, void *stream)
+{
+    SeedArgs a;
+    if (!d_counts || !d_prefix || !d_cand_read || !d_cand_window)
+        return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
+    if (int rc = seed_args(who, ref_len, window_len, stride, d_offsets, d_positions, seed_len, d_reads, read_len, n_reads, max_distance,
+                           both_strands, &a, per_read, d_read_lens))
+        return rc;
+    if (read_base < 0 || read_base > static_cast<int64_t>(INT32_MAX) - n_reads)
+        return refuse(who, BGSA_HIP_EINVAL, "read_base + n_reads must stay within int32");
+    if (n_reads == 0) return BGSA_HIP_OK;
+    const dim3 grid(static_cast<unsigned>((n_reads + 255) / 256));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t *counts = const_cast<int32_t *>(d_counts);
+    if (per_read)
+        hipLaunchKernelGGL((seed_candidates_kernel<true, true>), grid, dim3(256), 0, s, a, counts, d_prefix, read_base, d_cand_read, d_cand_window);
+    else
+        hipLaunchKernelGGL((seed_candidates_kernel<true, false>), grid, dim3(256), 0, s, a, counts, d_prefix, read_base, d_cand_read, d_cand_window);
+    BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
 
@@ -595,19 +684,17 @@ int bgsa_hip_seed_count_candidates_dev(int64_t ref_len, int window_len, int stri
                                        int seed_len, const char *d_reads, int read_len, int64_t n_reads, int max_distance,
                                        int both_strands, int64_t max_candidates, int32_t *d_counts, void *stream)
 {
-    const char *who = "seed_count_candidates_dev";
-    SeedArgs a;
-    if (!d_counts) return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
-    if (int rc = seed_args(who, ref_len, window_len, stride, d_offsets, d_positions, seed_len, d_reads, read_len, n_reads, max_distance,
-                           both_strands, &a))
-        return rc;
-    if (max_candidates < 0) return refuse(who, BGSA_HIP_EINVAL, "max_candidates is negative");
-    a.cap = max_candidates < (1ll << 30) ? max_candidates : (1ll << 30);   // a count stays an int32
-    if (n_reads == 0) return BGSA_HIP_OK;
-    hipLaunchKernelGGL(seed_candidates_kernel<false>, dim3(static_cast<unsigned>((n_reads + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), a, d_counts, nullptr, 0, nullptr, nullptr);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
+    return count_candidates("seed_count_candidates_dev", ref_len, window_len, stride, d_offsets, d_positions, seed_len, d_reads, nullptr, false,
+                            read_len, n_reads, max_distance, both_strands, max_candidates, d_counts, stream);
+}
+
+int bgsa_hip_seed_count_candidates_lens_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_offsets,
+                                            const int32_t *d_positions, int seed_len, const char *d_reads, const int32_t *d_read_lens,
+                                            int read_len, int64_t n_reads, int max_distance, int both_strands, int64_t max_candidates,
+                                            int32_t *d_counts, void *stream)
+{
+    return count_candidates("seed_count_candidates_lens_dev", ref_len, window_len, stride, d_offsets, d_positions, seed_len, d_reads,
+                            d_read_lens, true, read_len, n_reads, max_distance, both_strands, max_candidates, d_counts, stream);
 }
 
 int bgsa_hip_seed_emit_candidates_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_offsets, const int32_t *d_positions,
@@ -615,20 +702,19 @@ int bgsa_hip_seed_emit_candidates_dev(int64_t ref_len, int window_len, int strid
                                       int both_strands, const int32_t *d_counts, const int64_t *d_prefix, int64_t read_base,
                                       int32_t *d_cand_read, int32_t *d_cand_window, void *stream)
 {
-    const char *who = "seed_emit_candidates_dev";
-    SeedArgs a;
-    if (!d_counts || !d_prefix || !d_cand_read || !d_cand_window)
-        return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
-    if (int rc = seed_args(who, ref_len, window_len, stride, d_offsets, d_positions, seed_len, d_reads, read_len, n_reads, max_distance,
-                           both_strands, &a))
-        return rc;
-    if (read_base < 0 || read_base > static_cast<int64_t>(INT32_MAX) - n_reads)
-        return refuse(who, BGSA_HIP_EINVAL, "read_base + n_reads must stay within int32");
-    if (n_reads == 0) return BGSA_HIP_OK;
-    hipLaunchKernelGGL(seed_candidates_kernel<true>, dim3(static_cast<unsigned>((n_reads + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), a, const_cast<int32_t *>(d_counts), d_prefix, read_base, d_cand_read, d_cand_window);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
+    return emit_candidates("seed_emit_candidates_dev", ref_len, window_len, stride, d_offsets, d_positions, seed_len, d_reads, nullptr, false,
+                           read_len, n_reads, max_distance, both_strands, d_counts, d_prefix, read_base, d_cand_read, d_cand_window, stream);
+}
+
+int bgsa_hip_seed_emit_candidates_lens_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_offsets,
+                                           const int32_t *d_positions, int seed_len, const char *d_reads, const int32_t *d_read_lens,
+                                           int read_len, int64_t n_reads, int max_distance, int both_strands, const int32_t *d_counts,
+                                           const int64_t *d_prefix, int64_t read_base, int32_t *d_cand_read, int32_t *d_cand_window,
+                                           void *stream)
+{
+    return emit_candidates("seed_emit_candidates_lens_dev", ref_len, window_len, stride, d_offsets, d_positions, seed_len, d_reads,
+                           d_read_lens, true, read_len, n_reads, max_distance, both_strands, d_counts, d_prefix, read_base, d_cand_read,
+                           d_cand_window, stream);
 }
 
 size_t bgsa_hip_reference_verify_workspace_bytes(int window_len, int read_len, int64_t n_pairs)
@@ -642,13 +728,13 @@ size_t bgsa_hip_reference_verify_workspace_bytes(int window_len, int read_len, i
     return want > per ? want : per;
 }
 
-int bgsa_hip_reference_verify_pairs_dev(const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,
-                                        int read_len, int64_t read_count, int word_num, const int32_t *d_pair_window,
-                                        const int64_t *d_pair_subject, int64_t n_pairs, int64_t subject_base, int32_t *d_distance,
-                                        void *d_workspace, size_t workspace_bytes, void *stream)
+// per_lane: the *_lens call — d_read_lens is required and every lane verifies at its own length.
+static int verify_pairs(const char *who, const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,
+                        const int32_t *d_read_lens, bool per_lane, int read_len, int64_t read_count, int word_num,
+                        const int32_t *d_pair_window, const int64_t *d_pair_subject, int64_t n_pairs, int64_t subject_base,
+                        int32_t *d_distance, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    const char *who = "reference_verify_pairs_dev";
-    if (!d_reference || !d_peq || !d_pair_window || !d_pair_subject || !d_distance)
+    if (!d_reference || !d_peq || !d_pair_window || !d_pair_subject || !d_distance || (per_lane && !d_read_lens))
         return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the workspace of a read of <= 16 words and the stream may be NULL)");
     Geometry g;
     if (int rc = make_geometry(who, ref_len, window_len, stride, &g)) return rc;
@@ -664,7 +750,7 @@ int bgsa_hip_reference_verify_pairs_dev(const char *d_reference, int64_t ref_len
     if (n_pairs == 0) return BGSA_HIP_OK;
 
     VerifyArgs a{reinterpret_cast<const unsigned char *>(d_reference), g, d_peq, read_len, read_count, word_num, d_pair_window,
-                 d_pair_subject, n_pairs, subject_base, d_distance, static_cast<unsigned char *>(d_workspace), per};
+                 d_pair_subject, n_pairs, subject_base, per_lane ? d_read_lens : nullptr, d_distance, static_cast<unsigned char *>(d_workspace), per};
     int64_t chunk_waves = per ? static_cast<int64_t>(workspace_bytes / per) : kVerifyMaxWaves;
     if (chunk_waves > kVerifyMaxWaves) chunk_waves = kVerifyMaxWaves;
     for (int64_t first = 0; first < n_pairs; first += chunk_waves * kLanes) {
@@ -673,6 +759,26 @@ int bgsa_hip_reference_verify_pairs_dev(const char *d_reference, int64_t ref_len
         if (int rc = dispatch_verify(a, grid, first, static_cast<hipStream_t>(stream))) return rc;
     }
     return BGSA_HIP_OK;
+}
+
+int bgsa_hip_reference_verify_pairs_dev(const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,
+                                        int read_len, int64_t read_count, int word_num, const int32_t *d_pair_window,
+                                        const int64_t *d_pair_subject, int64_t n_pairs, int64_t subject_base, int32_t *d_distance,
+                                        void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return verify_pairs("reference_verify_pairs_dev", d_reference, ref_len, window_len, stride, d_peq, nullptr, false, read_len, read_count,
+                        word_num, d_pair_window, d_pair_subject, n_pairs, subject_base, d_distance, d_workspace, workspace_bytes, stream);
+}
+
+int bgsa_hip_reference_verify_pairs_lens_dev(const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,
+                                             const int32_t *d_read_lens, int read_len, int64_t read_count, int word_num,
+                                             const int32_t *d_pair_window, const int64_t *d_pair_subject, int64_t n_pairs,
+                                             int64_t subject_base, int32_t *d_distance, void *d_workspace, size_t workspace_bytes,
+                                             void *stream)
+{
+    return verify_pairs("reference_verify_pairs_lens_dev", d_reference, ref_len, window_len, stride, d_peq, d_read_lens, true, read_len,
+                        read_count, word_num, d_pair_window, d_pair_subject, n_pairs, subject_base, d_distance, d_workspace, workspace_bytes,
+                        stream);
 }
 
 int bgsa_hip_seed_select_dev(const int32_t *d_cand_window, const int32_t *d_cand_distance, const int64_t *d_segments, int64_t n_reads,

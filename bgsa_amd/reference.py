@@ -67,6 +67,26 @@ def seed_plan(read_len: int, max_distance: int, seed_len=None) -> tuple[int, int
     return bound, step, q
 
 
+def seed_plan_ragged(lens, max_distance: int, seed_len=None) -> list:
+    """[(indices, q)] for reads of the lengths `lens` within max_distance: the bins of bin_by_words(lens), in its order, each with the
+    seed length its pass uses.  seed_len=None: q = min(12, max(1, step of the bin's shortest read)), that read's step being
+    n // (min(max_distance, n) + 1) — the shortest read has the smallest step of its bin, so every longer read's pieces are at least
+    q apart too; a read no longer than the bound has step 0, gets q = 1 and is flagged too short (-3) by the candidate call.
+    seed_len given: that value for every bin, refused outside 1..SEED_LEN_MAX; the reads whose own step is below it are flagged.
+    One q per bin, not per read: a q per read would need one index per distinct step resident at once.  Pure Python: no device,
+    no library."""
+    if int(max_distance) < 0:
+        raise B.BgsaHipError("seed_plan_ragged: rc=-1: max_distance is negative")
+    if seed_len is not None and not 1 <= int(seed_len) <= SEED_LEN_MAX:
+        raise B.BgsaHipError(f"seed_plan_ragged: rc=-1: seed_len must lie in 1..{SEED_LEN_MAX}")
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    out = []
+    for idx in B.bin_by_words(lens):
+        n = int(lens[idx].min())
+        out.append((idx, int(seed_len) if seed_len is not None else min(12, max(1, n // (min(int(max_distance), n) + 1)))))
+    return out
+
+
 def blank_beyond(hits: "ReferenceHits", bound: int) -> "ReferenceHits":
     """map_reads' result with every slot whose distance exceeds `bound` (and every unused slot) blanked: scores INT32_MIN, windows,
     strand, ref_begin and ref_end -1, keep 0, cigar None.  This is what map_reads_seeded returns, bit for bit."""
@@ -283,12 +303,15 @@ class ReferenceMapper:
         return self.seed_indexes[q]
 
     def select_seeded(self, d_rows, n_reads: int, read_len: int, bound: int, seed_len: int, k_sel: int, max_candidates: int,
-                      block_rows: int = 1000):
+                      block_rows: int = 1000, d_lens=None):
         """The device half of map_reads_seeded's selection, for the reads the aligner holds AND whose ASCII rows d_rows (stride
         read_len + 1) are on the device: block_rows reads at a time count -> emit -> sort and deduplicate (torch) -> verify ->
         select.  Returns (scores[n_reads, k_sel] int32, window ids[n_reads, k_sel] int32, counts[n_reads] int32: the candidates
         of every read or its flag -1 / -2, stats: three device scalars emitted / unique / within the bound).  A flagged read
-        gets a list of unused slots."""
+        gets a list of unused slots.
+        d_lens (the bucket's int32 lengths, one per column; map_reads_seeded_ragged): read_len is the rows' width, every read is
+        counted, emitted and verified at its own length by the *_lens_dev calls, and a read too short for seed_len is flagged -3.
+        d_lens=None launches exactly the equal-length calls."""
         a, L = self.aligner, B.lib()
         torch, dev, W, S = a.torch, a.device, self.window_len, self.stride
         offsets, positions = self.seed_index(seed_len)
@@ -304,17 +327,21 @@ class ReferenceMapper:
             hi = min(lo + block, n_reads)
             rows = d_rows.data_ptr() + lo * (read_len + 1)
             reads = (rows, read_len, hi - lo, bound, int(self.both_strands))
-            B.check(L.bgsa_hip_seed_count_candidates_dev(*shape, *reads, int(max_candidates), counts[lo:hi].data_ptr(), a._stream()),
-                    "seed_count_candidates_dev")
+            count, emit, verify, lens_arg = L.bgsa_hip_seed_count_candidates_dev, L.bgsa_hip_seed_emit_candidates_dev, \
+                L.bgsa_hip_reference_verify_pairs_dev, ()
+            if d_lens is not None:
+                reads = (rows, d_lens[lo:hi].data_ptr()) + reads[1:]
+                count, emit, verify, lens_arg = L.bgsa_hip_seed_count_candidates_lens_dev, L.bgsa_hip_seed_emit_candidates_lens_dev, \
+                    L.bgsa_hip_reference_verify_pairs_lens_dev, (d_lens.data_ptr(),)
+            B.check(count(*shape, *reads, int(max_candidates), counts[lo:hi].data_ptr(), a._stream()), "seed_count_candidates_dev")
             ends = counts[lo:hi].clamp(min=0).to(torch.int64).cumsum(0)
             total = int(ends[-1].item())                    # the one scalar read back per block: it sizes the candidate arrays
             prefix = (ends - counts[lo:hi].clamp(min=0)).contiguous()
             cand_read = torch.empty(total, dtype=torch.int32, device=dev)
             cand_window = torch.empty(total, dtype=torch.int32, device=dev)
             if total:
-                B.check(L.bgsa_hip_seed_emit_candidates_dev(*shape, *reads, counts[lo:hi].data_ptr(), prefix.data_ptr(), 0,
-                                                            cand_read.data_ptr(), cand_window.data_ptr(), a._stream()),
-                        "seed_emit_candidates_dev")
+                B.check(emit(*shape, *reads, counts[lo:hi].data_ptr(), prefix.data_ptr(), 0, cand_read.data_ptr(), cand_window.data_ptr(),
+                             a._stream()), "seed_emit_candidates_dev")
             keys = torch.unique(cand_read.to(torch.int64) * n_ids2 + cand_window)      # sorted by (read, id), every pair once
             pair_read = keys // n_ids2
             pair_window = (keys - pair_read * n_ids2).to(torch.int32)
@@ -325,10 +352,9 @@ class ReferenceMapper:
                 if need and (getattr(self, "d_verify_work", None) is None or self.d_verify_work.numel() < need):
                     self.d_verify_work = torch.empty(need, dtype=torch.uint8, device=dev)
                 work = self.d_verify_work if need else None
-                B.check(L.bgsa_hip_reference_verify_pairs_dev(self.d_reference.data_ptr(), self.ref_len, W, S, a.d_peq.data_ptr(), read_len,
-                                                              a.ns, a.wn, pair_window.data_ptr(), pair_subject.data_ptr(), keys.numel(), 0,
-                                                              distance.data_ptr(), None if work is None else work.data_ptr(),
-                                                              0 if work is None else work.numel(), a._stream()),
+                B.check(verify(self.d_reference.data_ptr(), self.ref_len, W, S, a.d_peq.data_ptr(), *lens_arg, read_len, a.ns, a.wn,
+                               pair_window.data_ptr(), pair_subject.data_ptr(), keys.numel(), 0, distance.data_ptr(),
+                               None if work is None else work.data_ptr(), 0 if work is None else work.numel(), a._stream()),
                         "reference_verify_pairs_dev")
             segments = torch.searchsorted(pair_read, torch.arange(hi - lo + 1, dtype=torch.int64, device=dev)).contiguous()
             B.check(L.bgsa_hip_seed_select_dev(pair_window.data_ptr() if keys.numel() else None, distance.data_ptr() if keys.numel() else None,
@@ -413,6 +439,104 @@ class ReferenceMapper:
                 mine[rest] = theirs
             for at, row in zip(rest.tolist(), full.cigars):
                 out.cigars[at] = row
+        return out
+
+    def map_reads_seeded_ragged(self, reads, k_best: int = 1, max_distance=None, seed_len=None, max_candidates=None,
+                                block_rows: int = 1000, cigar_cap=None) -> ReferenceHits:
+        """map_reads_seeded for reads of MIXED lengths (byte strings or 1-D uint8 arrays, 1..1,024 bp, as map_reads_ragged takes them):
+        exact, and equal to blank_beyond(map_reads_ragged(reads, k_best, max_distance), max_distance) field by field and bit for bit,
+        in the caller's order.  The reads are binned by words (seed_plan_ragged: one seed length per bin); every bin is one bucket
+        whose padded ASCII rows stay on the device, and runs count -> emit -> sort and deduplicate -> verify -> select with every
+        read at its own length (the *_lens_dev calls; a bin of one length launches what map_reads_seeded launches), then the
+        placement map_reads_ragged makes for that bin.  A read with an 'N' in a piece (-1), with more than max_candidates
+        candidates (-2) or too short for its bin's seed and the bound (-3) goes through map_reads_ragged, all of them as one
+        sub-batch.  max_candidates, seed_len and block_rows never change a result.  max_distance is required; the other refusals
+        are map_reads_ragged's own, all made before anything is launched or allocated.  last_seed_stats says what happened."""
+        a = self.aligner
+        torch = a.torch
+        rows, lens = B.pad_ragged(reads)
+        ns, longest = rows.shape
+        if longest > 1024:
+            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-2: reads beyond 1,024 bp have no per-lane form (one length per call: map_reads)")
+        k_best = int(k_best)
+        if not 1 <= k_best <= B.V_NUM:
+            raise B.BgsaHipError(f"map_reads_seeded_ragged: rc=-1: k_best must lie in 1..{B.V_NUM}")
+        if max_distance is None:
+            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: max_distance is required: the seed filter is derived from it "
+                                 "(map_reads_ragged takes max_distance=None)")
+        limit = int(max_distance)
+        if limit < 0:
+            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: max_distance is negative")
+        plan = seed_plan_ragged(lens, limit, seed_len)
+        largest = max_stride(self.window_len, longest, min(limit, longest))
+        if self.stride > largest:
+            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
+            raise B.BgsaHipError(f"map_reads_seeded_ragged: rc=-1: at stride {self.stride} a placement of the longest read ({longest} bp) "
+                                 f"within distance {min(limit, longest)} can lie in no window of {self.window_len} bp: {allowed}")
+        if self.ref_len > INT32_MAX:
+            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: the index holds int32 positions: a reference beyond 2^31 - 1 bases goes "
+                                 "in parts")
+        k_sel = self.k_selected(k_best)
+        cap = self.window_len + longest if cigar_cap is None else int(cigar_cap)
+        if cap < 1:
+            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: cigar_cap is not positive")
+        max_candidates = max(self.n_ids // SEED_CAP_FRACTION, SEED_MIN_CANDIDATES) if max_candidates is None else int(max_candidates)
+        if max_candidates < 0:
+            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: max_candidates is negative")
+
+        scores = np.full((ns, k_sel), INT32_MIN, dtype=np.int32)
+        strand, windows = np.full_like(scores, -1), np.full_like(scores, -1)
+        keep = np.zeros_like(scores)
+        ref_begin, ref_end = np.full((ns, k_sel), -1, dtype=np.int64), np.full((ns, k_sel), -1, dtype=np.int64)
+        cigars = [[None] * k_sel for _ in range(ns)]
+        flags = np.zeros(ns, dtype=np.int32)
+        totals, bins = [0, 0, 0], []
+        for idx, q in plan:
+            mine = lens[idx]
+            width, mixed = int(mine.max()), bool((mine != mine[0]).any())
+            bound = min(limit, width)
+            bins.append(dict(words=(width + 31) // 32, reads=int(idx.size), q=q, emitted=0, unique=0))
+            if not mixed and width // (bound + 1) < q:      # a bin of one length too short for its seed: the C call would refuse it
+                flags[idx] = -3
+                continue
+            padded, a.extra = B.pad_rows(rows[idx, :width])
+            a.ns_real = int(idx.size)
+            d_rows = torch.from_numpy(B.rows_to_buffer(padded)).to(a.device)
+            d_lens = None
+            if mixed:
+                d_lens = torch.from_numpy(np.concatenate([mine, np.full(a.extra, width, dtype=np.int32)]).astype(np.int32)).to(a.device)
+            a.set_subject_rows_device(d_rows, padded.shape[0], width, self.window_len, d_lens=d_lens)
+            if mixed:
+                a.mark_reads_ragged()
+            d_scores, d_ids, d_counts, stats = self.select_seeded(d_rows, int(idx.size), width, bound, q, k_sel, max_candidates, block_rows,
+                                                                  d_lens=d_lens)
+            d_strand, d_begin, d_end, d_keep, d_n_ops, d_cigar = self.place_hits(d_ids, limit, cap, block_rows, ragged=mixed)
+            a.check_faults()
+            flags[idx] = d_counts.cpu().numpy()
+            kept = d_keep.cpu().numpy()
+            scores[idx], strand[idx], keep[idx], windows[idx] = d_scores.cpu().numpy(), d_strand.cpu().numpy(), kept, d_ids.cpu().numpy()
+            ref_begin[idx], ref_end[idx] = d_begin.cpu().numpy(), d_end.cpu().numpy()
+            runs_n, runs = d_n_ops.cpu().numpy(), d_cigar.cpu().numpy().view(np.uint32)
+            for c, r in zip(*np.nonzero(kept)):
+                if runs_n[c, r] > cap:
+                    raise B.BgsaHipError(f"map_reads_seeded_ragged: hit {r} of read {idx[c]} has {runs_n[c, r]} runs, its row holds {cap} "
+                                         "(raise cigar_cap)")
+                cigars[idx[c]][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : runs_n[c, r]].tolist())
+            emitted, unique, within = (int(x.item()) for x in stats)
+            bins[-1].update(emitted=emitted, unique=unique)
+            totals = [totals[0] + emitted, totals[1] + unique, totals[2] + within]
+        out = ReferenceHits(scores, strand, ref_begin, ref_end, keep, cigars, windows)
+        rest = np.flatnonzero(flags < 0)
+        if rest.size:        # the reads the filter does not cover: the exhaustive path, blanked, into the caller's order
+            full = blank_beyond(self.map_reads_ragged([rows[i, : lens[i]] for i in rest], k_best, limit, block_rows, cigar_cap), limit)
+            for field, theirs in zip(out[:5] + (out.windows,), full[:5] + (full.windows,)):
+                field[rest] = theirs
+            for at, row in zip(rest.tolist(), full.cigars):
+                out.cigars[at] = row
+        self.last_seed_stats = dict(reads_seeded=int((flags >= 0).sum()), reads_fallback_n=int((flags == -1).sum()),
+                                    reads_fallback_cap=int((flags == -2).sum()), reads_fallback_short=int((flags == -3).sum()),
+                                    candidates_emitted=totals[0], candidates_unique=totals[1], candidates_within_bound=totals[2],
+                                    seed_len=None if seed_len is None else int(seed_len), max_candidates=max_candidates, bins=bins)
         return out
 
     def map_reads_ragged(self, reads, k_best: int = 1, max_distance=None, block_rows: int = 1000, cigar_cap=None) -> ReferenceHits:

@@ -738,7 +738,23 @@ int bgsa_hip_reference_placements_dev(int64_t ref_len, int window_len, int strid
  * nothing.  BGSA_HIP_EINVAL, checked before the first HIP call: a NULL pointer (the stream, the workspace of a narrow verify and
  * the candidate arrays of an empty select excepted), seed_len outside 1..13, a shape outside 1 <= S <= W <= L, ref_len above
  * INT32_MAX, 2 * n_windows above INT32_MAX, a negative count, step < seed_len, a workspace too small, a word_num that is not
- * ceil(read_len / 32), read_count no positive multiple of 64, k outside 1..64. */
+ * ceil(read_len / 32), read_count no positive multiple of 64, k outside 1..64.
+ * READS OF MIXED LENGTHS IN ONE BUCKET (the three *_lens_dev calls).  d_read_lens: int32, one entry per column of the bucket,
+ * padding columns included, with the rules of bgsa_hip_myers_place_score_lens_dev: a length is clamped to [0, read_len] and
+ * clamped again wherever it forms an index; NULL is BGSA_HIP_EINVAL.  read_len is the bucket's width: d_reads are rows of stride
+ * read_len + 1 and d_peq is what bgsa_hip_handle_reads_dev built at read_len.
+ * bgsa_hip_seed_count_candidates_lens_dev / _emit_candidates_lens_dev: read r is its row's first n_r = d_read_lens[r] characters,
+ * with B_r = min(max_distance, n_r) and step_r = n_r / (B_r + 1); its pieces start at j * step_r, j = 0 .. B_r, and are seed_len
+ * long; the four candidate inequalities above hold with n_r and B_r.  Flag -3: step_r < seed_len, or n_r == 0 — the read is too
+ * short for this seed and bound, and nothing of its row is read.  The whole-call refusal of step < seed_len does not apply: the
+ * flag replaces it.  -1 looks only at the pieces, which lie inside n_r: the pad behind a read's end never flags it.  -2 as above.
+ * Emit skips every negative count.
+ * bgsa_hip_reference_verify_pairs_lens_dev: lane p verifies column c = d_pair_subject[p] - subject_base at n = d_read_lens[c]:
+ * d_distance[p] = the Myers semi-global distance of the read's first n characters inside the window, bit for bit minus the score
+ * bgsa_hip_myers_place_score_lens_dev writes for that (window, column); n == 0 gives 0.  What the columns above n hold never
+ * enters a result.  Workspace, chunking, ownership and the "no window" rule are those of bgsa_hip_reference_verify_pairs_dev;
+ * any lengths may share a bucket, at every width up to 32 words.  bgsa_hip_seed_select_dev needs no per-read form: a semi-global
+ * distance never exceeds n_r. */
 int64_t bgsa_hip_seed_index_offsets(int seed_len);
 size_t bgsa_hip_seed_index_workspace_bytes(int64_t ref_len, int seed_len);
 int bgsa_hip_seed_index_build_dev(const char *d_reference, int64_t ref_len, int seed_len, int32_t *d_offsets, int32_t *d_positions,
@@ -755,6 +771,20 @@ int bgsa_hip_reference_verify_pairs_dev(const char *d_reference, int64_t ref_len
                                         int read_len, int64_t read_count, int word_num, const int32_t *d_pair_window,
                                         const int64_t *d_pair_subject, int64_t n_pairs, int64_t subject_base, int32_t *d_distance,
                                         void *d_workspace, size_t workspace_bytes, void *stream);
+int bgsa_hip_seed_count_candidates_lens_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_offsets,
+                                            const int32_t *d_positions, int seed_len, const char *d_reads, const int32_t *d_read_lens,
+                                            int read_len, int64_t n_reads, int max_distance, int both_strands, int64_t max_candidates,
+                                            int32_t *d_counts, void *stream);
+int bgsa_hip_seed_emit_candidates_lens_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_offsets,
+                                           const int32_t *d_positions, int seed_len, const char *d_reads, const int32_t *d_read_lens,
+                                           int read_len, int64_t n_reads, int max_distance, int both_strands, const int32_t *d_counts,
+                                           const int64_t *d_prefix, int64_t read_base, int32_t *d_cand_read, int32_t *d_cand_window,
+                                           void *stream);
+int bgsa_hip_reference_verify_pairs_lens_dev(const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,
+                                             const int32_t *d_read_lens, int read_len, int64_t read_count, int word_num,
+                                             const int32_t *d_pair_window, const int64_t *d_pair_subject, int64_t n_pairs,
+                                             int64_t subject_base, int32_t *d_distance, void *d_workspace, size_t workspace_bytes,
+                                             void *stream);
 int bgsa_hip_seed_select_dev(const int32_t *d_cand_window, const int32_t *d_cand_distance, const int64_t *d_segments, int64_t n_reads,
                              int max_distance, int k, int32_t *d_hit_scores, int32_t *d_hit_windows, void *stream);
 
