@@ -369,15 +369,28 @@ class DeviceAligner:
                                f"least nq * (qlen + 1) + 8 = {nq * (qlen + 1) + 8} bytes")
         self.nq, self.qlen, self.d_content = nq, qlen, d_content
 
+    def _set_bucket(self, rows: np.ndarray, lens=None, qlen: int | None = None, reads_ragged: bool = False):
+        """The one upload of a subject bucket: rows [n, slen] uint8 ASCII, padded here to a multiple of 64 with 'N' reads (extra,
+        ns_real), packed as a row buffer, uploaded and preprocessed (set_subject_rows_device).  lens: None, or the n rows' own
+        lengths (a mixed-length bucket; the pad columns get slen); reads_ragged marks such a bucket as one of set_reads_ragged.
+        Returns (the device row buffer — ASCII, ns rows of slen + 1 bytes —, the device lengths or None): the aligner keeps the
+        lengths and drops the rows, a caller that reads them again (ReferenceMapper's seed filter) keeps them."""
+        torch = self.torch
+        s, self.extra = pad_rows(rows)
+        self.ns_real = rows.shape[0]
+        d_rows = torch.from_numpy(rows_to_buffer(s)).to(self.device)
+        d_lens = None
+        if lens is not None:
+            lens = np.concatenate([np.asarray(lens, dtype=np.int32), np.full(self.extra, s.shape[1], dtype=np.int32)])
+            d_lens = torch.from_numpy(lens).to(self.device)
+        self.set_subject_rows_device(d_rows, s.shape[0], s.shape[1], qlen, d_lens=d_lens)
+        if reads_ragged:
+            self.mark_reads_ragged()
+        return d_rows, d_lens
+
     def set_subjects(self, subjects: np.ndarray, qlen: int | None = None) -> None:
         """subjects: [ns, slen] uint8 ASCII (padded here to a multiple of 64 with 'N' reads)."""
-        torch = self.torch
-        s, self.extra = pad_rows(subjects)
-        self.ns_real = subjects.shape[0]
-        self.ns, self.slen = s.shape
-        buf = rows_to_buffer(s)
-        d_rows = torch.from_numpy(buf).to(self.device)
-        self.set_subject_rows_device(d_rows, self.ns, self.slen, qlen)
+        self._set_bucket(subjects, qlen=qlen)
 
     def set_subjects_ragged(self, subjects, qlen: int | None = None) -> None:
         """subjects: byte strings or 1-D uint8 arrays of MIXED lengths, as one bucket of the longest one's width (pad_ragged, then
@@ -388,15 +401,10 @@ class DeviceAligner:
         call.  The certified Myers band is off for such a bucket (full rows).  If all lengths are equal this IS set_subjects: no
         lengths are passed and the band stays available.  Queries keep one length per aligner: group queries by length.  To keep a
         short read from being scored at the width of the longest, bin the subjects first (bin_by_words, align_all_pairs_ragged)."""
-        torch = self.torch
         rows, lens = pad_ragged(subjects)
         if (lens == lens[0]).all():
             return self.set_subjects(rows, qlen)
-        s, self.extra = pad_rows(rows)
-        self.ns_real = rows.shape[0]
-        lens = np.concatenate([lens, np.full(self.extra, rows.shape[1], dtype=np.int32)])
-        d_rows = torch.from_numpy(rows_to_buffer(s)).to(self.device)
-        self.set_subject_rows_device(d_rows, s.shape[0], s.shape[1], qlen, d_lens=torch.from_numpy(lens).to(self.device))
+        self._set_bucket(rows, lens, qlen)
 
     def _reads_ragged_refusals(self, what: str) -> None:
         if self.algo != ALGO_MYERS or not self.semi_global or self.scores == (0, 1, 1):
@@ -412,7 +420,6 @@ class DeviceAligner:
         semi_global=True and not +distance: anything else raises rc=-2 before anything is allocated.  If all lengths are equal this
         IS set_subjects.  place_pairs_banded keeps refusing a mixed-length bucket.  To keep a short read from being scored at the
         width of the longest, bin the reads first (bin_by_words; ReferenceMapper.map_reads_ragged does)."""
-        torch = self.torch
         self._reads_ragged_refusals("set_reads_ragged")
         rows, lens = pad_ragged(reads)
         if (lens == lens[0]).all():
@@ -420,12 +427,7 @@ class DeviceAligner:
         if rows.shape[1] > 1024:
             raise BgsaHipError("set_reads_ragged: rc=-2: reads beyond 1,024 bp (word_num > 32) run as column blocks, which have no "
                                "per-lane form")
-        s, self.extra = pad_rows(rows)
-        self.ns_real = rows.shape[0]
-        lens = np.concatenate([lens, np.full(self.extra, rows.shape[1], dtype=np.int32)])
-        d_rows = torch.from_numpy(rows_to_buffer(s)).to(self.device)
-        self.set_subject_rows_device(d_rows, s.shape[0], s.shape[1], qlen, d_lens=torch.from_numpy(lens).to(self.device))
-        self.mark_reads_ragged()
+        self._set_bucket(rows, lens, qlen, reads_ragged=True)
 
     def mark_reads_ragged(self) -> None:
         """Marks the bucket set_subject_rows_device(..., d_lens=) has just set as one of set_reads_ragged: its lengths are reads' own

@@ -4,6 +4,11 @@ reference coordinates (include/bgsa_hip.h "a reference as the query set"; INTEGR
 The geometry is stated once in the header and restated here (window_plan, max_stride): L mapped bytes, 1 <= S <= W <= L,
 n_windows = 1 + ceil((L - W) / S), start(w) = min(w * S, L - W); forward window w has id w, its reverse complement id
 n_windows + w.
+
+ONE pipeline maps reads, behind four entry points: check_call refuses, a plan names the bins [(indices, seed length or None)],
+ReferenceMapper._map_bins runs every bin as one bucket (_map_bucket: upload, select_windows or select_seeded, place_hits) and
+scatters it into the caller's order (decode_cigars), and the seeded entry points send the reads their filter does not cover through
+the exhaustive entry point of the same kind (merge_fallback, seed_stats).  The helpers at module level need no device.
 """
 from __future__ import annotations
 
@@ -116,6 +121,104 @@ class Placement(NamedTuple):
     cigar: str
 
 
+# ---- the host side of the four map_reads entry points: no device, no library ---------------------------------------------------
+def check_call(who: str, longest: int, ragged: bool, k_best, max_distance, seeded: bool, cigar_cap, max_candidates,
+               window_len: int, stride: int, ref_len: int, n_ids: int, limit_1024: bool, plan=None) -> tuple:
+    """Every refusal of the map_reads entry point `who`, in one order: the 1,024 bp limit (limit_1024: every entry point but
+    map_reads), k_best, max_distance (seeded: required), the seed plan (plan(max_distance), a call that raises or returns what the
+    caller needs: seed_plan or seed_plan_ragged), the stride rule for the longest read, and for a seeded call the int32 index, then
+    cigar_cap and max_candidates.  ragged picks the wording for a list of mixed lengths.  Returns (k_best, bound, cap,
+    max_candidates, plan's result): bound = min(max_distance, longest), 0 for max_distance=None; cap = window_len + longest unless
+    cigar_cap says otherwise; max_candidates None unless seeded, its default max(n_ids // 8, 256).  Nothing is launched or
+    allocated here, so a refused call leaves the mapper as it was."""
+    longest = int(longest)
+    if limit_1024 and longest > 1024:
+        why = "have no per-lane form (one length per call: map_reads)" if ragged else "have no verify kernel (map_reads takes them)"
+        raise B.BgsaHipError(f"{who}: rc=-2: reads beyond 1,024 bp {why}")
+    k_best = int(k_best)
+    if not 1 <= k_best <= B.V_NUM:
+        raise B.BgsaHipError(f"{who}: rc=-1: k_best must lie in 1..{B.V_NUM}")
+    if seeded and max_distance is None:
+        raise B.BgsaHipError(f"{who}: rc=-1: max_distance is required: the seed filter is derived from it "
+                             f"({who.replace('_seeded', '')} takes max_distance=None)")
+    if max_distance is not None and int(max_distance) < 0:
+        raise B.BgsaHipError(f"{who}: rc=-1: max_distance is negative")
+    planned = None if plan is None else plan(int(max_distance))
+    bound = 0 if max_distance is None else min(int(max_distance), longest)
+    largest = max_stride(window_len, longest, bound)
+    if stride > largest:
+        allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
+        read = f"the longest read ({longest} bp)" if ragged else f"a {longest} bp read"
+        raise B.BgsaHipError(f"{who}: rc=-1: at stride {stride} a placement of {read} within distance {bound} can lie in no window of "
+                             f"{window_len} bp: {allowed}")
+    if seeded and ref_len > INT32_MAX:
+        raise B.BgsaHipError(f"{who}: rc=-1: the index holds int32 positions: a reference beyond 2^31 - 1 bases goes in parts")
+    cap = window_len + longest if cigar_cap is None else int(cigar_cap)
+    if cap < 1:
+        raise B.BgsaHipError(f"{who}: rc=-1: cigar_cap is not positive")
+    if seeded:
+        max_candidates = max(n_ids // SEED_CAP_FRACTION, SEED_MIN_CANDIDATES) if max_candidates is None else int(max_candidates)
+        if max_candidates < 0:
+            raise B.BgsaHipError(f"{who}: rc=-1: max_candidates is negative")
+    return k_best, bound, cap, (max_candidates if seeded else None), planned
+
+
+def hit_arrays(hits: ReferenceHits) -> tuple:
+    """The six arrays of a result, cigars left out: scores, strand, ref_begin, ref_end, keep, windows."""
+    return hits[:5] + (hits.windows,)
+
+
+def decode_cigars(who: str, keep, n_ops, runs, cap: int, idx, cigars: list) -> None:
+    """The edit scripts of one bin into the caller's order: keep and n_ops [n, k_sel], runs [n, k_sel, cap] uint32 (length << 4 | op)
+    are the host copies of what place_hits returns for the bin, idx[c] is where the bin's read c stands in the caller's order.
+    cigars[idx[c]][r] becomes the string of every kept slot; the others are left as they are (None).  A kept hit with more runs
+    than its row holds raises, naming that read in the caller's order."""
+    at = np.asarray(idx).tolist()
+    kept = np.nonzero(keep)
+    for c, r, n in zip(kept[0].tolist(), kept[1].tolist(), n_ops[kept].tolist()):
+        if n > cap:
+            raise B.BgsaHipError(f"{who}: hit {r} of read {at[c]} has {n} runs, its row holds {cap} (raise cigar_cap)")
+        cigars[at[c]][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, :n].tolist())
+
+
+def merge_fallback(out: ReferenceHits, rest, full: ReferenceHits) -> None:
+    """Row i of `full` — the exhaustive result, blanked, of the reads the seed filter does not cover — into row rest[i] of `out`:
+    the six arrays and the cigar rows.  Nothing else of `out` changes."""
+    for mine, theirs in zip(hit_arrays(out), hit_arrays(full)):
+        mine[rest] = theirs
+    for at, row in zip(np.asarray(rest).tolist(), full.cigars):
+        out.cigars[at] = row
+
+
+def seed_stats(flags, totals, seed_len, max_candidates: int, bins=None) -> dict:
+    """last_seed_stats from the reads' flags (a candidate count, or -1 an 'N' in a piece, -2 above max_candidates, -3 too short for
+    the seed) and the totals (emitted, unique, within the bound).  bins (map_reads_seeded_ragged: one dict per bin) adds the keys
+    reads_fallback_short and bins; without it the dict is map_reads_seeded's."""
+    flags = np.asarray(flags)
+    stats = dict(reads_seeded=int((flags >= 0).sum()), reads_fallback_n=int((flags == -1).sum()),
+                 reads_fallback_cap=int((flags == -2).sum()))
+    if bins is not None:
+        stats["reads_fallback_short"] = int((flags == -3).sum())
+    stats.update(candidates_emitted=int(totals[0]), candidates_unique=int(totals[1]), candidates_within_bound=int(totals[2]),
+                 seed_len=seed_len, max_candidates=max_candidates)
+    if bins is not None:
+        stats["bins"] = bins
+    return stats
+
+
+class SeedBucket(NamedTuple):
+    """What the steps of select_seeded share for one resident bucket (ReferenceMapper.seed_bucket)."""
+    d_rows: object          # the bucket's ASCII rows on the device, read_len + 1 bytes each
+    read_len: int           # the rows' width
+    bound: int
+    shape: tuple            # the leading arguments of the candidate calls: the geometry, the index, the seed length
+    count: object           # the three C calls: the equal-length ones, or the *_lens_dev ones
+    emit: object
+    verify: object
+    lens_of: object         # lens_of(lo, hi): the extra argument of count and emit for the reads [lo, hi): () or (pointer,)
+    lens_all: tuple         # the extra argument of verify: () or (the bucket's lengths,)
+
+
 class ReferenceMapper:
     """One reference, resident on the device as mapped codes, and a Myers semi-global aligner over its windows.
 
@@ -155,6 +258,7 @@ class ReferenceMapper:
         B.check(B.lib().bgsa_hip_map_queries_dev(self.d_reference.data_ptr(), self.ref_len, a._stream()), "map_queries")
         self.d_rows = None      # the query rows of one segment / of one block's hit windows, grown on demand
         self.seed_indexes = {}  # seed_len -> (offsets, positions) device tensors (map_reads_seeded builds them on first use)
+        self.d_verify_work = None   # the carries of a verify beyond 16 words, grown on demand
         self.last_seed_stats = None
 
     def _rows_buffer(self, n_rows: int):
@@ -232,6 +336,84 @@ class ReferenceMapper:
                                                         keep[lo:hi].data_ptr(), a._stream()), "reference_placements_dev")
         return strand, ref_begin, ref_end, keep, n_ops, cigar
 
+    # ---- the one pipeline behind map_reads, map_reads_ragged, map_reads_seeded and map_reads_seeded_ragged ----------------------
+    def _check(self, who: str, longest: int, ragged: bool, k_best, max_distance, cigar_cap, seeded: bool = False, max_candidates=None,
+               plan=None) -> tuple:
+        """check_call with this mapper's geometry; map_reads alone takes reads beyond 1,024 bp."""
+        return check_call(who, longest, ragged, k_best, max_distance, seeded, cigar_cap, max_candidates, self.window_len, self.stride,
+                          self.ref_len, self.n_ids, who != "map_reads", plan)
+
+    @staticmethod
+    def _one_length(who: str, reads) -> np.ndarray:
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        if reads.ndim != 2 or reads.shape[0] < 1 or reads.shape[1] < 1:
+            raise B.BgsaHipError(f"{who}: rc=-1: reads must be [ns, n] with ns, n >= 1 (one read length per call)")
+        return reads
+
+    def _map_bucket(self, rows: np.ndarray, lens, k_sel: int, limit, cap: int, block_rows: int, seed=None) -> tuple:
+        """One bucket through the pipeline: rows [n, width] ASCII and lens (the reads' own lengths, or None where all are width
+        long) are uploaded (DeviceAligner._set_bucket), the k_sel best windows of every read selected — seed None: select_windows
+        over every window; seed (q, max_candidates): select_seeded within min(limit, width) —, placed within limit (place_hits, per
+        read where lens is given) and the stream checked for faults.  limit None (exhaustive only): no bound where lens is given,
+        else the worst selected distance, one scalar read back.  Returns host arrays: (the six of hit_arrays, n_ops, runs as uint32,
+        the reads' seed flags, (emitted, unique, within the bound)); the last two None without a seed."""
+        a = self.aligner
+        torch = a.torch
+        d_rows, d_lens = a._set_bucket(rows, lens, qlen=self.window_len, reads_ragged=lens is not None)
+        flags = totals = None
+        if seed is None:
+            d_rows = None      # only the seed filter reads the ASCII rows again
+            scores, ids = self.select_windows(k_sel, block_rows)
+            if limit is None and lens is None:
+                limit = -int(torch.where(ids >= 0, scores, torch.zeros_like(scores)).min().item())
+        else:
+            scores, ids, counts, stats = self.select_seeded(d_rows, rows.shape[0], rows.shape[1], min(limit, rows.shape[1]), seed[0], k_sel,
+                                                            seed[1], block_rows, d_lens=d_lens)
+        strand, ref_begin, ref_end, keep, n_ops, cigar = self.place_hits(ids, limit, cap, block_rows, ragged=lens is not None)
+        a.check_faults()
+        if seed is not None:
+            flags, totals = counts.cpu().numpy(), tuple(int(x.item()) for x in stats)
+        arrays = tuple(x.cpu().numpy() for x in (scores, strand, ref_begin, ref_end, keep, ids))
+        return arrays, n_ops.cpu().numpy(), cigar.cpu().numpy().view(np.uint32), flags, totals
+
+    def _map_bins(self, who: str, rows: np.ndarray, lens: np.ndarray, plan, k_sel: int, limit, cap: int, block_rows: int,
+                  max_candidates=None) -> tuple:
+        """The bins of `plan` — [(indices into rows, seed length or None for the exhaustive path)] —, each as one bucket of its own
+        width through _map_bucket, scattered into the caller's order.  A bin of one length goes without lengths and launches the
+        equal-length kernels; a seeded one too short for its seed and the bound is flagged -3 here, without a call.  Returns
+        (hits, flags[ns], [emitted, unique, within], bins: one dict per bin for last_seed_stats)."""
+        ns = rows.shape[0]
+        blank = np.full((ns, k_sel), -1, dtype=np.int32)
+        out = ReferenceHits(np.full((ns, k_sel), INT32_MIN, dtype=np.int32), blank, np.full((ns, k_sel), -1, dtype=np.int64),
+                            np.full((ns, k_sel), -1, dtype=np.int64), np.zeros((ns, k_sel), dtype=np.int32),
+                            [[None] * k_sel for _ in range(ns)], blank.copy())
+        flags, totals, bins = np.zeros(ns, dtype=np.int32), [0, 0, 0], []
+        for idx, q in plan:
+            mine = lens[idx]
+            width, mixed = int(mine.max()), bool((mine != mine[0]).any())
+            bins.append(dict(words=(width + 31) // 32, reads=int(idx.size), q=q, emitted=0, unique=0))
+            if q is not None and not mixed and width // (min(limit, width) + 1) < q:      # the C call would refuse the bucket
+                flags[idx] = -3
+                continue
+            bucket = rows[:, :width] if idx.size == ns else rows[idx, :width]      # one bin of all reads: no copy
+            arrays, n_ops, runs, seen, stats = self._map_bucket(bucket, mine if mixed else None, k_sel, limit, cap, block_rows,
+                                                                None if q is None else (q, max_candidates))
+            for field, theirs in zip(hit_arrays(out), arrays):
+                field[idx] = theirs
+            decode_cigars(who, arrays[4], n_ops, runs, cap, idx, out.cigars)
+            if q is not None:
+                flags[idx] = seen
+                bins[-1].update(emitted=stats[0], unique=stats[1])
+                totals = [t + s for t, s in zip(totals, stats)]
+        return out, flags, totals, bins
+
+    def _map_uncovered(self, out: ReferenceHits, flags, exhaustive, bound: int) -> None:
+        """The reads the seed filter does not cover (a negative flag): one sub-batch through `exhaustive` (rest -> ReferenceHits),
+        blanked beyond bound, into the caller's order."""
+        rest = np.flatnonzero(flags < 0)
+        if rest.size:
+            merge_fallback(out, rest, blank_beyond(exhaustive(rest), bound))
+
     def map_reads(self, reads: np.ndarray, k_best: int = 1, max_distance=None, block_rows: int = 1000, cigar_cap=None) -> ReferenceHits:
         """reads: [ns, n] uint8 ASCII, one length.  Selects every read's k_sel = k_selected(k_best) best windows over both
         strands (top_queries, segment by segment: the number of segments never changes a result), places the read inside
@@ -242,45 +424,12 @@ class ReferenceMapper:
         an exact placement is sure of a window — is refused before anything is launched: some placement within the bound would
         lie in no window, and the best window's distance would not be the reference's optimum.
         cigar_cap=None: window_len + n runs per hit, which cannot overflow (4 bytes each: pass a smaller cap for many reads)."""
-        a = self.aligner
-        torch = a.torch
-        reads = np.ascontiguousarray(reads, dtype=np.uint8)
-        if reads.ndim != 2 or reads.shape[0] < 1 or reads.shape[1] < 1:
-            raise B.BgsaHipError("map_reads: rc=-1: reads must be [ns, n] with ns, n >= 1 (one read length per call)")
+        reads = self._one_length("map_reads", reads)
         ns, n = reads.shape
-        k_best = int(k_best)
-        if not 1 <= k_best <= B.V_NUM:
-            raise B.BgsaHipError(f"map_reads: rc=-1: k_best must lie in 1..{B.V_NUM}")
-        if max_distance is not None and int(max_distance) < 0:
-            raise B.BgsaHipError("map_reads: rc=-1: max_distance is negative")
-        bound = 0 if max_distance is None else min(int(max_distance), n)
-        largest = max_stride(self.window_len, n, bound)
-        if self.stride > largest:
-            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
-            raise B.BgsaHipError(f"map_reads: rc=-1: at stride {self.stride} a placement of a {n} bp read within distance {bound} can lie in "
-                                 f"no window of {self.window_len} bp: {allowed}")
-        k_sel = self.k_selected(k_best)
-        W = self.window_len
-        cap = W + n if cigar_cap is None else int(cigar_cap)
-        if cap < 1:
-            raise B.BgsaHipError("map_reads: rc=-1: cigar_cap is not positive")
-
-        a.set_subjects(reads, qlen=W)
-        scores, ids = self.select_windows(k_sel, block_rows)
-        if max_distance is None:
-            max_distance = -int(torch.where(ids >= 0, scores, torch.zeros_like(scores)).min().item())
-        strand, ref_begin, ref_end, keep, n_ops, cigar = self.place_hits(ids, int(max_distance), cap, block_rows)
-        a.check_faults()
-
-        kept = keep.cpu().numpy()
-        counts, runs = n_ops.cpu().numpy(), cigar.cpu().numpy().view(np.uint32)
-        cigars = [[None] * k_sel for _ in range(ns)]
-        for c, r in zip(*np.nonzero(kept)):
-            if counts[c, r] > cap:
-                raise B.BgsaHipError(f"map_reads: hit {r} of read {c} has {counts[c, r]} runs, its row holds {cap} (raise cigar_cap)")
-            cigars[c][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : counts[c, r]].tolist())
-        return ReferenceHits(scores.cpu().numpy(), strand.cpu().numpy(), ref_begin.cpu().numpy(), ref_end.cpu().numpy(), kept, cigars,
-                             ids.cpu().numpy())
+        k_best, _, cap, _, _ = self._check("map_reads", n, False, k_best, max_distance, cigar_cap)
+        limit = None if max_distance is None else int(max_distance)
+        plan = [(np.arange(ns), None)]      # one bin of the whole batch
+        return self._map_bins("map_reads", reads, np.full(ns, n, dtype=np.int32), plan, self.k_selected(k_best), limit, cap, block_rows)[0]
 
     # ---- seeded mapping: include/bgsa_hip.h "seeded read mapping" -----------------------------------------------------------
     def seed_index(self, seed_len: int):
@@ -302,6 +451,77 @@ class ReferenceMapper:
             self.seed_indexes[q] = (offsets, positions)
         return self.seed_indexes[q]
 
+    # The steps of select_seeded, for the reads [lo, hi) of one resident bucket: seed_bucket once, then seed_candidates ->
+    # seed_dedupe -> seed_verify -> seed_select per block.  scripts/measure_seeded_*.py time these same methods.
+    def seed_bucket(self, d_rows, read_len: int, bound: int, seed_len: int, d_lens=None) -> SeedBucket:
+        """What the four steps share: the index of seed_len (built on first use) and the C calls — d_lens None: the equal-length
+        ones; d_lens (the bucket's int32 lengths, one per column): the *_lens_dev ones, every read at its own length.  The
+        aligner holds the bucket; d_rows are its ASCII rows on the device, read_len + 1 bytes each."""
+        L = B.lib()
+        offsets, positions = self.seed_index(seed_len)
+        shape = (self.ref_len, self.window_len, self.stride, offsets.data_ptr(), positions.data_ptr(), int(seed_len))
+        if d_lens is None:
+            return SeedBucket(d_rows, int(read_len), int(bound), shape, L.bgsa_hip_seed_count_candidates_dev, L.bgsa_hip_seed_emit_candidates_dev,
+                              L.bgsa_hip_reference_verify_pairs_dev, lambda lo, hi: (), ())
+        return SeedBucket(d_rows, int(read_len), int(bound), shape, L.bgsa_hip_seed_count_candidates_lens_dev,
+                          L.bgsa_hip_seed_emit_candidates_lens_dev, L.bgsa_hip_reference_verify_pairs_lens_dev,
+                          lambda lo, hi: (d_lens[lo:hi].data_ptr(),), (d_lens.data_ptr(),))
+
+    def seed_candidates(self, job: SeedBucket, lo: int, hi: int, max_candidates: int, counts):
+        """Step 1: count (counts[lo:hi] filled: the candidates of every read, or its flag -1 / -2 / -3), an exclusive scan with its
+        one scalar read back — it sizes the lists —, emit.  Returns (cand_read int32[total]: the read's index in the block,
+        cand_window int32[total]), copies of one pair among them."""
+        a = self.aligner
+        torch, dev = a.torch, a.device
+        reads = (job.d_rows.data_ptr() + lo * (job.read_len + 1), *job.lens_of(lo, hi), job.read_len, hi - lo, job.bound, int(self.both_strands))
+        B.check(job.count(*job.shape, *reads, int(max_candidates), counts[lo:hi].data_ptr(), a._stream()), "seed_count_candidates_dev")
+        ends = counts[lo:hi].clamp(min=0).to(torch.int64).cumsum(0)
+        total = int(ends[-1].item())                    # the one scalar read back per block: it sizes the candidate arrays
+        prefix = (ends - counts[lo:hi].clamp(min=0)).contiguous()
+        cand_read = torch.empty(total, dtype=torch.int32, device=dev)
+        cand_window = torch.empty(total, dtype=torch.int32, device=dev)
+        if total:
+            B.check(job.emit(*job.shape, *reads, counts[lo:hi].data_ptr(), prefix.data_ptr(), 0, cand_read.data_ptr(), cand_window.data_ptr(),
+                             a._stream()), "seed_emit_candidates_dev")
+        return cand_read, cand_window
+
+    def seed_dedupe(self, cand_read, cand_window):
+        """Step 2: the candidates sorted by (read, window id), every pair once (torch.unique).  Returns (pair_read int64[n],
+        pair_window int32[n])."""
+        n_ids2 = 2 * self.n_windows
+        keys = self.aligner.torch.unique(cand_read.to(self.aligner.torch.int64) * n_ids2 + cand_window)
+        pair_read = keys // n_ids2
+        return pair_read, (keys - pair_read * n_ids2).to(self.aligner.torch.int32)
+
+    def seed_verify(self, job: SeedBucket, lo: int, pair_read, pair_window):
+        """Step 3: the exact distance of every pair's read (pair_read + lo in the bucket) inside its window, int32[n]."""
+        a, L = self.aligner, B.lib()
+        torch, dev = a.torch, a.device
+        n_pairs = pair_read.numel()
+        distance = torch.full((n_pairs,), -1, dtype=torch.int32, device=dev)
+        pair_subject = pair_read + lo
+        if n_pairs:
+            need = int(L.bgsa_hip_reference_verify_workspace_bytes(self.window_len, job.read_len, n_pairs))
+            if need and (self.d_verify_work is None or self.d_verify_work.numel() < need):
+                self.d_verify_work = torch.empty(need, dtype=torch.uint8, device=dev)
+            work = self.d_verify_work if need else None
+            B.check(job.verify(self.d_reference.data_ptr(), self.ref_len, self.window_len, self.stride, a.d_peq.data_ptr(), *job.lens_all,
+                               job.read_len, a.ns, a.wn, pair_window.data_ptr(), pair_subject.data_ptr(), n_pairs, 0, distance.data_ptr(),
+                               None if work is None else work.data_ptr(), 0 if work is None else work.numel(), a._stream()),
+                    "reference_verify_pairs_dev")
+        return distance
+
+    def seed_select(self, job: SeedBucket, lo: int, hi: int, pair_read, pair_window, distance, k_sel: int, scores, ids) -> None:
+        """Step 4: every read's k_sel best candidates within the bound into scores[lo:hi] and ids[lo:hi], the reads' segments of
+        the pair list found by searchsorted."""
+        a = self.aligner
+        torch = a.torch
+        n_pairs = pair_read.numel()
+        segments = torch.searchsorted(pair_read, torch.arange(hi - lo + 1, dtype=torch.int64, device=a.device)).contiguous()
+        B.check(B.lib().bgsa_hip_seed_select_dev(pair_window.data_ptr() if n_pairs else None, distance.data_ptr() if n_pairs else None,
+                                                 segments.data_ptr(), hi - lo, job.bound, k_sel, scores[lo:hi].data_ptr(), ids[lo:hi].data_ptr(),
+                                                 a._stream()), "seed_select_dev")
+
     def select_seeded(self, d_rows, n_reads: int, read_len: int, bound: int, seed_len: int, k_sel: int, max_candidates: int,
                       block_rows: int = 1000, d_lens=None):
         """The device half of map_reads_seeded's selection, for the reads the aligner holds AND whose ASCII rows d_rows (stride
@@ -312,56 +532,22 @@ class ReferenceMapper:
         d_lens (the bucket's int32 lengths, one per column; map_reads_seeded_ragged): read_len is the rows' width, every read is
         counted, emitted and verified at its own length by the *_lens_dev calls, and a read too short for seed_len is flagged -3.
         d_lens=None launches exactly the equal-length calls."""
-        a, L = self.aligner, B.lib()
-        torch, dev, W, S = a.torch, a.device, self.window_len, self.stride
-        offsets, positions = self.seed_index(seed_len)
-        n_ids2 = 2 * self.n_windows
+        torch, dev = self.aligner.torch, self.aligner.device
+        job = self.seed_bucket(d_rows, read_len, bound, seed_len, d_lens)
         scores = torch.empty((n_reads, k_sel), dtype=torch.int32, device=dev)
         ids = torch.empty((n_reads, k_sel), dtype=torch.int32, device=dev)
         counts = torch.empty(n_reads, dtype=torch.int32, device=dev)
         emitted = torch.zeros((), dtype=torch.int64, device=dev)
         unique, within = torch.zeros_like(emitted), torch.zeros_like(emitted)
-        shape = (self.ref_len, W, S, offsets.data_ptr(), positions.data_ptr(), int(seed_len))
         block = max(1, min(int(block_rows), n_reads))
         for lo in range(0, n_reads, block):
             hi = min(lo + block, n_reads)
-            rows = d_rows.data_ptr() + lo * (read_len + 1)
-            reads = (rows, read_len, hi - lo, bound, int(self.both_strands))
-            count, emit, verify, lens_arg = L.bgsa_hip_seed_count_candidates_dev, L.bgsa_hip_seed_emit_candidates_dev, \
-                L.bgsa_hip_reference_verify_pairs_dev, ()
-            if d_lens is not None:
-                reads = (rows, d_lens[lo:hi].data_ptr()) + reads[1:]
-                count, emit, verify, lens_arg = L.bgsa_hip_seed_count_candidates_lens_dev, L.bgsa_hip_seed_emit_candidates_lens_dev, \
-                    L.bgsa_hip_reference_verify_pairs_lens_dev, (d_lens.data_ptr(),)
-            B.check(count(*shape, *reads, int(max_candidates), counts[lo:hi].data_ptr(), a._stream()), "seed_count_candidates_dev")
-            ends = counts[lo:hi].clamp(min=0).to(torch.int64).cumsum(0)
-            total = int(ends[-1].item())                    # the one scalar read back per block: it sizes the candidate arrays
-            prefix = (ends - counts[lo:hi].clamp(min=0)).contiguous()
-            cand_read = torch.empty(total, dtype=torch.int32, device=dev)
-            cand_window = torch.empty(total, dtype=torch.int32, device=dev)
-            if total:
-                B.check(emit(*shape, *reads, counts[lo:hi].data_ptr(), prefix.data_ptr(), 0, cand_read.data_ptr(), cand_window.data_ptr(),
-                             a._stream()), "seed_emit_candidates_dev")
-            keys = torch.unique(cand_read.to(torch.int64) * n_ids2 + cand_window)      # sorted by (read, id), every pair once
-            pair_read = keys // n_ids2
-            pair_window = (keys - pair_read * n_ids2).to(torch.int32)
-            distance = torch.full((keys.numel(),), -1, dtype=torch.int32, device=dev)
-            pair_subject = pair_read + lo
-            if keys.numel():
-                need = int(L.bgsa_hip_reference_verify_workspace_bytes(W, read_len, keys.numel()))
-                if need and (getattr(self, "d_verify_work", None) is None or self.d_verify_work.numel() < need):
-                    self.d_verify_work = torch.empty(need, dtype=torch.uint8, device=dev)
-                work = self.d_verify_work if need else None
-                B.check(verify(self.d_reference.data_ptr(), self.ref_len, W, S, a.d_peq.data_ptr(), *lens_arg, read_len, a.ns, a.wn,
-                               pair_window.data_ptr(), pair_subject.data_ptr(), keys.numel(), 0, distance.data_ptr(),
-                               None if work is None else work.data_ptr(), 0 if work is None else work.numel(), a._stream()),
-                        "reference_verify_pairs_dev")
-            segments = torch.searchsorted(pair_read, torch.arange(hi - lo + 1, dtype=torch.int64, device=dev)).contiguous()
-            B.check(L.bgsa_hip_seed_select_dev(pair_window.data_ptr() if keys.numel() else None, distance.data_ptr() if keys.numel() else None,
-                                               segments.data_ptr(), hi - lo, bound, k_sel, scores[lo:hi].data_ptr(), ids[lo:hi].data_ptr(),
-                                               a._stream()), "seed_select_dev")
-            emitted += total
-            unique += keys.numel()
+            cand_read, cand_window = self.seed_candidates(job, lo, hi, max_candidates, counts)
+            pair_read, pair_window = self.seed_dedupe(cand_read, cand_window)
+            distance = self.seed_verify(job, lo, pair_read, pair_window)
+            self.seed_select(job, lo, hi, pair_read, pair_window, distance, k_sel, scores, ids)
+            emitted += cand_read.numel()
+            unique += pair_read.numel()
             within += ((distance >= 0) & (distance <= bound)).sum()
         return scores, ids, counts, (emitted, unique, within)
 
@@ -377,68 +563,16 @@ class ReferenceMapper:
         A read with an 'N' in one of its pieces, or with more than max_candidates candidates (default max(n_ids // 8, 256): the measured break-even), is not answered
         from candidates: those reads, and only those, go through map_reads as a sub-batch.  max_candidates never changes a result,
         only the time.  last_seed_stats says what happened."""
-        a = self.aligner
-        torch = a.torch
-        reads = np.ascontiguousarray(reads, dtype=np.uint8)
-        if reads.ndim != 2 or reads.shape[0] < 1 or reads.shape[1] < 1:
-            raise B.BgsaHipError("map_reads_seeded: rc=-1: reads must be [ns, n] with ns, n >= 1 (one read length per call)")
+        who = "map_reads_seeded"
+        reads = self._one_length(who, reads)
         ns, n = reads.shape
-        if n > 1024:
-            raise B.BgsaHipError("map_reads_seeded: rc=-2: reads beyond 1,024 bp have no verify kernel (map_reads takes them)")
-        k_best = int(k_best)
-        if not 1 <= k_best <= B.V_NUM:
-            raise B.BgsaHipError(f"map_reads_seeded: rc=-1: k_best must lie in 1..{B.V_NUM}")
-        if max_distance is None:
-            raise B.BgsaHipError("map_reads_seeded: rc=-1: max_distance is required: the seed filter is derived from it (map_reads "
-                                 "takes max_distance=None)")
-        if int(max_distance) < 0:
-            raise B.BgsaHipError("map_reads_seeded: rc=-1: max_distance is negative")
-        bound, _, q = seed_plan(n, int(max_distance), seed_len)
-        largest = max_stride(self.window_len, n, bound)
-        if self.stride > largest:
-            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
-            raise B.BgsaHipError(f"map_reads_seeded: rc=-1: at stride {self.stride} a placement of a {n} bp read within distance {bound} can "
-                                 f"lie in no window of {self.window_len} bp: {allowed}")
-        if self.ref_len > INT32_MAX:
-            raise B.BgsaHipError("map_reads_seeded: rc=-1: the index holds int32 positions: a reference beyond 2^31 - 1 bases goes in parts")
-        k_sel = self.k_selected(k_best)
-        cap = self.window_len + n if cigar_cap is None else int(cigar_cap)
-        if cap < 1:
-            raise B.BgsaHipError("map_reads_seeded: rc=-1: cigar_cap is not positive")
-        max_candidates = max(self.n_ids // SEED_CAP_FRACTION, SEED_MIN_CANDIDATES) if max_candidates is None else int(max_candidates)
-        if max_candidates < 0:
-            raise B.BgsaHipError("map_reads_seeded: rc=-1: max_candidates is negative")
-
-        # set_subjects(reads, qlen=W), keeping the ASCII rows: the candidate kernels read them
-        padded, a.extra = B.pad_rows(reads)
-        a.ns_real = ns
-        d_rows = torch.from_numpy(B.rows_to_buffer(padded)).to(a.device)
-        a.set_subject_rows_device(d_rows, padded.shape[0], n, self.window_len)
-        scores, ids, counts, totals = self.select_seeded(d_rows, ns, n, bound, q, k_sel, max_candidates, block_rows)
-        strand, ref_begin, ref_end, keep, n_ops, cigar = self.place_hits(ids, bound, cap, block_rows)
-        a.check_faults()
-
-        flags = counts.cpu().numpy()
-        self.last_seed_stats = dict(reads_seeded=int((flags >= 0).sum()), reads_fallback_n=int((flags == -1).sum()),
-                                    reads_fallback_cap=int((flags == -2).sum()), candidates_emitted=int(totals[0].item()),
-                                    candidates_unique=int(totals[1].item()), candidates_within_bound=int(totals[2].item()),
-                                    seed_len=q, max_candidates=max_candidates)
-        kept = keep.cpu().numpy()
-        runs_n, runs = n_ops.cpu().numpy(), cigar.cpu().numpy().view(np.uint32)
-        cigars = [[None] * k_sel for _ in range(ns)]
-        for c, r in zip(*np.nonzero(kept)):
-            if runs_n[c, r] > cap:
-                raise B.BgsaHipError(f"map_reads_seeded: hit {r} of read {c} has {runs_n[c, r]} runs, its row holds {cap} (raise cigar_cap)")
-            cigars[c][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : runs_n[c, r]].tolist())
-        out = ReferenceHits(scores.cpu().numpy(), strand.cpu().numpy(), ref_begin.cpu().numpy(), ref_end.cpu().numpy(), kept, cigars,
-                            ids.cpu().numpy())
-        rest = np.flatnonzero(flags < 0)
-        if rest.size:        # the reads the filter does not cover: the exhaustive path, blanked, into the caller's order
-            full = blank_beyond(self.map_reads(reads[rest], k_best, int(max_distance), block_rows, cigar_cap), bound)
-            for mine, theirs in zip(out[:5] + (out.windows,), full[:5] + (full.windows,)):
-                mine[rest] = theirs
-            for at, row in zip(rest.tolist(), full.cigars):
-                out.cigars[at] = row
+        k_best, bound, cap, max_candidates, (_, _, q) = self._check(who, n, False, k_best, max_distance, cigar_cap, True, max_candidates,
+                                                                    lambda limit: seed_plan(n, limit, seed_len))
+        plan = [(np.arange(ns), q)]      # one bin, placed within the bound the filter was derived from
+        out, flags, totals, _ = self._map_bins(who, reads, np.full(ns, n, dtype=np.int32), plan, self.k_selected(k_best), bound, cap,
+                                               block_rows, max_candidates)
+        self.last_seed_stats = seed_stats(flags, totals, q, max_candidates)
+        self._map_uncovered(out, flags, lambda rest: self.map_reads(reads[rest], k_best, int(max_distance), block_rows, cigar_cap), bound)
         return out
 
     def map_reads_seeded_ragged(self, reads, k_best: int = 1, max_distance=None, seed_len=None, max_candidates=None,
@@ -452,91 +586,15 @@ class ReferenceMapper:
         candidates (-2) or too short for its bin's seed and the bound (-3) goes through map_reads_ragged, all of them as one
         sub-batch.  max_candidates, seed_len and block_rows never change a result.  max_distance is required; the other refusals
         are map_reads_ragged's own, all made before anything is launched or allocated.  last_seed_stats says what happened."""
-        a = self.aligner
-        torch = a.torch
+        who = "map_reads_seeded_ragged"
         rows, lens = B.pad_ragged(reads)
-        ns, longest = rows.shape
-        if longest > 1024:
-            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-2: reads beyond 1,024 bp have no per-lane form (one length per call: map_reads)")
-        k_best = int(k_best)
-        if not 1 <= k_best <= B.V_NUM:
-            raise B.BgsaHipError(f"map_reads_seeded_ragged: rc=-1: k_best must lie in 1..{B.V_NUM}")
-        if max_distance is None:
-            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: max_distance is required: the seed filter is derived from it "
-                                 "(map_reads_ragged takes max_distance=None)")
+        k_best, _, cap, max_candidates, plan = self._check(who, rows.shape[1], True, k_best, max_distance, cigar_cap, True, max_candidates,
+                                                           lambda limit: seed_plan_ragged(lens, limit, seed_len))
         limit = int(max_distance)
-        if limit < 0:
-            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: max_distance is negative")
-        plan = seed_plan_ragged(lens, limit, seed_len)
-        largest = max_stride(self.window_len, longest, min(limit, longest))
-        if self.stride > largest:
-            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
-            raise B.BgsaHipError(f"map_reads_seeded_ragged: rc=-1: at stride {self.stride} a placement of the longest read ({longest} bp) "
-                                 f"within distance {min(limit, longest)} can lie in no window of {self.window_len} bp: {allowed}")
-        if self.ref_len > INT32_MAX:
-            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: the index holds int32 positions: a reference beyond 2^31 - 1 bases goes "
-                                 "in parts")
-        k_sel = self.k_selected(k_best)
-        cap = self.window_len + longest if cigar_cap is None else int(cigar_cap)
-        if cap < 1:
-            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: cigar_cap is not positive")
-        max_candidates = max(self.n_ids // SEED_CAP_FRACTION, SEED_MIN_CANDIDATES) if max_candidates is None else int(max_candidates)
-        if max_candidates < 0:
-            raise B.BgsaHipError("map_reads_seeded_ragged: rc=-1: max_candidates is negative")
-
-        scores = np.full((ns, k_sel), INT32_MIN, dtype=np.int32)
-        strand, windows = np.full_like(scores, -1), np.full_like(scores, -1)
-        keep = np.zeros_like(scores)
-        ref_begin, ref_end = np.full((ns, k_sel), -1, dtype=np.int64), np.full((ns, k_sel), -1, dtype=np.int64)
-        cigars = [[None] * k_sel for _ in range(ns)]
-        flags = np.zeros(ns, dtype=np.int32)
-        totals, bins = [0, 0, 0], []
-        for idx, q in plan:
-            mine = lens[idx]
-            width, mixed = int(mine.max()), bool((mine != mine[0]).any())
-            bound = min(limit, width)
-            bins.append(dict(words=(width + 31) // 32, reads=int(idx.size), q=q, emitted=0, unique=0))
-            if not mixed and width // (bound + 1) < q:      # a bin of one length too short for its seed: the C call would refuse it
-                flags[idx] = -3
-                continue
-            padded, a.extra = B.pad_rows(rows[idx, :width])
-            a.ns_real = int(idx.size)
-            d_rows = torch.from_numpy(B.rows_to_buffer(padded)).to(a.device)
-            d_lens = None
-            if mixed:
-                d_lens = torch.from_numpy(np.concatenate([mine, np.full(a.extra, width, dtype=np.int32)]).astype(np.int32)).to(a.device)
-            a.set_subject_rows_device(d_rows, padded.shape[0], width, self.window_len, d_lens=d_lens)
-            if mixed:
-                a.mark_reads_ragged()
-            d_scores, d_ids, d_counts, stats = self.select_seeded(d_rows, int(idx.size), width, bound, q, k_sel, max_candidates, block_rows,
-                                                                  d_lens=d_lens)
-            d_strand, d_begin, d_end, d_keep, d_n_ops, d_cigar = self.place_hits(d_ids, limit, cap, block_rows, ragged=mixed)
-            a.check_faults()
-            flags[idx] = d_counts.cpu().numpy()
-            kept = d_keep.cpu().numpy()
-            scores[idx], strand[idx], keep[idx], windows[idx] = d_scores.cpu().numpy(), d_strand.cpu().numpy(), kept, d_ids.cpu().numpy()
-            ref_begin[idx], ref_end[idx] = d_begin.cpu().numpy(), d_end.cpu().numpy()
-            runs_n, runs = d_n_ops.cpu().numpy(), d_cigar.cpu().numpy().view(np.uint32)
-            for c, r in zip(*np.nonzero(kept)):
-                if runs_n[c, r] > cap:
-                    raise B.BgsaHipError(f"map_reads_seeded_ragged: hit {r} of read {idx[c]} has {runs_n[c, r]} runs, its row holds {cap} "
-                                         "(raise cigar_cap)")
-                cigars[idx[c]][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : runs_n[c, r]].tolist())
-            emitted, unique, within = (int(x.item()) for x in stats)
-            bins[-1].update(emitted=emitted, unique=unique)
-            totals = [totals[0] + emitted, totals[1] + unique, totals[2] + within]
-        out = ReferenceHits(scores, strand, ref_begin, ref_end, keep, cigars, windows)
-        rest = np.flatnonzero(flags < 0)
-        if rest.size:        # the reads the filter does not cover: the exhaustive path, blanked, into the caller's order
-            full = blank_beyond(self.map_reads_ragged([rows[i, : lens[i]] for i in rest], k_best, limit, block_rows, cigar_cap), limit)
-            for field, theirs in zip(out[:5] + (out.windows,), full[:5] + (full.windows,)):
-                field[rest] = theirs
-            for at, row in zip(rest.tolist(), full.cigars):
-                out.cigars[at] = row
-        self.last_seed_stats = dict(reads_seeded=int((flags >= 0).sum()), reads_fallback_n=int((flags == -1).sum()),
-                                    reads_fallback_cap=int((flags == -2).sum()), reads_fallback_short=int((flags == -3).sum()),
-                                    candidates_emitted=totals[0], candidates_unique=totals[1], candidates_within_bound=totals[2],
-                                    seed_len=None if seed_len is None else int(seed_len), max_candidates=max_candidates, bins=bins)
+        out, flags, totals, bins = self._map_bins(who, rows, lens, plan, self.k_selected(k_best), limit, cap, block_rows, max_candidates)
+        self.last_seed_stats = seed_stats(flags, totals, None if seed_len is None else int(seed_len), max_candidates, bins)
+        self._map_uncovered(out, flags, lambda rest: self.map_reads_ragged([rows[i, : lens[i]] for i in rest], k_best, limit, block_rows,
+                                                                           cigar_cap), limit)
         return out
 
     def map_reads_ragged(self, reads, k_best: int = 1, max_distance=None, block_rows: int = 1000, cigar_cap=None) -> ReferenceHits:
@@ -549,51 +607,11 @@ class ReferenceMapper:
         order and equals, read by read, map_reads called once per exact length.
         The stride check is map_reads' rule applied with the LONGEST read (shorter reads span less); it is made before anything
         is launched.  cigar_cap=None: window_len + the longest read."""
-        a = self.aligner
         rows, lens = B.pad_ragged(reads)
-        ns, longest = rows.shape
-        if longest > 1024:
-            raise B.BgsaHipError("map_reads_ragged: rc=-2: reads beyond 1,024 bp have no per-lane form (one length per call: map_reads)")
-        k_best = int(k_best)
-        if not 1 <= k_best <= B.V_NUM:
-            raise B.BgsaHipError(f"map_reads_ragged: rc=-1: k_best must lie in 1..{B.V_NUM}")
-        if max_distance is not None and int(max_distance) < 0:
-            raise B.BgsaHipError("map_reads_ragged: rc=-1: max_distance is negative")
-        bound = 0 if max_distance is None else min(int(max_distance), longest)
-        largest = max_stride(self.window_len, longest, bound)
-        if self.stride > largest:
-            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
-            raise B.BgsaHipError(f"map_reads_ragged: rc=-1: at stride {self.stride} a placement of the longest read ({longest} bp) within "
-                                 f"distance {bound} can lie in no window of {self.window_len} bp: {allowed}")
-        k_sel = self.k_selected(k_best)
-        cap = self.window_len + longest if cigar_cap is None else int(cigar_cap)
-        if cap < 1:
-            raise B.BgsaHipError("map_reads_ragged: rc=-1: cigar_cap is not positive")
-
-        scores = np.empty((ns, k_sel), dtype=np.int32)
-        strand, keep, windows = np.empty_like(scores), np.empty_like(scores), np.empty_like(scores)
-        ref_begin, ref_end = np.empty((ns, k_sel), dtype=np.int64), np.empty((ns, k_sel), dtype=np.int64)
-        cigars = [[None] * k_sel for _ in range(ns)]
-        for idx in B.bin_by_words(lens):
-            a.set_reads_ragged([rows[i, : lens[i]] for i in idx], qlen=self.window_len)
-            d_scores, d_ids = self.select_windows(k_sel, block_rows)
-            limit = None if max_distance is None else int(max_distance)
-            if a.reads_ragged:
-                d_strand, d_begin, d_end, d_keep, d_n_ops, d_cigar = self.place_hits(d_ids, limit, cap, block_rows, ragged=True)
-            else:   # a bin of one length: map_reads' own placement
-                if limit is None:
-                    limit = -int(a.torch.where(d_ids >= 0, d_scores, a.torch.zeros_like(d_scores)).min().item())
-                d_strand, d_begin, d_end, d_keep, d_n_ops, d_cigar = self.place_hits(d_ids, limit, cap, block_rows)
-            a.check_faults()
-            kept = d_keep.cpu().numpy()
-            scores[idx], strand[idx], keep[idx], windows[idx] = d_scores.cpu().numpy(), d_strand.cpu().numpy(), kept, d_ids.cpu().numpy()
-            ref_begin[idx], ref_end[idx] = d_begin.cpu().numpy(), d_end.cpu().numpy()
-            counts, runs = d_n_ops.cpu().numpy(), d_cigar.cpu().numpy().view(np.uint32)
-            for c, r in zip(*np.nonzero(kept)):
-                if counts[c, r] > cap:
-                    raise B.BgsaHipError(f"map_reads_ragged: hit {r} of read {idx[c]} has {counts[c, r]} runs, its row holds {cap} (raise cigar_cap)")
-                cigars[idx[c]][r] = "".join(f"{w >> 4}{B.CIGAR_OPS[w & 15]}" for w in runs[c, r, : counts[c, r]].tolist())
-        return ReferenceHits(scores, strand, ref_begin, ref_end, keep, cigars, windows)
+        k_best, _, cap, _, _ = self._check("map_reads_ragged", rows.shape[1], True, k_best, max_distance, cigar_cap)
+        limit = None if max_distance is None else int(max_distance)
+        plan = [(idx, None) for idx in B.bin_by_words(lens)]
+        return self._map_bins("map_reads_ragged", rows, lens, plan, self.k_selected(k_best), limit, cap, block_rows)[0]
 
     @staticmethod
     def placements_of(hits: ReferenceHits, k_best: int = 1) -> list:

@@ -101,93 +101,58 @@ def main() -> int:
         lines.append(f"  {name:<58s} {m['median']:10.3f} ms  ({m['min']:.3f} .. {m['max']:.3f})  {note}")
 
     rows_all, _ = B.pad_ragged(reads)
-    n_ids2 = 2 * mapper.n_windows
     for (idx, q), seen in zip(plan, stats["bins"]):
         mine = lens[idx].astype(np.int32)
         width, n_bin = int(mine.max()), int(idx.size)
         mixed = bool((mine != mine[0]).any())
         lines += ["", f"bin of {seen['words']} words: {n_bin:,} reads of {int(mine.min())}..{width} bp, q = {q}; emitted {seen['emitted']:,}, unique "
                       f"{seen['unique']:,}"]
-        padded, a.extra = B.pad_rows(rows_all[idx, :width])
-        a.ns_real = n_bin
-        d_rows = torch.from_numpy(B.rows_to_buffer(padded)).to(dev)
-        d_lens = torch.from_numpy(np.concatenate([mine, np.full(a.extra, width, dtype=np.int32)])).to(dev)
-        a.set_subject_rows_device(d_rows, padded.shape[0], width, W, d_lens=d_lens if mixed else None)
-        if mixed:
-            a.mark_reads_ragged()
-        offsets, positions = mapper.seed_index(q)
-        shape = (mapper.ref_len, W, S, offsets.data_ptr(), positions.data_ptr(), q)
+        d_rows, d_lens = a._set_bucket(rows_all[idx, :width], mine if mixed else None, qlen=W, reads_ragged=mixed)
+        job = mapper.seed_bucket(d_rows, width, min(bound, width), q, d_lens)
         blocks = [(lo, min(lo + args.block_rows, n_bin)) for lo in range(0, n_bin, args.block_rows)]
         counts = torch.empty(n_bin, dtype=torch.int32, device=dev)
         kept = {}
-
-        def count_emit():
-            kept["cand"] = []
-            for lo, hi in blocks:
-                rows = (d_rows.data_ptr() + lo * (width + 1), d_lens[lo:hi].data_ptr(), width, hi - lo, min(bound, width), 1)
-                B.check(L.bgsa_hip_seed_count_candidates_lens_dev(*shape, *rows, stats["max_candidates"], counts[lo:hi].data_ptr(), stream), "count")
-                sizes = counts[lo:hi].clamp(min=0).to(torch.int64)
-                ends = sizes.cumsum(0)
-                total = int(ends[-1].item())
-                prefix = (ends - sizes).contiguous()
-                cand_read = torch.empty(total, dtype=torch.int32, device=dev)
-                cand_window = torch.empty(total, dtype=torch.int32, device=dev)
-                if total:
-                    B.check(L.bgsa_hip_seed_emit_candidates_lens_dev(*shape, *rows, counts[lo:hi].data_ptr(), prefix.data_ptr(), 0,
-                                                                     cand_read.data_ptr(), cand_window.data_ptr(), stream), "emit")
-                kept["cand"].append((cand_read, cand_window))
-        line("count + emit, per read (with the scan and its read back)", event_ms(torch, count_emit))
+        line("count + emit, per read (with the scan and its read back)", event_ms(torch, lambda: kept.__setitem__(
+            "cand", [mapper.seed_candidates(job, lo, hi, stats["max_candidates"], counts) for lo, hi in blocks])))
         flags = counts.cpu().numpy()
         lines.append(f"    flags: seeded {int((flags >= 0).sum()):,}, -1 {int((flags == -1).sum()):,}, -2 {int((flags == -2).sum()):,}, "
                      f"-3 {int((flags == -3).sum()):,}; blocks without a candidate: {sum(1 for c in kept['cand'] if not c[0].numel())}")
-
-        def dedupe():
-            kept["pairs"] = []
-            for (lo, hi), (cand_read, cand_window) in zip(blocks, kept["cand"]):
-                keys = torch.unique(cand_read.to(torch.int64) * n_ids2 + cand_window)
-                pair_read = keys // n_ids2
-                kept["pairs"].append((pair_read + lo, (keys - pair_read * n_ids2).to(torch.int32), pair_read))
-        line("sort / deduplicate (torch.unique)", event_ms(torch, dedupe))
-        n_unique = sum(p[0].numel() for p in kept["pairs"])
-
-        def verify(lens_call=True):
-            kept["distance"] = []
-            for subject, window, _ in kept["pairs"]:
-                distance = torch.full((subject.numel(),), -1, dtype=torch.int32, device=dev)
-                kept["distance"].append(distance)
-                if not subject.numel():                      # a block whose reads are all flagged: nothing to verify
-                    continue
-                head = (mapper.d_reference.data_ptr(), mapper.ref_len, W, S, a.d_peq.data_ptr())
-                tail = (width, a.ns, a.wn, window.data_ptr(), subject.data_ptr(), subject.numel(), 0, distance.data_ptr(), None, 0, stream)
-                if lens_call:
-                    B.check(L.bgsa_hip_reference_verify_pairs_lens_dev(*head, d_lens.data_ptr(), *tail), "verify lens")
-                else:
-                    B.check(L.bgsa_hip_reference_verify_pairs_dev(*head, *tail), "verify")
-        m_verify = event_ms(torch, verify)
+        line("sort / deduplicate (torch.unique)", event_ms(torch, lambda: kept.__setitem__("pairs", [mapper.seed_dedupe(*cand) for cand in kept["cand"]])))
+        n_unique = sum(pair_read.numel() for pair_read, _ in kept["pairs"])
+        m_verify = event_ms(torch, lambda: kept.__setitem__(
+            "distance", [mapper.seed_verify(job, lo, *pairs) for (lo, _), pairs in zip(blocks, kept["pairs"])]))
         line(f"verify (lens): {n_unique:,} pairs of <= {width} x {W} cells", m_verify,
              f"{n_unique * width * W / m_verify['median'] / 1e6:,.0f} GCUPS at the width")
         scores = torch.empty((n_bin, k_sel), dtype=torch.int32, device=dev)
         ids = torch.empty((n_bin, k_sel), dtype=torch.int32, device=dev)
 
         def select():
-            for (lo, hi), (_, window, pair_read), distance in zip(blocks, kept["pairs"], kept["distance"]):
-                segments = torch.searchsorted(pair_read, torch.arange(hi - lo + 1, dtype=torch.int64, device=dev)).contiguous()
-                B.check(L.bgsa_hip_seed_select_dev(window.data_ptr() if window.numel() else None, distance.data_ptr() if window.numel() else None, segments.data_ptr(), hi - lo, min(bound, width), k_sel,
-                                                   scores[lo:hi].data_ptr(), ids[lo:hi].data_ptr(), stream), "select")
+            for (lo, hi), pairs, distance in zip(blocks, kept["pairs"], kept["distance"]):
+                mapper.seed_select(job, lo, hi, *pairs, distance, k_sel, scores, ids)
         line("select (with the segment bounds by searchsorted)", event_ms(torch, select))
         line(f"placement ({'trace_pairs, per read' if mixed else 'banded'}): {n_bin * k_sel:,} slots",
              event_ms(torch, lambda: mapper.place_hits(ids, bound, args.cigar_cap, args.block_rows, ragged=mixed)))
         a.check_faults()
 
         if width == args.read_len:
-            # the lens instance with every length the width beside the equal-length instance: same bucket planes, same pairs
+            # the lens instance with every length the width beside the equal-length instance: same bucket planes, same pairs, the two
+            # C calls side by side
             whole = torch.full((a.ns,), width, dtype=torch.int32, device=dev)
-            own, d_lens = d_lens, whole
-            m_whole = event_ms(torch, verify)
+
+            def verify(*lens_arg):
+                call = L.bgsa_hip_reference_verify_pairs_lens_dev if lens_arg else L.bgsa_hip_reference_verify_pairs_dev
+                kept["distance"] = []
+                for (lo, _), (pair_read, window) in zip(blocks, kept["pairs"]):
+                    subject = pair_read + lo
+                    distance = torch.full((subject.numel(),), -1, dtype=torch.int32, device=dev)
+                    kept["distance"].append(distance)
+                    if subject.numel():                      # a block whose reads are all flagged: nothing to verify
+                        B.check(call(mapper.d_reference.data_ptr(), mapper.ref_len, W, S, a.d_peq.data_ptr(), *lens_arg, width, a.ns, a.wn,
+                                     window.data_ptr(), subject.data_ptr(), subject.numel(), 0, distance.data_ptr(), None, 0, stream), "verify")
+            m_whole = event_ms(torch, lambda: verify(whole.data_ptr()))
             got = torch.cat(kept["distance"])
-            m_equal = event_ms(torch, lambda: verify(False))
+            m_equal = event_ms(torch, verify)
             assert torch.equal(got, torch.cat(kept["distance"])), "the lens instance at the full width differs from the equal-length one"
-            d_lens = own
             lines.append(f"  the same {n_unique:,} pairs with every length {width}: lens instance {m_whole['median']:.3f} ms ({m_whole['min']:.3f} .. "
                          f"{m_whole['max']:.3f}), equal-length instance {m_equal['median']:.3f} ms ({m_equal['min']:.3f} .. {m_equal['max']:.3f}): "
                          f"ratio {m_whole['median'] / m_equal['median']:.3f}")

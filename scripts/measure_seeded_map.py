@@ -106,61 +106,24 @@ def main() -> int:
     del offsets, positions, work
 
     # the steps of select_seeded, one after the other over all blocks, each kept for the next
-    padded, a.extra = B.pad_rows(reads)
-    a.ns_real = ns
-    d_rows = torch.from_numpy(B.rows_to_buffer(padded)).to(dev)
-    a.set_subject_rows_device(d_rows, padded.shape[0], n, W)
-    offsets, positions = mapper.seed_index(q)
-    shape = (mapper.ref_len, W, S, offsets.data_ptr(), positions.data_ptr(), q)
+    d_rows, _ = a._set_bucket(reads, qlen=W)
+    job = mapper.seed_bucket(d_rows, n, bound, q)
     blocks = [(lo, min(lo + args.block_rows, ns)) for lo in range(0, ns, args.block_rows)]
     counts = torch.empty(ns, dtype=torch.int32, device=dev)
     kept = {}
-
-    def count_emit():
-        kept["cand"] = []
-        for lo, hi in blocks:
-            rows = (d_rows.data_ptr() + lo * (n + 1), n, hi - lo, bound, 1)
-            B.check(L.bgsa_hip_seed_count_candidates_dev(*shape, *rows, stats["max_candidates"], counts[lo:hi].data_ptr(), stream), "count")
-            sizes = counts[lo:hi].clamp(min=0).to(torch.int64)
-            ends = sizes.cumsum(0)
-            total = int(ends[-1].item())
-            prefix = (ends - sizes).contiguous()
-            cand_read = torch.empty(total, dtype=torch.int32, device=dev)
-            cand_window = torch.empty(total, dtype=torch.int32, device=dev)
-            if total:
-                B.check(L.bgsa_hip_seed_emit_candidates_dev(*shape, *rows, counts[lo:hi].data_ptr(), prefix.data_ptr(), 0, cand_read.data_ptr(),
-                                                            cand_window.data_ptr(), stream), "emit")
-            kept["cand"].append((cand_read, cand_window))
-    line("count + emit (with the scan and its scalar read back)", event_ms(torch, count_emit))
-    n_ids2 = 2 * mapper.n_windows
-
-    def dedupe():
-        kept["pairs"] = []
-        for (lo, hi), (cand_read, cand_window) in zip(blocks, kept["cand"]):
-            keys = torch.unique(cand_read.to(torch.int64) * n_ids2 + cand_window)
-            pair_read = keys // n_ids2
-            kept["pairs"].append((pair_read + lo, (keys - pair_read * n_ids2).to(torch.int32), pair_read))
-    line("sort / deduplicate (torch.unique)", event_ms(torch, dedupe))
-    n_unique = sum(p[0].numel() for p in kept["pairs"])
-
-    def verify():
-        kept["distance"] = []
-        for subject, window, _ in kept["pairs"]:
-            distance = torch.full((subject.numel(),), -1, dtype=torch.int32, device=dev)
-            B.check(L.bgsa_hip_reference_verify_pairs_dev(mapper.d_reference.data_ptr(), mapper.ref_len, W, S, a.d_peq.data_ptr(), n, a.ns, a.wn,
-                                                          window.data_ptr(), subject.data_ptr(), subject.numel(), 0, distance.data_ptr(), None, 0,
-                                                          stream), "verify")
-            kept["distance"].append(distance)
-    m_verify = event_ms(torch, verify)
+    line("count + emit (with the scan and its scalar read back)", event_ms(torch, lambda: kept.__setitem__(
+        "cand", [mapper.seed_candidates(job, lo, hi, stats["max_candidates"], counts) for lo, hi in blocks])))
+    line("sort / deduplicate (torch.unique)", event_ms(torch, lambda: kept.__setitem__("pairs", [mapper.seed_dedupe(*cand) for cand in kept["cand"]])))
+    n_unique = sum(pair_read.numel() for pair_read, _ in kept["pairs"])
+    m_verify = event_ms(torch, lambda: kept.__setitem__(
+        "distance", [mapper.seed_verify(job, lo, *pairs) for (lo, _), pairs in zip(blocks, kept["pairs"])]))
     line(f"verify: {n_unique:,} pairs of {n} x {W} cells", m_verify, f"{n_unique * n * W / m_verify['median'] / 1e6:,.0f} GCUPS")
     scores = torch.empty((ns, k_sel), dtype=torch.int32, device=dev)
     ids = torch.empty((ns, k_sel), dtype=torch.int32, device=dev)
 
     def select():
-        for (lo, hi), (_, window, pair_read), distance in zip(blocks, kept["pairs"], kept["distance"]):
-            segments = torch.searchsorted(pair_read, torch.arange(hi - lo + 1, dtype=torch.int64, device=dev)).contiguous()
-            B.check(L.bgsa_hip_seed_select_dev(window.data_ptr(), distance.data_ptr(), segments.data_ptr(), hi - lo, bound, k_sel,
-                                               scores[lo:hi].data_ptr(), ids[lo:hi].data_ptr(), stream), "select")
+        for (lo, hi), pairs, distance in zip(blocks, kept["pairs"], kept["distance"]):
+            mapper.seed_select(job, lo, hi, *pairs, distance, k_sel, scores, ids)
     line("select (with the segment bounds by searchsorted)", event_ms(torch, select))
     m_place = event_ms(torch, lambda: mapper.place_hits(ids, bound, args.cigar_cap, args.block_rows))
     line(f"placement: {ns * k_sel:,} slots in blocks of {args.block_rows:,} reads", m_place)
@@ -192,17 +155,9 @@ def main() -> int:
         out_scores = torch.empty((sample, k_sel), dtype=torch.int32, device=dev)
         out_ids = torch.empty((sample, k_sel), dtype=torch.int32, device=dev)
 
-        def sweep():
-            keys = torch.unique(cand_read.to(torch.int64) * n_ids2 + cand_window)
-            pair_read = keys // n_ids2
-            window = (keys - pair_read * n_ids2).to(torch.int32)
-            distance = torch.full((keys.numel(),), -1, dtype=torch.int32, device=dev)
-            B.check(L.bgsa_hip_reference_verify_pairs_dev(mapper.d_reference.data_ptr(), mapper.ref_len, W, S, a.d_peq.data_ptr(), n, a.ns, a.wn,
-                                                          window.data_ptr(), pair_read.data_ptr(), keys.numel(), 0, distance.data_ptr(), None, 0,
-                                                          stream), "verify")
-            segments = torch.searchsorted(pair_read, torch.arange(sample + 1, dtype=torch.int64, device=dev)).contiguous()
-            B.check(L.bgsa_hip_seed_select_dev(window.data_ptr(), distance.data_ptr(), segments.data_ptr(), sample, bound, k_sel,
-                                               out_scores.data_ptr(), out_ids.data_ptr(), stream), "select")
+        def sweep():      # the first `sample` reads of the resident bucket as one block
+            pairs = mapper.seed_dedupe(cand_read, cand_window)
+            mapper.seed_select(job, 0, sample, *pairs, mapper.seed_verify(job, 0, *pairs), k_sel, out_scores, out_ids)
         m = event_ms(torch, sweep)
         per_read = m["median"] / sample
         lines.append(f"  C = {c:>7,}   {per_read * 1e3:10.2f} us per read  ({m['median']:.3f} ms)   {per_read / per_read_full:.3f} x the exhaustive selection")

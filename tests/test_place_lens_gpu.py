@@ -284,6 +284,26 @@ def test_map_reads_ragged_equals_map_reads_per_length():
     assert all(got.cigars[c][r] is None for c, r in zip(*np.nonzero(unplaced)))
 
 
+@pytest.mark.parametrize("max_distance", [2, None])      # None: the bin's worst selected distance, one scalar read back
+def test_a_list_of_one_length_equals_map_reads(max_distance):
+    ref, _, _ = mapper_case()
+    rng = np.random.default_rng(64)
+    begins = rng.integers(0, REF_LEN - 70, size=70)
+    reads = np.stack([np.array(_edit(rng, list(ref[b: b + 67]), int(rng.integers(0, 4)), ACGT)[:64], np.uint8) for b in begins])
+    reads[1::2] = np.stack([M.reverse_complement(r) for r in reads[1::2]])
+    mapper = B.ReferenceMapper(ref, W, S, DEV)
+    want = mapper.map_reads(reads, k_best=2, max_distance=max_distance)
+    got = mapper.map_reads_ragged(list(reads), k_best=2, max_distance=max_distance)
+    for name in ("scores", "strand", "ref_begin", "ref_end", "keep", "windows"):
+        g, w = getattr(got, name), getattr(want, name)
+        assert g.shape == w.shape == (70, mapper.k_selected(2)) and g.dtype == w.dtype and np.array_equal(g, w), name
+    assert got.cigars == want.cigars
+    if max_distance is None:      # every selected hit is placed
+        assert (got.ref_begin[got.windows >= 0] >= 0).all() and (got.keep[:, 0] == 1).all()
+    else:
+        assert ((got.windows >= 0) & (got.ref_begin < 0)).any()
+
+
 def test_map_reads_ragged_refuses_a_stride_the_longest_read_rules_out():
     ref, reads, _ = mapper_case()
     longest = max(r.size for r in reads)

@@ -230,3 +230,194 @@ def test_host_pipeline_finds_reads_of_both_strands_where_they_were_taken():
 def test_python_driver_refuses_without_a_device():
     with pytest.raises(B.BgsaHipError, match="rc=-1"):
         B.window_plan(10, 20, 5)
+
+
+# ---- 8. the host side of the four map_reads entry points (bgsa_amd/reference.py), no device ----------------------------------
+from bgsa_amd import reference as RM  # noqa: E402
+
+WHO = ("map_reads", "map_reads_ragged", "map_reads_seeded", "map_reads_seeded_ragged")
+# every refusal, word for word as the four methods raised them before they shared check_call (geometry: see refuse())
+REFUSALS = {
+    "map_reads": {
+        "k_best": "map_reads: rc=-1: k_best must lie in 1..64",
+        "negative": "map_reads: rc=-1: max_distance is negative",
+        "stride": "map_reads: rc=-1: at stride 62 a placement of a 32 bp read within distance 4 can lie in no window of 96 bp: "
+                  "the largest stride allowed is 61",
+        "no_stride": "map_reads: rc=-1: at stride 1 a placement of a 32 bp read within distance 4 can lie in no window of 34 bp: "
+                     "no stride is (a longer window)",
+        "cigar_cap": "map_reads: rc=-1: cigar_cap is not positive",
+    },
+    "map_reads_ragged": {
+        "1024": "map_reads_ragged: rc=-2: reads beyond 1,024 bp have no per-lane form (one length per call: map_reads)",
+        "k_best": "map_reads_ragged: rc=-1: k_best must lie in 1..64",
+        "negative": "map_reads_ragged: rc=-1: max_distance is negative",
+        "stride": "map_reads_ragged: rc=-1: at stride 62 a placement of the longest read (32 bp) within distance 4 can lie in no window "
+                  "of 96 bp: the largest stride allowed is 61",
+        "no_stride": "map_reads_ragged: rc=-1: at stride 1 a placement of the longest read (32 bp) within distance 4 can lie in no window "
+                     "of 34 bp: no stride is (a longer window)",
+        "cigar_cap": "map_reads_ragged: rc=-1: cigar_cap is not positive",
+    },
+    "map_reads_seeded": {
+        "1024": "map_reads_seeded: rc=-2: reads beyond 1,024 bp have no verify kernel (map_reads takes them)",
+        "k_best": "map_reads_seeded: rc=-1: k_best must lie in 1..64",
+        "required": "map_reads_seeded: rc=-1: max_distance is required: the seed filter is derived from it (map_reads takes "
+                    "max_distance=None)",
+        "negative": "map_reads_seeded: rc=-1: max_distance is negative",
+        "seed_plan": "seed_plan: rc=-1: the 5 pieces of a 32 bp read within distance 4 start 6 bp apart, too close for seeds of 7 bp: "
+                     "seed_len 7 allows max_distance <= 3; max_distance 4 allows seed_len <= 6",
+        "stride": "map_reads_seeded: rc=-1: at stride 62 a placement of a 32 bp read within distance 4 can lie in no window of 96 bp: "
+                  "the largest stride allowed is 61",
+        "no_stride": "map_reads_seeded: rc=-1: at stride 1 a placement of a 32 bp read within distance 4 can lie in no window of 34 bp: "
+                     "no stride is (a longer window)",
+        "int32": "map_reads_seeded: rc=-1: the index holds int32 positions: a reference beyond 2^31 - 1 bases goes in parts",
+        "cigar_cap": "map_reads_seeded: rc=-1: cigar_cap is not positive",
+        "max_candidates": "map_reads_seeded: rc=-1: max_candidates is negative",
+    },
+    "map_reads_seeded_ragged": {
+        "1024": "map_reads_seeded_ragged: rc=-2: reads beyond 1,024 bp have no per-lane form (one length per call: map_reads)",
+        "k_best": "map_reads_seeded_ragged: rc=-1: k_best must lie in 1..64",
+        "required": "map_reads_seeded_ragged: rc=-1: max_distance is required: the seed filter is derived from it (map_reads_ragged "
+                    "takes max_distance=None)",
+        "negative": "map_reads_seeded_ragged: rc=-1: max_distance is negative",
+        "seed_plan": "seed_plan_ragged: rc=-1: seed_len must lie in 1..13",
+        "stride": "map_reads_seeded_ragged: rc=-1: at stride 62 a placement of the longest read (32 bp) within distance 4 can lie in no "
+                  "window of 96 bp: the largest stride allowed is 61",
+        "no_stride": "map_reads_seeded_ragged: rc=-1: at stride 1 a placement of the longest read (32 bp) within distance 4 can lie in no "
+                     "window of 34 bp: no stride is (a longer window)",
+        "int32": "map_reads_seeded_ragged: rc=-1: the index holds int32 positions: a reference beyond 2^31 - 1 bases goes in parts",
+        "cigar_cap": "map_reads_seeded_ragged: rc=-1: cigar_cap is not positive",
+        "max_candidates": "map_reads_seeded_ragged: rc=-1: max_candidates is negative",
+    },
+}
+# what breaks each rule, in the order the rules are checked
+BREAKS = [("1024", dict(longest=1025, W=1400)), ("k_best", dict(k_best=0)), ("required", dict(max_distance=None)),
+          ("negative", dict(max_distance=-1)), ("seed_plan", None), ("stride", dict(S=62)), ("int32", dict(ref_len=2 ** 31)),
+          ("cigar_cap", dict(cigar_cap=0)), ("max_candidates", dict(max_candidates=-1))]
+
+
+def check_call(who, longest=32, k_best=1, max_distance=4, cigar_cap=None, max_candidates=None, W=96, S=48, ref_len=3000, n_ids=124,
+               seed_len=None):
+    """check_call as the entry point `who` calls it: 32 bp reads within 4 on the 3,000 bp case of the GPU tests (W 96, S 48)."""
+    ragged, seeded = who.endswith("_ragged"), "_seeded" in who
+    plan = None
+    if seeded:
+        lens = np.full(3, longest, np.int32)
+        plan = (lambda limit: RM.seed_plan_ragged(lens, limit, seed_len)) if ragged else (lambda limit: RM.seed_plan(longest, limit, seed_len))
+    return RM.check_call(who, longest, ragged, k_best, max_distance, seeded, cigar_cap, max_candidates, W, S, ref_len, n_ids,
+                         who != "map_reads", plan)
+
+
+def broken(who, rule):
+    over = dict(BREAKS)[rule]
+    if over is None:      # the seed plan: overlapping seeds for one length, a seed length outside 1..13 for a list
+        over = dict(seed_len=14) if who.endswith("_ragged") else dict(seed_len=7)
+    return over
+
+
+@pytest.mark.parametrize("who", WHO)
+def test_every_refusal_keeps_its_text(who):
+    for rule, text in REFUSALS[who].items():
+        over = dict(W=34, S=1) if rule == "no_stride" else broken(who, rule)
+        with pytest.raises(B.BgsaHipError) as e:
+            check_call(who, **over)
+        assert str(e.value) == text, rule
+    for k_best in (65, -1):
+        with pytest.raises(B.BgsaHipError) as e:
+            check_call(who, k_best=k_best)
+        assert str(e.value) == REFUSALS[who]["k_best"]
+
+
+@pytest.mark.parametrize("who", WHO)
+def test_of_two_broken_rules_the_earlier_one_is_reported(who):
+    rules = [rule for rule, _ in BREAKS if rule in REFUSALS[who]]
+    for i, first in enumerate(rules):
+        for second in rules[i + 1:]:
+            over = {**broken(who, second), **broken(who, first)}
+            if len(over) < len(broken(who, second)) + len(broken(who, first)):
+                continue      # both rules are broken through the same argument: one call cannot break both
+            if "W" in over and "S" in over:
+                over["S"] = 1400      # beyond 1,024 bp the window is 1,400 bp: a stride that breaks the rule there too
+            with pytest.raises(B.BgsaHipError) as e:
+                check_call(who, **over)
+            assert str(e.value) == REFUSALS[who][first], (first, second)
+
+
+def test_only_map_reads_takes_a_read_beyond_1024_bp():
+    assert check_call("map_reads", longest=1025, W=1400, S=100)[:3] == (1, 4, 1400 + 1025)
+    for who in WHO[1:]:
+        with pytest.raises(B.BgsaHipError, match="rc=-2"):
+            check_call(who, longest=1025, W=1400, S=100)
+        assert check_call(who, longest=1024, W=1400, S=100)[2] == 1400 + 1024
+
+
+def test_max_distance_none_is_for_the_exhaustive_calls():
+    for who in WHO[:2]:
+        assert check_call(who, max_distance=None) == (1, 0, 96 + 32, None, None)          # the stride rule of an exact placement
+        with pytest.raises(B.BgsaHipError, match="within distance 0 .*largest stride allowed is 65"):
+            check_call(who, max_distance=None, S=66)
+    for who in WHO[2:]:
+        with pytest.raises(B.BgsaHipError, match="max_distance is required"):
+            check_call(who, max_distance=None)
+
+
+def test_what_an_accepted_call_returns():
+    assert check_call("map_reads", k_best=3, max_distance=40, cigar_cap=9, S=33) == (3, 32, 9, None, None)    # the bound stops at the read
+    assert check_call("map_reads_seeded") == (1, 4, 128, max(124 // 8, 256), (4, 6, 6))
+    assert check_call("map_reads_seeded", n_ids=83_682)[3] == 83_682 // 8
+    assert check_call("map_reads_seeded", max_candidates=0)[3] == 0
+    k_best, bound, cap, max_candidates, plan = check_call("map_reads_seeded_ragged", k_best=64, n_ids=4000)
+    assert (k_best, bound, cap, max_candidates) == (64, 4, 128, 500)
+    assert [(idx.tolist(), q) for idx, q in plan] == [([0, 1, 2], 6)]
+
+
+def test_cigars_are_decoded_into_the_callers_order():
+    eq, x, i = 7, 8, 1                                                      # the BAM op codes
+    keep = np.array([[1, 0], [0, 0], [0, 1]], np.int32)
+    n_ops = np.array([[3, 2], [1, 0], [0, 1]], np.int32)                    # a count in a slot that is not kept is not looked at
+    runs = np.zeros((3, 2, 4), np.uint32)
+    runs[0, 0, :3] = [(5 << 4) | eq, (1 << 4) | x, (26 << 4) | eq]
+    runs[0, 1, :2] = [(7 << 4) | i, (7 << 4) | i]
+    runs[2, 1, :2] = [(32 << 4) | eq, (9 << 4) | x]                         # beyond its count: not part of the script
+    idx = np.array([6, 2, 3])
+    cigars = [[None, None] for _ in range(8)]
+    cigars[5][1] = "kept"
+    RM.decode_cigars("map_reads_ragged", keep, n_ops, runs, 4, idx, cigars)
+    want = [[None, None] for _ in range(8)]
+    want[6][0], want[3][1], want[5][1] = "5=1X26=", "32=", "kept"
+    assert cigars == want
+    n_ops[2, 1] = 5
+    with pytest.raises(B.BgsaHipError) as e:
+        RM.decode_cigars("map_reads_seeded_ragged", keep, n_ops, runs, 4, idx, [[None, None] for _ in range(8)])
+    assert str(e.value) == "map_reads_seeded_ragged: hit 1 of read 3 has 5 runs, its row holds 4 (raise cigar_cap)"
+
+
+def hand_made_hits(ns, k_sel, base):
+    grid = base + np.arange(ns * k_sel).reshape(ns, k_sel)
+    return B.ReferenceHits(grid.astype(np.int32), (grid + 1).astype(np.int32), (grid + 2).astype(np.int64), (grid + 3).astype(np.int64),
+                           (grid + 4).astype(np.int32), [[f"{base}:{c}:{r}" for r in range(k_sel)] for c in range(ns)],
+                           (grid + 5).astype(np.int32))
+
+
+def test_the_fallback_lands_in_its_rows_and_nowhere_else():
+    out, before, full = hand_made_hits(6, 2, 0), hand_made_hits(6, 2, 0), hand_made_hits(2, 2, 1000)
+    RM.merge_fallback(out, np.array([4, 1]), full)
+    for name in B.ReferenceHits._fields:
+        got, old, new = getattr(out, name), getattr(before, name), getattr(full, name)
+        for c in range(6):
+            want = new[[4, 1].index(c)] if c in (4, 1) else old[c]
+            assert np.array_equal(got[c], want), (name, c)
+        if name != "cigars":
+            assert got.dtype == old.dtype
+
+
+def test_seed_stats_has_the_two_key_sets():
+    flags = np.array([5, 0, -1, -2, -2, -3, 17], np.int32)
+    one = RM.seed_stats(flags, (40, 30, 7), 6, 256)
+    assert one == dict(reads_seeded=3, reads_fallback_n=1, reads_fallback_cap=2, candidates_emitted=40, candidates_unique=30,
+                       candidates_within_bound=7, seed_len=6, max_candidates=256)
+    assert all(type(v) is int for v in one.values())
+    bins = [dict(words=1, reads=7, q=6, emitted=40, unique=30)]
+    for seed_len in (None, 6):
+        mixed = RM.seed_stats(flags, [40, 30, 7], seed_len, 256, bins)
+        assert mixed == dict(reads_seeded=3, reads_fallback_n=1, reads_fallback_cap=2, reads_fallback_short=1, candidates_emitted=40,
+                             candidates_unique=30, candidates_within_bound=7, seed_len=seed_len, max_candidates=256, bins=bins)

@@ -273,6 +273,27 @@ def test_max_distance_none_places_every_selected_hit(case):
     assert ((got.windows >= 0) == (got.ref_begin >= 0)).all()
 
 
+def test_map_reads_takes_reads_beyond_1024_bp(torch_gpu):
+    """33 words: the three other entry points refuse such a read, map_reads does not."""
+    ref_len, w_len, stride, n, bound, edits = 3000, 1200, 100, 1056, 8, 3
+    rng = np.random.default_rng(1056)
+    ref = ACGT[rng.integers(4, size=ref_len)].copy()
+    begins = (700, 1500)
+    exact = ref[begins[0]: begins[0] + n].copy()
+    edited = np.array(_edit(rng, list(ref[begins[1]: begins[1] + n + edits]), edits, ACGT)[:n], np.uint8)
+    reads = np.stack([exact, M.reverse_complement(edited)])
+    assert B.max_stride(w_len, n, bound) >= stride
+    got = B.ReferenceMapper(ref, w_len, stride).map_reads(reads, k_best=1, max_distance=bound)
+    for c, (strand, planted) in enumerate(((0, 0), (1, edits))):
+        assert got.keep[c, 0] == 1 and got.strand[c, 0] == strand, c
+        begin, end = int(got.ref_begin[c, 0]), int(got.ref_end[c, 0])
+        assert 0 <= begin <= begins[c] + planted and begins[c] + n - planted <= end <= ref_len, (c, begin, end)
+        assert -int(got.scores[c, 0]) <= planted and (planted or got.cigars[c][0] == f"{n}=")
+        runs = [(int(length), CHAR_OP[op]) for length, op in re.findall(r"(\d+)([=XID])", got.cigars[c][0])]
+        read = M.reverse_complement(reads[c]) if strand else reads[c]
+        T.validate(ref[begin:end], read, T.FREE_QUERY, T.UNIT, int(got.scores[c, 0]), (0, end - begin, 0, n), runs)
+
+
 # ---- 4. one strand ----------------------------------------------------------------------------------------------------------
 def test_forward_strand_only(case):
     both = case["got"]

@@ -322,6 +322,29 @@ def test_select_equals_the_helper(torch_gpu, k):
     assert k == 1 or tied >= 10
 
 
+def test_the_four_steps_compose_to_select_seeded(torch_gpu, case):
+    torch, mapper, reads = torch_gpu, case["mapper"], case["reads"]
+    ns, k_sel = reads.shape[0], mapper.k_selected(3)
+    cap = max(mapper.n_ids // 8, 256)
+    d_rows, d_lens = mapper.aligner._set_bucket(reads, qlen=W)
+    assert d_lens is None
+    want_scores, want_ids, want_counts, _ = mapper.select_seeded(d_rows, ns, N, BOUND, Q, k_sel, cap, block_rows=ns)
+    job = mapper.seed_bucket(d_rows, N, BOUND, Q)
+    scores = torch.full((ns, k_sel), SENT, dtype=torch.int32, device="cuda")
+    ids, counts = torch.full_like(scores, SENT), torch.full((ns,), SENT, dtype=torch.int32, device="cuda")
+    cand_read, cand_window = mapper.seed_candidates(job, 0, ns, cap, counts)
+    pair_read, pair_window = mapper.seed_dedupe(cand_read, cand_window)
+    distance = mapper.seed_verify(job, 0, pair_read, pair_window)
+    mapper.seed_select(job, 0, ns, pair_read, pair_window, distance, k_sel, scores, ids)
+    mapper.aligner.check_faults()
+    seeded = ~case["flagged"]
+    assert cand_read.numel() == sum(len(c) for c, f in zip(case["cands"], case["flagged"]) if not f)
+    assert pair_read.numel() == sum(len(set(c)) for c, f in zip(case["cands"], case["flagged"]) if not f) == distance.numel()
+    for got, want in ((scores, want_scores), (ids, want_ids), (counts, want_counts)):
+        assert got.dtype == want.dtype and torch.equal(got, want)
+    assert np.array_equal(ids.cpu().numpy()[seeded], R.blank(case["full"][3], BOUND)["windows"][seeded])     # and to map_reads' lists
+
+
 # ---- 5. end to end ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("k_best", [1, 3])
 def test_map_reads_seeded_equals_the_blanked_map_reads_and_host_pipeline(case, k_best):
