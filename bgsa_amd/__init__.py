@@ -166,6 +166,13 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
+    # paired reads (the same: an older build lacks them)
+    for name, types, restype in (("bgsa_hip_pair_rescue_slots", [i64, i32, i32, i64], i64),
+                                 ("bgsa_hip_pair_rescue_windows_dev", [i64, i32, i32, vp, vp, vp, vp, i64, i32, i32, i64, vp, vp], i32),
+                                 ("bgsa_hip_pair_select_dev", [vp] * 5 + [i32] + [vp] * 5 + [i32, i64, i64, i64] + [vp] * 8, i32)):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = restype
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -1166,4 +1173,5 @@ def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: 
 
 
 # reads mapped onto one reference: windows cut on the device, both strands, reference coordinates (bgsa_amd/reference.py)
-from .reference import Placement, ReferenceHits, ReferenceMapper, blank_beyond, max_stride, seed_plan, seed_plan_ragged, window_plan  # noqa: E402
+from .reference import (PairedHits, Placement, ReferenceHits, ReferenceMapper, blank_beyond, max_stride, rescue_region,  # noqa: E402
+                        rescue_slots, seed_plan, seed_plan_ragged, window_plan)

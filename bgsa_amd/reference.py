@@ -9,6 +9,11 @@ ONE pipeline maps reads, behind four entry points: check_call refuses, a plan na
 ReferenceMapper._map_bins runs every bin as one bucket (_map_bucket: upload, select_windows or select_seeded, place_hits) and
 scatters it into the caller's order (decode_cigars), and the seeded entry points send the reads their filter does not cover through
 the exhaustive entry point of the same kind (merge_fallback, seed_stats).  The helpers at module level need no device.
+
+Paired reads (include/bgsa_hip.h "paired reads") are that pipeline with a second source of candidates:
+map_pairs maps each end through map_reads_seeded (or map_reads), then per end joins the windows its mate's hits point at
+(rescue_slots, rescue_region, pair_rescue_windows) to the end's own, runs the seeded steps and place_hits on the union at the
+rescue bound, and chooses the best proper pair on the device (pair_select); check_pair_call makes every refusal first.
 """
 from __future__ import annotations
 
@@ -102,6 +107,78 @@ def blank_beyond(hits: "ReferenceHits", bound: int) -> "ReferenceHits":
                          np.where(gone, 0, hits.keep).astype(np.int32), cigars, np.where(gone, -1, hits.windows).astype(np.int32))
 
 
+def rescue_slots(ref_len: int, window_len: int, stride: int, insert_max: int) -> int:
+    """R of include/bgsa_hip.h "paired reads": the most rescue windows one anchor can name, min(n_windows, ceil((insert_max + W - 1)
+    / S) + 1) — a region is at most insert_max long, so the starts of the windows that meet it lie in a range of insert_max + W - 1
+    bases: that many strides' worth of regular windows, and the anchored last one.  Pure Python: no device, no library."""
+    n_windows = window_plan(ref_len, window_len, stride)[0]
+    if int(insert_max) < 1:
+        raise B.BgsaHipError("rescue_slots: rc=-1: insert_max is not positive")
+    return min(n_windows, -(-(int(insert_max) + int(window_len) - 1) // int(stride)) + 1)
+
+
+def rescue_region(strand: int, begin: int, end: int, insert_max: int, ref_len: int) -> tuple[int, int]:
+    """[lo, hi) on the forward reference in which the mate of an anchor on `strand` with interval [begin, end) lies (library type FR:
+    the mate is on strand 1 - strand, the forward-strand mate upstream): [begin, min(L, begin + insert_max)) behind a forward
+    anchor, [max(0, end - insert_max), end) in front of a reverse one.  Pure Python: no device, no library."""
+    if int(strand) == 0:
+        return int(begin), min(int(ref_len), int(begin) + int(insert_max))
+    return max(0, int(end) - int(insert_max)), int(end)
+
+
+def check_pair_call(both_strands: bool, shape1, shape2, insert_min, insert_max, k_best, max_distance, rescue_distance, seeded: bool,
+                    seed_len, max_candidates, cigar_cap, window_len: int, stride: int, ref_len: int, n_ids: int) -> dict:
+    """Every refusal of map_pairs, in one order: a mapper of one strand, unequal row counts, the insert range, a missing
+    max_distance, rescue_distance below max_distance, the stride rule at rescue_distance for end 1 then end 2, k_pair beyond 64 —
+    the message names the largest k_best and the largest insert_max that fit —, then what the per-end entry point refuses
+    (check_call, end 1 then end 2: the 1,024 bp limit, k_best, a negative bound, the seed plan, cigar_cap, max_candidates).
+    shape_e = (ns, n_e).  Returns what the stages need: k_best, k_sel, R, k_pair, rescue_distance, and per end the rescue bound
+    and the cigar cap.  Nothing is launched or allocated here, so a refused call leaves the mapper as it was."""
+    who = "map_pairs"
+    W, S = int(window_len), int(stride)
+    if not both_strands:
+        raise B.BgsaHipError(f"{who}: rc=-1: the mates of a pair lie on opposite strands: the mapper needs both_strands=True")
+    if shape1[0] != shape2[0]:
+        raise B.BgsaHipError(f"{who}: rc=-1: row c of both arrays is pair c, got {shape1[0]} and {shape2[0]} rows")
+    if not 1 <= int(insert_min) <= int(insert_max) <= INT32_MAX:
+        raise B.BgsaHipError(f"{who}: rc=-1: needs 1 <= insert_min <= insert_max, got {insert_min} and {insert_max}")
+    if max_distance is None:
+        raise B.BgsaHipError(f"{who}: rc=-1: max_distance is required: the single-end lists and the rescue bound are derived from it")
+    rescue_distance = int(max_distance) if rescue_distance is None else int(rescue_distance)
+    if rescue_distance < int(max_distance):
+        raise B.BgsaHipError(f"{who}: rc=-1: rescue_distance {rescue_distance} is below max_distance {int(max_distance)}")
+    lens = (int(shape1[1]), int(shape2[1]))
+    for e, n in enumerate(lens, start=1):
+        largest = max_stride(W, n, rescue_distance)
+        if S > largest:
+            allowed = f"the largest stride allowed is {largest}" if largest >= 1 else "no stride is (a longer window)"
+            raise B.BgsaHipError(f"{who}: rc=-1: at stride {S} a placement of end {e} ({n} bp) within rescue_distance {min(rescue_distance, n)} "
+                                 f"can lie in no window of {W} bp: {allowed}")
+    n_windows = window_plan(ref_len, W, S)[0]
+    per_locus = -(-W // S) + 1
+
+    def k_pair_of(k: int, slots: int) -> int:
+        return min(B.V_NUM, k * per_locus) + k * slots
+    k_best, R = int(k_best), rescue_slots(ref_len, W, S, insert_max)
+    k_sel, k_pair = min(B.V_NUM, max(k_best, 0) * per_locus), k_pair_of(max(k_best, 0), R)
+    if k_pair > B.V_NUM:
+        fits = max((k for k in range(1, min(k_best, B.V_NUM)) if k_pair_of(k, R) <= B.V_NUM), default=0)
+        room = (B.V_NUM - k_sel) // k_best      # rescue slots per anchor that fit beside the single-end list
+        widest = int(insert_max) if n_windows <= room else (room - 1) * S - W + 1
+        by_k = f"at insert_max {int(insert_max)} the largest k_best is {fits}" if fits else f"no k_best fits insert_max {int(insert_max)}"
+        by_insert = f"at k_best {k_best} the largest insert_max is {widest}" if room >= 1 and widest >= 1 else f"no insert_max fits k_best {k_best}"
+        raise B.BgsaHipError(f"{who}: rc=-1: k_pair = k_sel + k_best * R = {k_sel} + {k_best} * {R} = {k_pair} slots per end exceed "
+                             f"{B.V_NUM}: {by_k}; {by_insert}")
+    bounds, caps = [], []
+    for n in lens:
+        plan = (lambda limit, n=n: seed_plan(n, limit, seed_len)) if seeded else None
+        cap = check_call(who, n, False, k_best, max_distance, seeded, cigar_cap, max_candidates, W, S, ref_len, n_ids, True, plan)[2]
+        bounds.append(min(rescue_distance, n))
+        caps.append(cap)
+    return dict(k_best=k_best, k_sel=k_sel, rescue_slots=R, k_pair=k_pair, rescue_distance=rescue_distance, bounds=tuple(bounds),
+                caps=tuple(caps))
+
+
 class ReferenceHits(NamedTuple):
     """What ReferenceMapper.map_reads returns, numpy, one row per read and one column per selected hit, best first."""
     scores: np.ndarray      # [ns, k_sel] int32: minus the distance of the read inside its r-th best window; INT32_MIN = unused slot
@@ -119,6 +196,21 @@ class Placement(NamedTuple):
     ref_end: int
     distance: int
     cigar: str
+
+
+class PairedHits(NamedTuple):
+    """What ReferenceMapper.map_pairs returns, numpy, one row per pair (include/bgsa_hip.h "paired reads")."""
+    end1: ReferenceHits     # end 1's final list, k_pair wide: its single-end hits and the rescued ones, best first
+    end2: ReferenceHits
+    rescued1: np.ndarray    # [ns, k_pair] bool: the slot's window is not among the end's single-end windows
+    rescued2: np.ndarray
+    proper: np.ndarray      # [ns] int32: 1 = a proper combination was chosen
+    slot1: np.ndarray       # [ns] int32: the chosen slot of end1 (not proper: its first kept slot), -1 = none
+    slot2: np.ndarray
+    insert: np.ndarray      # [ns] int64: R.end - F.begin of the chosen combination, 0 when not proper
+    cost: np.ndarray        # [ns] int32: d1 + d2 of the chosen slots
+    n_best: np.ndarray      # [ns] int32: the proper combinations at the chosen cost
+    next_cost: np.ndarray   # [ns] int32: the smallest proper cost above the chosen one, -1 = none
 
 
 # ---- the host side of the four map_reads entry points: no device, no library ---------------------------------------------------
@@ -260,6 +352,7 @@ class ReferenceMapper:
         self.seed_indexes = {}  # seed_len -> (offsets, positions) device tensors (map_reads_seeded builds them on first use)
         self.d_verify_work = None   # the carries of a verify beyond 16 words, grown on demand
         self.last_seed_stats = None
+        self.last_pair_stats = None
 
     def _rows_buffer(self, n_rows: int):
         need = n_rows * (self.window_len + 1) + 8
@@ -612,6 +705,154 @@ class ReferenceMapper:
         limit = None if max_distance is None else int(max_distance)
         plan = [(idx, None) for idx in B.bin_by_words(lens)]
         return self._map_bins("map_reads_ragged", rows, lens, plan, self.k_selected(k_best), limit, cap, block_rows)[0]
+
+    # ---- paired reads: include/bgsa_hip.h "paired reads" --------------------------------------------------------------------
+    # The steps of map_pairs' stage B for the pairs [lo, hi) of one end's resident bucket: pair_rescue_windows -> pair_union ->
+    # seed_dedupe -> seed_verify -> seed_select, then place_hits over the whole end; stage C is pair_select.
+    # scripts/measure_pair_map.py times these same methods.
+    def verify_bucket(self, d_rows, read_len: int, bound: int) -> SeedBucket:
+        """What seed_verify and seed_select need of a resident bucket of one read length, without an index: the bucket's rows, its
+        width, the bound the selection keeps and the equal-length verify call."""
+        return SeedBucket(d_rows, int(read_len), int(bound), None, None, None, B.lib().bgsa_hip_reference_verify_pairs_dev, lambda lo, hi: (), ())
+
+    def pair_rescue_windows(self, anchors, lo: int, hi: int, k_anchor: int, insert_max: int):
+        """Step 1: the rescue windows of the pairs [lo, hi).  anchors = the mate's (strand, ref_begin, ref_end, keep) as device tensors
+        [ns, k].  Returns int32[hi - lo, k_anchor * R]: ids ascending within an anchor's group of R, -1 elsewhere."""
+        a = self.aligner
+        strand, ref_begin, ref_end, keep = anchors
+        slots = rescue_slots(self.ref_len, self.window_len, self.stride, insert_max)
+        rescue = a.torch.empty((hi - lo, int(k_anchor) * slots), dtype=a.torch.int32, device=a.device)
+        B.check(B.lib().bgsa_hip_pair_rescue_windows_dev(self.ref_len, self.window_len, self.stride, strand[lo:hi].data_ptr(),
+                                                         ref_begin[lo:hi].data_ptr(), ref_end[lo:hi].data_ptr(), keep[lo:hi].data_ptr(), hi - lo,
+                                                         strand.shape[1], int(k_anchor), int(insert_max), rescue.data_ptr(), a._stream()),
+                "pair_rescue_windows_dev")
+        return rescue
+
+    def pair_union(self, own_ids, rescue):
+        """Step 2: an end's own window ids [n, k_sel] and its rescue windows [n, k_anchor * R] as one candidate list (cand_read
+        int32: the pair's index in the block, cand_window int32), the unused entries (-1) left out; seed_dedupe sorts it and
+        keeps every id once."""
+        torch = self.aligner.torch
+        both = torch.cat((own_ids, rescue), dim=1)
+        rows = torch.arange(both.shape[0], dtype=torch.int32, device=both.device).unsqueeze(1).expand_as(both)
+        used = both >= 0
+        return rows[used], both[used]
+
+    def rescue_end(self, reads: np.ndarray, own: ReferenceHits, mate: ReferenceHits, k_best: int, k_pair: int, insert_max: int, bound: int,
+                   cap: int, block_rows: int = 1000):
+        """Stage B for one end: the bucket uploaded, block_rows pairs at a time the rescue windows of the mate's anchors joined to
+        the end's own ids, verified and selected within `bound`, then placed.  Returns device tensors — (scores, strand, ref_begin,
+        ref_end, keep, ids, rescued: all [ns, k_pair]), n_ops, cigar — and four device scalars: the anchors, the rescue windows
+        emitted, the unique pairs verified, the slots rescued."""
+        a = self.aligner
+        torch, dev = a.torch, a.device
+        ns, n = reads.shape
+        d_rows, _ = a._set_bucket(reads, None, qlen=self.window_len)
+        job = self.verify_bucket(d_rows, n, bound)
+        own_ids = torch.from_numpy(np.ascontiguousarray(own.windows)).to(dev)
+        anchors = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (mate.strand, mate.ref_begin, mate.ref_end, mate.keep))
+        scores = torch.empty((ns, k_pair), dtype=torch.int32, device=dev)
+        ids = torch.empty((ns, k_pair), dtype=torch.int32, device=dev)
+        rescued = torch.empty((ns, k_pair), dtype=torch.bool, device=dev)
+        emitted = torch.zeros((), dtype=torch.int64, device=dev)
+        verified = torch.zeros_like(emitted)
+        block = max(1, min(int(block_rows), ns))
+        for lo in range(0, ns, block):
+            hi = min(lo + block, ns)
+            rescue = self.pair_rescue_windows(anchors, lo, hi, k_best, insert_max)
+            cand_read, cand_window = self.pair_union(own_ids[lo:hi], rescue)
+            pair_read, pair_window = self.seed_dedupe(cand_read, cand_window)
+            distance = self.seed_verify(job, lo, pair_read, pair_window)
+            self.seed_select(job, lo, hi, pair_read, pair_window, distance, k_pair, scores, ids)
+            rescued[lo:hi] = (ids[lo:hi] >= 0) & ~(ids[lo:hi, :, None] == own_ids[lo:hi, None, :]).any(dim=2)
+            emitted += (rescue >= 0).sum()
+            verified += pair_read.numel()
+        strand, ref_begin, ref_end, keep, n_ops, cigar = self.place_hits(ids, bound, cap, block_rows)
+        n_anchors = (anchors[3] != 0).sum(dim=1).clamp(max=k_best).sum()
+        return (scores, strand, ref_begin, ref_end, keep, ids, rescued), n_ops, cigar, (n_anchors, emitted, verified, rescued.sum())
+
+    def pair_select(self, one, two, insert_min: int, insert_max: int, block_rows: int = 1000):
+        """Stage C: the best proper combination of every pair.  one, two = (scores, strand, ref_begin, ref_end, keep) of the two
+        ends' final lists, device tensors [ns, k].  Returns device tensors (proper, slot1, slot2, insert int64, cost, n_best,
+        next_cost), int32 unless said, one entry per pair."""
+        a = self.aligner
+        torch, dev = a.torch, a.device
+        ns = one[0].shape[0]
+        out = [torch.empty(ns, dtype=torch.int64 if i == 3 else torch.int32, device=dev) for i in range(7)]
+        block = max(1, min(int(block_rows), ns))
+        for lo in range(0, ns, block):
+            hi = min(lo + block, ns)
+            B.check(B.lib().bgsa_hip_pair_select_dev(*(x[lo:hi].data_ptr() for x in one), one[0].shape[1],
+                                                     *(x[lo:hi].data_ptr() for x in two), two[0].shape[1], hi - lo, int(insert_min),
+                                                     int(insert_max), *(x[lo:hi].data_ptr() for x in out), a._stream()), "pair_select_dev")
+        return tuple(out)
+
+    def map_pairs(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, k_best: int = 1, max_distance=None,
+                  rescue_distance=None, seeded: bool = True, seed_len=None, max_candidates=None, block_rows: int = 1000,
+                  cigar_cap=None) -> PairedHits:
+        """Paired-end mapping, library type FR (include/bgsa_hip.h "paired reads"): reads1[ns, n1] and reads2[ns, n2] uint8 ASCII,
+        row c of both is pair c; the lengths may differ, each in 1..1,024.
+        Stage A maps each end alone: map_reads_seeded(reads_e, k_best, max_distance, ...), or with seeded=False map_reads blanked
+        beyond min(max_distance, n_e) — the same lists.  Stage B gives every end a second source of candidates: the windows that
+        meet the regions its mate's first k_best kept hits point at (rescue_region; at most R = rescue_slots(...) per anchor), joined
+        to the end's own windows, verified exactly, the k_pair = k_sel + k_best * R best within min(rescue_distance, n_e) selected
+        and placed within that bound.  So the copy of a repeat beside a unique mate, and a mate with more than max_distance edits,
+        are found without raising the bound — and with it shortening the seed — for every read.  Stage C chooses, per pair, the
+        proper combination of the two final lists of least cost d1 + d2, ties by (slot1, slot2).
+        rescue_distance=None: max_distance.  Refused before anything is launched or allocated (check_pair_call states the order): a
+        mapper of one strand, unequal row counts, a bad insert range, a missing max_distance, rescue_distance < max_distance, a
+        stride above max_stride(window_len, n_e, rescue_distance), k_pair > 64 (nothing is truncated silently), and what
+        map_reads_seeded / map_reads refuse.  block_rows, seed_len and max_candidates never change a result.
+        last_pair_stats says what happened; with seeded=True its key seed holds the two ends' last_seed_stats."""
+        who = "map_pairs"
+        reads = (self._one_length(who, reads1), self._one_length(who, reads2))
+        call = check_pair_call(self.both_strands, reads[0].shape, reads[1].shape, insert_min, insert_max, k_best, max_distance,
+                               rescue_distance, seeded, seed_len, max_candidates, cigar_cap, self.window_len, self.stride, self.ref_len,
+                               self.n_ids)
+        a = self.aligner
+        k_best, k_pair, limit = call["k_best"], call["k_pair"], int(max_distance)
+        single, seed = [], []
+        for rows in reads:      # stage A: the existing entry points, their fallbacks and stats included
+            if seeded:
+                single.append(self.map_reads_seeded(rows, k_best, limit, seed_len, max_candidates, block_rows, cigar_cap))
+                seed.append(self.last_seed_stats)
+            else:
+                single.append(blank_beyond(self.map_reads(rows, k_best, limit, block_rows, cigar_cap), min(limit, rows.shape[1])))
+        ends, lists, counts = [], [], []
+        for e, rows in enumerate(reads):      # stage B: end e's bucket resident, its mate's lists as anchors
+            final, n_ops, cigar, seen = self.rescue_end(rows, single[e], single[1 - e], k_best, k_pair, int(insert_max), call["bounds"][e],
+                                                        call["caps"][e], block_rows)
+            a.check_faults()
+            arrays = tuple(x.cpu().numpy() for x in final)
+            cigars = [[None] * k_pair for _ in range(rows.shape[0])]
+            decode_cigars(who, arrays[4], n_ops.cpu().numpy(), cigar.cpu().numpy().view(np.uint32), call["caps"][e], np.arange(rows.shape[0]),
+                          cigars)
+            ends.append((ReferenceHits(*arrays[:5], cigars, arrays[5]), arrays[6]))
+            lists.append(final)
+            counts.append(seen)
+        chosen = self.pair_select(lists[0][:5], lists[1][:5], insert_min, insert_max, block_rows)      # stage C
+        # ... and once more without the rescued slots: the pairs that are proper only through one of them
+        plain = self.pair_select(*((*x[:4], x[4] * (~x[6]).to(x[4].dtype)) for x in lists), insert_min, insert_max, block_rows)
+        a.check_faults()
+        proper, slot1, slot2, insert, cost, n_best, next_cost = (x.cpu().numpy() for x in chosen)
+        totals = [int(sum(seen[i] for seen in counts).item()) for i in range(4)]
+        self.last_pair_stats = dict(pairs=int(proper.size), anchors=totals[0], rescue_windows=totals[1], pairs_verified=totals[2],
+                                    slots_rescued=totals[3], proper=int(proper.sum()),
+                                    proper_through_rescue=int(((chosen[0] == 1) & (plain[0] == 0)).sum().item()), k_pair=k_pair,
+                                    rescue_slots=call["rescue_slots"], rescue_distance=call["rescue_distance"],
+                                    seed=tuple(seed) if seeded else None)
+        return PairedHits(ends[0][0], ends[1][0], ends[0][1], ends[1][1], proper, slot1, slot2, insert, cost, n_best, next_cost)
+
+    @staticmethod
+    def pairs_of(paired: PairedHits) -> list:
+        """Per pair (end 1's chosen Placement or None, end 2's, proper): the chosen slots of map_pairs' result — the proper
+        combination, or without one each end's first kept hit — for callers who want no more than that."""
+        def chosen(hits: ReferenceHits, c: int, r: int):
+            if r < 0:
+                return None
+            return Placement(int(hits.strand[c, r]), int(hits.ref_begin[c, r]), int(hits.ref_end[c, r]), -int(hits.scores[c, r]), hits.cigars[c][r])
+        return [(chosen(paired.end1, c, int(paired.slot1[c])), chosen(paired.end2, c, int(paired.slot2[c])), bool(paired.proper[c]))
+                for c in range(paired.proper.shape[0])]
 
     @staticmethod
     def placements_of(hits: ReferenceHits, k_best: int = 1) -> list:

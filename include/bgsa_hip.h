@@ -788,6 +788,67 @@ int bgsa_hip_reference_verify_pairs_lens_dev(const char *d_reference, int64_t re
 int bgsa_hip_seed_select_dev(const int32_t *d_cand_window, const int32_t *d_cand_distance, const int64_t *d_segments, int64_t n_reads,
                              int max_distance, int k, int32_t *d_hit_scores, int32_t *d_hit_windows, void *stream);
 
+/* ---- paired reads: the windows a mate can lie in, given the other end's placement, and the choice of the best proper pair ----
+ * The calls above treat a read as a single end.  These two name, for an end of a pair, the windows next to its mate's placements
+ * (so that the copy of a repeat beside a unique mate, or a mate beyond the single-end bound, is verified at all) and choose the
+ * best proper combination of the two ends' lists.  Verification, selection and placement of the windows named here are
+ * bgsa_hip_reference_verify_pairs_dev, bgsa_hip_seed_select_dev and bgsa_hip_reference_placements_dev, unchanged.
+ * DEFINITIONS (normative; bgsa_amd/reference.py: rescue_slots, rescue_region, ReferenceMapper.map_pairs and tests/pair_reference.py
+ * restate them).  Geometry, window ids, strands, keep, k_sel and the stride rule are those of "a reference as the query set": L
+ * mapped bytes, W the window length, S the stride.  Library type FR only: the mates lie on opposite strands and the forward-strand
+ * mate is upstream.
+ *   inputs     reads1[ns][n1] and reads2[ns][n2], one length per end, each in 1..1,024; row c of both is pair c.  1 <= insert_min
+ *              <= insert_max.  k_best and max_distance are required; rescue_distance >= max_distance (default: max_distance).
+ *   stage A    each end alone: H_e = the seeded mapping of reads_e at (k_best, max_distance), or the exhaustive one with every
+ *              slot beyond min(max_distance, n_e) blanked — the same lists, k_sel wide.
+ *   stage B    the anchors of end e in pair c are the first k_best kept slots of the OTHER end's H, in list order.  An anchor on
+ *              strand s with interval [b, e) puts the mate on strand 1 - s, in the region [b, min(L, b + insert_max)) for s = 0 and
+ *              [max(0, e - insert_max), e) for s = 1.  Its rescue windows are the ids, on the mate's strand, of every forward
+ *              window w with start(w) < region_hi and start(w) + W > region_lo: window starts never decrease, so one contiguous
+ *              id range, of at most R = min(n_windows, ceil((insert_max + W - 1) / S) + 1) ids (attained).  The final list of end
+ *              e in pair c: the union of H_e[c]'s window ids and the rescue windows of all its anchors, each id once, every id
+ *              verified exactly, the k_pair = k_sel + k_best * R best of distance in [0, min(rescue_distance, n_e)] by (distance
+ *              ascending, id ascending) — bgsa_hip_seed_select_dev's order — placed within that bound: a hit list of width k_pair
+ *              with the ordinary keep.  A slot is RESCUED when its id is not among H_e[c]'s.  k_pair > 64 is refused, so nothing
+ *              is truncated and the slots that are not rescued carry H_e[c]'s scores and windows, in order.
+ *   stage C    over the kept slots r1 of end 1's final list and r2 of end 2's, a combination is PROPER when the strands differ
+ *              and, F the forward-strand hit and R the reverse-strand one, F.begin <= R.begin, F.end <= R.end and insert_min <=
+ *              R.end - F.begin <= insert_max.  Its cost is d1 + d2; the chosen one is the minimum by (cost, r1, r2).  Per pair:
+ *              proper (0 | 1), slot1, slot2, insert (R.end - F.begin; 0 when not proper), cost, n_best (the proper combinations
+ *              at the chosen cost), next_cost (the smallest proper cost above it, -1: none).  No proper combination: proper 0,
+ *              slot_e = end e's first kept slot or -1, cost = the sum of the distances of the slots that exist, n_best 0,
+ *              next_cost -1.
+ *   limit      a window reports only its best placement, so a proper placement of a mate can be hidden by an equal or better
+ *              improper one in the same window: the result is what the stages produce.  The stride rule applied at
+ *              rescue_distance guarantees that every placement within that bound that lies wholly in a region lies wholly in at
+ *              least one rescue window.
+ * bgsa_hip_pair_rescue_slots: host only, no device — R; -1 with bgsa_hip_last_error() set for a shape outside 1 <= S <= W <= L
+ * or an insert_max outside [1, 2^31 - 1].
+ * bgsa_hip_pair_rescue_windows_dev: the anchor lists are d_strand / d_ref_begin / d_ref_end / d_keep [n_pairs][k], the layout
+ * bgsa_hip_reference_placements_dev writes.  The r-th slot with keep != 0, r < k_anchor, is anchor r; it fills entries [r * R,
+ * (r + 1) * R) of d_rescue[pair][k_anchor * R] (int32) with its rescue ids ascending, -1 behind them; a pair with fewer anchors
+ * leaves the remaining groups at -1, so every entry of d_rescue is written.  A kept slot whose strand is neither 0 nor 1 or whose
+ * interval is not 0 <= begin <= end <= L is an anchor without a region (a group of -1).  An id is a value and never forms an
+ * address.  k and k_anchor in 1..64.  One wave per pair.
+ * bgsa_hip_pair_select_dev: both ends' final lists (d_scores = minus the distance, d_strand, d_ref_begin, d_ref_end, d_keep; [n_pairs][k1]
+ * and [n_pairs][k2], k1 and k2 in 1..64) and the insert range in, the seven outputs of stage C out (d_insert int64, the others
+ * int32, one entry per pair).  A slot takes part when keep != 0, its strand is 0 or 1, ref_begin >= 0 and its score lies in
+ * [-(2^30 - 1), 0].  One wave per pair: lanes take r1, each lane loops over r2, a wave-wide minimum over the key cost << 12 | r1 << 6
+ * | r2 chooses, a second pass counts.
+ * Both device calls only launch on `stream`: no allocation, no synchronisation; n_pairs == 0 is BGSA_HIP_OK and launches nothing.
+ * BGSA_HIP_EINVAL, checked before the first HIP call: a NULL pointer (the stream excepted), a shape outside 1 <= S <= W <= L,
+ * 2 * n_windows above INT32_MAX, insert_max outside [1, 2^31 - 1], insert_min outside [1, insert_max], k / k_anchor / k1 / k2
+ * outside 1..64, a negative n_pairs. */
+int64_t bgsa_hip_pair_rescue_slots(int64_t ref_len, int window_len, int stride, int64_t insert_max);
+int bgsa_hip_pair_rescue_windows_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_strand, const int64_t *d_ref_begin,
+                                     const int64_t *d_ref_end, const int32_t *d_keep, int64_t n_pairs, int k, int k_anchor,
+                                     int64_t insert_max, int32_t *d_rescue, void *stream);
+int bgsa_hip_pair_select_dev(const int32_t *d_scores1, const int32_t *d_strand1, const int64_t *d_ref_begin1, const int64_t *d_ref_end1,
+                             const int32_t *d_keep1, int k1, const int32_t *d_scores2, const int32_t *d_strand2,
+                             const int64_t *d_ref_begin2, const int64_t *d_ref_end2, const int32_t *d_keep2, int k2, int64_t n_pairs,
+                             int64_t insert_min, int64_t insert_max, int32_t *d_proper, int32_t *d_slot1, int32_t *d_slot2,
+                             int64_t *d_insert, int32_t *d_cost, int32_t *d_n_best, int32_t *d_next_cost, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
