@@ -18,7 +18,7 @@
 //     B = Eq | (D0 & Hp)     diagonal: '=' (1) or 'X' (0); otherwise: up 'I' (1) or left 'D' (0)
 // 8 * word_num bytes per row and pair, laid out [chunk wave][row][vector][word][lane] uint32: every wave store is one
 // coalesced 256-byte row, and a traceback step is two loads and two bit tests.
-#include "pair_trace.h"   // the argument block, owned_pair, the history's addressing and the run-length tail
+#include "pair_trace.h"   // the argument block, owned_pair, the Myers word and the class masks, the history, the chunk loop
 
 namespace bgsa {
 
@@ -66,26 +66,14 @@ __global__ __launch_bounds__(kLanes) void align_pairs_forward_kernel(PairArgs a,
 #pragma unroll 1
         for (int r = 0; r < rows; r++) {
             const uint32_t c = (codes >> (4 * r)) & 15u;
-            // the lane's class as five all-or-nothing masks: the Eq word is a branch-free and/or over the planes
-            const uint32_t k1 = 0u - (c == 1), k2 = 0u - (c == 2), k3 = 0u - (c == 3), k4 = 0u - (c == 4), k0 = ~(k1 | k2 | k3 | k4);
+            const ClassMasks k = class_masks<false>(c);
             uint32_t carry = 0, hp_in = 1, hn_in = 0;
 #pragma unroll
             for (int w = 0; w < NW; w++) {
-                const uint32_t e = (peq[0][w] & k0) | (peq[1][w] & k1) | (peq[2][w] & k2) | (peq[3][w] & k3) | (peq[4][w] & k4);
-                const uint32_t x = pv[w];
-                const unsigned long long s = static_cast<unsigned long long>(x & e) + x + carry;
-                carry = static_cast<uint32_t>(s >> 32);
-                const uint32_t d0 = (static_cast<uint32_t>(s) ^ x) | e | mv[w];
-                const uint32_t hp = ~(d0 | x) | mv[w];
-                const uint32_t hn = d0 & x;
-                const uint32_t hps = (hp << 1) | hp_in;
-                const uint32_t hns = (hn << 1) | hn_in;
-                hp_in = hp >> 31;
-                hn_in = hn >> 31;
-                pv[w] = ~(d0 | hps) | hns;
-                mv[w] = d0 & hps;
-                h[static_cast<size_t>(w) * kLanes] = e | ~d0;
-                h[static_cast<size_t>(wn + w) * kLanes] = e | (d0 & hp);
+                const uint32_t e = class_eq(peq, w, k);
+                const MyersWord s = myers_word(e, pv[w], mv[w], carry, hp_in, hn_in);
+                h[static_cast<size_t>(w) * kLanes] = e | ~s.d0;
+                h[static_cast<size_t>(wn + w) * kLanes] = e | (s.d0 & s.hp);
             }
             h += row_words;
         }
@@ -135,41 +123,18 @@ __global__ __launch_bounds__(kLanes) void align_pairs_traceback_kernel(PairArgs 
     a.n_ops[p] = encode_runs(ops, steps, a.cigar + static_cast<size_t>(p) * a.cigar_cap, a.cigar_cap);
 }
 
-struct PairRun {
-    PairArgs args;
-    size_t workspace_bytes;
-    hipStream_t stream;
-};
-
-// The pair list in chunks of as many whole waves as the workspace holds, one after the other on the stream.
-int run_pairs(void *workspace, void *ctx)
+// One chunk: the forward kernel of the subject's width, then the traceback.
+int launch_pairs(const PairArgs &a, dim3 grid, int64_t first, hipStream_t stream)
 {
-    const PairRun &r = *static_cast<const PairRun *>(ctx);
-    PairArgs a = r.args;
-    a.workspace = static_cast<unsigned char *>(workspace);
-    int64_t chunk_waves = static_cast<int64_t>(r.workspace_bytes / a.wave_bytes);
-    if (chunk_waves > kMaxChunkWaves) chunk_waves = kMaxChunkWaves;
-    for (int64_t first = 0; first < a.n_pairs; first += chunk_waves * kLanes) {
-        const int64_t left = (a.n_pairs - first + kLanes - 1) / kLanes;
-        const dim3 grid(static_cast<unsigned>(left < chunk_waves ? left : chunk_waves));
-        const int rc = PairWidths::dispatch(a.word_num, "myers_align_pairs", [&](auto width) {
-            hipLaunchKernelGGL((align_pairs_forward_kernel<decltype(width)::value>), grid, dim3(kLanes), 0, r.stream, a, first);
-            BGSA_HIP_TRY(hipGetLastError());
-            return BGSA_HIP_OK;
-        });
-        if (rc) return rc;
-        hipLaunchKernelGGL(align_pairs_traceback_kernel, grid, dim3(kLanes), 0, r.stream, a, first);
+    const int rc = PairWidths::dispatch(a.word_num, "myers_align_pairs", [&](auto width) {
+        hipLaunchKernelGGL((align_pairs_forward_kernel<decltype(width)::value>), grid, dim3(kLanes), 0, stream, a, first);
         BGSA_HIP_TRY(hipGetLastError());
-    }
+        return BGSA_HIP_OK;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(align_pairs_traceback_kernel, grid, dim3(kLanes), 0, stream, a, first);
+    BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
-}
-
-int refuse(int rc, const char *why)
-{
-    char msg[200];
-    snprintf(msg, sizeof msg, "myers_align_pairs_dev: %s", why);
-    set_error_text(msg);
-    return rc;
 }
 
 }  // namespace
@@ -189,11 +154,7 @@ size_t bgsa_hip_align_pairs_min_workspace_bytes(int ref_len, int read_len)
 size_t bgsa_hip_align_pairs_workspace_bytes(int ref_len, int read_len, int64_t n_pairs)
 {
     if (ref_len <= 0 || read_len <= 0 || n_pairs < 0) return 0;
-    const size_t per = pair_wave_bytes(ref_len, read_len);
-    const size_t cap = BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE;
-    const unsigned long long waves = n_pairs > 0 ? (static_cast<unsigned long long>(n_pairs) + kLanes - 1) / kLanes : 1;
-    const size_t want = waves > cap / per ? cap : static_cast<size_t>(waves) * per;   // min(all pairs in one pass, the cap)
-    return want > per ? want : per;                                                    // one wave always fits
+    return pair_workspace_for(pair_wave_bytes(ref_len, read_len), n_pairs);
 }
 
 int bgsa_hip_myers_align_pairs_dev(const char *d_content, const hip_read_t *d_peq, int ref_len, int read_len, int64_t read_count,
@@ -212,32 +173,25 @@ int bgsa_hip_myers_align_pairs_lens_dev(const char *d_content, const hip_read_t 
                                         int32_t *d_distance, int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap, void *d_workspace,
                                         size_t workspace_bytes, void *stream)
 {
-    if (!d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_distance || !d_n_ops || !d_cigar)
-        return refuse(BGSA_HIP_EINVAL, "a NULL pointer (only the workspace may be NULL)");
-    if (n_pairs < 0) return refuse(BGSA_HIP_EINVAL, "n_pairs is negative");
-    if (ref_len <= 0 || read_len <= 0 || n_queries <= 0 || cigar_cap <= 0)
-        return refuse(BGSA_HIP_EINVAL, "ref_len, read_len, n_queries and cigar_cap must be positive");
-    if (read_count <= 0 || read_count % HIP_V_NUM != 0) return refuse(BGSA_HIP_EINVAL, "read_count must be a positive multiple of 64");
+    const char *who = "myers_align_pairs_dev";
+    if (int rc = check_pair_call(who, !d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_distance || !d_n_ops || !d_cigar,
+                                 "a NULL pointer (only the workspace may be NULL)", n_pairs, ref_len, read_len, n_queries, cigar_cap, read_count))
+        return rc;
     if (word_num != bgsa_hip_word_num(BGSA_ALGO_MYERS, ref_len, read_len, 0))
-        return refuse(BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(BGSA_ALGO_MYERS, ...)");
-    if (word_num > kMaxWords) return refuse(BGSA_HIP_EUNSUPPORTED, "subjects beyond 1,024 bp (word_num > 32) are not covered");
+        return refuse(who, BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(BGSA_ALGO_MYERS, ...)");
+    if (word_num > kMaxWords) return refuse(who, BGSA_HIP_EUNSUPPORTED, "subjects beyond 1,024 bp (word_num > 32) are not covered");
     const size_t per = pair_wave_bytes(ref_len, read_len);
-    if (d_workspace && workspace_bytes < per)
-        return refuse(BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_align_pairs_min_workspace_bytes()");
+    if (d_workspace && workspace_bytes < per) return refuse(who, BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_align_pairs_min_workspace_bytes()");
     if (n_pairs == 0) return BGSA_HIP_OK;
 
-    PairRun r{};
-    r.args = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
-                      subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), nullptr, d_read_lens};
-    r.stream = static_cast<hipStream_t>(stream);
-    r.args.fault_word = device_fault_word();
-    if (!r.args.fault_word) return BGSA_HIP_EHIP;
-    if (d_workspace) {
-        r.workspace_bytes = workspace_bytes;
-        return run_pairs(d_workspace, &r);
-    }
-    r.workspace_bytes = bgsa_hip_align_pairs_workspace_bytes(ref_len, read_len, n_pairs);
-    return with_own_scratch(r.stream, r.workspace_bytes, run_pairs, &r);
+    PairArgs args{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
+                  subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), device_fault_word(), d_read_lens};
+    if (!args.fault_word) return BGSA_HIP_EHIP;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return run_pair_chunks(d_workspace, workspace_bytes, per, n_pairs, s, [&](unsigned char *workspace, dim3 grid, int64_t first) {
+        args.workspace = workspace;
+        return launch_pairs(args, grid, first, s);
+    });
 }
 
 }  // extern "C"

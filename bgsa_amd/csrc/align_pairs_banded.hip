@@ -15,6 +15,8 @@
 // popc(pv & mask) - popc(mv & mask) >= D, and D' <= B certifies D' = D.  A certified pair is traced back from (m, n) through
 // the two history vectors of align_pairs.hip (A = Eq | ~D0, B = Eq | (D0 & Hp)) with the same preference, so the script is
 // that call's; any other pair is beyond the bound.  The windows depend on (m, n, B) only: they are wave-uniform.
+// The row's word is myers_word of bgsa_common.h; the class masks and the score of the stored state are class_masks and
+// state_score of pair_trace.h.
 //
 // One wave's slice: [history][state][op bytes].
 //   history  [row][vector A|B][window word][lane] uint32, the word stride band_words = the widest block window of the shape;
@@ -107,10 +109,7 @@ __global__ __launch_bounds__(kLanes) void align_pairs_banded_forward_kernel(Band
     unsigned char *slice = a.workspace + static_cast<size_t>(blockIdx.x) * a.wave_bytes;
     uint32_t *h = reinterpret_cast<uint32_t *>(slice) + lane;
     uint32_t *state = reinterpret_cast<uint32_t *>(slice + g.state_off) + lane;   // [pv | mv][word][lane]
-    for (int w = 0; w < wn; w++) {
-        state[static_cast<size_t>(w) * kLanes] = ~0u;
-        state[static_cast<size_t>(wn + w) * kLanes] = 0u;
-    }
+    state_init(state, wn);
 
     const unsigned char *row = reinterpret_cast<const unsigned char *>(a.content) + static_cast<size_t>(q) * (m + 1);
     const size_t row_words = static_cast<size_t>(2) * g.band_words * kLanes;
@@ -146,29 +145,15 @@ __global__ __launch_bounds__(kLanes) void align_pairs_banded_forward_kernel(Band
 
 #pragma unroll 1
         for (int r = 0; r < rows; r++) {
-            const uint32_t c = static_cast<uint32_t>(lo) & 15u;
-            lo = (lo >> 4) | (hi << 60);
-            hi >>= 4;
-            const uint32_t k1 = 0u - (c == 1), k2 = 0u - (c == 2), k3 = 0u - (c == 3), k4 = 0u - (c == 4), k0 = ~(k1 | k2 | k3 | k4);
+            const ClassMasks k = class_masks<false>(next_class(lo, hi));
             uint32_t carry = 0, hp_in = 1, hn_in = 0;
 #pragma unroll
             for (int w = 0; w < WB; w++) {
                 if (w < wb) {   // a window narrower than WB runs its own words only
-                    const uint32_t e = (peq[0][w] & k0) | (peq[1][w] & k1) | (peq[2][w] & k2) | (peq[3][w] & k3) | (peq[4][w] & k4);
-                    const uint32_t x = pv[w];
-                    const unsigned long long s = static_cast<unsigned long long>(x & e) + x + carry;
-                    carry = static_cast<uint32_t>(s >> 32);
-                    const uint32_t d0 = (static_cast<uint32_t>(s) ^ x) | e | mv[w];
-                    const uint32_t hp = ~(d0 | x) | mv[w];
-                    const uint32_t hn = d0 & x;
-                    const uint32_t hps = (hp << 1) | hp_in;
-                    const uint32_t hns = (hn << 1) | hn_in;
-                    hp_in = hp >> 31;
-                    hn_in = hn >> 31;
-                    pv[w] = ~(d0 | hps) | hns;
-                    mv[w] = d0 & hps;
-                    h[static_cast<size_t>(w) * kLanes] = e | ~d0;
-                    h[static_cast<size_t>(g.band_words + w) * kLanes] = e | (d0 & hp);
+                    const uint32_t e = class_eq(peq, w, k);
+                    const MyersWord s = myers_word(e, pv[w], mv[w], carry, hp_in, hn_in);
+                    h[static_cast<size_t>(w) * kLanes] = e | ~s.d0;
+                    h[static_cast<size_t>(g.band_words + w) * kLanes] = e | (s.d0 & s.hp);
                 }
             }
             h += row_words;
@@ -183,12 +168,7 @@ __global__ __launch_bounds__(kLanes) void align_pairs_banded_forward_kernel(Band
         }
     }
 
-    int score = m;
-    for (int w = 0; w < wn; w++) {
-        const int rem = n - 32 * w;
-        const uint32_t mask = rem >= 32 ? ~0u : ((1u << rem) - 1u);   // rem >= 1: w < word_num
-        score += __popc(state[static_cast<size_t>(w) * kLanes] & mask) - __popc(state[static_cast<size_t>(wn + w) * kLanes] & mask);
-    }
+    const int score = state_score(state, wn, n, m);
     const bool certified = score <= g.max_distance;
     a.distance[p] = certified ? score : BGSA_HIP_DISTANCE_BEYOND;
     if (!certified) a.n_ops[p] = 0;
@@ -249,46 +229,23 @@ __global__ __launch_bounds__(kLanes) void align_pairs_banded_beyond_kernel(PairA
     a.n_ops[p] = 0;
 }
 
-struct BandRun {
-    BandArgs args;
-    size_t workspace_bytes;
-    hipStream_t stream;
-};
-
-// The pair list in chunks of as many whole waves as the workspace holds, one after the other on the stream.
-int run_banded(void *workspace, void *ctx)
+// One chunk: no band at all, or the forward kernel of the widest window, then the traceback.
+int launch_banded(const BandArgs &g, dim3 grid, int64_t first, hipStream_t stream)
 {
-    const BandRun &r = *static_cast<const BandRun *>(ctx);
-    BandArgs g = r.args;
-    g.p.workspace = static_cast<unsigned char *>(workspace);
-    int64_t chunk_waves = static_cast<int64_t>(r.workspace_bytes / g.p.wave_bytes);
-    if (chunk_waves > kMaxChunkWaves) chunk_waves = kMaxChunkWaves;
-    for (int64_t first = 0; first < g.p.n_pairs; first += chunk_waves * kLanes) {
-        const int64_t left = (g.p.n_pairs - first + kLanes - 1) / kLanes;
-        const dim3 grid(static_cast<unsigned>(left < chunk_waves ? left : chunk_waves));
-        if (g.band_words == 0) {
-            hipLaunchKernelGGL(align_pairs_banded_beyond_kernel, grid, dim3(kLanes), 0, r.stream, g.p, first);
-            BGSA_HIP_TRY(hipGetLastError());
-            continue;
-        }
-        const int rc = BandWidths::dispatch(g.band_words, "myers_align_pairs_banded", [&](auto width) {
-            hipLaunchKernelGGL((align_pairs_banded_forward_kernel<decltype(width)::value>), grid, dim3(kLanes), 0, r.stream, g, first);
-            BGSA_HIP_TRY(hipGetLastError());
-            return BGSA_HIP_OK;
-        });
-        if (rc) return rc;
-        hipLaunchKernelGGL(align_pairs_banded_traceback_kernel, grid, dim3(kLanes), 0, r.stream, g, first);
+    if (g.band_words == 0) {
+        hipLaunchKernelGGL(align_pairs_banded_beyond_kernel, grid, dim3(kLanes), 0, stream, g.p, first);
         BGSA_HIP_TRY(hipGetLastError());
+        return BGSA_HIP_OK;
     }
+    const int rc = BandWidths::dispatch(g.band_words, "myers_align_pairs_banded", [&](auto width) {
+        hipLaunchKernelGGL((align_pairs_banded_forward_kernel<decltype(width)::value>), grid, dim3(kLanes), 0, stream, g, first);
+        BGSA_HIP_TRY(hipGetLastError());
+        return BGSA_HIP_OK;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(align_pairs_banded_traceback_kernel, grid, dim3(kLanes), 0, stream, g, first);
+    BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
-}
-
-int refuse(int rc, const char *why)
-{
-    char msg[260];
-    snprintf(msg, sizeof msg, "myers_align_pairs_banded_dev: %s", why);
-    set_error_text(msg);
-    return rc;
 }
 
 // The largest max_distance whose windows the kernels hold for this shape (band_words is monotone in it), or -1.
@@ -327,11 +284,7 @@ size_t bgsa_hip_align_pairs_banded_min_workspace_bytes(int ref_len, int read_len
 size_t bgsa_hip_align_pairs_banded_workspace_bytes(int ref_len, int read_len, int max_distance, int64_t n_pairs)
 {
     if (ref_len <= 0 || read_len <= 0 || max_distance < 0 || n_pairs < 0) return 0;
-    const size_t per = banded_wave_bytes(ref_len, read_len, band_words_of(ref_len, read_len, max_distance));
-    const size_t cap = BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE;
-    const unsigned long long waves = n_pairs > 0 ? (static_cast<unsigned long long>(n_pairs) + kLanes - 1) / kLanes : 1;
-    const size_t want = waves > cap / per ? cap : static_cast<size_t>(waves) * per;   // min(all pairs in one pass, the cap)
-    return want > per ? want : per;                                                    // one wave always fits
+    return pair_workspace_for(banded_wave_bytes(ref_len, read_len, band_words_of(ref_len, read_len, max_distance)), n_pairs);
 }
 
 int bgsa_hip_myers_align_pairs_banded_dev(const char *d_content, const hip_read_t *d_peq, int ref_len, int read_len, int64_t read_count,
@@ -339,16 +292,14 @@ int bgsa_hip_myers_align_pairs_banded_dev(const char *d_content, const hip_read_
                                           int n_queries, int64_t subject_base, int max_distance, int32_t *d_distance, int32_t *d_n_ops,
                                           uint32_t *d_cigar, int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    if (!d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_distance || !d_n_ops || !d_cigar)
-        return refuse(BGSA_HIP_EINVAL, "a NULL pointer (only the workspace may be NULL)");
-    if (n_pairs < 0) return refuse(BGSA_HIP_EINVAL, "n_pairs is negative");
-    if (ref_len <= 0 || read_len <= 0 || n_queries <= 0 || cigar_cap <= 0)
-        return refuse(BGSA_HIP_EINVAL, "ref_len, read_len, n_queries and cigar_cap must be positive");
-    if (read_count <= 0 || read_count % HIP_V_NUM != 0) return refuse(BGSA_HIP_EINVAL, "read_count must be a positive multiple of 64");
+    const char *who = "myers_align_pairs_banded_dev";
+    if (int rc = check_pair_call(who, !d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_distance || !d_n_ops || !d_cigar,
+                                 "a NULL pointer (only the workspace may be NULL)", n_pairs, ref_len, read_len, n_queries, cigar_cap, read_count))
+        return rc;
     if (word_num != bgsa_hip_word_num(BGSA_ALGO_MYERS, ref_len, read_len, 0))
-        return refuse(BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(BGSA_ALGO_MYERS, ...)");
-    if (max_distance < 0) return refuse(BGSA_HIP_EINVAL, "max_distance is negative");
-    if (static_cast<long long>(ref_len) + read_len > 0x7fffffff) return refuse(BGSA_HIP_EUNSUPPORTED, "ref_len + read_len beyond 2^31 - 1");
+        return refuse(who, BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(BGSA_ALGO_MYERS, ...)");
+    if (max_distance < 0) return refuse(who, BGSA_HIP_EINVAL, "max_distance is negative");
+    if (static_cast<long long>(ref_len) + read_len > 0x7fffffff) return refuse(who, BGSA_HIP_EUNSUPPORTED, "ref_len + read_len beyond 2^31 - 1");
     const int band_words = band_words_of(ref_len, read_len, max_distance);
     if (band_words > kBandTraceMaxWords) {
         char why[200];
@@ -359,32 +310,29 @@ int bgsa_hip_myers_align_pairs_banded_dev(const char *d_content, const hip_read_
         else
             snprintf(why, sizeof why, "the band of max_distance %d is %d words wide, the kernels hold %d: no bound fits %d x %d bp",
                      max_distance, band_words, kBandTraceMaxWords, ref_len, read_len);
-        return refuse(BGSA_HIP_EUNSUPPORTED, why);
+        return refuse(who, BGSA_HIP_EUNSUPPORTED, why);
     }
     const size_t per = banded_wave_bytes(ref_len, read_len, band_words);
     if (d_workspace && workspace_bytes < per)
-        return refuse(BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_align_pairs_banded_min_workspace_bytes()");
+        return refuse(who, BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_align_pairs_banded_min_workspace_bytes()");
     if (n_pairs == 0) return BGSA_HIP_OK;
 
-    BandRun r{};
+    BandArgs args{};
     const size_t hist = banded_hist_bytes(ref_len, band_words);
-    r.args.p = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
-                        subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, hist, nullptr, nullptr};
+    args.p = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
+                      subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, hist, device_fault_word(), nullptr};
+    if (!args.p.fault_word) return BGSA_HIP_EHIP;
     const int bound = effective_bound(ref_len, read_len, max_distance);
-    r.args.max_distance = bound < 0 ? 0 : bound;
-    if (band_words > 0) band_diagonals(ref_len, read_len, bound, &r.args.dlo, &r.args.dhi);
-    r.args.band_words = band_words;
-    r.args.state_off = hist;
-    r.args.ops_off = hist + banded_state_bytes(read_len);
-    r.stream = static_cast<hipStream_t>(stream);
-    r.args.p.fault_word = device_fault_word();
-    if (!r.args.p.fault_word) return BGSA_HIP_EHIP;
-    if (d_workspace) {
-        r.workspace_bytes = workspace_bytes;
-        return run_banded(d_workspace, &r);
-    }
-    r.workspace_bytes = bgsa_hip_align_pairs_banded_workspace_bytes(ref_len, read_len, max_distance, n_pairs);
-    return with_own_scratch(r.stream, r.workspace_bytes, run_banded, &r);
+    args.max_distance = bound < 0 ? 0 : bound;
+    if (band_words > 0) band_diagonals(ref_len, read_len, bound, &args.dlo, &args.dhi);
+    args.band_words = band_words;
+    args.state_off = hist;
+    args.ops_off = hist + banded_state_bytes(read_len);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return run_pair_chunks(d_workspace, workspace_bytes, per, n_pairs, s, [&](unsigned char *workspace, dim3 grid, int64_t first) {
+        args.p.workspace = workspace;
+        return launch_banded(args, grid, first, s);
+    });
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ constexpr int kMaxWords = 32;          // longest subject kept entirely in VGPRs
 
 void set_error(const char *what, hipError_t e, const char *file, int line);
 void set_error_text(const char *text);
+int refuse(const char *who, int rc, const char *why);   // capi.hip: sets the error text "who: why", returns rc
 
 #define BGSA_HIP_TRY(expr)                                              \
     do {                                                                \
@@ -619,6 +620,29 @@ __device__ __forceinline__ int lane_read_len(const int32_t *read_lens, size_t co
 {
     const int n = read_lens[column];
     return n < 0 ? 0 : (n > read_len ? read_len : n);
+}
+
+// One word of the 8-operation Myers row in compiler-scheduled C++: the add with carry, D0, Hp, Hn, the two
+// vectors shifted one column up with their carry-ins, the new pv and mv.  `e` is the word's match mask.  carry, hp_in and
+// hn_in come from the word below (the row edge: 0, 1 — 0 for a free column 0 —, 0) and leave for the word above.
+struct MyersWord {
+    uint32_t d0, hp, hn;
+};
+__device__ __forceinline__ MyersWord myers_word(uint32_t e, uint32_t &pv, uint32_t &mv, uint32_t &carry, uint32_t &hp_in, uint32_t &hn_in)
+{
+    const uint32_t x = pv;
+    const unsigned long long s = static_cast<unsigned long long>(x & e) + x + carry;
+    carry = static_cast<uint32_t>(s >> 32);
+    const uint32_t d0 = (static_cast<uint32_t>(s) ^ x) | e | mv;
+    const uint32_t hp = ~(d0 | x) | mv;
+    const uint32_t hn = d0 & x;
+    const uint32_t hps = (hp << 1) | hp_in;
+    const uint32_t hns = (hn << 1) | hn_in;
+    hp_in = hp >> 31;
+    hn_in = hn >> 31;
+    pv = ~(d0 | hps) | hns;
+    mv = d0 & hps;
+    return {d0, hp, hn};
 }
 
 __device__ __forceinline__ void note_stream_fault(unsigned *fault_word, int left)

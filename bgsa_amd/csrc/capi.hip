@@ -34,6 +34,13 @@ void set_error(const char *what, hipError_t e, const char *file, int line)
     g_last_error = buf;
 }
 void set_error_text(const char *text) { g_last_error = text; }
+int refuse(const char *who, int rc, const char *why)
+{
+    char msg[320];
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    set_error_text(msg);
+    return rc;
+}
 
 static thread_local int g_last_q_tile = 0;
 void note_query_tile(int q_tile) { g_last_q_tile = q_tile; }

@@ -48,18 +48,10 @@ __global__ __launch_bounds__(256) void myers_long_kernel(
                 uint32_t carry = 0, hp_in = 1, hn_in = 0;
                 for (int w = 0; w < word_num; w++) {
                     const uint32_t e = eq[w * kLanes];
-                    const uint32_t pv = st[(2 * w) * kLanes], mv = st[(2 * w + 1) * kLanes];
-                    const unsigned long long s = static_cast<unsigned long long>(pv & e) + pv + carry;
-                    carry = static_cast<uint32_t>(s >> 32);
-                    const uint32_t d0 = ((static_cast<uint32_t>(s)) ^ pv) | e | mv;
-                    const uint32_t hp = ~(d0 | pv) | mv;
-                    const uint32_t hn = d0 & pv;
-                    const uint32_t hps = (hp << 1) | hp_in;
-                    const uint32_t hns = (hn << 1) | hn_in;
-                    hp_in = hp >> 31;
-                    hn_in = hn >> 31;
-                    st[(2 * w) * kLanes] = ~(d0 | hps) | hns;
-                    st[(2 * w + 1) * kLanes] = d0 & hps;
+                    uint32_t pv = st[(2 * w) * kLanes], mv = st[(2 * w + 1) * kLanes];
+                    myers_word(e, pv, mv, carry, hp_in, hn_in);
+                    st[(2 * w) * kLanes] = pv;
+                    st[(2 * w + 1) * kLanes] = mv;
                 }
             }
             int score = ref_len;

@@ -19,18 +19,13 @@
 //                 (a wave-uniform index: v_readlane), every lane keeps the smallest key cost << 12 | r1 << 6 | r2 of its proper
 //                 combinations, and a butterfly of __shfl_xor reduces it.  A second pass over the same combinations counts those
 //                 at the chosen cost and finds the smallest cost above it.  No LDS, no scratch.
-#include "bgsa_common.h"
+#include "reference_geometry.h"   // Geometry, make_geometry
 
 namespace bgsa {
 
 namespace {
 
 constexpr int64_t kScoreFloor = -((1ll << 30) - 1);      // a live slot's score lies in [kScoreFloor, 0]: a cost fits an int32
-
-struct Geometry {
-    int64_t ref_len, n_windows, last_start;
-    int window_len, stride;
-};
 
 // ---- rescue windows --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pair_rescue_windows_kernel(Geometry g, const int32_t *__restrict__ strand,
@@ -203,24 +198,11 @@ __global__ __launch_bounds__(256) void pair_select_kernel(EndList one, EndList t
 }
 
 // ---- checks ------------------------------------------------------------------------------------------------------------------
-int refuse(const char *who, const char *why)
+// The shape of reference_windows.hip's calls, then insert_max and R.  0, or BGSA_HIP_EINVAL with its text set.
+int rescue_geometry(const char *who, int64_t ref_len, int window_len, int stride, int64_t insert_max, Geometry *out, int64_t *slots)
 {
-    char msg[300];
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    set_error_text(msg);
-    return BGSA_HIP_EINVAL;
-}
-
-// The shape of reference_windows.hip's calls and R.  0, or BGSA_HIP_EINVAL with its text set.
-int make_geometry(const char *who, int64_t ref_len, int window_len, int stride, int64_t insert_max, Geometry *out, int64_t *slots)
-{
-    if (ref_len < 1) return refuse(who, "ref_len is not positive");
-    if (stride < 1) return refuse(who, "the stride is below 1");
-    if (stride > window_len) return refuse(who, "the stride exceeds the window length");
-    if (window_len > ref_len) return refuse(who, "the window is longer than the reference");
-    if (insert_max < 1 || insert_max > static_cast<int64_t>(INT32_MAX)) return refuse(who, "insert_max must lie in [1, 2^31 - 1]");
-    const int64_t rest = ref_len - window_len;
-    *out = Geometry{ref_len, 1 + (rest + stride - 1) / stride, rest, window_len, stride};
+    if (int rc = make_geometry(who, ref_len, window_len, stride, out)) return rc;
+    if (insert_max < 1 || insert_max > static_cast<int64_t>(INT32_MAX)) return refuse(who, BGSA_HIP_EINVAL, "insert_max must lie in [1, 2^31 - 1]");
     const int64_t span = (insert_max + window_len - 1 + stride - 1) / stride + 1;
     *slots = span < out->n_windows ? span : out->n_windows;
     return BGSA_HIP_OK;
@@ -243,7 +225,7 @@ int64_t bgsa_hip_pair_rescue_slots(int64_t ref_len, int window_len, int stride, 
 {
     Geometry g;
     int64_t slots = 0;
-    return make_geometry("pair_rescue_slots", ref_len, window_len, stride, insert_max, &g, &slots) ? -1 : slots;
+    return rescue_geometry("pair_rescue_slots", ref_len, window_len, stride, insert_max, &g, &slots) ? -1 : slots;
 }
 
 int bgsa_hip_pair_rescue_windows_dev(int64_t ref_len, int window_len, int stride, const int32_t *d_strand, const int64_t *d_ref_begin,
@@ -251,14 +233,14 @@ int bgsa_hip_pair_rescue_windows_dev(int64_t ref_len, int window_len, int stride
                                      int64_t insert_max, int32_t *d_rescue, void *stream)
 {
     const char *who = "pair_rescue_windows_dev";
-    if (!d_strand || !d_ref_begin || !d_ref_end || !d_keep || !d_rescue) return refuse(who, "a NULL pointer (only the stream may be NULL)");
+    if (!d_strand || !d_ref_begin || !d_ref_end || !d_keep || !d_rescue) return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
     Geometry g;
     int64_t slots = 0;
-    if (int rc = make_geometry(who, ref_len, window_len, stride, insert_max, &g, &slots)) return rc;
-    if (2 * g.n_windows > static_cast<int64_t>(INT32_MAX)) return refuse(who, "the windows on two strands do not fit int32 window ids");
-    if (k < 1 || k > HIP_V_NUM) return refuse(who, "k must lie in 1..64 (one wavefront holds a list, one slot per lane)");
-    if (k_anchor < 1 || k_anchor > HIP_V_NUM) return refuse(who, "k_anchor must lie in 1..64");
-    if (n_pairs < 0 || n_pairs > static_cast<int64_t>(INT32_MAX) * kWavesPerBlock) return refuse(who, "n_pairs is negative or beyond one launch");
+    if (int rc = rescue_geometry(who, ref_len, window_len, stride, insert_max, &g, &slots)) return rc;
+    if (2 * g.n_windows > static_cast<int64_t>(INT32_MAX)) return refuse(who, BGSA_HIP_EINVAL, "the windows on two strands do not fit int32 window ids");
+    if (k < 1 || k > HIP_V_NUM) return refuse(who, BGSA_HIP_EINVAL, "k must lie in 1..64 (one wavefront holds a list, one slot per lane)");
+    if (k_anchor < 1 || k_anchor > HIP_V_NUM) return refuse(who, BGSA_HIP_EINVAL, "k_anchor must lie in 1..64");
+    if (n_pairs < 0 || n_pairs > static_cast<int64_t>(INT32_MAX) * kWavesPerBlock) return refuse(who, BGSA_HIP_EINVAL, "n_pairs is negative or beyond one launch");
     if (n_pairs == 0) return BGSA_HIP_OK;
     hipLaunchKernelGGL(pair_rescue_windows_kernel, dim3(static_cast<unsigned>((n_pairs + kWavesPerBlock - 1) / kWavesPerBlock)),
                        dim3(kWavesPerBlock * kLanes), 0, static_cast<hipStream_t>(stream), g, d_strand, d_ref_begin, d_ref_end, d_keep, n_pairs,
@@ -276,11 +258,11 @@ int bgsa_hip_pair_select_dev(const int32_t *d_scores1, const int32_t *d_strand1,
     const char *who = "pair_select_dev";
     if (!end_list_ok(d_scores1, d_strand1, d_ref_begin1, d_ref_end1, d_keep1) || !end_list_ok(d_scores2, d_strand2, d_ref_begin2, d_ref_end2, d_keep2) ||
         !d_proper || !d_slot1 || !d_slot2 || !d_insert || !d_cost || !d_n_best || !d_next_cost)
-        return refuse(who, "a NULL pointer (only the stream may be NULL)");
-    if (k1 < 1 || k1 > HIP_V_NUM || k2 < 1 || k2 > HIP_V_NUM) return refuse(who, "k1 and k2 must lie in 1..64 (one wavefront holds a list)");
+        return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
+    if (k1 < 1 || k1 > HIP_V_NUM || k2 < 1 || k2 > HIP_V_NUM) return refuse(who, BGSA_HIP_EINVAL, "k1 and k2 must lie in 1..64 (one wavefront holds a list)");
     if (insert_min < 1 || insert_max < insert_min || insert_max > static_cast<int64_t>(INT32_MAX))
-        return refuse(who, "needs 1 <= insert_min <= insert_max <= 2^31 - 1");
-    if (n_pairs < 0 || n_pairs > static_cast<int64_t>(INT32_MAX) * kWavesPerBlock) return refuse(who, "n_pairs is negative or beyond one launch");
+        return refuse(who, BGSA_HIP_EINVAL, "needs 1 <= insert_min <= insert_max <= 2^31 - 1");
+    if (n_pairs < 0 || n_pairs > static_cast<int64_t>(INT32_MAX) * kWavesPerBlock) return refuse(who, BGSA_HIP_EINVAL, "n_pairs is negative or beyond one launch");
     if (n_pairs == 0) return BGSA_HIP_OK;
     const EndList one{d_scores1, d_strand1, d_ref_begin1, d_ref_end1, d_keep1, k1}, two{d_scores2, d_strand2, d_ref_begin2, d_ref_end2, d_keep2, k2};
     hipLaunchKernelGGL(pair_select_kernel, dim3(static_cast<unsigned>((n_pairs + kWavesPerBlock - 1) / kWavesPerBlock)),

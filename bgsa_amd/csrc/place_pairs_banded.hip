@@ -27,7 +27,9 @@
 //              B = Eq | (D0 & Hp)): diagonal, then up 'I', then left 'D'; it stops at the first cell with j = 0, whose row is
 //              q_begin; on query row 0 what is left of the subject is 'D'.
 //
-// tests/place_reference.py restates all of it on Python integers.
+// tests/place_reference.py restates all of it on Python integers.  The rows of locate and forward are written out here, not
+// through myers_word (bgsa_common.h) and class_masks / state_score (pair_trace.h) as align_pairs_banded.hip's are: with the
+// helpers these kernels grew by one to three instructions and two timed lines missed their rule (LABNOTES §31.5).
 //
 // One wave's slice: [history][state][carry][op bytes].
 //   history  [virtual row][vector A|B][window word][lane] uint32, the word stride band_words = the widest window of (n, B)
@@ -374,43 +376,20 @@ __global__ __launch_bounds__(kLanes) void place_pairs_traceback_kernel(PlaceArgs
     a.n_ops[p] = encode_runs(ops, steps, a.cigar + static_cast<size_t>(p) * a.cigar_cap, a.cigar_cap);
 }
 
-struct PlaceRun {
-    PlaceArgs args;
-    size_t workspace_bytes;
-    hipStream_t stream;
-};
-
-// The pair list in chunks of as many whole waves as the workspace holds, one after the other on the stream.
-int run_place(void *workspace, void *ctx)
+// One chunk: locate, the forward kernel of the widest window, the traceback.
+int launch_place(const PlaceArgs &g, dim3 grid, int64_t first, hipStream_t stream)
 {
-    const PlaceRun &r = *static_cast<const PlaceRun *>(ctx);
-    PlaceArgs g = r.args;
-    g.p.workspace = static_cast<unsigned char *>(workspace);
-    int64_t chunk_waves = static_cast<int64_t>(r.workspace_bytes / g.p.wave_bytes);
-    if (chunk_waves > kMaxChunkWaves) chunk_waves = kMaxChunkWaves;
-    for (int64_t first = 0; first < g.p.n_pairs; first += chunk_waves * kLanes) {
-        const int64_t left = (g.p.n_pairs - first + kLanes - 1) / kLanes;
-        const dim3 grid(static_cast<unsigned>(left < chunk_waves ? left : chunk_waves));
-        hipLaunchKernelGGL(place_pairs_locate_kernel, grid, dim3(kLanes), 0, r.stream, g, first);
+    hipLaunchKernelGGL(place_pairs_locate_kernel, grid, dim3(kLanes), 0, stream, g, first);
+    BGSA_HIP_TRY(hipGetLastError());
+    const int rc = PlaceWidths::dispatch(g.band_words, "myers_place_pairs_banded", [&](auto width) {
+        hipLaunchKernelGGL((place_pairs_forward_kernel<decltype(width)::value>), grid, dim3(kLanes), 0, stream, g, first);
         BGSA_HIP_TRY(hipGetLastError());
-        const int rc = PlaceWidths::dispatch(g.band_words, "myers_place_pairs_banded", [&](auto width) {
-            hipLaunchKernelGGL((place_pairs_forward_kernel<decltype(width)::value>), grid, dim3(kLanes), 0, r.stream, g, first);
-            BGSA_HIP_TRY(hipGetLastError());
-            return BGSA_HIP_OK;
-        });
-        if (rc) return rc;
-        hipLaunchKernelGGL(place_pairs_traceback_kernel, grid, dim3(kLanes), 0, r.stream, g, first);
-        BGSA_HIP_TRY(hipGetLastError());
-    }
+        return BGSA_HIP_OK;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(place_pairs_traceback_kernel, grid, dim3(kLanes), 0, stream, g, first);
+    BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
-}
-
-int refuse(int rc, const char *why)
-{
-    char msg[260];
-    snprintf(msg, sizeof msg, "myers_place_pairs_banded_dev: %s", why);
-    set_error_text(msg);
-    return rc;
 }
 
 // The largest max_distance whose windows the kernels hold for a read of n bp (band_words is monotone in it).
@@ -444,11 +423,7 @@ size_t bgsa_hip_place_pairs_banded_min_workspace_bytes(int ref_len, int read_len
 size_t bgsa_hip_place_pairs_banded_workspace_bytes(int ref_len, int read_len, int max_distance, int64_t n_pairs)
 {
     if (ref_len <= 0 || read_len <= 0 || max_distance < 0 || n_pairs < 0) return 0;
-    const size_t per = place_wave_bytes(ref_len, read_len, max_distance, place_band_words_of(read_len, max_distance));
-    const size_t cap = BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE;
-    const unsigned long long waves = n_pairs > 0 ? (static_cast<unsigned long long>(n_pairs) + kLanes - 1) / kLanes : 1;
-    const size_t want = waves > cap / per ? cap : static_cast<size_t>(waves) * per;   // min(all pairs in one pass, the cap)
-    return want > per ? want : per;                                                    // one wave always fits
+    return pair_workspace_for(place_wave_bytes(ref_len, read_len, max_distance, place_band_words_of(read_len, max_distance)), n_pairs);
 }
 
 int bgsa_hip_myers_place_pairs_banded_dev(const char *d_content, const hip_read_t *d_peq, int ref_len, int read_len, int64_t read_count,
@@ -457,48 +432,44 @@ int bgsa_hip_myers_place_pairs_banded_dev(const char *d_content, const hip_read_
                                           int32_t *d_n_ops, uint32_t *d_cigar, int cigar_cap, void *d_workspace, size_t workspace_bytes,
                                           void *stream)
 {
-    if (!d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_distance || !d_span || !d_n_ops || !d_cigar)
-        return refuse(BGSA_HIP_EINVAL, "a NULL pointer (only the workspace and the stream may be NULL)");
-    if (n_pairs < 0) return refuse(BGSA_HIP_EINVAL, "n_pairs is negative");
-    if (ref_len <= 0 || read_len <= 0 || n_queries <= 0 || cigar_cap <= 0)
-        return refuse(BGSA_HIP_EINVAL, "ref_len, read_len, n_queries and cigar_cap must be positive");
-    if (read_count <= 0 || read_count % HIP_V_NUM != 0) return refuse(BGSA_HIP_EINVAL, "read_count must be a positive multiple of 64");
+    const char *who = "myers_place_pairs_banded_dev";
+    if (int rc = check_pair_call(who, !d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_distance || !d_span || !d_n_ops || !d_cigar,
+                                 "a NULL pointer (only the workspace and the stream may be NULL)", n_pairs, ref_len, read_len, n_queries, cigar_cap,
+                                 read_count))
+        return rc;
     if (word_num != bgsa_hip_word_num(BGSA_ALGO_MYERS, ref_len, read_len, 0))
-        return refuse(BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(BGSA_ALGO_MYERS, ...)");
-    if (max_distance < 0) return refuse(BGSA_HIP_EINVAL, "max_distance is negative");
+        return refuse(who, BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(BGSA_ALGO_MYERS, ...)");
+    if (max_distance < 0) return refuse(who, BGSA_HIP_EINVAL, "max_distance is negative");
     if (!place_counts_fit(ref_len, read_len, max_distance))
-        return refuse(BGSA_HIP_EUNSUPPORTED, "ref_len + read_len + min(max_distance, read_len) beyond 2^31 - 1");
+        return refuse(who, BGSA_HIP_EUNSUPPORTED, "ref_len + read_len + min(max_distance, read_len) beyond 2^31 - 1");
     const int band_words = place_band_words_of(read_len, max_distance);
     if (band_words > kPlaceMaxWords) {
         char why[200];
         snprintf(why, sizeof why, "the windows of max_distance %d are %d words wide, the kernels hold %d: a %d bp read takes max_distance <= %d",
                  max_distance, band_words, kPlaceMaxWords, read_len, largest_place_bound(read_len));
-        return refuse(BGSA_HIP_EUNSUPPORTED, why);
+        return refuse(who, BGSA_HIP_EUNSUPPORTED, why);
     }
     const size_t per = place_wave_bytes(ref_len, read_len, max_distance, band_words);
     if (d_workspace && workspace_bytes < per)
-        return refuse(BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_place_pairs_banded_min_workspace_bytes()");
+        return refuse(who, BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_place_pairs_banded_min_workspace_bytes()");
     if (n_pairs == 0) return BGSA_HIP_OK;
 
-    PlaceRun r{};
+    PlaceArgs args{};
     const size_t hist = place_hist_bytes(read_len, max_distance, band_words);
-    r.args.p = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
-                        subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, hist, nullptr, nullptr};
-    r.args.span = d_span;
-    r.args.bound = place_bound(read_len, max_distance);
-    r.args.band_words = band_words;
-    r.args.state_off = hist;
-    r.args.carry_off = hist + place_state_bytes(read_len);
-    r.args.ops_off = r.args.carry_off + place_carry_bytes(ref_len);
-    r.stream = static_cast<hipStream_t>(stream);
-    r.args.p.fault_word = device_fault_word();
-    if (!r.args.p.fault_word) return BGSA_HIP_EHIP;
-    if (d_workspace) {
-        r.workspace_bytes = workspace_bytes;
-        return run_place(d_workspace, &r);
-    }
-    r.workspace_bytes = bgsa_hip_place_pairs_banded_workspace_bytes(ref_len, read_len, max_distance, n_pairs);
-    return with_own_scratch(r.stream, r.workspace_bytes, run_place, &r);
+    args.p = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
+                      subject_base, d_distance, d_n_ops, d_cigar, cigar_cap, nullptr, per, hist, device_fault_word(), nullptr};
+    if (!args.p.fault_word) return BGSA_HIP_EHIP;
+    args.span = d_span;
+    args.bound = place_bound(read_len, max_distance);
+    args.band_words = band_words;
+    args.state_off = hist;
+    args.carry_off = hist + place_state_bytes(read_len);
+    args.ops_off = args.carry_off + place_carry_bytes(ref_len);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return run_pair_chunks(d_workspace, workspace_bytes, per, n_pairs, s, [&](unsigned char *workspace, dim3 grid, int64_t first) {
+        args.p.workspace = workspace;
+        return launch_place(args, grid, first, s);
+    });
 }
 
 }  // extern "C"

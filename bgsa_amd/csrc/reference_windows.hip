@@ -19,7 +19,7 @@
 // are per lane; `keep` walks the list once, hit r broadcasting its interval to the lanes behind it.
 //
 // No allocation, no synchronisation, no workspace.
-#include "bgsa_common.h"
+#include "reference_geometry.h"   // Geometry, window_start, make_geometry
 
 namespace bgsa {
 
@@ -28,17 +28,6 @@ namespace {
 constexpr int kNewline = '\n';
 constexpr int kCodeN = 4;
 constexpr unsigned kMaxBlocks = 2048;   // a memory-bound grid: beyond it the threads stride
-
-struct Geometry {
-    int64_t ref_len, n_windows, last_start;   // last_start = L - W, where the last window is anchored
-    int window_len, stride;
-};
-
-__host__ __device__ inline int64_t window_start(const Geometry &g, int64_t w)
-{
-    const int64_t at = w * g.stride;
-    return at < g.last_start ? at : g.last_start;
-}
 
 // Code `col` of the row of window id `id`; an id outside [0, 2 n_windows) is a row of N.
 __device__ __forceinline__ unsigned window_code(const char *__restrict__ reference, const Geometry &g, int64_t id, int col)
@@ -147,23 +136,10 @@ __global__ __launch_bounds__(256) void reference_placements_kernel(Geometry g, c
     }
 }
 
-// The geometry's own checks, shared by all four entry points.  Sets the error text and returns false on a bad shape.
-bool make_geometry(const char *who, int64_t ref_len, int window_len, int stride, Geometry *out)
+// The geometry's own checks with this file's longer word on a wide stride, shared by all four entry points.
+int windows_geometry(const char *who, int64_t ref_len, int window_len, int stride, Geometry *out)
 {
-    const char *why = nullptr;
-    if (ref_len < 1) why = "ref_len is not positive";
-    else if (stride < 1) why = "the stride is below 1";
-    else if (stride > window_len) why = "the stride exceeds the window length (reference bases no window would hold)";
-    else if (window_len > ref_len) why = "the window is longer than the reference";
-    if (why) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: %s", who, why);
-        set_error_text(msg);
-        return false;
-    }
-    const int64_t rest = ref_len - window_len;
-    *out = Geometry{ref_len, 1 + (rest + stride - 1) / stride, rest, window_len, stride};
-    return true;
+    return make_geometry(who, ref_len, window_len, stride, out, "the stride exceeds the window length (reference bases no window would hold)");
 }
 
 // ... and what the device calls add: window ids are int32.
@@ -188,13 +164,13 @@ extern "C" {
 int64_t bgsa_hip_reference_window_count(int64_t ref_len, int window_len, int stride)
 {
     Geometry g;
-    return make_geometry("reference_window_count", ref_len, window_len, stride, &g) ? g.n_windows : -1;
+    return windows_geometry("reference_window_count", ref_len, window_len, stride, &g) ? -1 : g.n_windows;
 }
 
 int64_t bgsa_hip_reference_window_start(int64_t ref_len, int window_len, int stride, int64_t window)
 {
     Geometry g;
-    if (!make_geometry("reference_window_start", ref_len, window_len, stride, &g)) return -1;
+    if (windows_geometry("reference_window_start", ref_len, window_len, stride, &g)) return -1;
     if (window < 0 || window >= g.n_windows) {
         set_error_text("reference_window_start: the window lies outside [0, n_windows)");
         return -1;
@@ -210,7 +186,7 @@ int bgsa_hip_reference_windows_dev(const char *d_reference, int64_t ref_len, int
         return BGSA_HIP_EINVAL;
     }
     Geometry g;
-    if (!make_geometry("reference_windows_dev", ref_len, window_len, stride, &g)) return BGSA_HIP_EINVAL;
+    if (int rc = windows_geometry("reference_windows_dev", ref_len, window_len, stride, &g)) return rc;
     if (int rc = check_ids_fit("reference_windows_dev", g)) return rc;
     if (n_rows < 0 || n_rows > static_cast<int64_t>(INT32_MAX)) {
         set_error_text("reference_windows_dev: n_rows must lie in [0, 2^31 - 1] (rows are query indices)");
@@ -245,7 +221,7 @@ int bgsa_hip_reference_placements_dev(int64_t ref_len, int window_len, int strid
         return BGSA_HIP_EINVAL;
     }
     Geometry g;
-    if (!make_geometry("reference_placements_dev", ref_len, window_len, stride, &g)) return BGSA_HIP_EINVAL;
+    if (int rc = windows_geometry("reference_placements_dev", ref_len, window_len, stride, &g)) return rc;
     if (int rc = check_ids_fit("reference_placements_dev", g)) return rc;
     if (k < 1 || k > HIP_V_NUM) {
         set_error_text("reference_placements_dev: k must lie in 1..64 (one wavefront holds a read's list, one hit per lane)");

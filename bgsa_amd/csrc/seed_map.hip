@@ -31,7 +31,8 @@
 //                row exists anywhere.  A template instance per block width keeps a narrow read's registers low: the words are
 //                all live for the whole row loop (36 / 64 / 142 / 228 VGPRs at 1 / 5 / 16 / 32 words, no scratch; LABNOTES §27.2).
 //   select       one wave per read: k rounds, each the minimum (distance, id) key above the last one taken.
-#include "bgsa_common.h"
+#include "pair_trace.h"           // the Myers word, the class masks, the chunk loop and the workspace rule
+#include "reference_geometry.h"   // Geometry, window_start, make_geometry
 
 namespace bgsa {
 
@@ -44,19 +45,7 @@ constexpr int kScanBlock = 256 * kScanItems;
 constexpr int kVerifyRows = 32;            // window characters fetched per block of rows
 constexpr int kVerifyWords = 16;           // words of a column block: 5 Peq planes + pv + mv in 112 registers
 constexpr int kVerifyMaxWords = 32;
-constexpr int64_t kVerifyMaxWaves = 1 << 22;
 constexpr unsigned kMaxBlocks = 1u << 20;
-
-struct Geometry {
-    int64_t ref_len, n_windows, last_start;
-    int window_len, stride;
-};
-
-__host__ __device__ inline int64_t window_start(const Geometry &g, int64_t w)
-{
-    const int64_t at = w * g.stride;
-    return at < g.last_start ? at : g.last_start;
-}
 
 // ---- index -------------------------------------------------------------------------------------------------------------------
 // One thread rolls over kSeedChunk positions.  Fill == false: offsets[code + 1]++.  Fill == true: positions[cursor[code]++] = p.
@@ -407,34 +396,19 @@ __global__ __launch_bounds__(kLanes) void reference_verify_pairs_kernel(VerifyAr
             uint32_t out_hp = 0, out_hn = 0, out_add = 0;
 #pragma unroll 1
             for (int r = 0; r < rows; r++) {
-                const uint32_t c = static_cast<uint32_t>(lo) & 15u;
-                lo = (lo >> 4) | (hi << 60);
-                hi >>= 4;
-                const uint32_t k0 = 0u - (c == 0), k1 = 0u - (c == 1), k2 = 0u - (c == 2), k3 = 0u - (c == 3), k4 = 0u - (c == 4);
+                const ClassMasks k = class_masks<true>(next_class(lo, hi));
                 uint32_t carry = (in_add >> r) & 1u, hp_in = (in_hp >> r) & 1u, hn_in = (in_hn >> r) & 1u;
                 uint32_t top_hp = 0, top_hn = 0;
 #pragma unroll
                 for (int w = 0; w < WB; w++) {
                     if (w < wb) {
-                        const uint32_t eq = (peq[0][w] & k0) | (peq[1][w] & k1) | (peq[2][w] & k2) | (peq[3][w] & k3) | (peq[4][w] & k4);
-                        const uint32_t x = pv[w];
-                        const unsigned long long sum = static_cast<unsigned long long>(x & eq) + x + carry;
-                        carry = static_cast<uint32_t>(sum >> 32);
-                        const uint32_t d0 = (static_cast<uint32_t>(sum) ^ x) | eq | mv[w];
-                        const uint32_t hp = ~(d0 | x) | mv[w];
-                        const uint32_t hn = d0 & x;
-                        const uint32_t hps = (hp << 1) | hp_in;
-                        const uint32_t hns = (hn << 1) | hn_in;
-                        hp_in = hp >> 31;
-                        hn_in = hn >> 31;
-                        pv[w] = ~(d0 | hps) | hns;
-                        mv[w] = d0 & hps;
+                        const MyersWord s = myers_word(class_eq(peq, w, k), pv[w], mv[w], carry, hp_in, hn_in);
                         if (Lens) {
-                            top_hp = w == own_w ? hp : top_hp;
-                            top_hn = w == own_w ? hn : top_hn;
+                            top_hp = w == own_w ? s.hp : top_hp;
+                            top_hn = w == own_w ? s.hn : top_hn;
                         } else {
-                            top_hp = hp;
-                            top_hn = hn;
+                            top_hp = s.hp;
+                            top_hn = s.hn;
                         }
                     }
                 }
@@ -523,24 +497,11 @@ __global__ __launch_bounds__(256) void seed_select_kernel(const int32_t *__restr
 }
 
 // ---- checks ----------------------------------------------------------------------------------------------------------------------
-int refuse(const char *who, int rc, const char *why)
+// The shape of reference_windows.hip's calls, with index positions and window ids in int32.  0, or the error with its text set.
+int seed_geometry(const char *who, int64_t ref_len, int window_len, int stride, Geometry *out)
 {
-    char msg[300];
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    set_error_text(msg);
-    return rc;
-}
-
-// The shape of reference_windows.hip's calls, with window ids in int32.  0, or the error with its text set.
-int make_geometry(const char *who, int64_t ref_len, int window_len, int stride, Geometry *out)
-{
-    if (ref_len < 1) return refuse(who, BGSA_HIP_EINVAL, "ref_len is not positive");
     if (ref_len > static_cast<int64_t>(INT32_MAX)) return refuse(who, BGSA_HIP_EINVAL, "ref_len beyond 2^31 - 1 (index positions are int32)");
-    if (stride < 1) return refuse(who, BGSA_HIP_EINVAL, "the stride is below 1");
-    if (stride > window_len) return refuse(who, BGSA_HIP_EINVAL, "the stride exceeds the window length");
-    if (window_len > ref_len) return refuse(who, BGSA_HIP_EINVAL, "the window is longer than the reference");
-    const int64_t rest = ref_len - window_len;
-    *out = Geometry{ref_len, 1 + (rest + stride - 1) / stride, rest, window_len, stride};
+    if (int rc = make_geometry(who, ref_len, window_len, stride, out)) return rc;
     if (2 * out->n_windows > static_cast<int64_t>(INT32_MAX))
         return refuse(who, BGSA_HIP_EINVAL, "the windows on two strands do not fit int32 window ids");
     return BGSA_HIP_OK;
@@ -618,7 +579,7 @@ static int seed_args(const char *who, int64_t ref_len, int window_len, int strid
     if (!d_offsets || !d_positions || !d_reads || (per_read && !d_read_lens)) return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
     if (!seed_len_ok(seed_len)) return refuse(who, BGSA_HIP_EINVAL, "seed_len must lie in 1..13");
     Geometry g;
-    if (int rc = make_geometry(who, ref_len, window_len, stride, &g)) return rc;
+    if (int rc = seed_geometry(who, ref_len, window_len, stride, &g)) return rc;
     if (read_len < 1 || max_distance < 0) return refuse(who, BGSA_HIP_EINVAL, "read_len must be positive and max_distance not negative");
     if (n_reads < 0 || n_reads > static_cast<int64_t>(INT32_MAX)) return refuse(who, BGSA_HIP_EINVAL, "n_reads must lie in [0, 2^31 - 1]");
     const int bound = max_distance < read_len ? max_distance : read_len;
@@ -721,11 +682,7 @@ size_t bgsa_hip_reference_verify_workspace_bytes(int window_len, int read_len, i
 {
     if (window_len < 1 || read_len < 1 || n_pairs < 0) return 0;
     const size_t per = verify_wave_bytes(window_len, (read_len + 31) / 32);
-    const unsigned long long waves = n_pairs > 0 ? (static_cast<unsigned long long>(n_pairs) + kLanes - 1) / kLanes : 1;
-    const size_t cap = BGSA_HIP_ALIGN_PAIRS_MAX_WORKSPACE;
-    if (per == 0) return 0;
-    const size_t want = waves > cap / per ? cap : static_cast<size_t>(waves) * per;
-    return want > per ? want : per;
+    return per ? pair_workspace_for(per, n_pairs) : 0;
 }
 
 // per_lane: the *_lens call — d_read_lens is required and every lane verifies at its own length.
@@ -737,7 +694,7 @@ static int verify_pairs(const char *who, const char *d_reference, int64_t ref_le
     if (!d_reference || !d_peq || !d_pair_window || !d_pair_subject || !d_distance || (per_lane && !d_read_lens))
         return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the workspace of a read of <= 16 words and the stream may be NULL)");
     Geometry g;
-    if (int rc = make_geometry(who, ref_len, window_len, stride, &g)) return rc;
+    if (int rc = seed_geometry(who, ref_len, window_len, stride, &g)) return rc;
     if (n_pairs < 0) return refuse(who, BGSA_HIP_EINVAL, "n_pairs is negative");
     if (read_len < 1) return refuse(who, BGSA_HIP_EINVAL, "read_len is not positive");
     if (read_count <= 0 || read_count % HIP_V_NUM != 0) return refuse(who, BGSA_HIP_EINVAL, "read_count must be a positive multiple of 64");
@@ -751,14 +708,8 @@ static int verify_pairs(const char *who, const char *d_reference, int64_t ref_le
 
     VerifyArgs a{reinterpret_cast<const unsigned char *>(d_reference), g, d_peq, read_len, read_count, word_num, d_pair_window,
                  d_pair_subject, n_pairs, subject_base, per_lane ? d_read_lens : nullptr, d_distance, static_cast<unsigned char *>(d_workspace), per};
-    int64_t chunk_waves = per ? static_cast<int64_t>(workspace_bytes / per) : kVerifyMaxWaves;
-    if (chunk_waves > kVerifyMaxWaves) chunk_waves = kVerifyMaxWaves;
-    for (int64_t first = 0; first < n_pairs; first += chunk_waves * kLanes) {
-        const int64_t left = (n_pairs - first + kLanes - 1) / kLanes;
-        const dim3 grid(static_cast<unsigned>(left < chunk_waves ? left : chunk_waves));
-        if (int rc = dispatch_verify(a, grid, first, static_cast<hipStream_t>(stream))) return rc;
-    }
-    return BGSA_HIP_OK;
+    return for_each_chunk(n_pairs, per, workspace_bytes,
+                          [&](dim3 grid, int64_t first) { return dispatch_verify(a, grid, first, static_cast<hipStream_t>(stream)); });
 }
 
 int bgsa_hip_reference_verify_pairs_dev(const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,

@@ -179,12 +179,6 @@ __global__ __launch_bounds__(kLanes) void trace_pairs_traceback_kernel(TraceArgs
     a.n_ops[p] = encode_runs(ops, steps, a.cigar + static_cast<size_t>(p) * a.cigar_cap, a.cigar_cap);
 }
 
-struct TraceRun {
-    TraceArgs args;
-    size_t workspace_bytes;
-    hipStream_t stream;
-};
-
 template <int MODE>
 int launch_forward(const TraceArgs &t, dim3 grid, size_t lds, hipStream_t stream, int64_t first)
 {
@@ -193,26 +187,16 @@ int launch_forward(const TraceArgs &t, dim3 grid, size_t lds, hipStream_t stream
     return BGSA_HIP_OK;
 }
 
-// The pair list in chunks of as many whole waves as the workspace holds, one after the other on the stream.
-int run_trace(void *workspace, void *ctx)
+// One chunk: the forward kernel of the mode, then the traceback.
+int launch_trace(const TraceArgs &t, dim3 grid, int64_t first, hipStream_t stream)
 {
-    const TraceRun &r = *static_cast<const TraceRun *>(ctx);
-    TraceArgs t = r.args;
-    PairArgs &a = t.p;
-    a.workspace = static_cast<unsigned char *>(workspace);
-    const size_t lds = trace_lds_bytes(a.read_len);
-    int64_t chunk_waves = static_cast<int64_t>(r.workspace_bytes / a.wave_bytes);
-    if (chunk_waves > kMaxChunkWaves) chunk_waves = kMaxChunkWaves;
-    for (int64_t first = 0; first < a.n_pairs; first += chunk_waves * kLanes) {
-        const int64_t left = (a.n_pairs - first + kLanes - 1) / kLanes;
-        const dim3 grid(static_cast<unsigned>(left < chunk_waves ? left : chunk_waves));
-        const int rc = t.mode == kGlobal      ? launch_forward<kGlobal>(t, grid, lds, r.stream, first)
-                       : t.mode == kFreeQuery ? launch_forward<kFreeQuery>(t, grid, lds, r.stream, first)
-                                              : launch_forward<kFreeSubject>(t, grid, lds, r.stream, first);
-        if (rc) return rc;
-        hipLaunchKernelGGL(trace_pairs_traceback_kernel, grid, dim3(kLanes), 0, r.stream, t, first);
-        BGSA_HIP_TRY(hipGetLastError());
-    }
+    const size_t lds = trace_lds_bytes(t.p.read_len);
+    const int rc = t.mode == kGlobal      ? launch_forward<kGlobal>(t, grid, lds, stream, first)
+                   : t.mode == kFreeQuery ? launch_forward<kFreeQuery>(t, grid, lds, stream, first)
+                                          : launch_forward<kFreeSubject>(t, grid, lds, stream, first);
+    if (rc) return rc;
+    hipLaunchKernelGGL(trace_pairs_traceback_kernel, grid, dim3(kLanes), 0, stream, t, first);
+    BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
 
@@ -237,13 +221,7 @@ int allow_wide_rows(int mode, size_t lds)
     return BGSA_HIP_OK;
 }
 
-int refuse(int rc, const char *why)
-{
-    char msg[320];
-    snprintf(msg, sizeof msg, "trace_pairs_dev: %s", why);
-    set_error_text(msg);
-    return rc;
-}
+constexpr const char *kWho = "trace_pairs_dev";
 
 }  // namespace
 
@@ -290,7 +268,7 @@ int bgsa_hip_myers_place_trace_pairs_lens_dev(const char *d_content, const hip_r
 {
     const bgsa_hip_params_t params = {BGSA_ALGO_MYERS, BGSA_ALIGN_SEMIGLOBAL, 0, -1, -1, 0};
     if (!d_read_lens)
-        return refuse(BGSA_HIP_EINVAL, "d_read_lens is NULL (bgsa_hip_myers_place_trace_pairs_lens_dev takes the bucket's lengths; "
+        return refuse(kWho, BGSA_HIP_EINVAL, "d_read_lens is NULL (bgsa_hip_myers_place_trace_pairs_lens_dev takes the bucket's lengths; "
                                        "equal lengths: bgsa_hip_trace_pairs_dev)");
     return trace_pairs_entry(&params, d_content, d_peq, d_read_lens, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject,
                              n_pairs, n_queries, subject_base, d_score, d_span, d_n_ops, d_cigar, cigar_cap, d_workspace, workspace_bytes,
@@ -303,26 +281,24 @@ static int trace_pairs_entry(const bgsa_hip_params_t *params, const char *d_cont
                              int64_t subject_base, int32_t *d_score, int32_t *d_span, int32_t *d_n_ops, uint32_t *d_cigar,
                              int cigar_cap, void *d_workspace, size_t workspace_bytes, void *stream, bool semi_lens)
 {
-    if (!params || !d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_score || !d_span || !d_n_ops || !d_cigar)
-        return refuse(BGSA_HIP_EINVAL, "a NULL pointer (only the workspace and the stream may be NULL)");
-    if (n_pairs < 0) return refuse(BGSA_HIP_EINVAL, "n_pairs is negative");
-    if (ref_len <= 0 || read_len <= 0 || n_queries <= 0 || cigar_cap <= 0)
-        return refuse(BGSA_HIP_EINVAL, "ref_len, read_len, n_queries and cigar_cap must be positive");
-    if (read_count <= 0 || read_count % HIP_V_NUM != 0) return refuse(BGSA_HIP_EINVAL, "read_count must be a positive multiple of 64");
+    if (int rc = check_pair_call(kWho, !params || !d_content || !d_peq || !d_pair_query || !d_pair_subject || !d_score || !d_span || !d_n_ops || !d_cigar,
+                                 "a NULL pointer (only the workspace and the stream may be NULL)", n_pairs, ref_len, read_len, n_queries, cigar_cap,
+                                 read_count))
+        return rc;
     if (params->algo == BGSA_ALGO_BANDED)
-        return refuse(BGSA_HIP_EUNSUPPORTED, "the banded filter's pairs are not traced back (it reports a thresholded distance, not an alignment)");
-    if (params->algo != BGSA_ALGO_MYERS && params->algo != BGSA_ALGO_BITPAL) return refuse(BGSA_HIP_EINVAL, "unknown algorithm");
+        return refuse(kWho, BGSA_HIP_EUNSUPPORTED, "the banded filter's pairs are not traced back (it reports a thresholded distance, not an alignment)");
+    if (params->algo != BGSA_ALGO_MYERS && params->algo != BGSA_ALGO_BITPAL) return refuse(kWho, BGSA_HIP_EINVAL, "unknown algorithm");
     if (params->alignment != BGSA_ALIGN_GLOBAL && params->alignment != BGSA_ALIGN_SEMIGLOBAL)
-        return refuse(BGSA_HIP_EINVAL, "alignment is neither global nor semi-global");
+        return refuse(kWho, BGSA_HIP_EINVAL, "alignment is neither global nor semi-global");
     if (params->algo == BGSA_ALGO_MYERS && params->match == 0 && params->mismatch == 1 && params->gap == 1)
-        return refuse(BGSA_HIP_EUNSUPPORTED, "Myers +distance (0, 1, 1) aligns the same as -distance: use the (0, -1, -1) aligner");
+        return refuse(kWho, BGSA_HIP_EUNSUPPORTED, "Myers +distance (0, 1, 1) aligns the same as -distance: use the (0, -1, -1) aligner");
     if (params->gap >= 0 || params->match <= params->mismatch)
-        return refuse(BGSA_HIP_EINVAL, "scores need gap < 0 and match > mismatch");
+        return refuse(kWho, BGSA_HIP_EINVAL, "scores need gap < 0 and match > mismatch");
     if (word_num != bgsa_hip_word_num(params->algo, ref_len, read_len, params->k))
-        return refuse(BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(params->algo, ...)");
-    if (word_num > kMaxWords) return refuse(BGSA_HIP_EUNSUPPORTED, "subjects beyond 1,024 bp (word_num > 32) are not covered");
+        return refuse(kWho, BGSA_HIP_EINVAL, "word_num is not bgsa_hip_word_num(params->algo, ...)");
+    if (word_num > kMaxWords) return refuse(kWho, BGSA_HIP_EUNSUPPORTED, "subjects beyond 1,024 bp (word_num > 32) are not covered");
     if (d_read_lens && params->alignment != BGSA_ALIGN_GLOBAL && !semi_lens)
-        return refuse(BGSA_HIP_EUNSUPPORTED, "per-subject lengths are traced in global mode only (semi-global buckets take subjects of one length)");
+        return refuse(kWho, BGSA_HIP_EUNSUPPORTED, "per-subject lengths are traced in global mode only (semi-global buckets take subjects of one length)");
     // Myers scores -distance whatever the three ints hold (as the scoring calls: make_plan)
     const bool myers = params->algo == BGSA_ALGO_MYERS;
     const int match = myers ? 0 : params->match, mismatch = myers ? -1 : params->mismatch, gap = myers ? -1 : params->gap;
@@ -332,31 +308,27 @@ static int trace_pairs_entry(const bgsa_hip_params_t *params, const char *d_cont
         char why[200];
         snprintf(why, sizeof why, "max(|match|, |mismatch|, |gap|) * (ref_len + read_len) = %lld exceeds 32767: the DP row is kept in 16 bits",
                  widest * (static_cast<long long>(ref_len) + read_len));
-        return refuse(BGSA_HIP_EUNSUPPORTED, why);
+        return refuse(kWho, BGSA_HIP_EUNSUPPORTED, why);
     }
     const size_t per = pair_wave_bytes(ref_len, read_len);
-    if (d_workspace && workspace_bytes < per)
-        return refuse(BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_align_pairs_min_workspace_bytes()");
+    if (d_workspace && workspace_bytes < per) return refuse(kWho, BGSA_HIP_EINVAL, "workspace smaller than bgsa_hip_align_pairs_min_workspace_bytes()");
     if (n_pairs == 0) return BGSA_HIP_OK;
 
-    TraceRun r{};
-    r.args.p = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
-                        subject_base, d_score, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), nullptr, d_read_lens};
-    r.args.span = d_span;
-    r.args.match = match;
-    r.args.mismatch = mismatch;
-    r.args.gap = gap;
-    r.args.mode = params->alignment == BGSA_ALIGN_GLOBAL ? kGlobal : (myers ? kFreeQuery : kFreeSubject);
-    r.stream = static_cast<hipStream_t>(stream);
-    r.args.p.fault_word = device_fault_word();
-    if (!r.args.p.fault_word) return BGSA_HIP_EHIP;
-    if (int rc = allow_wide_rows(r.args.mode, trace_lds_bytes(read_len))) return rc;
-    if (d_workspace) {
-        r.workspace_bytes = workspace_bytes;
-        return run_trace(d_workspace, &r);
-    }
-    r.workspace_bytes = bgsa_hip_align_pairs_workspace_bytes(ref_len, read_len, n_pairs);
-    return with_own_scratch(r.stream, r.workspace_bytes, run_trace, &r);
+    TraceArgs args{};
+    args.p = PairArgs{d_content, d_peq, ref_len, read_len, read_count, word_num, d_pair_query, d_pair_subject, n_pairs, n_queries,
+                      subject_base, d_score, d_n_ops, d_cigar, cigar_cap, nullptr, per, pair_hist_bytes(ref_len, read_len), device_fault_word(), d_read_lens};
+    if (!args.p.fault_word) return BGSA_HIP_EHIP;
+    args.span = d_span;
+    args.match = match;
+    args.mismatch = mismatch;
+    args.gap = gap;
+    args.mode = params->alignment == BGSA_ALIGN_GLOBAL ? kGlobal : (myers ? kFreeQuery : kFreeSubject);
+    if (int rc = allow_wide_rows(args.mode, trace_lds_bytes(read_len))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return run_pair_chunks(d_workspace, workspace_bytes, per, n_pairs, s, [&](unsigned char *workspace, dim3 grid, int64_t first) {
+        args.p.workspace = workspace;
+        return launch_trace(args, grid, first, s);
+    });
 }
 
 }  // extern "C"
