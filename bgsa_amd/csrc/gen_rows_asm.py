@@ -22,6 +22,10 @@ dispatch of the next code (s_and / s_lshr_b64 / s_mul / s_add / s_addc / s_setpc
 taken branch and no loop counter.  All five bodies have the same byte length (same opcodes and
 operand classes), so the jump target is base + code * stride, both computed by the assembler from
 label differences.
+
+Layout of this file: the knobs and width lists; the skeleton, once (prologue, dispatch, refill / end / fail slots, done, slot
+padding, reg_for, the operand lists and cxx_function, and the two slot tables eight_slots and pair_slots); then one emitter per
+loop, which states only what is particular to it; then the headers' texts and main().
 """
 from __future__ import annotations
 
@@ -33,8 +37,9 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 import rows_ir as R  # noqa: E402
 
 MYERS_NW = [1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20, 22, 24, 25]  # Peq masks resident: 8 VALU per word (25 words = 253 VGPRs, the last width with two waves per SIMD)
-# resident Peq masks with 9 registers per word (rows_ir.myers_parked_body): 26 and 28 words (801..896 bp) fit 256 VGPRs at all,
-# 18 words (545..576 bp) drop from 183 to 165 VGPRs = three waves per SIMD instead of two
+# the widths that needed 9 registers per word before the eight-instruction row had them anyway (then rows_ir.myers_parked_body, now
+# myers_body like every other width): 26 and 28 words (801..896 bp) fit 256 VGPRs at all, 18 words (545..576 bp) drop from 183 to 165
+# VGPRs = three waves per SIMD instead of two.  The header emits them behind the widths of MYERS_NW.
 MYERS_PARKED_NW = [18, 26, 28]
 # 30 and 32 words (897..1024 bp) with the Peq planes resident (round 5): the two carry chains take turns over blocks of
 # MYERS_SPLIT words (rows_ir.myers_body(split=K)), so a row holds 2K temporaries instead of 2*nw: 7*nw + 2K + the kernel's own
@@ -93,11 +98,36 @@ CLOBBERS = ["s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69"
             "vcc", "scc", "memory"]
 
 
-def dispatch() -> list[str]:
+# ---- the threaded-code skeleton: every row loop below is put together from these pieces ------------------------------------
+STRIDE = "(L_body1_%= - L_body0_%=)"   # the slot stride of the loops whose slots are labelled L_body<n>
+PBASE = 2                              # first fixed VGPR of the 'P' registers (rows_ir.Body)
+WAIT_SCALAR, WAIT_ALL = "s_waitcnt lgkmcnt(0)", "s_waitcnt vmcnt(0) lgkmcnt(0)"
+
+
+def prologue(first: str = "L_body0_%=", extra=()) -> list[str]:
+    """Stream prologue: the first two windows on their way, the fetch budget, the dispatch base = address of slot `first`.
+    extra = a loop's own set-up lines, placed behind the loads so that they run under them."""
     return [
-        f"s_and_b32 {S_C}, {S_WIN_LO}, 7",
+        f"s_mov_b64 {S_PTR}, %[qp]",
+        f"s_mov_b32 {S_LEFT}, %[nwin]",
+        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
+        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
+        *extra,
+        f"s_getpc_b64 {S_PC}",
+        "L_anchor_%=:",
+        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, ({first} - L_anchor_%=)",
+        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
+        WAIT_SCALAR,  # scalar loads may return out of order: only 0 is safe
+    ]
+
+
+def dispatch(mask: str = "7", stride: str = STRIDE) -> list[str]:
+    """Jump to the slot of the next stream code: base + (code & mask) * stride.  Nothing that writes SCC may come between
+    s_add_u32 and s_addc_u32 when a loop places these lines between its own (weave_dispatch, gen_banded_cut_function)."""
+    return [
+        f"s_and_b32 {S_C}, {S_WIN_LO}, {mask}",
         f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
-        f"s_mul_i32 {S_C}, {S_C}, (L_body1_%= - L_body0_%=)",
+        f"s_mul_i32 {S_C}, {S_C}, {stride}",
         f"s_add_u32 {S_PC_LO}, {S_BASE_LO}, {S_C}",
         f"s_addc_u32 {S_PC_HI}, {S_BASE_HI}, 0",
         f"s_setpc_b64 {S_PC}",
@@ -136,107 +166,158 @@ def weave_dispatch(body_lines: list[str], disp_lines: list[str], tail: int = 14)
     return out
 
 
-def fail_slot() -> list[str]:
-    """Slot of a byte value that is no stream code: leave the loop and say so (S_LEFT = -2)."""
-    return [f"s_mov_b32 {S_LEFT}, -2", "s_branch L_done_%="]
-
-
-def done(wait: str = "s_waitcnt lgkmcnt(0)") -> list[str]:
-    """Common exit: every path out of the loop lands here; the caller gets S_LEFT (see above)."""
-    return ["L_done_%=:", wait, f"s_mov_b32 %[left], {S_LEFT}"]
-
-
-def gen_function(fn_name: str, template_args: str, body: R.Body, n_state: int, n_eq: int,
-                 n_planes: int = 0) -> str:
-    """n_planes > 0: the body reads class-independent code planes B[] instead of per-class masks."""
-    slot_of, n_slots = body.allocate_temps()
-
-    def reg_for(c: int):
-        def reg(name: str) -> str:
-            if name.startswith("S"):
-                return f"%[s{name[1:]}]"
-            if name.startswith("E"):
-                return f"%[e{c}_{name[1:]}]"
-            if name.startswith("B"):
-                return f"%[b{name[1:]}]"
-            if name.startswith("$c"):
-                return S_PARK[int(name[2:])]
-            return f"%[t{slot_of[name]}]"
-        return reg
-
-    asm: list[str] = []
-    asm += [
-        f"s_mov_b64 {S_PTR}, %[qp]",
-        f"s_mov_b32 {S_LEFT}, %[nwin]",
-        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-        f"s_getpc_b64 {S_PC}",
-        "L_anchor_%=:",
-        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, (L_body0_%= - L_anchor_%=)",
-        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
-        "s_waitcnt lgkmcnt(0)",  # scalar loads may return out of order: only 0 is safe
-    ]
-    asm += dispatch()
-    for c in range(5):
-        asm.append(f"L_body{c}_%=:")
-        asm += body.emit_asm(reg_for(c), c)
-        asm += dispatch()
-    # END (code 5) and REFILL (code 6) live in slots of the same stride as the row bodies.
-    asm.append("L_body5_%=:")
-    asm.append("s_branch L_done_%=")
-    asm.append(".fill ((L_body1_%= - L_body0_%=) - 4) / 4, 4, 0xbf800000")  # s_nop padding, never executed
-    asm.append("L_body6_%=:")
-    asm += [
-        # Exit condition every wave reaches: a well-formed stream never exhausts this budget (its
-        # END code comes first); a corrupt one stops here instead of walking memory.
+def refill() -> list[str]:
+    """REFILL slot (without its dispatch): the prefetched window becomes the current one, the one behind it is fetched.
+    Exit condition every wave reaches: a well-formed stream never exhausts this budget (its END code comes first); a
+    corrupt one stops here instead of walking memory."""
+    return [
         f"s_sub_u32 {S_LEFT}, {S_LEFT}, 1",
         "s_cbranch_scc1 L_done_%=",
-        "s_waitcnt lgkmcnt(0)",
+        WAIT_SCALAR,
         f"s_mov_b64 {S_WIN}, {S_NXT}",
         f"s_add_u32 {S_PTR_LO}, {S_PTR_LO}, 8",
         f"s_addc_u32 {S_PTR_HI}, {S_PTR_HI}, 0",
         f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
     ]
-    asm += dispatch()
-    asm.append("L_refill_end_%=:")
-    asm.append(".fill ((L_body1_%= - L_body0_%=) - (L_refill_end_%= - L_body6_%=)) / 4, 4, 0xbf800000")
-    asm.append("L_body7_%=:")  # the dispatch masks the code with 7: the one value that is no code lands here
-    asm += fail_slot()
-    asm += done()
 
-    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(n_state)]
-    outs += ['[left] "=s"(left)']
-    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
+
+def end_slot() -> list[str]:
+    return ["s_branch L_done_%="]
+
+
+def fail_slot() -> list[str]:
+    """Slot of a byte value that is no stream code: leave the loop and say so (S_LEFT = -2)."""
+    return [f"s_mov_b32 {S_LEFT}, -2", "s_branch L_done_%="]
+
+
+def done(wait: str = WAIT_SCALAR) -> list[str]:
+    """Common exit: every path out of the loop lands here; the caller gets S_LEFT (see above)."""
+    return ["L_done_%=:", wait, f"s_mov_b32 %[left], {S_LEFT}"]
+
+
+def slot(start: str, lines: list[str], end: str | int, stride: str = STRIDE) -> list[str]:
+    """A slot shorter than the stride, filled up to it with s_nop (never executed).  end = the label that closes the slot's
+    code, or its length in bytes."""
+    used = str(end) if isinstance(end, int) else f"({end} - {start})"
+    return [f"{start}:"] + lines + ([] if isinstance(end, int) else [f"{end}:"]) + [f".fill ({stride} - {used}) / 4, 4, 0xbf800000"]
+
+
+def reg_for(c: int, slot_of: dict, eq=None, scalars=None):
+    """rows_ir operand name -> asm operand of the body copy of class c: S<i> state, E<j> the class's match words (eq(j, c) where a
+    loop keeps them under names of its own), B<i> code planes, P<n> fixed VGPRs, $c<i> parked carry chains, a loop's own scalars
+    ($mask, $sh, $one ...), everything else a temporary."""
+    def reg(name: str) -> str:
+        if name.startswith("S"):
+            return f"%[s{name[1:]}]"
+        if name.startswith("E"):
+            return eq(name[1:], c) if eq else f"%[e{c}_{name[1:]}]"
+        if name.startswith("B"):
+            return f"%[b{name[1:]}]"
+        if name.startswith("P"):
+            return f"v{PBASE + int(name[1:])}"
+        if name.startswith("$c"):
+            return S_PARK[int(name[2:])]
+        if scalars and name in scalars:
+            return scalars[name]
+        return f"%[t{slot_of[name]}]"
+    return reg
+
+
+def band_scalars(sh: str, mask: str = "%[vmask]") -> dict:
+    """The banded bodies' scalars.  The band mask lives in a VGPR: a three-source VOP3 with an SGPR source issues in the
+    half-rate class (scripts/ubench: k3_sgpr 4.4 cycles against 2.7-2.95 with three VGPRs)."""
+    return {"$mask": mask, "$mask_lo": mask, "$mask_hi": "%[vmask_hi]", "$sh": sh, "$one": "1"}
+
+
+def state_ops(n: int) -> list[str]:
+    return [f'[s{i}] "+v"(state[{i}])' for i in range(n)]
+
+
+def tmp_ops(n: int) -> list[str]:
+    return [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n)]
+
+
+def mask_ops(n_eq: int, n_planes: int = 0) -> tuple[list[str], str]:
+    """Input operands and C++ parameter of the match masks: per-class words P[5][n_eq], or class-independent code planes B[]."""
     if n_planes:
-        ins = [f'[b{j}] "v"(B[{j}])' for j in range(n_planes)]
-        masks_param = f"const uint32_t (&B)[{n_planes}]"
+        return [f'[b{j}] "v"(B[{j}])' for j in range(n_planes)], f"const uint32_t (&B)[{n_planes}]"
+    return [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(n_eq)], f"const uint32_t (&P)[5][{n_eq}]"
+
+
+LEFT_OUT = '[left] "=s"(left)'
+STREAM_INS = ['[qp] "s"(stream)', '[nwin] "s"(n_windows)']
+
+
+def clobbers(scalars=(), first=()) -> list[str]:
+    """CLOBBERS plus a loop's own hard-coded registers (scripts/check_asm_kernels.py restates the sets as an independent check)."""
+    return [*first, *CLOBBERS[:-3], *scalars, *CLOBBERS[-3:]]
+
+
+def cxx_function(head: str, decls: list[str], asm: list[str], outs: list[str], ins: list[str], clob: list[str], tail=()) -> str:
+    """head (comment and signature) { decls; asm volatile(lines : outs : ins : clob); tail; }"""
+    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
+    return (f"\n{head}\n{{\n" + "".join(f"    {d}\n" for d in decls) +
+            f"    asm volatile(\n{text}\n        : {', '.join(outs)}\n        : {', '.join(ins)}\n        : " +
+            ", ".join(f'"{x}"' for x in clob) + ");\n" + "".join(f"    {t}\n" for t in tail) + "}\n")
+
+
+def eight_slots(row, slot7: list[str], extra=(), wait: str = WAIT_SCALAR) -> list[str]:
+    """The plain loop: slots 0..4 = row(c) of the five classes, 5 = END, 6 = REFILL, 7 = slot7 (the dispatch masks the code
+    with 7, so the one value that is no code of the plain stream lands there)."""
+    asm = prologue(extra=extra) + dispatch()
+    for c in range(5):
+        asm += [f"L_body{c}_%=:"] + row(c) + dispatch()
+    # END (code 5) and REFILL (code 6) live in slots of the same stride as the row bodies.
+    asm += slot("L_body5_%=", end_slot(), 4)
+    asm += slot("L_body6_%=", refill() + dispatch(), "L_refill_end_%=")
+    asm += ["L_body7_%=:"] + slot7
+    return asm + done(wait)
+
+
+def pair_slots(row, last, extra=(), event: list[str] | None = None, wait: str = WAIT_SCALAR) -> list[str]:
+    """Two rows per token (the dispatch is the loop's scalar bottleneck).  Slots 0..24: rows of classes a, b (code 5a + b),
+    25..29: one row (the odd last row), 30 END, 31 REFILL (bgsa_common.h: pair_stream_window); slot stride = a two-row body.
+    row(c) = a row, last(c) = the
+    token's last row AND the next dispatch.  Without events the dispatch masks with 0x1f and all 32 slots exist: no byte value
+    can leave the table.  With them (bgsa_common.h: banded_stream_layout) it masks with 0x3f: every value that is no token
+    lands in a fail slot, and 63 = EVENT <arg> is the last slot, so it may be longer than the slot stride."""
+    mask = "0x1f" if event is None else "0x3f"
+    L, E = "L_body{}_%=".format, "L_end{}_%=".format
+    asm = prologue(extra=extra) + dispatch(mask)
+    for a in range(5):
+        for b in range(5):
+            asm += [f"{L(5 * a + b)}:"] + row(a) + last(b)
+    for c in range(5):
+        asm += slot(L(25 + c), last(c), E(25 + c))
+    asm += slot(L(30), end_slot(), E(30))
+    if event is None:
+        asm += [f"{L(31)}:"] + refill() + dispatch(mask)
     else:
-        ins = [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(n_eq)]
-        masks_param = f"const uint32_t (&P)[5][{n_eq}]"
-    ins.append('[qp] "s"(stream)')
-    ins.append('[nwin] "s"(n_windows)')
+        asm += slot(L(31), refill() + dispatch(mask), E(31))
+        for s in range(32, 63):
+            asm += slot(L(s), fail_slot(), E(s))
+        asm += [f"{L(63)}:"] + event + dispatch(mask)
+    return asm + done(wait)
+
+
+# ---- the emitters: what is particular to each loop ---------------------------------------------------------------------
+
+def gen_function(fn_name: str, template_args: str, body: R.Body, n_state: int, n_eq: int,
+                 n_planes: int = 0) -> str:
+    """n_planes > 0: the body reads class-independent code planes B[] instead of per-class masks."""
+    slot_of, n_slots = body.allocate_temps()
+    asm = eight_slots(lambda c: body.emit_asm(reg_for(c, slot_of), c), fail_slot())
+    ins, masks_param = mask_ops(n_eq, n_planes)
     parks = ["s72", "s73", "s74", "s75"] if any(op.kind in ("savecc", "loadcc") for op in body.ops) else []
-    clob = ", ".join(f'"{c}"' for c in CLOBBERS[:-3] + parks + CLOBBERS[-3:])
     nops = sum(line.startswith("s_nop") for line in body.emit_asm(lambda x: S_PARK[int(x[2:])] if x.startswith("$c") else x, 0))
-    return f"""
-// {body.valu_count()} VALU per row, {n_slots} temporaries, {nops} hazard nops{f", {body.salu_count()} scalar moves of VCC" if parks else ""}
+    head = f"""// {body.valu_count()} VALU per row, {n_slots} temporaries, {nops} hazard nops{f", {body.salu_count()} scalar moves of VCC" if parks else ""}
 template <>
 __device__ __forceinline__ int {fn_name}<{template_args}>(uint32_t (&state)[{n_state}],
                                                    {masks_param},
                                                    const unsigned long long stream,
-                                                   const int n_windows)
-{{
-    uint32_t tmp[{max(n_slots, 1)}];
-    int left;
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-    return left;
-}}
-"""
+                                                   const int n_windows)"""
+    return cxx_function(head, [f"uint32_t tmp[{max(n_slots, 1)}];", "int left;"], asm,
+                        state_ops(n_state) + [LEFT_OUT] + tmp_ops(n_slots), ins + STREAM_INS, clobbers(parks), ["return left;"])
 
 
 def gen_band_function(nw: int, groups: int = 1) -> str:
@@ -259,72 +340,21 @@ def gen_band_function(nw: int, groups: int = 1) -> str:
     full = sched(R.myers_body(nw, 1, balanced=MYERS_BALANCED) if groups == 1 else
                  R.myers_window_body(nw, 0, nw - 1, groups=groups, balanced=MYERS_BALANCED))
     slot_of, n_slots = full.allocate_temps()
-    stride = f"(L_g{k_full}s1_%= - L_g{k_full}s0_%=)"
+    stride = f"(L_g{k_full}s1_%= - L_g{k_full}s0_%=)"   # the full group's bodies define it
+    disp = dispatch(stride=stride)
 
-    def reg_for(c: int, slots: dict):
-        def reg(name: str) -> str:
-            if name.startswith("S"):
-                return f"%[s{name[1:]}]"
-            if name.startswith("E"):
-                return f"%[e{c}_{name[1:]}]"
-            return f"%[t{slots[name]}]"
-        return reg
-
-    def disp() -> list[str]:
-        return [
-            f"s_and_b32 {S_C}, {S_WIN_LO}, 7",
-            f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
-            f"s_mul_i32 {S_C}, {S_C}, {stride}",
-            f"s_add_u32 {S_PC_LO}, {S_BASE_LO}, {S_C}",
-            f"s_addc_u32 {S_PC_HI}, {S_BASE_HI}, 0",
-            f"s_setpc_b64 {S_PC}",
-        ]
-
-    def pad(k: int, s: int) -> str:   # fill slot s of group k up to the stride (the full group's bodies define it)
-        return f".fill ({stride} - (L_g{k}e{s}_%= - L_g{k}s{s}_%=)) / 4, 4, 0xbf800000"
-
-    asm: list[str] = [
-        f"s_mov_b64 {S_PTR}, %[qp]",
-        f"s_mov_b32 {S_LEFT}, %[nwin]",
-        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-        f"s_getpc_b64 {S_PC}",
-        "L_anchor_%=:",
-        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, (L_g{k_full}s0_%= - L_anchor_%=)",   # the stream's first SETWIN picks the window
-        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
-        "s_waitcnt lgkmcnt(0)",
-    ]
-    asm += disp()
+    asm = prologue(f"L_g{k_full}s0_%=") + disp      # the stream's first SETWIN picks the window
     for k, (a, b) in enumerate(windows):
         body = full if (a, b) == (0, nw - 1) else sched(R.myers_window_body(nw, a, b, groups=groups, balanced=MYERS_BALANCED))
         slots, n = (slot_of, n_slots) if body is full else body.allocate_temps()
         assert n <= n_slots
+        S, E = f"L_g{k}s{{}}_%=".format, f"L_g{k}e{{}}_%=".format
         for c in range(5):
-            asm.append(f"L_g{k}s{c}_%=:")
-            asm += body.emit_asm(reg_for(c, slots), c)
-            asm += disp()
-            if body is not full:
-                asm.append(f"L_g{k}e{c}_%=:")
-                asm.append(pad(k, c))
-        asm.append(f"L_g{k}s5_%=:")     # END
-        asm.append("s_branch L_done_%=")
-        asm.append(f"L_g{k}e5_%=:")
-        asm.append(pad(k, 5))
-        asm.append(f"L_g{k}s6_%=:")     # REFILL
-        asm += [
-            f"s_sub_u32 {S_LEFT}, {S_LEFT}, 1",
-            "s_cbranch_scc1 L_done_%=",
-            "s_waitcnt lgkmcnt(0)",
-            f"s_mov_b64 {S_WIN}, {S_NXT}",
-            f"s_add_u32 {S_PTR_LO}, {S_PTR_LO}, 8",
-            f"s_addc_u32 {S_PTR_HI}, {S_PTR_HI}, 0",
-            f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-        ]
-        asm += disp()
-        asm.append(f"L_g{k}e6_%=:")
-        asm.append(pad(k, 6))
-        asm.append(f"L_g{k}s7_%=:")     # SETWIN <window byte>
-        asm += [
+            lines = body.emit_asm(reg_for(c, slots), c) + disp
+            asm += [f"{S(c)}:"] + lines if body is full else slot(S(c), lines, E(c), stride)
+        asm += slot(S(5), end_slot(), E(5), stride)
+        asm += slot(S(6), refill() + disp, E(6), stride)
+        setwin = [                          # SETWIN <window byte>
             f"s_and_b32 {S_C}, {S_WIN_LO}, 0xff",
             f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
             f"s_cmp_ge_u32 {S_C}, {len(windows)}",
@@ -339,140 +369,40 @@ def gen_band_function(nw: int, groups: int = 1) -> str:
             f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, {S_C}",
             f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
         ]
-        asm += disp()
-        asm.append(f"L_g{k}e7_%=:")
-        asm.append(pad(k, 7))
-    asm.append("L_fail_%=:")
-    asm += fail_slot()
-    asm += done()
+        asm += slot(S(7), setwin + disp, E(7), stride)
+    asm += ["L_fail_%=:"] + fail_slot() + done()
 
-    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(2 * groups * nw)]
-    outs += ['[left] "=s"(left)']
-    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
-    ins = [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(groups * nw)]
-    ins += ['[qp] "s"(stream)', '[nwin] "s"(n_windows)', '[band] "s"(band)']
-    clob = ", ".join(f'"{c}"' for c in CLOBBERS)
-    return f"""
-// {len(windows)} windows; full rows {full.valu_count()} VALU, {n_slots} temporaries
+    head = f"""// {len(windows)} windows; full rows {full.valu_count()} VALU, {n_slots} temporaries
 template <>
 __device__ __forceinline__ int myers_band_rows_asm<{nw}, {groups}>(uint32_t (&state)[{2 * groups * nw}],
                                                   const uint32_t (&P)[5][{groups * nw}],
                                                   const unsigned long long stream,
-                                                  const int n_windows, const int band)
-{{
-    uint32_t tmp[{n_slots}];
-    int left;
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-    return left;
-}}
-"""
+                                                  const int n_windows, const int band)"""
+    return cxx_function(head, [f"uint32_t tmp[{n_slots}];", "int left;"], asm,
+                        state_ops(2 * groups * nw) + [LEFT_OUT] + tmp_ops(n_slots),
+                        mask_ops(groups * nw)[0] + STREAM_INS + ['[band] "s"(band)'], clobbers(), ["return left;"])
 
 
 def gen_pair_function(fn_name: str, template_args: str, body: R.Body, n_state: int, n_eq: int) -> str:
     """Row loop for bodies too short to hide the scalar dispatch (Myers on short subjects: 10-20 VALU
-    per row): every stream token carries TWO rows.  Slots: 0..24 two rows of classes a, b (code 5a + b),
-    25..29 one row (the odd last row), 30 END, 31 REFILL (bgsa_common.h: pair_stream_window)."""
+    per row): every stream token carries TWO rows (pair_slots, no events; same exit condition as gen_function)."""
     slot_of, n_slots = body.allocate_temps()
-
-    def reg_for(c: int):
-        def reg(name: str) -> str:
-            if name.startswith("S"):
-                return f"%[s{name[1:]}]"
-            if name.startswith("E"):
-                return f"%[e{c}_{name[1:]}]"
-            return f"%[t{slot_of[name]}]"
-        return reg
-
-    def disp() -> list[str]:
-        return [
-            f"s_and_b32 {S_C}, {S_WIN_LO}, 0x1f",
-            f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
-            f"s_mul_i32 {S_C}, {S_C}, (L_body1_%= - L_body0_%=)",
-            f"s_add_u32 {S_PC_LO}, {S_BASE_LO}, {S_C}",
-            f"s_addc_u32 {S_PC_HI}, {S_BASE_HI}, 0",
-            f"s_setpc_b64 {S_PC}",
-        ]
-
-    def pad(slot: int) -> str:
-        return f".fill ((L_body1_%= - L_body0_%=) - (L_end{slot}_%= - L_body{slot}_%=)) / 4, 4, 0xbf800000"
-
-    asm = [
-        f"s_mov_b64 {S_PTR}, %[qp]",
-        f"s_mov_b32 {S_LEFT}, %[nwin]",
-        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-        f"s_getpc_b64 {S_PC}",
-        "L_anchor_%=:",
-        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, (L_body0_%= - L_anchor_%=)",
-        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
-        "s_waitcnt lgkmcnt(0)",
-    ]
-    asm += disp()
-    for a in range(5):
-        for b2 in range(5):
-            asm.append(f"L_body{5 * a + b2}_%=:")
-            asm += body.emit_asm(reg_for(a), a)
-            asm += body.emit_asm(reg_for(b2), b2)
-            asm += disp()
-    for c in range(5):
-        asm.append(f"L_body{25 + c}_%=:")
-        asm += body.emit_asm(reg_for(c), c)
-        asm += disp()
-        asm.append(f"L_end{25 + c}_%=:")
-        asm.append(pad(25 + c))
-    asm.append("L_body30_%=:")  # END
-    asm.append("s_branch L_done_%=")
-    asm.append("L_end30_%=:")
-    asm.append(pad(30))
-    asm.append("L_body31_%=:")  # REFILL (same exit condition as gen_function)
-    asm += [
-        f"s_sub_u32 {S_LEFT}, {S_LEFT}, 1",
-        "s_cbranch_scc1 L_done_%=",
-        "s_waitcnt lgkmcnt(0)",
-        f"s_mov_b64 {S_WIN}, {S_NXT}",
-        f"s_add_u32 {S_PTR_LO}, {S_PTR_LO}, 8",
-        f"s_addc_u32 {S_PTR_HI}, {S_PTR_HI}, 0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-    ]
-    asm += disp()
-    asm += done()   # the dispatch masks with 0x1f and all 32 slots exist: no byte value can leave the table
-
-    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(n_state)]
-    outs += ['[left] "=s"(left)']
-    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
-    ins = [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(n_eq)]
-    ins.append('[qp] "s"(stream)')
-    ins.append('[nwin] "s"(n_windows)')
-    clob = ", ".join(f'"{c}"' for c in CLOBBERS)
-    return f"""
-// two rows per token: {2 * body.valu_count()} VALU per token, {n_slots} temporaries
+    row = lambda c: body.emit_asm(reg_for(c, slot_of), c)
+    asm = pair_slots(row, lambda c: row(c) + dispatch("0x1f"))
+    ins, masks_param = mask_ops(n_eq)
+    head = f"""// two rows per token: {2 * body.valu_count()} VALU per token, {n_slots} temporaries
 template <>
 __device__ __forceinline__ int {fn_name}<{template_args}>(uint32_t (&state)[{n_state}],
-                                                   const uint32_t (&P)[5][{n_eq}],
+                                                   {masks_param},
                                                    const unsigned long long stream,
-                                                   const int n_windows)
-{{
-    uint32_t tmp[{max(n_slots, 1)}];
-    int left;
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-    return left;
-}}
-"""
+                                                   const int n_windows)"""
+    return cxx_function(head, [f"uint32_t tmp[{max(n_slots, 1)}];", "int left;"], asm,
+                        state_ops(n_state) + [LEFT_OUT] + tmp_ops(n_slots), ins + STREAM_INS, clobbers(), ["return left;"])
 
 
 def gen_banded_function(wide: bool, phase: bool = False) -> str:
     """Row loop of the banded kernel: 32-bit band word (k <= 15) or a 64-bit pair (k <= 31).  Same
-    threaded-code skeleton plus stream code 63 = EVENT (followed by an argument byte): test/latch the
+    threaded-code skeleton (pair_slots) plus stream code 63 = EVENT (followed by an argument byte): test/latch the
     reject mask, reset the error count at row k, advance the match-string words every 32 rows
     (rows_ir.banded_tokens).  phase: the band held in place (rows_ir.banded_phase_body, k <= 11) — the rows read
     the phase's window of their class (W[c]) and a re-anchor event (bit 16) every banded_phase_rows(k) rows shifts
@@ -490,112 +420,24 @@ def gen_banded_function(wide: bool, phase: bool = False) -> str:
     # survivor compaction (banded.hip "survivor queue"): rows done = 32 * S_CHUNK + S_SH; a test at or after row
     # S_PUSHROW that finds 1..S_PUSHMAX lanes alive ends the wave with S_EARLY = 1, the alive lanes go to the queue
     S_CHUNK, S_PUSHROW, S_PUSHMAX, S_EARLY, S_CNT = "s92", "s93", "s94", "s95", "s79"
-    clobbers = CLOBBERS[:-3] + ["s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79"] + [f"s{i}" for i in range(80, 96)] + \
-        ["vcc", "scc", "memory"]
 
-    def reg_for(c: int):
-        def reg(name: str) -> str:
-            if name.startswith("S"):
-                return f"%[s{name[1:]}]"
-            if name.startswith("E"):
-                return f"%[w{c}]" if phase else f"%[m{name[1:]}_{c}]"
-            if name in ("$mask", "$mask_lo"):
-                # the band mask lives in a VGPR: a three-source VOP3 with an SGPR source issues in the half-rate class
-                # (scripts/ubench: k3_sgpr 4.4 cycles against 2.7-2.95 with three VGPRs)
-                return "%[vmask]"
-            if name == "$mask_hi":
-                return "%[vmask_hi]"
-            if name == "$sh":
-                return S_SH
-            if name == "$one":
-                return "1"
-            return f"%[t{slot_of[name]}]"
-        return reg
-
-    def disp() -> list[str]:
-        # token codes 0..31 and 63 (bgsa_common.h: banded_stream_layout); slot stride = a two-row body
-        return [
-            f"s_and_b32 {S_C}, {S_WIN_LO}, 0x3f",
-            f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
-            f"s_mul_i32 {S_C}, {S_C}, (L_body1_%= - L_body0_%=)",
-            f"s_add_u32 {S_PC_LO}, {S_BASE_LO}, {S_C}",
-            f"s_addc_u32 {S_PC_HI}, {S_BASE_HI}, 0",
-            f"s_setpc_b64 {S_PC}",
-        ]
-
-    def pad(slot: int) -> str:
-        """s_nop filler (never executed) up to the common slot stride."""
-        return f".fill ((L_body1_%= - L_body0_%=) - (L_end{slot}_%= - L_body{slot}_%=)) / 4, 4, 0xbf800000"
-
-    asm = [
-        f"s_mov_b64 {S_PTR}, %[qp]",
-        f"s_mov_b32 {S_LEFT}, %[nwin]",
-        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-        f"s_mov_b32 {S_THR}, %[thr]",
-    ] + ([f"s_mov_b32 {S_PH}, %[phase]", f"s_mov_b32 {S_MASK0}, %[mask0]"] if phase else []) + [
+    extra = [f"s_mov_b32 {S_THR}, %[thr]"] + ([f"s_mov_b32 {S_PH}, %[phase]", f"s_mov_b32 {S_MASK0}, %[mask0]"] if phase else []) + [
         f"s_mov_b32 {S_SH}, 0",
         f"s_mov_b64 {S_DEAD}, 0",
         f"s_mov_b32 {S_CHUNK}, 0",
         f"s_mov_b32 {S_EARLY}, 0",
         f"s_mov_b32 {S_PUSHROW}, %[pushrow]",
         f"s_mov_b32 {S_PUSHMAX}, %[pushmax]",
-    ]
-    asm += [f"s_mov_b64 {S_BASE[c]}, %[base{c}]" for c in range(5)]
-    asm += [
-        f"s_getpc_b64 {S_PC}",
-        "L_anchor_%=:",
-        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, (L_body0_%= - L_anchor_%=)",
-        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
-        "s_waitcnt lgkmcnt(0)",
-    ]
-    asm += disp()
-    for a in range(5):          # slots 0..24: two rows per token (the dispatch is the loop's scalar bottleneck)
-        for b2 in range(5):
-            asm.append(f"L_body{5 * a + b2}_%=:")
-            asm += body.emit_asm(reg_for(a), a)
-            asm.append(f"s_add_u32 {S_SH}, {S_SH}, 1")
-            asm += body.emit_asm(reg_for(b2), b2)
-            asm.append(f"s_add_u32 {S_SH}, {S_SH}, 1")
-            asm += disp()
-    for c in range(5):          # slots 25..29: one row
-        asm.append(f"L_body{25 + c}_%=:")
-        asm += body.emit_asm(reg_for(c), c)
-        asm.append(f"s_add_u32 {S_SH}, {S_SH}, 1")
-        asm += disp()
-        asm.append(f"L_end{25 + c}_%=:")
-        asm.append(pad(25 + c))
-    asm.append("L_body30_%=:")  # END
-    asm.append("s_branch L_done_%=")
-    asm.append("L_end30_%=:")
-    asm.append(pad(30))
-    asm.append("L_body31_%=:")  # REFILL
-    asm += [
-        f"s_sub_u32 {S_LEFT}, {S_LEFT}, 1",
-        "s_cbranch_scc1 L_done_%=",
-        "s_waitcnt lgkmcnt(0)",
-        f"s_mov_b64 {S_WIN}, {S_NXT}",
-        f"s_add_u32 {S_PTR_LO}, {S_PTR_LO}, 8",
-        f"s_addc_u32 {S_PTR_HI}, {S_PTR_HI}, 0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-    ]
-    asm += disp()
-    asm.append("L_end31_%=:")
-    asm.append(pad(31))
-    for slot in range(32, 63):   # the dispatch masks with 0x3f: every value that is no token lands in a fail slot
-        asm.append(f"L_body{slot}_%=:")
-        asm += fail_slot()
-        asm.append(f"L_end{slot}_%=:")
-        asm.append(pad(slot))
-    asm.append("L_body63_%=:")  # EVENT <arg>: the last slot, so it may be longer than the slot stride
-    asm += [
+    ] + [f"s_mov_b64 {S_BASE[c]}, %[base{c}]" for c in range(5)]
+    test = [f"v_bcnt_u32_b32 %[t0], %[s5], %[s{acc}]", f"v_cmp_lt_u32 vcc, {S_THR}, %[t0]"] if phase else \
+           [f"v_cmp_lt_u32 vcc, {S_THR}, %[s{acc}]"]
+    event = [
         f"s_and_b32 {S_ARG}, {S_WIN_LO}, 0xff",
         f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
         # by far the most frequent event is the plain test (argument 4): its own short path, no bit tests
         f"s_cmp_eq_u32 {S_ARG}, 4",
         "s_cbranch_scc0 L_ev_general_%=",
-    ] + ([f"v_bcnt_u32_b32 %[t0], %[s5], %[s{acc}]", f"v_cmp_lt_u32 vcc, {S_THR}, %[t0]"] if phase else
-         [f"v_cmp_lt_u32 vcc, {S_THR}, %[s{acc}]"]) + [
+    ] + test + [
         f"s_andn2_b64 {S_TMP}, exec, vcc",
         "s_cbranch_scc0 L_ev_alldead_%=",
         f"s_lshl_b32 {S_CNT}, {S_CHUNK}, 5",
@@ -615,8 +457,7 @@ def gen_banded_function(wide: bool, phase: bool = False) -> str:
         # bit 2: test err > limit on every lane; bit 3: latch the reject mask (last checkpoint)
         f"s_bitcmp1_b32 {S_ARG}, 2",
         "s_cbranch_scc0 L_ev_reset_%=",
-    ] + ([f"v_bcnt_u32_b32 %[t0], %[s5], %[s{acc}]", f"v_cmp_lt_u32 vcc, {S_THR}, %[t0]"] if phase else
-         [f"v_cmp_lt_u32 vcc, {S_THR}, %[s{acc}]"]) + [
+    ] + test + [
         f"s_bitcmp1_b32 {S_ARG}, 3",
         "s_cbranch_scc0 L_ev_all_%=",
         f"s_mov_b64 {S_DEAD}, vcc",
@@ -648,17 +489,17 @@ def gen_banded_function(wide: bool, phase: bool = False) -> str:
         "s_waitcnt vmcnt(0)",
     ]
     for c in range(5):
-        asm += [f"v_mov_b32 %[m{w}_{c}], %[m{w + 1}_{c}]" for w in range(n_m - 1)]
+        event += [f"v_mov_b32 %[m{w}_{c}], %[m{w + 1}_{c}]" for w in range(n_m - 1)]
     for c in range(5):
-        asm.append(f"global_load_dword %[m{n_m - 1}_{c}], %[voff], {S_BASE[c]}")
-    asm += [
+        event.append(f"global_load_dword %[m{n_m - 1}_{c}], %[voff], {S_BASE[c]}")
+    event += [
         "v_add_u32 %[voff], 0x100, %[voff]",
         f"s_mov_b32 {S_SH}, 0",
         f"s_add_u32 {S_CHUNK}, {S_CHUNK}, 1",
         "L_ev_anchor_%=:",
     ]
     if phase:
-        asm += [
+        event += [
             f"s_bitcmp1_b32 {S_ARG}, 4",  # bit 4: the phase is over -> the band back to bit 0, its error bits counted, new windows
             "s_cbranch_scc0 L_ev_out_%=",
             f"v_lshrrev_b32 %[s0], {S_PH}, %[s0]",
@@ -668,28 +509,23 @@ def gen_banded_function(wide: bool, phase: bool = False) -> str:
             f"v_mov_b32 %[s3], {S_MASK0}",
             "v_mov_b32 %[s4], 1",
         ]
-        asm += [f"v_alignbit_b32 %[w{c}], %[m1_{c}], %[m0_{c}], {S_SH}" for c in range(5)]
-    asm += [
-        "L_ev_out_%=:",
-    ]
-    asm += disp()
-    asm += done("s_waitcnt vmcnt(0) lgkmcnt(0)")
-    asm.append(f"s_mov_b64 %[dead], {S_DEAD}")
-    asm.append(f"s_mov_b32 %[early], {S_EARLY}")
+        event += [f"v_alignbit_b32 %[w{c}], %[m1_{c}], %[m0_{c}], {S_SH}" for c in range(5)]
+    event.append("L_ev_out_%=:")
 
-    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(n_state)]
-    outs += [f'[m{w}_{c}] "+v"(M[{c}][{w}])' for c in range(5) for w in range(n_m)]
+    eq = (lambda j, c: f"%[w{c}]") if phase else (lambda j, c: f"%[m{j}_{c}]")
+    row = lambda c: body.emit_asm(reg_for(c, slot_of, eq, band_scalars(S_SH)), c) + [f"s_add_u32 {S_SH}, {S_SH}, 1"]
+    asm = pair_slots(row, lambda c: row(c) + dispatch("0x3f"), extra, event, WAIT_ALL)
+    asm += [f"s_mov_b64 %[dead], {S_DEAD}", f"s_mov_b32 %[early], {S_EARLY}"]
+
+    outs = state_ops(n_state) + [f'[m{w}_{c}] "+v"(M[{c}][{w}])' for c in range(5) for w in range(n_m)]
     if phase:
         outs += [f'[w{c}] "+v"(W[{c}])' for c in range(5)]
-    outs += ['[voff] "+v"(voff)', '[dead] "=s"(dead)', '[left] "=s"(left)', '[early] "=s"(early)']
-    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
-    ins = ['[qp] "s"(stream)', '[nwin] "s"(n_windows)'] + \
+    outs += ['[voff] "+v"(voff)', '[dead] "=s"(dead)', LEFT_OUT, '[early] "=s"(early)'] + tmp_ops(n_slots)
+    ins = STREAM_INS + \
           (['[phase] "s"(phase_rows)', '[mask0] "s"(band_mask)'] if phase else ['[vmask] "v"(band_mask)']) + \
           (['[vmask_hi] "v"(band_mask_hi)'] if wide else []) + \
           ['[thr] "s"(limit)', '[pushrow] "s"(push_row)', '[pushmax] "s"(push_max)']
     ins += [f'[base{c}] "s"(base[{c}])' for c in range(5)]
-    clob = ", ".join(f'"{x}"' for x in clobbers)
     fn_name = "banded_rows_phase_asm32" if phase else f"banded_rows_asm{64 if wide else 32}"
     w_param = "uint32_t (&W)[5], " if phase else ""
     last_param = "phase_rows" if phase else "band_mask_hi"
@@ -697,8 +533,7 @@ def gen_banded_function(wide: bool, phase: bool = False) -> str:
                  "// the phase's error bits}; W[c] = the phase's match window of class c; phase_rows = banded_phase_rows(k).  After the\n"
                  "// loop the state sits at the offset of the rows of the LAST phase: the caller shifts VP / VN down by that and adds\n"
                  "// popcount(error bits) to the errors.\n") if phase else ""
-    return f"""
-// {body.valu_count()} VALU per row ({sum(op.kind in ('lshr1', 'alignbit') for op in body.ops)} of them slow-class), {n_slots} temporaries
+    head = f"""// {body.valu_count()} VALU per row ({sum(op.kind in ('lshr1', 'alignbit') for op in body.ops)} of them slow-class), {n_slots} temporaries
 // state = {{VP, VN, errors since row k}} (VP lo/hi, VN lo/hi, errors when wide); M[c][..] = consecutive
 // 32-bit words of class c's offset match string (the last one is the prefetch target); voff = byte
 // offset of the next word to fetch relative to base[c]; returns the reject mask (lanes whose error
@@ -711,18 +546,9 @@ def gen_banded_function(wide: bool, phase: bool = False) -> str:
                                                               const unsigned long long stream, const int n_windows,
                                                               const uint32_t band_mask, const uint32_t {last_param},
                                                               const uint32_t limit, const uint32_t push_row,
-                                                              const uint32_t push_max, int &left, int &early)
-{{
-    uint32_t tmp[{max(n_slots, 1)}];
-    unsigned long long dead;
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-    return dead;
-}}
-"""
+                                                              const uint32_t push_max, int &left, int &early)"""
+    return cxx_function(head, [f"uint32_t tmp[{max(n_slots, 1)}];", "unsigned long long dead;"], asm, outs, ins,
+                        clobbers([f"s{i}" for i in range(72, 96)]), ["return dead;"])
 
 
 def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) -> str:
@@ -731,7 +557,7 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
     shift counter and event, the next token's dispatch woven under the last row, solid-survivor pushes — around the
     funnel-shift rows of thresholds 13 .. 15 (rows_ir.banded_funnel_body: one v_alignbit per group in the row, three
     match-string words per class and group, the last one the prefetch target) and 16 .. 31 (the 64-bit pair: four words);
-    no cut events.  Same threaded-code skeleton, stream and events as gen_banded_function, plus EVENT bit 5 = cut.
+    no cut events.  Same threaded-code skeleton (pair_slots), stream and events as gen_banded_function, plus EVENT bit 5 = cut.
     Per group and class TWO registers: m0 = the window the rows shift (A: at an advance the 32-bit match-string word the
     next 32 rows start in), m1 = the word behind it (B).  advance (bit 1, every 32 rows): A <- B, fetch B (awaited by
     the next cut, 16 or 8 rows later); cut (bit 5, every `cutrows` rows in between): A <- {B >> rows cut so far, A} >>
@@ -747,9 +573,7 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
     funnel, wide = form != "cut", form == "funnel64"
     assert wide or not sh64
     body = R.banded_cut_body(G) if not funnel else R.schedule(R.banded_funnel_body(G, wide, sh64=sh64), 8)
-    PBASE = 2                                            # first fixed VGPR of the 'P' registers (rows_ir.Body)
-    n_fixed = 2 * G if sh64 else 0
-    P = lambda n: f"v{PBASE + n}"
+    fixed = [f"v{PBASE + i}" for i in range(2 * G if sh64 else 0)]   # the 'P' registers of the sh64 form
     per_state = 5 if wide else 3
     n_state = per_state * G
     acc = [per_state * g + per_state - 1 for g in range(G)]
@@ -763,43 +587,15 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
     S_BASE = [f"s[{80 + 2 * c}:{81 + 2 * c}]" for c in range(5)]
     S_CHUNK, S_PUSHROW, S_PUSHMAX, S_EARLY = "s92", "s93", "s94", "s95"
     S_PUSHSOLID, S_THRSOLID = "s56", "s55"
-    clobbers = [P(i) for i in range(n_fixed)] + ["s55", "s56", "s57", "s58", "s59"] + CLOBBERS[:-3] + [f"s{i}" for i in range(72, 100)] + \
-               ["vcc", "scc", "memory"]
+    disp = dispatch("0x3f")
 
-    def reg_for(c: int):
-        def reg(name: str) -> str:
-            if name.startswith("P"):
-                return P(int(name[1:]))
-            if name.startswith("S"):
-                return f"%[s{name[1:]}]"
-            if name.startswith("E") and funnel:
-                j = int(name[1:])
-                return f"%[m{j % n_eq}_{c}_{j // n_eq}]"
-            if name.startswith("E"):
-                return f"%[m0_{c}_{name[1:]}]"       # the window: register A
-            if name in ("$mask", "$mask_lo"):
-                return "%[vmask]"
-            if name == "$mask_hi":
-                return "%[vmask_hi]"
-            if name == "$sh":
-                return S_SH
-            if name == "$one":
-                return "1"
-            return f"%[t{slot_of[name]}]"
-        return reg
+    def eq(j: str, c: int) -> str:
+        if funnel:
+            return f"%[m{int(j) % n_eq}_{c}_{int(j) // n_eq}]"
+        return f"%[m0_{c}_{j}]"       # the window: register A
 
-    def disp() -> list[str]:
-        return [
-            f"s_and_b32 {S_C}, {S_WIN_LO}, 0x3f",
-            f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
-            f"s_mul_i32 {S_C}, {S_C}, (L_body1_%= - L_body0_%=)",
-            f"s_add_u32 {S_PC_LO}, {S_BASE_LO}, {S_C}",
-            f"s_addc_u32 {S_PC_HI}, {S_BASE_HI}, 0",
-            f"s_setpc_b64 {S_PC}",
-        ]
-
-    def pad(slot: int) -> str:
-        return f".fill ((L_body1_%= - L_body0_%=) - (L_end{slot}_%= - L_body{slot}_%=)) / 4, 4, 0xbf800000"
+    def rows(c: int) -> list[str]:
+        return body.emit_asm(reg_for(c, slot_of, eq, band_scalars(S_SH)), c)
 
     def test(tag: str) -> list[str]:
         """err > limit on every lane of every group -> vcc (group 0), S_VCC1 (group 1); alive masks; scc = any alive."""
@@ -857,11 +653,7 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
         out += [f"s_mov_b32 {S_EARLY}, 1", "s_branch L_done_%="]
         return out
 
-    asm = [
-        f"s_mov_b64 {S_PTR}, %[qp]",
-        f"s_mov_b32 {S_LEFT}, %[nwin]",
-        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
+    extra = [
         f"s_mov_b32 {S_THR}, %[thr]",
         f"s_mov_b32 {S_CUTROWS}, %[cutrows]",
         f"s_mov_b32 {S_SH}, 0",
@@ -873,16 +665,9 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
         f"s_mov_b32 {S_PUSHSOLID}, %[pushsolid]",
         f"s_mov_b32 {S_THRSOLID}, %[solidthr]",
     ]
-    asm += [f"s_mov_b64 {S_DEAD[g]}, 0" for g in range(G)]
-    asm += [f"s_mov_b64 {S_BASE[c]}, %[base{c}]" for c in range(5)]
-    asm += [
-        f"s_getpc_b64 {S_PC}",
-        "L_anchor_%=:",
-        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, (L_body0_%= - L_anchor_%=)",
-        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
-        "s_waitcnt lgkmcnt(0)",
-    ]
-    asm += disp()
+    extra += [f"s_mov_b64 {S_DEAD[g]}, 0" for g in range(G)]
+    extra += [f"s_mov_b64 {S_BASE[c]}, %[base{c}]" for c in range(5)]
+
     def last_row_and_dispatch(c: int) -> list[str]:
         """The token's last row with the next token's dispatch computed UNDER it: the five scalar instructions that turn
         the next code into a jump target are a dependent chain (s_and -> s_mul -> s_add -> s_addc) followed by a taken
@@ -890,15 +675,14 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
         or five waves per SIMD that shows (two waves must be ready at any time to issue a vector instruction every other
         cycle).  Woven between the row's vector instructions they cost issue slots only; the row's shift counter moves up
         right behind the instructions that read it, so nothing but VALU sits between s_add and s_addc (SCC)."""
-        rows = body.emit_asm(reg_for(c), c)
         if os.environ.get("BGSA_GEN_BANDED_WEAVE", "1") == "0":   # A/B builds: the dispatch behind the row
-            return rows + [f"s_add_u32 {S_SH}, {S_SH}, 1"] + disp()
+            return rows(c) + [f"s_add_u32 {S_SH}, {S_SH}, 1"] + disp
         n_head = G * (2 if wide else 1)                      # the window shifts read S_SH (the scheduler keeps them in front)
-        assert all(S_SH in ln for ln in rows[:n_head]) and not any(S_SH in ln for ln in rows[n_head:])
-        head, rest = rows[:n_head], rows[n_head:]
+        row = rows(c)
+        head, rest = row[:n_head], row[n_head:]
+        assert all(S_SH in ln for ln in head) and not any(S_SH in ln for ln in rest)
         out = head + [f"s_add_u32 {S_SH}, {S_SH}, 1"]
-        d = disp()
-        scalars, jump = d[:-1], d[-1]
+        scalars, jump = disp[:-1], disp[-1]
         gap = max(1, (len(rest) - 2) // (len(scalars) + 1))
         k_next = 0
         for i, ln in enumerate(rest):
@@ -910,69 +694,35 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
         out.append(jump)
         return out
 
-    for a in range(5):          # slots 0..24: two rows per token
-        for b2 in range(5):
-            asm.append(f"L_body{5 * a + b2}_%=:")
-            asm += body.emit_asm(reg_for(a), a)
-            asm.append(f"s_add_u32 {S_SH}, {S_SH}, 1")
-            asm += last_row_and_dispatch(b2)
-    for c in range(5):          # slots 25..29: one row
-        asm.append(f"L_body{25 + c}_%=:")
-        asm += last_row_and_dispatch(c)
-        asm.append(f"L_end{25 + c}_%=:")
-        asm.append(pad(25 + c))
-    asm.append("L_body30_%=:")  # END
-    asm.append("s_branch L_done_%=")
-    asm.append("L_end30_%=:")
-    asm.append(pad(30))
-    asm.append("L_body31_%=:")  # REFILL
-    asm += [
-        f"s_sub_u32 {S_LEFT}, {S_LEFT}, 1",
-        "s_cbranch_scc1 L_done_%=",
-        "s_waitcnt lgkmcnt(0)",
-        f"s_mov_b64 {S_WIN}, {S_NXT}",
-        f"s_add_u32 {S_PTR_LO}, {S_PTR_LO}, 8",
-        f"s_addc_u32 {S_PTR_HI}, {S_PTR_HI}, 0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-    ]
-    asm += disp()
-    asm.append("L_end31_%=:")
-    asm.append(pad(31))
-    for slot in range(32, 63):   # every value of the 6-bit dispatch mask that is no token: a fail slot
-        asm.append(f"L_body{slot}_%=:")
-        asm += fail_slot()
-        asm.append(f"L_end{slot}_%=:")
-        asm.append(pad(slot))
-    asm.append("L_body63_%=:")  # EVENT <arg>: the last slot, so it may be longer than the slot stride
-    asm += [
+    event = [
         f"s_and_b32 {S_ARG}, {S_WIN_LO}, 0xff",
         f"s_lshr_b64 {S_WIN}, {S_WIN}, 8",
         f"s_cmp_eq_u32 {S_ARG}, 4",           # the plain test, by far the most frequent event: its own short path
         "s_cbranch_scc0 L_ev_general_%=",
     ]
-    asm += test("p") + alive()
-    asm += ["s_cbranch_scc0 L_ev_alldead_%="]
-    asm += push_or("L_ev_out_%=", "p")
-    asm += ["L_ev_alldead_%=:"] + [f"s_mov_b64 {S_DEAD[g]}, exec" for g in range(G)] + ["s_branch L_done_%="]
-    asm += [
+    event += test("p") + alive()
+    event += ["s_cbranch_scc0 L_ev_alldead_%="]
+    event += push_or("L_ev_out_%=", "p")
+    event += ["L_ev_alldead_%=:"] + [f"s_mov_b64 {S_DEAD[g]}, exec" for g in range(G)] + ["s_branch L_done_%="]
+    event += [
         "L_ev_general_%=:",
         f"s_bitcmp1_b32 {S_ARG}, 2",          # bit 2: test; bit 3: latch the reject masks (the reference's last checkpoint)
         "s_cbranch_scc0 L_ev_reset_%=",
     ]
-    asm += test("g") + alive()
-    asm += ["s_cbranch_scc0 L_ev_alldead_%=",
-            f"s_bitcmp1_b32 {S_ARG}, 3",
-            "s_cbranch_scc0 L_ev_nolatch_%="]
-    asm += latch_from_alive()
-    asm += ["L_ev_nolatch_%=:"]
-    asm += push_or("L_ev_reset_%=", "g")
-    asm += [
+    event += test("g") + alive()
+    event += ["s_cbranch_scc0 L_ev_alldead_%=",
+              f"s_bitcmp1_b32 {S_ARG}, 3",
+              "s_cbranch_scc0 L_ev_nolatch_%="]
+    event += latch_from_alive()
+    event += ["L_ev_nolatch_%=:"]
+    event += push_or("L_ev_reset_%=", "g")
+    event += [
         "L_ev_reset_%=:",
         f"s_bitcmp1_b32 {S_ARG}, 0",          # bit 0: scoring starts (row k)
         "s_cbranch_scc0 L_ev_adv_%=",
     ]
-    asm += [f"v_mov_b32 %[s{a}], 0" for a in acc]
-    asm += [
+    event += [f"v_mov_b32 %[s{a}], 0" for a in acc]
+    event += [
         "L_ev_adv_%=:",
         f"s_bitcmp1_b32 {S_ARG}, 1",          # bit 1: next 32 rows
         "s_cbranch_scc0 L_ev_cut_%=",
@@ -980,12 +730,12 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
     ]
     for g in range(G):       # (vmcnt(0): a word fetched by the previous advance that no cut has waited for yet)
         for w in range(n_m - 1):
-            asm += [f"v_mov_b32 %[m{w}_{c}_{g}], %[m{w + 1}_{c}_{g}]" for c in range(5)]
+            event += [f"v_mov_b32 %[m{w}_{c}_{g}], %[m{w + 1}_{c}_{g}]" for c in range(5)]
     for g in range(G):
         for c in range(5):
-            asm.append(f"global_load_dword %[m{n_m - 1}_{c}_{g}], %[voff{g}], {S_BASE[c]}")
-    asm += [f"v_add_u32 %[voff{g}], 0x100, %[voff{g}]" for g in range(G)]
-    asm += [
+            event.append(f"global_load_dword %[m{n_m - 1}_{c}_{g}], %[voff{g}], {S_BASE[c]}")
+    event += [f"v_add_u32 %[voff{g}], 0x100, %[voff{g}]" for g in range(G)]
+    event += [
         f"s_mov_b32 {S_SH}, 0",
         f"s_mov_b32 {S_CUT}, 0",
         f"s_add_u32 {S_CHUNK}, {S_CHUNK}, 1",
@@ -998,36 +748,32 @@ def gen_banded_cut_function(groups: int, form: str = "cut", sh64: bool = False) 
         "s_cbranch_scc0 L_ev_cut_again_%=",
     ]
     for g in range(G):       # the first cut behind an advance: B's low bits follow A's
-        asm += [f"v_alignbit_b32 %[m0_{c}_{g}], %[m1_{c}_{g}], %[m0_{c}_{g}], {S_CUTROWS}" for c in range(5)]
-    asm += ["s_branch L_ev_cut_done_%=", "L_ev_cut_again_%=:"]
+        event += [f"v_alignbit_b32 %[m0_{c}_{g}], %[m1_{c}_{g}], %[m0_{c}_{g}], {S_CUTROWS}" for c in range(5)]
+    event += ["s_branch L_ev_cut_done_%=", "L_ev_cut_again_%=:"]
     for g in range(G):       # a later one: the bits of B that earlier cuts took are gone first
         for c in range(5):
-            asm += [f"v_lshrrev_b32 %[t0], {S_CUT}, %[m1_{c}_{g}]",
-                    f"v_alignbit_b32 %[m0_{c}_{g}], %[t0], %[m0_{c}_{g}], {S_CUTROWS}"]
-    asm += ["L_ev_cut_done_%=:", f"s_add_u32 {S_CUT}, {S_CUT}, {S_CUTROWS}", "L_ev_out_%=:"]
-    asm += disp()
-    asm += done("s_waitcnt vmcnt(0) lgkmcnt(0)")
+            event += [f"v_lshrrev_b32 %[t0], {S_CUT}, %[m1_{c}_{g}]",
+                      f"v_alignbit_b32 %[m0_{c}_{g}], %[t0], %[m0_{c}_{g}], {S_CUTROWS}"]
+    event += ["L_ev_cut_done_%=:", f"s_add_u32 {S_CUT}, {S_CUT}, {S_CUTROWS}", "L_ev_out_%=:"]
+
+    asm = pair_slots(lambda c: rows(c) + [f"s_add_u32 {S_SH}, {S_SH}, 1"], last_row_and_dispatch, extra, event, WAIT_ALL)
     asm += [f"s_mov_b64 %[dead{g}], {S_DEAD[g]}" for g in range(G)]
     asm.append(f"s_mov_b32 %[early], {S_EARLY}")
 
-    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(n_state)]
+    outs = state_ops(n_state)
     outs += [f'[m{w}_{c}_{g}] "+v"(M[{g}][{c}][{w}])' for g in range(G) for c in range(5) for w in range(n_m)]
     outs += [f'[voff{g}] "+v"(voff[{g}])' for g in range(G)]
     outs += [f'[dead{g}] "=s"(dead[{g}])' for g in range(G)]
-    outs += ['[left] "=s"(left)', '[early] "=s"(early)']
-    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
-    ins = ['[qp] "s"(stream)', '[nwin] "s"(n_windows)', '[vmask] "v"(band_mask)'] + (['[vmask_hi] "v"(band_mask_hi)'] if wide else []) + \
+    outs += [LEFT_OUT, '[early] "=s"(early)'] + tmp_ops(n_slots)
+    ins = STREAM_INS + ['[vmask] "v"(band_mask)'] + (['[vmask_hi] "v"(band_mask_hi)'] if wide else []) + \
           ['[thr] "s"(limit)', '[cutrows] "s"(cut_rows)',
            '[pushrow] "s"(push_row)', '[pushmax] "s"(push_max)', '[pushsolid] "s"(push_row_solid)', '[solidthr] "s"(solid_limit)']
     ins += [f'[base{c}] "s"(base[{c}])' for c in range(5)]
-    clob = ", ".join(f'"{x}"' for x in clobbers)
     if funnel:
         bits = 64 if wide else 32
         sfx = "s" if sh64 else ""
-        note = f"  D0 >> 1 is ONE v_lshrrev_b64 on the fixed pair {P(0)}:{P(1)} (clobbered by name)." if sh64 else ""
-        return f"""
-// Funnel-shift banded rows ({bits}-bit band: thresholds {'16 .. 31' if wide else '13 .. 15'}), {G} subject group{'s' if G > 1 else ''} per wave: {body.valu_count()} VALU per row
+        note = f"  D0 >> 1 is ONE v_lshrrev_b64 on the fixed pair {fixed[0]}:{fixed[1]} (clobbered by name)." if sh64 else ""
+        head = f"""// Funnel-shift banded rows ({bits}-bit band: thresholds {'16 .. 31' if wide else '13 .. 15'}), {G} subject group{'s' if G > 1 else ''} per wave: {body.valu_count()} VALU per row
 // ({sum(op.kind in ('alignbit',) for op in body.ops)} funnel shifts among them), {n_slots} temporaries.  state[{per_state}g ..] = {{VP, VN, errors since row k}} of group g
 // (VP lo / hi, VN lo / hi, errors when the band is a pair); M[g][c] = {n_m} consecutive 32-bit words of class c's offset match string, the last
 // one the prefetch target; voff[g] = byte offset of the next word to fetch relative to base[c] (group 1: the group stride included);
@@ -1038,18 +784,9 @@ __device__ __forceinline__ void banded_funnel{bits}{sfx}_rows_asm_g{G}(uint32_t 
                                                        const uint32_t band_mask, {'const uint32_t band_mask_hi, ' if wide else ''}const uint32_t cut_rows,
                                                        const uint32_t limit, const uint32_t push_row, const uint32_t push_row_solid, const uint32_t solid_limit,
                                                        const uint32_t push_max, unsigned long long (&dead)[{G}],
-                                                       int &left, int &early)
-{{
-    uint32_t tmp[{max(n_slots, 1)}];
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-}}
-"""
-    return f"""
-// One-word-window banded rows, {G} subject group{'s' if G > 1 else ''} per wave: {body.valu_count()} VALU per row, all fast class
+                                                       int &left, int &early)"""
+    else:
+        head = f"""// One-word-window banded rows, {G} subject group{'s' if G > 1 else ''} per wave: {body.valu_count()} VALU per row, all fast class
 // ({sum(op.kind in ('alignbit',) for op in body.ops)} funnel shifts in the row; the cut event holds them), {n_slots} temporaries.
 // state[3g..3g+2] = {{VP, VN, errors since row k}} of group g; M[g][c] = {{window (in: word 0), the word behind it (in: word 1)}}
 // of class c's offset match string; voff[g] = byte offset of the next word to fetch (in: word 2) relative
@@ -1063,16 +800,9 @@ __device__ __forceinline__ void banded_cut_rows_asm_g{G}(uint32_t (&state)[{n_st
                                                        const uint32_t band_mask, const uint32_t cut_rows,
                                                        const uint32_t limit, const uint32_t push_row, const uint32_t push_row_solid, const uint32_t solid_limit,
                                                        const uint32_t push_max, unsigned long long (&dead)[{G}],
-                                                       int &left, int &early)
-{{
-    uint32_t tmp[{max(n_slots, 1)}];
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-}}
-"""
+                                                       int &left, int &early)"""
+    return cxx_function(head, [f"uint32_t tmp[{max(n_slots, 1)}];"], asm, outs, ins,
+                        clobbers([f"s{i}" for i in range(72, 100)], fixed + ["s55", "s56", "s57", "s58", "s59"]))
 
 
 def gen_banded_chunk_function() -> str:
@@ -1089,31 +819,17 @@ def gen_banded_chunk_function() -> str:
     row; a chunk that holds row k (error count starts), the last checkpoint (reject mask latched) or the query's end
     runs a second copy of the 32 rows with a two-instruction check behind every row.  Tests every 8 rows are inline,
     enabled by a per-chunk mask; every 32 rows the words move down one slot and the next one, fetched from global
-    memory during the chunk, takes the free slot."""
+    memory during the chunk, takes the free slot.  No dispatch, no stream windows: of the skeleton it uses reg_for and
+    the wrapper only."""
     body = R.banded_body()
     slot_of, n_slots = body.allocate_temps()
     TOK0 = 60                       # s[60:91]: the 32 row tokens of the current chunk
     S_RET, S_RET_LO, S_RET_HI = "s[92:93]", "s92", "s93"
-    clobbers = [f"s{i}" for i in range(60, 94)] + ["vcc", "scc", "memory"]
     NM = 3
 
     def reg_row(j: int):
-        pipe = j % 3
-        def reg(name: str) -> str:
-            if name.startswith("S"):
-                return f"%[s{name[1:]}]"
-            if name == "E0":
-                return f"%[lo{pipe}]"
-            if name == "E1":
-                return f"%[hi{pipe}]"
-            if name in ("$mask", "$mask_lo"):
-                return "%[mask]"
-            if name == "$sh":
-                return str(j)
-            if name == "$one":
-                return "1"
-            return f"%[t{slot_of[name]}]"
-        return reg
+        eq = lambda e, c: f"%[{'lo' if e == '0' else 'hi'}{j % 3}]"
+        return reg_for(0, slot_of, eq, band_scalars(str(j), "%[mask]"))
 
     def fetch(j: int) -> list[str]:
         pipe = j % 3
@@ -1248,20 +964,16 @@ def gen_banded_chunk_function() -> str:
         "s_waitcnt vmcnt(0) lgkmcnt(0)",
     ]
 
-    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(3)]
+    outs = state_ops(3)
     outs += [f'[voff{c}] "+v"(voff[{c}])' for c in range(5)]
     outs += ['[tokoff] "+s"(tokoff)', '[dead] "=&s"(dead)', '[early] "=&s"(early)', '[row0] "=&s"(row0)', '[ev] "=&s"(ev)',
              '[testen] "=&s"(testen)', '[cnt] "=&s"(cnt)', '[jreg] "=&s"(jreg)', '[alive] "=&s"(alive)']
     outs += [f'[lo{i}] "=&v"(lo[{i}])' for i in range(3)] + [f'[hi{i}] "=&v"(hi[{i}])' for i in range(3)]
     outs += [f'[next{c}] "=&v"(nxt[{c}])' for c in range(5)]
-    outs += ['[vaddr] "=&v"(vaddr)']
-    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
+    outs += ['[vaddr] "=&v"(vaddr)'] + tmp_ops(n_slots)
     ins = ['[lanebase] "v"(lanebase)', '[tokbase] "s"(tokens)', '[gbase] "s"(gbase)', '[mask] "v"(band_mask)', '[thr] "s"(limit)',
            '[k] "s"(k)', '[last] "s"(last)', '[len] "s"(len)', '[pushrow] "s"(push_row)', '[pushmax] "s"(push_max)']
-    clob = ", ".join(f'"{x}"' for x in clobbers)
-    return f"""
-// Straight-line banded rows, 32-bit band (gen_rows_asm.py: gen_banded_chunk_function): {body.valu_count()} + 1 VALU and two LDS reads per
+    head = f"""// Straight-line banded rows, 32-bit band (gen_rows_asm.py: gen_banded_chunk_function): {body.valu_count()} + 1 VALU and two LDS reads per
 // row, no scalar instruction per row outside the chunks that hold row k, the last checkpoint or the query's end.
 // state = {{VP, VN, errors since row k}}; lanebase = LDS byte address of this lane's dword in the wave's match-word block
 // ([class][slot][lane], slots = words of the current chunk: lo, hi, next); tokens + tokoff = this query's row tokens
@@ -1272,154 +984,70 @@ __device__ __forceinline__ unsigned long long banded_chunk_rows_asm32(uint32_t (
                                                                    const unsigned long long gbase, const uint32_t band_mask,
                                                                    const uint32_t limit, const uint32_t k, const uint32_t last,
                                                                    const uint32_t len, const uint32_t push_row, const uint32_t push_max,
-                                                                   int &early_out)
-{{
-    uint32_t tmp[{max(n_slots, 1)}], lo[3], hi[3], nxt[5], vaddr, row0, ev, testen, cnt, jreg;
-    int early;
-    unsigned long long dead, alive;
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-    early_out = early;
-    return dead;
-}}
-"""
+                                                                   int &early_out)"""
+    decls = [f"uint32_t tmp[{max(n_slots, 1)}], lo[3], hi[3], nxt[5], vaddr, row0, ev, testen, cnt, jreg;", "int early;",
+             "unsigned long long dead, alive;"]
+    return cxx_function(head, decls, asm, outs, ins, clobbers([f"s{i}" for i in range(72, 94)]),   # s[60:93]: the tokens and S_RET
+                        ["early_out = early;", "return dead;"])
 
 
 def gen_blocked_function(fn_name: str, nw: int, body: R.Body, n_base: int, n_chains: int, n_planes: int, n_eq: int) -> str:
-    """Row loop of a column-block kernel: one block of a long subject.  Stream code 7 (no
+    """Row loop of a column-block kernel: one block of a long subject.  The plain loop (eight_slots) with stream code 7 (no
     argument) every 32 rows = CARRY: store the carry-out words of the finished 32 rows to the
     wave's carry buffer, fetch the carry-in words of the next 32 rows.  State = n_base block
     registers, then n_chains carry-in words, then n_chains carry-out words."""
     slot_of, n_slots = body.allocate_temps()
     S_CB = "s[80:81]"
-    clobbers = CLOBBERS[:-3] + ["s80", "s81", "vcc", "scc", "memory"]
     cin = [n_base + i for i in range(n_chains)]
     cout = [n_base + n_chains + i for i in range(n_chains)]
 
-    def reg_for(c: int):
-        def reg(name: str) -> str:
-            if name.startswith("S"):
-                return f"%[s{name[1:]}]"
-            if name.startswith("B"):
-                return f"%[b{name[1:]}]"
-            if name.startswith("E"):
-                return f"%[e{c}_{name[1:]}]"
-            return f"%[t{slot_of[name]}]"
-        return reg
-
-    asm = [
-        f"s_mov_b64 {S_PTR}, %[qp]",
-        f"s_mov_b32 {S_LEFT}, %[nwin]",
-        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-        f"s_mov_b64 {S_CB}, %[cbase]",
-        f"s_getpc_b64 {S_PC}",
-        "L_anchor_%=:",
-        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, (L_body0_%= - L_anchor_%=)",
-        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
-        "s_waitcnt lgkmcnt(0)",
-    ]
-    asm += dispatch()
-    for c in range(5):
-        asm.append(f"L_body{c}_%=:")
-        asm += body.emit_asm(reg_for(c), c)
-        asm += dispatch()
-    asm.append("L_body5_%=:")
-    asm.append("s_branch L_done_%=")
-    asm.append(".fill ((L_body1_%= - L_body0_%=) - 4) / 4, 4, 0xbf800000")
-    asm.append("L_body6_%=:")
-    asm += [
-        f"s_sub_u32 {S_LEFT}, {S_LEFT}, 1",
-        "s_cbranch_scc1 L_done_%=",
-        "s_waitcnt lgkmcnt(0)",
-        f"s_mov_b64 {S_WIN}, {S_NXT}",
-        f"s_add_u32 {S_PTR_LO}, {S_PTR_LO}, 8",
-        f"s_addc_u32 {S_PTR_HI}, {S_PTR_HI}, 0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-    ]
-    asm += dispatch()
-    asm.append("L_refill_end_%=:")
-    asm.append(".fill ((L_body1_%= - L_body0_%=) - (L_refill_end_%= - L_body6_%=)) / 4, 4, 0xbf800000")
-    asm.append(f"L_body7_%=:")  # CARRY: chunk j out, chunk j+1 in ([chunk][chain][64 lanes] dwords)
+    carry = []   # CARRY: chunk j out, chunk j+1 in ([chunk][chain][64 lanes] dwords)
     # (the instruction offset is 13-bit signed: beyond 15 chains voff itself moves on in between)
     moved = 0
     for i in range(n_chains):
         if 256 * i - moved > 3840:
-            asm.append(f"v_add_u32 %[voff], 0x{256 * i - moved:x}, %[voff]")
+            carry.append(f"v_add_u32 %[voff], 0x{256 * i - moved:x}, %[voff]")
             moved = 256 * i
-        asm.append(f"global_store_dword %[voff], %[s{cout[i]}], {S_CB} offset:{256 * i - moved}")
-    asm.append(f"v_add_u32 %[voff], 0x{256 * n_chains - moved:x}, %[voff]")
+        carry.append(f"global_store_dword %[voff], %[s{cout[i]}], {S_CB} offset:{256 * i - moved}")
+    carry.append(f"v_add_u32 %[voff], 0x{256 * n_chains - moved:x}, %[voff]")
     moved = 0
     for i in range(n_chains):
         if 256 * i - moved > 3840:
-            asm.append(f"v_add_u32 %[voff], 0x{256 * i - moved:x}, %[voff]")
+            carry.append(f"v_add_u32 %[voff], 0x{256 * i - moved:x}, %[voff]")
             moved = 256 * i
-        asm.append(f"global_load_dword %[s{cin[i]}], %[voff], {S_CB} offset:{256 * i - moved} sc1")
+        carry.append(f"global_load_dword %[s{cin[i]}], %[voff], {S_CB} offset:{256 * i - moved} sc1")
     if moved:
-        asm.append(f"v_add_u32 %[voff], 0x{(-moved) & 0xFFFFFFFF:x}, %[voff]")
-    asm.append("s_waitcnt vmcnt(0)")
-    asm += dispatch()
-    asm += done("s_waitcnt vmcnt(0) lgkmcnt(0)")   # codes 0..7 all exist here (7 = CARRY)
+        carry.append(f"v_add_u32 %[voff], 0x{(-moved) & 0xFFFFFFFF:x}, %[voff]")
+    carry.append("s_waitcnt vmcnt(0)")
+    asm = eight_slots(lambda c: body.emit_asm(reg_for(c, slot_of), c), carry + dispatch(),   # codes 0..7 all exist here (7 = CARRY)
+                      [f"s_mov_b64 {S_CB}, %[cbase]"], WAIT_ALL)
 
     n_state = n_base + 2 * n_chains
-    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(n_state)]
-    outs += ['[voff] "+v"(voff)', '[left] "=s"(left)']
-    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
-    if n_planes:
-        ins = [f'[b{j}] "v"(B[{j}])' for j in range(n_planes)]
-        masks_param = f"const uint32_t (&B)[{n_planes}]"
-    else:
-        ins = [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(n_eq)]
-        masks_param = f"const uint32_t (&P)[5][{n_eq}]"
-    ins += ['[qp] "s"(stream)', '[nwin] "s"(n_windows)', '[cbase] "s"(carry_base)']
-    clob = ", ".join(f'"{x}"' for x in clobbers)
+    ins, masks_param = mask_ops(n_eq, n_planes)
     nops = sum(line.startswith("s_nop") for line in body.emit_asm(lambda x: x, 0))
-    return f"""
-// {body.valu_count()} VALU per row, {n_slots} temporaries, {n_chains} carry chains, {nops} hazard nops
+    head = f"""// {body.valu_count()} VALU per row, {n_slots} temporaries, {n_chains} carry chains, {nops} hazard nops
 template <>
 __device__ __forceinline__ int {fn_name}<{nw}>(uint32_t (&state)[{n_state}], {masks_param},
                                                        uint32_t &voff, const unsigned long long carry_base,
-                                                       const unsigned long long stream, const int n_windows)
-{{
-    uint32_t tmp[{max(n_slots, 1)}];
-    int left;
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-    return left;
-}}
-"""
+                                                       const unsigned long long stream, const int n_windows)"""
+    return cxx_function(head, [f"uint32_t tmp[{max(n_slots, 1)}];", "int left;"], asm,
+                        state_ops(n_state) + ['[voff] "+v"(voff)', LEFT_OUT] + tmp_ops(n_slots),
+                        ins + STREAM_INS + ['[cbase] "s"(carry_base)'], clobbers(["s80", "s81"]), ["return left;"])
 
 
 def gen_packed_blocked_function(fn_name: str, nw: int, body: R.Body, n_base: int, n_words: int, n_eq: int) -> str:
     """Row loop of a packed-carry column-block kernel (rows_ir.make_blocked_packed): the carries of one row are bits of
-    n_words words per direction, exchanged with the neighbouring blocks EVERY row.  Plain stream (codes 0..4, END,
-    REFILL; no CARRY token).  State = n_base block registers, n_words carry-in words, n_words carry-out words; operand
+    n_words words per direction, exchanged with the neighbouring blocks EVERY row.  Plain stream and loop (eight_slots: codes
+    0..4, END, REFILL; no CARRY token).  State = n_base block registers, n_words carry-in words, n_words carry-out words; operand
     `nxt` = the carry-in words of the NEXT row, fetched while this row is computed.  Per row: wait for the words
     fetched one row ago, move them in, fetch the next row's, run the body, store the carry-out words over this row's
     carry-in words (the block to the right reads them there), advance the row offset.  The buffer holds one row more
     than the query has, so the last row's fetch stays inside it."""
     slot_of, n_slots = body.allocate_temps()
     S_CB = "s[80:81]"
-    clobbers = CLOBBERS[:-3] + ["s80", "s81", "vcc", "scc", "memory"]
     cin = [n_base + j for j in range(n_words)]
     cout = [n_base + n_words + j for j in range(n_words)]
     row_bytes = 256 * n_words
-
-    def reg_for(c: int):
-        def reg(name: str) -> str:
-            if name.startswith("S"):
-                return f"%[s{name[1:]}]"
-            if name.startswith("E"):
-                return f"%[e{c}_{name[1:]}]"
-            return f"%[t{slot_of[name]}]"
-        return reg
 
     def row(c: int) -> list[str]:
         pre = ["s_waitcnt vmcnt(0)"]
@@ -1427,72 +1055,20 @@ def gen_packed_blocked_function(fn_name: str, nw: int, body: R.Body, n_base: int
         pre += [f"global_load_dword %[n{j}], %[voff], {S_CB} offset:{row_bytes + 256 * j} sc1" for j in range(n_words)]
         post = [f"global_store_dword %[voff], %[s{cout[j]}], {S_CB} offset:{256 * j}" for j in range(n_words)]
         post.append(f"v_add_u32 %[voff], 0x{row_bytes:x}, %[voff]")
-        return pre + body.emit_asm(reg_for(c), c) + post + dispatch()
+        return pre + body.emit_asm(reg_for(c, slot_of), c) + post
 
-    asm = [
-        f"s_mov_b64 {S_PTR}, %[qp]",
-        f"s_mov_b32 {S_LEFT}, %[nwin]",
-        f"s_load_dwordx2 {S_WIN}, {S_PTR}, 0x0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-        f"s_mov_b64 {S_CB}, %[cbase]",
-        f"s_getpc_b64 {S_PC}",
-        "L_anchor_%=:",
-        f"s_add_u32 {S_BASE_LO}, {S_PC_LO}, (L_body0_%= - L_anchor_%=)",
-        f"s_addc_u32 {S_BASE_HI}, {S_PC_HI}, 0",
-        "s_waitcnt lgkmcnt(0)",
-    ]
-    asm += dispatch()
-    for c in range(5):
-        asm.append(f"L_body{c}_%=:")
-        asm += row(c)
-    asm.append("L_body5_%=:")
-    asm.append("s_branch L_done_%=")
-    asm.append(".fill ((L_body1_%= - L_body0_%=) - 4) / 4, 4, 0xbf800000")
-    asm.append("L_body6_%=:")
-    asm += [
-        f"s_sub_u32 {S_LEFT}, {S_LEFT}, 1",
-        "s_cbranch_scc1 L_done_%=",
-        "s_waitcnt lgkmcnt(0)",
-        f"s_mov_b64 {S_WIN}, {S_NXT}",
-        f"s_add_u32 {S_PTR_LO}, {S_PTR_LO}, 8",
-        f"s_addc_u32 {S_PTR_HI}, {S_PTR_HI}, 0",
-        f"s_load_dwordx2 {S_NXT}, {S_PTR}, 0x8",
-    ]
-    asm += dispatch()
-    asm.append("L_refill_end_%=:")
-    asm.append(".fill ((L_body1_%= - L_body0_%=) - (L_refill_end_%= - L_body6_%=)) / 4, 4, 0xbf800000")
-    asm.append("L_body7_%=:")
-    asm += fail_slot()
-    asm += done("s_waitcnt vmcnt(0) lgkmcnt(0)")
-
+    asm = eight_slots(row, fail_slot(), [f"s_mov_b64 {S_CB}, %[cbase]"], WAIT_ALL)
     n_state = n_base + 2 * n_words
-    text = "\n".join(f'        "{line}\\n\\t"' if not line.endswith(":") else f'        "{line}\\n"' for line in asm)
-    outs = [f'[s{i}] "+v"(state[{i}])' for i in range(n_state)]
-    outs += [f'[n{j}] "+v"(next_in[{j}])' for j in range(n_words)]
-    outs += ['[voff] "+v"(voff)', '[left] "=s"(left)']
-    outs += [f'[t{i}] "=&v"(tmp[{i}])' for i in range(n_slots)]
-    ins = [f'[e{c}_{j}] "v"(P[{c}][{j}])' for c in range(5) for j in range(n_eq)]
-    ins += ['[qp] "s"(stream)', '[nwin] "s"(n_windows)', '[cbase] "s"(carry_base)']
-    clob = ", ".join(f'"{x}"' for x in clobbers)
-    return f"""
-// {body.valu_count()} VALU per row, {n_slots} temporaries, {n_words} packed carry word(s) per direction
+    ins, masks_param = mask_ops(n_eq)
+    head = f"""// {body.valu_count()} VALU per row, {n_slots} temporaries, {n_words} packed carry word(s) per direction
 template <>
-__device__ __forceinline__ int {fn_name}<{nw}>(uint32_t (&state)[{n_state}], const uint32_t (&P)[5][{n_eq}],
+__device__ __forceinline__ int {fn_name}<{nw}>(uint32_t (&state)[{n_state}], {masks_param},
                                                        uint32_t (&next_in)[{n_words}], uint32_t &voff,
                                                        const unsigned long long carry_base,
-                                                       const unsigned long long stream, const int n_windows)
-{{
-    uint32_t tmp[{max(n_slots, 1)}];
-    int left;
-    asm volatile(
-{text}
-        : {", ".join(outs)}
-        : {", ".join(ins)}
-        : {clob});
-    return left;
-}}
-"""
-
+                                                       const unsigned long long stream, const int n_windows)"""
+    return cxx_function(head, [f"uint32_t tmp[{max(n_slots, 1)}];", "int left;"], asm,
+                        state_ops(n_state) + [f'[n{j}] "+v"(next_in[{j}])' for j in range(n_words)] + ['[voff] "+v"(voff)', LEFT_OUT] + tmp_ops(n_slots),
+                        ins + STREAM_INS + ['[cbase] "s"(carry_base)'], clobbers(["s80", "s81"]), ["return left;"])
 
 class BitpalDomainError(ValueError):
     """A score set whose kernels do not fit the register file: says which quantity is over which budget."""
@@ -1650,10 +1226,9 @@ def main() -> int:
              "__device__ __forceinline__ int myers_rows_asm(uint32_t (&state)[2 * G * NW],\n"
              "                                               const uint32_t (&P)[5][G * NW],\n"
              "                                               const unsigned long long stream, const int n_windows);\n"]
-    for nw in MYERS_NW:  # G = 1 only: two groups per wave measured slower (fewer waves per SIMD)
-        if nw not in MYERS_PARKED_NW:
-            parts.append(gen_function("myers_rows_asm", f"{nw}, 1", ilp(R.myers_body(nw, 1, balanced=MYERS_BALANCED)), 2 * nw, nw))
-    for nw in MYERS_PARKED_NW:  # 9 registers per word: HN parked in the VP register
+    # G = 1 only: two groups per wave measured slower (fewer waves per SIMD).  One body for every width (rows_ir.myers_body: 8 VALU per
+    # word; the nine-register myers_parked_body is no longer emitted here); MYERS_PARKED_NW only fixes the order of the header: its widths last.
+    for nw in [w for w in MYERS_NW if w not in MYERS_PARKED_NW] + MYERS_PARKED_NW:
         parts.append(gen_function("myers_rows_asm", f"{nw}, 1", ilp(R.myers_body(nw, 1, balanced=MYERS_BALANCED)), 2 * nw, nw))
     for nw in MYERS_SPLIT_NW:   # the chains in turns over blocks of MYERS_SPLIT words: 7 registers per word + 2 * MYERS_SPLIT
         parts.append(gen_function("myers_rows_asm", f"{nw}, 1", ilp(R.myers_body(nw, 1, split=MYERS_SPLIT, park=MYERS_PARK, balanced=MYERS_BALANCED)), 2 * nw, nw))
