@@ -195,6 +195,10 @@ def lib() -> ctypes.CDLL:
     L.bgsa_hip_myers_band_stats.argtypes = [vp, i32]
     if hasattr(L, "bgsa_hip_myers_band_groups"):   # (an older build loaded through BGSA_HIP_LIB lacks it)
         L.bgsa_hip_myers_band_groups.argtypes = [i32, i64, i32, i32, i32]
+    if hasattr(L, "bgsa_hip_myers_band_rescue"):   # (the same)
+        L.bgsa_hip_myers_band_rescue.argtypes = [i32, i32, i32, i64]
+        L.bgsa_hip_myers_band_rescue_half.argtypes = [i32]
+        L.bgsa_hip_myers_band_rescue_stats.argtypes = [vp, i32]
     if hasattr(L, "bgsa_hip_myers_prefix_depths"):   # (the same)
         L.bgsa_hip_myers_prefix_depths.argtypes = [i32, i64, i32, i32, i32, i32, ip, i32]
         L.bgsa_hip_myers_band_segments.argtypes = [vp, i32, i32, ip, i32, vp, i32, ip]

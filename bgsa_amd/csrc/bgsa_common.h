@@ -110,6 +110,8 @@ int myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_le
 // returns their number, 0 where the launch does not share.  Launches nothing; the tile it assumes is plan_tasks', which asks the
 // runtime for the device's CU count once (256 where there is no device).
 int myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_len, int n_queries, int mixed_lengths, int *depths);
+// The half-width of a global Myers launch that rescues its uncertified lanes (myers_band.h), 0 where it does not (host only).
+int myers_band_rescue(int ref_len, int read_len, int n_queries, int64_t read_count);
 
 // Packed query stream (one per query, 8-byte windows): codes 0..4 = A C G T N row, 5 = END,
 // 6 = REFILL.  Window i < n_windows-1 holds characters 7i..7i+6 and a REFILL; the last window

@@ -263,7 +263,9 @@ static size_t plan_workspace_bytes(const Plan &plan, int ref_len, int read_len, 
     // the longer of the plain stream and the Myers band stream (myers_band.h), whichever kernel the plan picks: one size for
     // every plain plan, as the score sets that reduce to edit distance run the Myers kernels
     // ... in segments (prefix sharing), with the sorted order of the launch's queries behind the task counter
-    return band_segments_stride_bound(ref_len) * static_cast<size_t>(n_queries) + kTaskCounterBytes + prefix_order_bytes(n_queries);   // bgsa_common.h "dynamic task handout"
+    // ... and behind those the pool of a launch that rescues (myers_band.h), by the subject length alone
+    return band_segments_stride_bound(ref_len) * static_cast<size_t>(n_queries) + kTaskCounterBytes + prefix_order_bytes(n_queries) +   // bgsa_common.h "dynamic task handout"
+           rescue_pool_bytes(read_len, n_queries);
 }
 
 int ab_knob_refused(const char *what)
@@ -679,6 +681,26 @@ int bgsa_hip_myers_band_stats(unsigned long long *out, int clear)
     if (!word) return BGSA_HIP_OK;  // nothing was ever launched on this device
     BGSA_HIP_TRY(hipMemcpy(out, band_stats_words(word), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (clear) BGSA_HIP_TRY(hipMemset(band_stats_words(word), 0, 2 * sizeof(unsigned long long)));
+    return BGSA_HIP_OK;
+}
+
+int bgsa_hip_myers_band_rescue_half(int len) { return len > 0 ? band_rescue_half(len) : 0; }
+
+int bgsa_hip_myers_band_rescue(int ref_len, int read_len, int n_queries, int64_t read_count)
+{
+    return myers_band_rescue(ref_len, read_len, n_queries, read_count);
+}
+
+int bgsa_hip_myers_band_rescue_stats(unsigned long long *out, int clear)
+{
+    if (!out) return BGSA_HIP_EINVAL;
+    out[0] = out[1] = 0;
+    int dev = 0;
+    unsigned *word = nullptr;
+    if (int rc = existing_fault_word(&dev, &word)) return rc;
+    if (!word) return BGSA_HIP_OK;  // nothing was ever launched on this device
+    BGSA_HIP_TRY(hipMemcpy(out, band_stats_words(word) + 2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (clear) BGSA_HIP_TRY(hipMemset(band_stats_words(word) + 2, 0, 2 * sizeof(unsigned long long)));
     return BGSA_HIP_OK;
 }
 

@@ -37,16 +37,21 @@ __host__ __device__ inline int band_window_index(int nw, int a, int b) { return 
 // (rows_ir.py: myers_band_half, LABNOTES §11): 150 bp -> h = 48, B = 97.
 inline int band_default_half(int len) { return (9 * len + 192) / 32; }
 
+// The half-width of a two-group launch that RESCUES (below, "rescue"): three less, 150 bp -> h = 45, B = 91.  There about one
+// random pair in a thousand is not certified (LABNOTES §33), and those lanes are scored again one by one instead of their
+// waves.  rows_ir.py: myers_band_rescue_half.
+inline int band_rescue_half(int len) { return band_default_half(len) - 3; }
+
 // The half-width of a launch: BGSA_MYERS_BAND=0 turns the band off, =N sets h = N (A/B knob); default by the
-// longer of the two lengths.
-inline int band_half(int m, int n)
+// longer of the two lengths.  rescue: the launch scores its uncertified lanes again one by one (band_rescue_half).
+inline int band_half(int m, int n, bool rescue = false)
 {
     static const int knob = [] {
         const char *e = getenv("BGSA_MYERS_BAND");
         return e ? atoi(e) : -1;
     }();
     if (knob >= 0) return knob;
-    return band_default_half(m > n ? m : n);
+    return rescue ? band_rescue_half(m > n ? m : n) : band_default_half(m > n ? m : n);
 }
 
 // The windows of every row of an m-row query against nw-word subjects of length n: false (s->n = 0) when the band is off
@@ -205,7 +210,8 @@ inline unsigned long long prefix_segments_word(const PrefixPlan &p)
 int launch_prefix_order(const char *d_content, int ref_len, int ref_start, int ref_end, int q_tile, const PrefixPlan &p,
                         unsigned *d_words, hipStream_t stream);   // preprocess.hip
 int launch_pack_band_segments(const char *d_content, int ref_len, const BandSchedule &s, const PrefixPlan &p, int ref_start,
-                              int ref_end, void *d_streams, hipStream_t stream, unsigned *d_words);   // preprocess.hip
+                              int ref_end, void *d_streams, hipStream_t stream, unsigned *d_words,
+                              unsigned rescue_entries = 0);   // preprocess.hip
 
 // The guard's pair of one launch, {queries redone, queries banded} (myers_global_asm_kernel<NW, 1, *, true>): 64 bytes behind
 // the task counter, inside the kTaskCounterBytes behind the streams; zeroed by the packer with the counter.
@@ -214,16 +220,69 @@ __host__ __device__ inline unsigned long long *band_launch_words(unsigned *task_
     return reinterpret_cast<unsigned long long *>(task_counter + 16);
 }
 
-// Packs the band streams of queries ref_start .. ref_end - 1 and zeroes the task counter d_words[0] and the guard's pair.
+// Packs the band streams of queries ref_start .. ref_end - 1 and zeroes the task counter d_words[0], the guard's pair and the
+// rescue's words (below; rescue_entries: the pool's capacity, 0 for a launch that does not rescue).
 int launch_pack_band(const char *d_content, int ref_len, const BandSchedule &s, int ref_start, int ref_end, void *d_streams,
-                     hipStream_t stream, unsigned *d_words);   // preprocess.hip
+                     hipStream_t stream, unsigned *d_words, unsigned rescue_entries = 0);   // preprocess.hip
 
-// Certificate statistics, per device: [0] = queries a wave ran again with full rows, [1] = queries a wave ran banded.
+// Certificate statistics, per device: [0] = queries a wave ran again with full rows, [1] = queries a wave ran banded,
+// [2] = lanes rescued, [3] = group-queries a rescuing wave sent through the full rows after all (below).
 // They live behind the sticky fault word (bgsa_common.h: device_fault_word, a 64-byte allocation) and are read and
-// cleared by bgsa_hip_myers_band_stats().
+// cleared by bgsa_hip_myers_band_stats() and bgsa_hip_myers_band_rescue_stats().
 __host__ __device__ inline unsigned long long *band_stats_words(unsigned *fault_word)
 {
     return reinterpret_cast<unsigned long long *>(fault_word + 2);
+}
+
+// ---- rescue ----------------------------------------------------------------------------------------------------
+// A two-group launch on a large bucket runs a narrower band (band_rescue_half) and does not send a wave through the full rows
+// for a few uncertified lanes: a live group with 1 .. kRescueMaxLanes lanes above B writes {query, subject} of each into the
+// launch's POOL, those lanes store no score, and myers_band_rescue_kernel scores the pool's pairs afterwards, one pair per
+// lane with full rows.  A group with more such lanes, or a pool that is full, takes the wave through the full rows as ever.
+// The pool lies in the workspace behind the prefix entries and their keys; band_launch_words [2], [3] are the launch's
+// {lanes rescued (counted by the rescue kernel), group-queries redone because of the lane limit or a full pool}, [4] counts
+// the entries claimed, and the word behind it holds the pool's capacity.  The packers zero the five and write the capacity.
+constexpr int kRescueMaxLanes = 8;
+constexpr int kRescueMinLen = 65, kRescueMaxLen = 160;   // the two-group band kernels: 3..5 words
+struct RescueEntry {
+    int q, subject;   // q relative to ref_start; {-1, -1}: claimed by a wave that found the pool full
+};
+__host__ __device__ inline unsigned long long *rescue_claimed(unsigned *task_counter) { return band_launch_words(task_counter) + 4; }
+__host__ __device__ inline unsigned *rescue_capacity(unsigned *task_counter) { return task_counter + 26; }
+// ... and the next one where the pool begins, in entries behind the prefix entries: behind them and their keys
+// (rescue_pool_offset: the packers write it, so that the kernels need no query count for it).
+__host__ __device__ inline unsigned *rescue_offset(unsigned *task_counter) { return task_counter + 27; }
+__host__ __device__ inline unsigned rescue_pool_offset(int n_queries)
+{
+    return static_cast<unsigned>((static_cast<size_t>(n_queries) * (sizeof(PrefixEntry) + sizeof(uint32_t)) + 7) / 8);
+}
+__device__ __forceinline__ RescueEntry *rescue_pool(unsigned *task_counter)
+{
+    const unsigned at = __builtin_amdgcn_readfirstlane(*rescue_offset(task_counter));
+    return reinterpret_cast<RescueEntry *>(reinterpret_cast<unsigned char *>(task_counter) + kTaskCounterBytes) + at;
+}
+// Where a launch may rescue by default: lengths at which no more than 2 in 1,000 random pairs lie above the rescue band's B,
+// and nearly equal ones, which is where that rate was measured (LABNOTES §33).  band_default_half rounds down, and where it
+// loses a quarter or more of a column the rate at h - 3 reaches or passes that — 66 and 80 bp: 4 in 1,000.
+constexpr int kRescueMaxDelta = 3;
+inline bool band_rescue_lengths(int m, int n)
+{
+    const int len = m > n ? m : n;
+    return n >= kRescueMinLen && n <= kRescueMaxLen && abs(n - m) <= kRescueMaxDelta && (9 * len + 192) % 32 < 8;
+}
+// What plan_workspace_bytes adds for the pool: 4,096 entries per query, 512 MiB at the most; only where a launch may rescue.
+inline size_t rescue_pool_bytes(int read_len, int n_queries)
+{
+    if (read_len < kRescueMinLen || read_len > kRescueMaxLen || n_queries <= 0) return 0;
+    const size_t want = static_cast<size_t>(n_queries) << 15, most = static_cast<size_t>(512) << 20;
+    return want < most ? want : most;
+}
+// Its entries.  The task counter in front is aligned up by as much as prefix_order_bytes' spare 256 bytes and the pool by 7
+// more, so the last eight entries stay unused.
+inline long long rescue_pool_entries(int read_len, int n_queries)
+{
+    const long long n = static_cast<long long>(rescue_pool_bytes(read_len, n_queries) / sizeof(RescueEntry));
+    return n > 8 ? n - 8 : 0;
 }
 
 }  // namespace bgsa

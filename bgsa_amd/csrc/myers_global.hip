@@ -194,6 +194,14 @@ constexpr int kBandPairMaxWords = 5;  // widest band loop with two subject group
 // schedule and the limit certify one (m, n), DESIGN §4.2.
 // the band kernels' snapshots of a sharing launch (dynamic LDS: launch_asm sizes it by the launch's depths; none without sharing)
 extern __shared__ uint4 prefix_slots[];
+// The lane's number formed where it is asked for, two instructions the compiler neither hoists nor keeps: for the kernels at
+// their register limit, where a lane number kept across a row loop for a rare use costs the loop a register or a spill.
+__device__ __forceinline__ unsigned lane_now()
+{
+    unsigned l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
 // SHARE (prefix sharing, myers_band.h) is a separate instantiation of the band kernels: a launch that does not share runs a
 // kernel without the segment loop, the entry load and the slots (within one VGPR and two SGPRs of what it was before; the
 // loop cost such a launch about 0.4 % while every band kernel carried it, LABNOTES §24.4).
@@ -204,13 +212,16 @@ extern __shared__ uint4 prefix_slots[];
 // a later change that needs more registers will not show up as a lost wave but as scratch, so whoever changes these kernels
 // runs -Rpass-analysis=kernel-resource-usage again and looks at ScratchSize (0 everywhere today) as well as at the waves.
 // 1 (every other kernel) asks for nothing.
+// RESCUE (myers_band.h; two groups only) is one more separate instantiation: it changes the certificate block behind the
+// score popcounts and nothing else, and every launch that does not rescue runs the kernel it ran before.  The same figures
+// hold for it (LABNOTES §33): forced where it shares, found by the compiler where it does not.
 constexpr int band_kernel_waves(int nw, int g, bool dyn, bool share)
 {
     if (!share) return 1;
     if (g == 2) return nw == 3 ? 8 : (nw == 4 ? (dyn ? 6 : 7) : 5);
     return nw <= 5 ? 8 : (nw == 6 ? (dyn ? 7 : 8) : (nw == 7 ? (dyn ? 6 : 7) : (dyn ? 5 : 6)));
 }
-template <int NW, int G, bool DYN = false, bool BAND = false, bool LENS = false, bool SHARE = false>
+template <int NW, int G, bool DYN = false, bool BAND = false, bool LENS = false, bool SHARE = false, bool RESCUE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel_waves(NW, G, DYN, SHARE)))) void myers_global_asm_kernel(
     const unsigned char *__restrict__ streams, const uint32_t *__restrict__ peq,
     int16_t *__restrict__ out, int ref_len, int read_len, long long ld, int n_groups, int word_num,
@@ -223,6 +234,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                   "band: 3..8 words, one subject group per wave — or two up to 5 words");
     static_assert(!(LENS && BAND), "the certified band is derived from one (m, n): a length-aware launch runs full rows");
     static_assert(!SHARE || BAND, "prefix sharing: the band kernels only");
+    static_assert(!RESCUE || (BAND && G == 2), "rescue: the two-group band kernels only");
     // LENS: the lane's length is loaded once per task and kept across the row loops, one VGPR per group — except beyond 8 words,
     // where the widths sit at their occupancy steps (20 words 238, 28 and 32 words 255 VGPRs): there the epilogue loads it again
     // per query, one dword per lane against >= 10 words x ref_len rows.
@@ -240,6 +252,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
         if (task >= n_tasks) return;
     }
     int band_on = 1, unreported = 0;   // wave-uniform (BAND): the guard, and the banded queries not yet added to band_launch[1]
+    // the lane that reports for the wave.  RESCUE: its number is formed where it is asked for — the kernels that share sit at their
+    // register limit, and `lane` kept for the rare reports costs them a spill
+    [[maybe_unused]] auto reporting_lane = [&]() {
+        if constexpr (RESCUE) {
+            return lane_now() == 0;
+        } else
+            return lane == 0;
+    };
     do {
         int group0, tile;
         if constexpr (DYN) {
@@ -309,9 +329,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                 // a wave whose guard is off shares nothing.  Without SHARE: one segment, the band stream as ever.
                 const int n_depths = SHARE ? static_cast<int>(prefix_segments >> 56) : 0;   // wave-uniform: a kernel argument
                 const bool sharing = SHARE && band_on;
-                [[maybe_unused]] uint4 *const slots = prefix_slots + ((threadIdx.x >> 6) * G) * kLanes + lane;   // [depth][wave][group][lane]
+                // [depth][wave][group][lane].  RESCUE: formed again at either use, like reporting_lane() and for its reason
+                [[maybe_unused]] auto wave_slots = [&]() {
+                    if constexpr (RESCUE) {
+                        return prefix_slots + __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * G) * kLanes + lane_now();
+                    } else
+                        return prefix_slots + ((threadIdx.x >> 6) * G) * kLanes + lane;
+                };
                 if (!sharing) seg = 0;
                 if (SHARE && seg) {
+                    const uint4 *const slots = wave_slots();
 #pragma unroll
                     for (int gi = 0; gi < G; gi++) {
                         const uint4 v = slots[((seg - 1) * kWavesPerBlock * G + gi) * kLanes];
@@ -329,6 +356,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                                                                     __builtin_amdgcn_readfirstlane(band));
                         note_stream_fault(fault_word, left);
                         if (SHARE && sharing && band && seg < n_depths) {
+                            uint4 *const slots = wave_slots();
 #pragma unroll
                             for (int gi = 0; gi < G; gi++)
                                 slots[(seg * kWavesPerBlock * G + gi) * kLanes] =
@@ -352,11 +380,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                         if (gi < n_live && __builtin_amdgcn_ballot_w64(score[gi] > band_limit) != 0) n_over++;
                     if (n_over == 0) break;
                     if constexpr (G == 1) n_over = 1;   // (what it is: said so that the one-group kernels keep their code)
+                    if constexpr (RESCUE) {
+                        // No group with more than kRescueMaxLanes lanes above B: the wave claims a pool entry per such lane — one
+                        // atomic —, each of them writes its pair at base + its rank under the ballots, and the loop ends with the
+                        // banded scores: the store below leaves those lanes out.  A claim that does not fit the pool marks what it
+                        // holds of it as void, so that every entry below the capacity is written, and the wave goes on as it does
+                        // for a group over the limit: the redo, the guard's pair, and the count of either in band_launch[3].
+                        const unsigned c0 = __popcll(__builtin_amdgcn_ballot_w64(score[0] > band_limit)),
+                                       c1 = n_live > 1 ? __popcll(__builtin_amdgcn_ballot_w64(score[1] > band_limit)) : 0u;
+                        unsigned forced = (c0 > kRescueMaxLanes ? 1u : 0u) + (c1 > kRescueMaxLanes ? 1u : 0u);
+                        if (forced == 0) {
+                            unsigned *const words = reinterpret_cast<unsigned *>(band_launch) - 16;   // band_launch_words() of them
+                            unsigned long long claim = 0;
+                            if (reporting_lane()) claim = atomicAdd(rescue_claimed(words), static_cast<unsigned long long>(c0 + c1));
+                            // (32-bit scalars from here on: there is no scalar 64-bit "less than", and a vector one makes the branches below divergent)
+                            const unsigned base = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(claim)),
+                                           base_hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(claim >> 32));
+                            const unsigned capacity = __builtin_amdgcn_readfirstlane(*rescue_capacity(words));
+                            const unsigned room = (base_hi == 0 && base < capacity) ? capacity - base : 0u;   // entries of the claim below the capacity
+                            const bool fits = c0 + c1 <= room;
+                            RescueEntry *const mine = rescue_pool(words) + base;   // (dereferenced where room > 0)
+                            // (the lane number formed here: kept across the row loop it would cost the loop a register)
+                            const unsigned column = lane_now() + static_cast<unsigned>(group0) * kLanes;
+#pragma unroll
+                            for (int gi = 0; gi < G; gi++) {
+                                const bool up = gi < n_live && score[gi] > band_limit;
+                                const unsigned long long over = __builtin_amdgcn_ballot_w64(up);
+                                const unsigned at = (gi ? c0 : 0u) + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(over >> 32),
+                                                                                              __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(over), 0u));
+                                if (up && at < room)
+                                    mine[at] = fits ? RescueEntry{q, static_cast<int>(column + gi * kLanes)} : RescueEntry{-1, -1};
+                            }
+                            if (fits) break;
+                            forced = static_cast<unsigned>(n_over);
+                        }
+                        if (reporting_lane()) atomicAdd(&band_launch[3], static_cast<unsigned long long>(forced));
+                    }
                     band = 0;   // a lane is not certified: the whole wave runs the query again with full rows
                     seg = 0;    // ... from row 0
                     unsigned long long r = static_cast<unsigned long long>(n_over),
                                        b = static_cast<unsigned long long>(unreported) + n_live;
-                    if (lane == 0) {
+                    if (reporting_lane()) {
                         r += atomicAdd(&band_launch[0], r);
                         b += atomicAdd(&band_launch[1], b);
                     }
@@ -373,7 +437,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                 unreported += tried;
 #pragma unroll
                 for (int gi = 0; gi < G; gi++)
-                    if (gi < n_live) dst[static_cast<size_t>(q) * ld + gi * kLanes] = static_cast<int16_t>(-score[gi]);
+                    if (gi < n_live && !(RESCUE && band && score[gi] > band_limit))   // (band still set: those lanes are in the pool)
+                        dst[static_cast<size_t>(q) * ld + gi * kLanes] = static_cast<int16_t>(-score[gi]);
             } else {
                 int left;
                 if constexpr (NW <= kPairMaxWords)  // short rows: two per stream token (launch_asm packs it so)
@@ -388,8 +453,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                     if constexpr (kLenPerQuery) {
                         // (the lane number formed here: an address kept per lane across the row loop is two VGPRs these widths lack —
                         // 28 words: 255 -> 326, 32 words: 255 -> 258, one wave per SIMD instead of two)
-                        unsigned lane_e;
-                        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+                        const unsigned lane_e = lane_now();
                         n_cols = group0 + gi < n_groups ? lane_read_len(read_lens, static_cast<size_t>(group0 + gi) * kLanes + lane_e, read_len) : 0;
                     }
                     else if constexpr (LENS)
@@ -411,7 +475,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
         if constexpr (DYN) task = resolve_wave_task(task_issued);
     } while (DYN && task < n_tasks);
     if constexpr (BAND) {
-        if (lane == 0 && unreported) atomicAdd(&band_launch[1], static_cast<unsigned long long>(unreported));
+        if (reporting_lane() && unreported) atomicAdd(&band_launch[1], static_cast<unsigned long long>(unreported));
     }
 }
 
@@ -489,8 +553,7 @@ __global__ __launch_bounds__(256) void myers_semi_asm_kernel(
         int n_cols = own_len;
         if constexpr (kLenPerQuery) {
             // (the lane number formed here: an address kept per lane across the row loop is two VGPRs this width lacks)
-            unsigned lane_e;
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+            const unsigned lane_e = lane_now();
             n_cols = lane_read_len(read_lens, static_cast<size_t>(group) * kLanes + lane_e, read_len);
         }
         // (LENS: the NW masks depend on the task only: laundered, or the compiler forms them once per task and keeps NW more VGPRs
@@ -957,6 +1020,117 @@ __global__ void band_stats_add_kernel(const unsigned long long *__restrict__ lau
 {
     atomicAdd(&stats[0], launch[0]);   // launches on other streams may add at the same time
     atomicAdd(&stats[1], launch[1]);
+    atomicAdd(&stats[2], launch[2]);   // the rescue's pair (myers_band.h): zero behind a launch that does not rescue
+    atomicAdd(&stats[3], launch[3]);
+}
+
+// ---- rescue (myers_band.h) ----
+// BGSA_MYERS_BAND_RESCUE=0|1 (read once) forces it off or on for every banded launch with two groups per wave (tests, A/B);
+// BGSA_MYERS_BAND_RESCUE_POOL=N caps the pool's entries (tests).
+constexpr bool kRescueDefault = true;
+// The fewest queries of a launch that rescues by default.  The rescue kernel's time has a floor — one lane's full rows, some
+// tenths of a millisecond however few the entries — against a gain of about 2 % of the row kernel's 0.057 ms per query and
+// million subjects: 100-query launches (the reference's blocks) come out level or behind, LABNOTES §33.5.
+constexpr int kRescueMinQueries = 1000;
+static int rescue_knob()
+{
+    static const int v = [] {
+        const char *e = getenv("BGSA_MYERS_BAND_RESCUE");
+        return (e && (e[0] == '0' || e[0] == '1') && e[1] == 0) ? e[0] - '0' : -1;
+    }();
+    return v;
+}
+static long long rescue_pool_knob()
+{
+    static const long long v = [] {
+        const char *e = getenv("BGSA_MYERS_BAND_RESCUE_POOL");
+        return e ? atoll(e) : -1ll;
+    }();
+    return v;
+}
+// The pool's capacity for a two-group banded launch of nq queries against read_count subjects, 0 where it does not rescue.
+// By default: a bucket that carries two groups by its size, at least kRescueMinQueries queries, lengths at which at most 2 in
+// 1,000 random pairs are not certified (band_rescue_lengths), and a pool twice what that rate fills.
+long long rescue_entries_for(int ref_len, int read_len, int nq, int64_t read_count)
+{
+    if (read_len < kRescueMinLen || read_len > kRescueMaxLen || nq <= 0 || read_count < 2 * kLanes || read_count > 0x7fffffffll) return 0;
+    const long long pool = static_cast<long long>(rescue_pool_bytes(read_len, nq) / sizeof(RescueEntry));
+    long long entries = rescue_pool_entries(read_len, nq);
+    if (rescue_pool_knob() >= 0 && rescue_pool_knob() < entries) entries = rescue_pool_knob();
+    if (rescue_knob() >= 0) return rescue_knob() ? entries : 0;
+    if (!kRescueDefault || nq < kRescueMinQueries || read_count < kBandPairMinReads || !band_rescue_lengths(ref_len, read_len)) return 0;
+    return 2e-3 * nq * static_cast<double>(read_count) <= static_cast<double>(pool / 2) ? entries : 0;
+}
+// The half-width and the schedule of a banded launch with `groups` subject groups per wave; *entries = the pool's capacity
+// where it rescues (then h is the rescue half-width, or BGSA_MYERS_BAND's), else 0.  A shape whose rescue band has no
+// schedule (|n - m| above its B) keeps the default band and does not rescue.
+int band_half_for(int ref_len, int read_len, int nw, int groups, int nq, int64_t read_count, BandSchedule *sched, long long *entries)
+{
+    *entries = groups == 2 && nw <= kBandPairMaxWords ? rescue_entries_for(ref_len, read_len, nq, read_count) : 0;
+    if (*entries > 0) {
+        const int h = band_half(ref_len, read_len, true);
+        if (band_schedule(ref_len, read_len, h, nw, sched)) return h;
+        *entries = 0;
+    }
+    const int h = band_half(ref_len, read_len);
+    band_schedule(ref_len, read_len, h, nw, sched);
+    return h;
+}
+
+// The pool's pairs, one per lane, with full rows: exact by themselves, so no band, no certificate and no stream.  Persistent
+// waves read the number of entries on the device and take chunks of 64.  A lane behind the last entry, or on an entry that is
+// void or names no pair of the launch, runs pair (0, 0) and stores nothing.
+template <int NW>
+__global__ __launch_bounds__(256) void myers_band_rescue_kernel(unsigned *__restrict__ words, const char *__restrict__ content,
+                                                                const uint32_t *__restrict__ peq, int16_t *__restrict__ out,
+                                                                int ref_len, int read_len, long long ld, int word_num, int ref_start,
+                                                                int n_queries)
+{
+    const unsigned long long claimed = *rescue_claimed(words), capacity = *rescue_capacity(words);
+    const unsigned long long count = claimed < capacity ? claimed : capacity;
+    const RescueEntry *pool = rescue_pool(words);
+    const unsigned lane = threadIdx.x & (kLanes - 1);
+    const unsigned long long n_waves = static_cast<unsigned long long>(gridDim.x) * kWavesPerBlock;
+    unsigned rescued = 0;
+    for (unsigned long long chunk = static_cast<unsigned long long>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+         chunk * kLanes < count; chunk += n_waves) {
+        const unsigned long long at = chunk * kLanes + lane;
+        RescueEntry e = pool[at < count ? at : count - 1];
+        const bool live = at < count && e.q >= 0 && e.q < n_queries && e.subject >= 0 && e.subject < ld;
+        if (!live) e = RescueEntry{0, 0};
+        const uint32_t *g = peq + (static_cast<size_t>(e.subject / kLanes) * kChars * word_num) * kLanes + e.subject % kLanes;
+        uint32_t P[kChars][NW], pv[NW], mv[NW];
+#pragma unroll
+        for (int c = 0; c < kChars; c++)
+#pragma unroll
+            for (int w = 0; w < NW; w++) P[c][w] = w < word_num ? g[(c * word_num + w) * kLanes] : 0u;
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            pv[w] = ~0u;
+            mv[w] = 0u;
+        }
+        const unsigned char *row = reinterpret_cast<const unsigned char *>(content) + static_cast<size_t>(ref_start + e.q) * (ref_len + 1);
+        for (int r = 0; r < ref_len; r++) {
+            unsigned c = row[r];
+            if (c > 4) c = 0;   // as the streams: out-of-alphabet bytes behave as 'A'
+            uint32_t carry = 0, hp_in = 1, hn_in = 0;   // the row edge of the global mode
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+                const uint32_t eq = c == 0 ? P[0][w] : c == 1 ? P[1][w] : c == 2 ? P[2][w] : c == 3 ? P[3][w] : P[4][w];
+                myers_word(eq, pv[w], mv[w], carry, hp_in, hn_in);
+            }
+        }
+        int score = ref_len;
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            const int rem = read_len - 32 * w;
+            const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+            score += __popc(pv[w] & m) - __popc(mv[w] & m);
+        }
+        if (live) out[static_cast<size_t>(e.q) * ld + e.subject] = static_cast<int16_t>(-score);
+        rescued += __popcll(__builtin_amdgcn_ballot_w64(live));
+    }
+    if (lane == 0 && rescued) atomicAdd(&band_launch_words(words)[2], static_cast<unsigned long long>(rescued));
 }
 
 // Every instantiation of myers_global_asm_kernel through one pointer type (a function pointer has no default arguments: the
@@ -1001,9 +1175,10 @@ int launch_asm(const ScoreArgs &a)
     PrefixPlan prefix;   // n = 0: the launch packs and runs as ever, on the kernel it ran on before
     int h = 0;
     bool band = false;
+    long long rescue = 0;   // the pool's capacity of a launch that rescues (myers_band.h)
     if constexpr ((G == 1 || kBandPair) && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
-        h = band_half(a.ref_len, a.read_len);
-        band = !lens && band_schedule(a.ref_len, a.read_len, h, NW, &sched);
+        if (!lens) h = band_half_for(a.ref_len, a.read_len, NW, G, nq, a.read_count, &sched, &rescue);
+        band = !lens && sched.n > 0;
         if (band) {
             on_grid = myers_global_asm_kernel<NW, G, false, true>;
             on_counter = myers_global_asm_kernel<NW, G, true, true>;
@@ -1011,6 +1186,14 @@ int launch_asm(const ScoreArgs &a)
             if (prefix.n) {
                 on_grid = myers_global_asm_kernel<NW, G, false, true, false, true>;
                 on_counter = myers_global_asm_kernel<NW, G, true, true, false, true>;
+            }
+            if constexpr (kBandPair) {
+                if (rescue > 0) {
+                    on_grid = prefix.n ? myers_global_asm_kernel<NW, G, false, true, false, true, true>
+                                       : myers_global_asm_kernel<NW, G, false, true, false, false, true>;
+                    on_counter = prefix.n ? myers_global_asm_kernel<NW, G, true, true, false, true, true>
+                                          : myers_global_asm_kernel<NW, G, true, true, false, false, true>;
+                }
             }
         }
     }
@@ -1033,8 +1216,10 @@ int launch_asm(const ScoreArgs &a)
     if (prefix.n)
         if (int rc = launch_prefix_order(a.d_content, a.ref_len, a.ref_start, a.ref_end, plan.q_tile, prefix, words, a.stream))
             return rc;
-    if (int rc = prefix.n ? launch_pack_band_segments(a.d_content, a.ref_len, sched, prefix, a.ref_start, a.ref_end, a.d_workspace, a.stream, words)
-                 : band   ? launch_pack_band(a.d_content, a.ref_len, sched, a.ref_start, a.ref_end, a.d_workspace, a.stream, words)
+    if (int rc = prefix.n ? launch_pack_band_segments(a.d_content, a.ref_len, sched, prefix, a.ref_start, a.ref_end, a.d_workspace, a.stream, words,
+                                                       static_cast<unsigned>(rescue))
+                 : band   ? launch_pack_band(a.d_content, a.ref_len, sched, a.ref_start, a.ref_end, a.d_workspace, a.stream, words,
+                                             static_cast<unsigned>(rescue))
                  : kPairs ? launch_pack_query_pairs(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter)
                           : launch_pack_queries(a.d_content, a.ref_len, a.ref_start, a.ref_end, a.d_workspace, a.stream, lg.counter))
         return rc;
@@ -1049,6 +1234,14 @@ int launch_asm(const ScoreArgs &a)
                        fault, lg.counter, band ? 2 * h + 1 : 0, guard, a.d_read_lens, prefix_segments_word(prefix),
                        static_cast<const PrefixEntry *>(prefix_entries(words)));
     BGSA_HIP_TRY(hipGetLastError());
+    if constexpr (kBandPair) {
+        if (rescue > 0) {   // unconditionally: how many entries there are is read on the device
+            hipLaunchKernelGGL(myers_band_rescue_kernel<NW>, dim3(persistent_blocks()), dim3(256), 0, a.stream, words, a.d_content, a.d_peq,
+                               a.results<int16_t>(), a.ref_len, a.read_len, static_cast<long long>(a.read_count), a.word_num,
+                               a.ref_start, nq);
+            BGSA_HIP_TRY(hipGetLastError());
+        }
+    }
     if (band) {
         hipLaunchKernelGGL(band_stats_add_kernel, dim3(1), dim3(1), 0, a.stream, static_cast<const unsigned long long *>(guard),
                            band_stats_words(fault));
@@ -1273,7 +1466,9 @@ int myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_
     const MyersChoice c = myers_select(word_num, 0, read_count, ref_len, read_len, mixed_lengths != 0);
     if ((c.family != MyersFamily::kAsm && c.family != MyersFamily::kAsmBandPairs) || mixed_lengths) return 0;
     BandSchedule sched;
-    if (!band_schedule(ref_len, read_len, band_half(ref_len, read_len), c.nw, &sched)) return 0;
+    long long rescue = 0;
+    band_half_for(ref_len, read_len, c.nw, c.G, n_queries, read_count, &sched, &rescue);
+    if (sched.n == 0) return 0;
     // the tile launch_asm picks for the band widths (3..8 words: a counter kernel, tiles up to query_tile_max())
     const int64_t n_waves = (read_count / kLanes + c.G - 1) / c.G;
     const TaskPlan plan = plan_tasks(n_queries, n_waves, static_cast<long long>(ref_len) * c.nw * c.G, 32, true, query_tile_max());
@@ -1281,6 +1476,19 @@ int myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_
     prefix_select(ref_len, c.nw, sched, n_queries, plan.q_tile, read_count, &p);
     for (int j = 0; j < p.n; j++) depths[j] = p.depth[j];
     return p.n;
+}
+
+int myers_band_rescue(int ref_len, int read_len, int n_queries, int64_t read_count)
+{
+    if (ref_len <= 0 || read_len <= 0 || n_queries < 1 || read_count < 1) return 0;
+    const int word_num = (read_len + 31) / 32;
+    if (word_num > kMaxWords) return 0;
+    const MyersChoice c = myers_select(word_num, 0, read_count, ref_len, read_len, false);
+    if (c.family != MyersFamily::kAsmBandPairs) return 0;
+    BandSchedule sched;
+    long long rescue = 0;
+    const int h = band_half_for(ref_len, read_len, c.nw, c.G, n_queries, read_count, &sched, &rescue);
+    return rescue > 0 ? h : 0;
 }
 
 const char *myers_kernel_name(int word_num, int semi_global)

@@ -233,16 +233,25 @@ int launch_pack_banded(const char *d_content, int len, int k, int phase, int cut
     return BGSA_HIP_OK;
 }
 
+// The guard's pair and the rescue's words of a launch (myers_band.h): what thread 0 of either band packer writes.
+__device__ __forceinline__ void zero_band_launch_words(unsigned *words, unsigned rescue_entries, int n_queries)
+{
+    *rescue_offset(words) = rescue_pool_offset(n_queries);
+    for (int j = 0; j < 4; j++) band_launch_words(words)[j] = 0ull;
+    *rescue_claimed(words) = 0ull;
+    *rescue_capacity(words) = rescue_entries;
+}
+
 // One thread per 8-byte window of a band stream (myers_band.h), END beyond the stream's end up to the stride.  The schedule
 // travels by value: it is the same for every query of a launch.
 __global__ __launch_bounds__(256) void pack_band_kernel(const char *__restrict__ content, unsigned long long *__restrict__ streams,
                                                         int len, BandSchedule sched, int ref_start, int n_queries, int per,
-                                                        unsigned *__restrict__ words)
+                                                        unsigned *__restrict__ words, unsigned rescue_entries)
 {
     const long long tid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (tid == 0) {   // the task counter and the guard's pair (myers_band.h: band_launch_words), as in pack_queries_kernel
         words[0] = 0u;
-        band_launch_words(words)[0] = band_launch_words(words)[1] = 0ull;
+        zero_band_launch_words(words, rescue_entries, n_queries);
     }
     if (tid >= static_cast<long long>(n_queries) * per) return;
     const int q = static_cast<int>(tid / per), i = static_cast<int>(tid % per);
@@ -255,7 +264,7 @@ __global__ __launch_bounds__(256) void pack_band_kernel(const char *__restrict__
 }
 
 int launch_pack_band(const char *d_content, int ref_len, const BandSchedule &s, int ref_start, int ref_end, void *d_streams,
-                     hipStream_t stream, unsigned *d_words)
+                     hipStream_t stream, unsigned *d_words, unsigned rescue_entries)
 {
     const int nq = ref_end - ref_start;
     if (nq <= 0) return BGSA_HIP_OK;
@@ -266,7 +275,7 @@ int launch_pack_band(const char *d_content, int ref_len, const BandSchedule &s, 
     }
     const long long total = static_cast<long long>(nq) * (stride / 8);
     hipLaunchKernelGGL(pack_band_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, d_content,
-                       static_cast<unsigned long long *>(d_streams), ref_len, s, ref_start, nq, stride / 8, d_words);
+                       static_cast<unsigned long long *>(d_streams), ref_len, s, ref_start, nq, stride / 8, d_words, rescue_entries);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
@@ -347,12 +356,13 @@ int launch_prefix_order(const char *d_content, int ref_len, int ref_start, int r
 // One thread per 8-byte window of a query's segments: the segment that holds the window, then band_rows_layout on it.
 __global__ __launch_bounds__(256) void pack_band_segments_kernel(const char *__restrict__ content, unsigned long long *__restrict__ streams,
                                                                  int len, BandSchedule sched, PrefixPlan plan, int ref_start,
-                                                                 int n_queries, int per, unsigned *__restrict__ words)
+                                                                 int n_queries, int per, unsigned *__restrict__ words,
+                                                                 unsigned rescue_entries)
 {
     const long long tid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (tid == 0) {   // as pack_band_kernel
         words[0] = 0u;
-        band_launch_words(words)[0] = band_launch_words(words)[1] = 0ull;
+        zero_band_launch_words(words, rescue_entries, n_queries);
     }
     if (tid >= static_cast<long long>(n_queries) * per) return;
     const int q = static_cast<int>(tid / per), i = static_cast<int>(tid % per);
@@ -368,7 +378,7 @@ __global__ __launch_bounds__(256) void pack_band_segments_kernel(const char *__r
 }
 
 int launch_pack_band_segments(const char *d_content, int ref_len, const BandSchedule &s, const PrefixPlan &p, int ref_start,
-                              int ref_end, void *d_streams, hipStream_t stream, unsigned *d_words)
+                              int ref_end, void *d_streams, hipStream_t stream, unsigned *d_words, unsigned rescue_entries)
 {
     const int nq = ref_end - ref_start;
     if (nq <= 0) return BGSA_HIP_OK;
@@ -379,7 +389,7 @@ int launch_pack_band_segments(const char *d_content, int ref_len, const BandSche
     }
     const long long total = static_cast<long long>(nq) * (stride / 8);
     hipLaunchKernelGGL(pack_band_segments_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, d_content,
-                       static_cast<unsigned long long *>(d_streams), ref_len, s, p, ref_start, nq, stride / 8, d_words);
+                       static_cast<unsigned long long *>(d_streams), ref_len, s, p, ref_start, nq, stride / 8, d_words, rescue_entries);
     BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }

@@ -637,6 +637,12 @@ def myers_band_half(length: int) -> int:
     return (9 * length + 192) // 32
 
 
+def myers_band_rescue_half(length: int) -> int:
+    """Half-width of a launch that scores its uncertified lanes again one by one (myers_band.h: band_rescue_half): three
+    below the default, where about one random pair in a thousand lies above B (LABNOTES §33)."""
+    return myers_band_half(length) - 3
+
+
 def myers_band_windows(m: int, n: int, h: int, nw: int):
     """Per query row i = 1..m the window (a, b) of words that holds the band's columns, or None when the band is off for
     this shape (the row windows would not save a fifth of the word-rows, or |n - m| leaves no room).  Same rule as

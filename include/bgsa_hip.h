@@ -914,7 +914,22 @@ int bgsa_hip_query_stream(int algo, const char *mapped_row, int ref_len, int k, 
  * is longer, out of order, out of range or reaches rows beyond the first two words turns sharing off: the answer is then 0.
  * bgsa_hip_myers_band_segments: the stream of one mapped query row cut at these depths, as a sharing launch packs it — one
  * band stream per segment, each beginning with its SETWIN; offsets[0 .. n_depths + 1] = where each begins, and the length.
- * Returns the length (<= cap bytes written), or 0 when the shape does not qualify (host only, no GPU). */
+ * Returns the length (<= cap bytes written), or 0 when the shape does not qualify (host only, no GPU).
+ * Rescue: a launch with two groups per wave on a large bucket runs a band three narrower (bgsa_hip_myers_band_rescue_half:
+ * 150 bp -> h = 45) and scores its few uncertified lanes — up to eight per group and query — again one by one in a kernel of
+ * its own instead of sending their waves through the full rows; the scores do not change.  The workspace of plans with
+ * read_len 65..160 carries its pool (32 KiB per query, 512 MiB at the most).  BGSA_MYERS_BAND_RESCUE=0|1 (read once) forces it
+ * off or on for every two-group banded launch; BGSA_MYERS_BAND_RESCUE_POOL=N caps the pool's entries (tests).
+ * bgsa_hip_myers_band_rescue: the half-width such a launch of n_queries queries against read_count subjects would use, 0
+ * where it does not rescue — by default fewer than 1,000 queries, a small bucket, lengths outside the rule (host only, no GPU).
+ * bgsa_hip_myers_band_rescue_stats: the current device's counts since the last clear — out[0] = lanes rescued, out[1] =
+ * group-queries a rescuing wave ran again with full rows because a group held more than eight uncertified lanes or the pool
+ * was full (they are among out[0] of bgsa_hip_myers_band_stats too; call after synchronising).
+ * bgsa_hip_myers_band_rescue_half: FOR TESTS — the half-width formula alone, whatever the launch (the library's side of
+ * rows_ir.py: myers_band_rescue_half); a caller asks bgsa_hip_myers_band_rescue. */
+int bgsa_hip_myers_band_rescue_half(int len);
+int bgsa_hip_myers_band_rescue(int ref_len, int read_len, int n_queries, int64_t read_count);
+int bgsa_hip_myers_band_rescue_stats(unsigned long long *out, int clear);
 int bgsa_hip_myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_len, int n_queries, int mixed_lengths,
                                  int *depths, int cap);
 int bgsa_hip_myers_band_segments(const char *mapped_row, int ref_len, int read_len, const int *depths, int n_depths,
