@@ -37,8 +37,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 import rows_ir as R  # noqa: E402
 
 MYERS_NW = [1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20, 22, 24, 25]  # Peq masks resident: 8 VALU per word (25 words = 253 VGPRs, the last width with two waves per SIMD)
-# the widths that needed 9 registers per word before the eight-instruction row had them anyway (then rows_ir.myers_parked_body, now
-# myers_body like every other width): 26 and 28 words (801..896 bp) fit 256 VGPRs at all, 18 words (545..576 bp) drop from 183 to 165
+# the widths that needed 9 registers per word before the eight-instruction row had them anyway (then a body of their own with HN parked in the
+# VP register, since removed from rows_ir; now myers_body like every other width): 26 and 28 words (801..896 bp) fit 256 VGPRs at all, 18 words (545..576 bp) drop from 183 to 165
 # VGPRs = three waves per SIMD instead of two.  The header emits them behind the widths of MYERS_NW.
 MYERS_PARKED_NW = [18, 26, 28]
 # 30 and 32 words (897..1024 bp) with the Peq planes resident (round 5): the two carry chains take turns over blocks of
@@ -1227,7 +1227,7 @@ def main() -> int:
              "                                               const uint32_t (&P)[5][G * NW],\n"
              "                                               const unsigned long long stream, const int n_windows);\n"]
     # G = 1 only: two groups per wave measured slower (fewer waves per SIMD).  One body for every width (rows_ir.myers_body: 8 VALU per
-    # word; the nine-register myers_parked_body is no longer emitted here); MYERS_PARKED_NW only fixes the order of the header: its widths last.
+    # word; the nine-register parked body of rounds 1-3 is gone from rows_ir); MYERS_PARKED_NW only fixes the order of the header: its widths last.
     for nw in [w for w in MYERS_NW if w not in MYERS_PARKED_NW] + MYERS_PARKED_NW:
         parts.append(gen_function("myers_rows_asm", f"{nw}, 1", ilp(R.myers_body(nw, 1, balanced=MYERS_BALANCED)), 2 * nw, nw))
     for nw in MYERS_SPLIT_NW:   # the chains in turns over blocks of MYERS_SPLIT words: 7 registers per word + 2 * MYERS_SPLIT

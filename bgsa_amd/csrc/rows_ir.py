@@ -31,9 +31,30 @@ links of a chain and pads with s_nop if an ordering ever leaves fewer than two).
 """
 from __future__ import annotations
 
+import functools
+import os
 from dataclasses import dataclass, field
 
 import numpy as np
+
+
+def _knob(name: str, default: str) -> str:
+    """A build-time switch of the generators: the environment's BGSA_GEN_<name>, read once when this file is imported."""
+    return os.environ.get(f"BGSA_GEN_{name}", default)
+
+
+CLASS_CODE = np.zeros(256, dtype=np.uint8)      # the alphabet map of original/BGSA_CPU/global.c:9-15, as a byte table for arrays:
+CLASS_CODE[list(b"ACGTN")] = range(5)           # A C G T N = 0..4, every other character 0
+
+
+def class_code(ch) -> int:
+    """The class of one query character."""
+    return int(CLASS_CODE[int(ch)])
+
+
+def _low_mask(bits: int) -> np.uint32:
+    """The lowest `bits` bits of a word (none below 1, all from 32 on): the columns of a word that belong to the subject."""
+    return np.uint32(0xFFFFFFFF if bits >= 32 else (0 if bits <= 0 else (1 << bits) - 1))
 
 
 def tt(fn) -> int:
@@ -517,7 +538,127 @@ def dependent_pairs(body: "Body") -> int:
 # Myers unit-cost global (reference original/BGSA_CPU/align_core.c:65-132)
 # =================================================================================================
 
-MYERS_EIGHT = __import__('os').environ.get('BGSA_GEN_MYERS_EIGHT', '1') != '0'   # '0': the 10-instruction rows of rounds 1-3 (A/B builds)
+MYERS_EIGHT = _knob('MYERS_EIGHT', '1') != '0'   # '0': the 10-instruction rows of rounds 1-3 (A/B builds)
+
+
+def _state(first: int = 0):
+    """Names of VP and VN of word w where the rows' state starts at word `first` of the S registers."""
+    return (lambda w: f"S{(first + w) * 2}"), (lambda w: f"S{(first + w) * 2 + 1}")
+
+
+def _plane_mask(b: Body, name: str, wild: bool = False):
+    """The match mask of word w rebuilt from its code planes B[3w..3w+2] (MATCH3) into the temporary `name` ('{w}' = the word)."""
+    return lambda w: b.MATCH3(name.format(w=w), f"B{w * 3}", f"B{w * 3 + 1}", f"B{w * 3 + 2}", wild)
+
+
+def _myers_eight(b: Body, nw: int, VP, VN, mask, a: str = "a{w}", m: str = "m{w}", split: int = 0, balanced: bool = False,
+                 edge: int = 1, tap=(None, None), park=None, place=()) -> None:
+    """THE eight-instruction Myers cell (myers_body's docstring), appended to `b` for `nw` words: every eight-instruction body
+    is a call of this.  Per word
+        phase A:  a = VP & E ; m = VP + a (chain 0) ; a = HNs = m ^ VP ^ a ; m = M2 = E | VN | HNs ; VP = HP = VN | ~(M2 | VP)
+        phase B:  VP = HP + HP (chain 1) ; VN = M2 & HPs ; VP = (M2 & HNs) | ~(M2 | HPs)
+    VP(w), VN(w): the state registers; mask(w): the register that holds word w's match mask (it may emit the instruction
+    that forms it: _plane_mask); a, m: the names of the two temporaries, '{w}' = the word.  The names are part of the
+    emitted text's contract — allocate_temps frees in name order, the schedulers run on the named ops.
+    split = K > 0, balanced: see myers_body.
+    edge: the row edge D[i][0] - D[i-1][0], chain 1's carry-in into HP at bit 0 of word 0.  1 (global): a SETC1, and every link
+    of the chain is an ADDC; 0 (semi-global): the chain's first link is an ADD_CO, as chain 0's always is.
+    tap[c]: a call that reads the carry LEAVING chain c behind its last link (SUBBZ / ADDCZ into a running score), or None.
+    park = (save, load): how a pausing chain waits between the blocks, save(c) / load(c); the default is a scalar pair.
+    place: where the chain ends sit, all of them behind an instruction of a block's LAST word.  The events, in the order they
+    are emitted where two share a place:
+        park0  save chain 0 (not in the last block)                   tap0  tap[0] (last block)
+        take1  chain 1's carry: the edge's SETC1 in the first block, load(1) afterwards
+        park1  save chain 1 (not in the last block)                   tap1  tap[1] (last block)
+        take0  load chain 0 (not in the last block)
+    and the places: 'sum', 'hn', 'm2', 'hp' = behind that instruction of phase A ('hp' is the phase's end also where balanced
+    forms HP later), 'ahead' = two instructions in front of phase A's end ('sum' where balanced leaves the word's HP to
+    phase B, else 'hn'), 'shift', 'vn', 'vp' = behind that instruction of phase B.  The hazard padding and the schedulers see
+    this order, so every caller states the one it has always had."""
+    A, M = (lambda w: a.format(w=w)), (lambda w: m.format(w=w))
+    save, load = park or (b.SAVECC, b.LOADCC)
+    place = {"park0": "sum", "tap0": "m2", "take1": "ahead", "park1": "shift", "tap1": "vn", "take0": "vn", **dict(place)}
+    hp = lambda w: b.BITOP3(VP(w), M(w), VN(w), VP(w), lambda m_, vn, vp: (m_ & vn) | ~(m_ | vp))
+    blocks = [(0, nw)] if split <= 0 else [(lo, min(nw, lo + split)) for lo in range(0, nw, split)]
+    for j, (lo, hi) in enumerate(blocks):
+        first, last = j == 0, j == len(blocks) - 1
+        ahead = "sum" if balanced and hi - lo > 1 else "hn"
+
+        def at(here, w):
+            for ev in ("park0", "tap0", "take1", "park1", "tap1", "take0"):
+                if w != hi - 1 or here != (ahead if place[ev] == "ahead" else place[ev]):
+                    continue
+                c = int(ev[-1])
+                if ev.startswith("park") and not last:
+                    save(c)
+                elif ev.startswith("tap") and last and tap[c]:
+                    tap[c]()
+                elif ev == "take1" and first and edge:
+                    b.SETC1()
+                elif ev.startswith("take") and not (first if c else last):
+                    load(c)
+
+        for w in range(lo, hi):      # phase A: the addition's carry chain
+            e = mask(w)
+            b.AND(A(w), VP(w), e)
+            (b.ADDC if w else b.ADD_CO)(M(w), VP(w), A(w))
+            at("sum", w)
+            b.BITOP3(A(w), M(w), VP(w), A(w), lambda s_, vp, a_: s_ ^ vp ^ a_)
+            at("hn", w)
+            b.BITOP3(M(w), e, VN(w), A(w), lambda e_, vn, hn: e_ | vn | hn)
+            at("m2", w)
+            if not balanced or w == lo:
+                hp(w)
+            at("hp", w)
+        for w in range(lo, hi):      # phase B: HP << 1 across words, then the new deltas
+            (b.ADDC if w or edge else b.ADD_CO)(VP(w), VP(w), VP(w))
+            if balanced and w + 1 < hi:
+                hp(w + 1)
+            at("shift", w)
+            b.AND(VN(w), M(w), VP(w))
+            at("vn", w)
+            b.BITOP3(VP(w), M(w), A(w), VP(w), lambda m_, hn, hp_: (m_ & hn) | ~(m_ | hp_))
+            at("vp", w)
+
+
+def _myers_ten(b: Body, nw: int, P, M, mask, d: str = "d{w}", hp: str = "hp{w}", hn: str | None = None,
+               edge: int = 1, tap=(None, None), early: int = 0) -> None:
+    """THE ten-instruction Myers cell of rounds 1-3 (BGSA_GEN_MYERS_EIGHT=0 builds it; full 32-bit words, hardware carries
+    instead of the reference's software carry bit, align_core.c:79-83,91-96), appended to `b` for `nw` words:
+        phase A:  D0 = (((P & E) + P) ^ P) | E | M                    (the addition's chain)
+        phase C:  HP = ~(D0 | P) | M ; HN = D0 & P ; HP <<= 1         (the HP shift's chain, carry-in = edge)
+        phase D:  HN <<= 1 (its chain) ; M' = D0 & HP ; P' = ~(D0 | HP) | HN
+    P(w), M(w): the state registers VP, VN; mask(w), edge as in _myers_eight; d, hp, hn: the temporaries' names, hn = None: HN
+    is parked in the P register between the phases (nine registers per word instead of ten).
+    tap = (behind phase C, behind phase D): calls that read the carry leaving the HP / the HN shift, or None.
+    early = n: the new M of the first n words is formed behind phase C, so that tap[0] keeps two instructions' distance from
+    the chain's last link."""
+    D, HP = (lambda w: d.format(w=w)), (lambda w: hp.format(w=w))
+    HN = P if hn is None else (lambda w: hn.format(w=w))
+    new_m = lambda w: b.AND(M(w), D(w), HP(w))
+    for w in range(nw):  # phase A: the addition's carry chain
+        e = mask(w)
+        b.AND(D(w), P(w), e)   # (P & (E|M)) == (P & E): P & M == 0 is an invariant
+        (b.ADDC if w else b.ADD_CO)(D(w), D(w), P(w))
+        b.BITOP3(D(w), D(w), P(w), M(w), lambda a, p, m: (a ^ p) | m)
+        b.OR(D(w), D(w), e)
+    if edge:
+        b.SETC1()  # D[i][0] - D[i-1][0] = +1 enters HP at bit 0 of word 0
+    for w in range(nw):  # phase C: HP << 1 across words
+        b.BITOP3(HP(w), D(w), P(w), M(w), lambda d_, p, m: ~(d_ | p) | m)
+        b.AND(HN(w), D(w), P(w))
+        (b.ADDC if w or edge else b.ADD_CO)(HP(w), HP(w), HP(w))
+    for w in range(min(early, nw)):
+        new_m(w)
+    if tap[0]:
+        tap[0]()
+    for w in range(nw):  # phase D: HN << 1 across words, then the new vertical deltas
+        (b.ADDC if w else b.ADD_CO)(HN(w), HN(w), HN(w))
+        if w >= early:
+            new_m(w)
+        b.BITOP3(P(w), D(w), HP(w), HN(w), lambda d_, hp_, hn_: ~(d_ | hp_) | hn_)
+    if tap[1]:
+        tap[1]()
 
 
 def myers_body(nw: int, groups: int = 1, split: int = 0, park: str = "sgpr", balanced: bool = False) -> Body:
@@ -547,49 +688,12 @@ def myers_body(nw: int, groups: int = 1, split: int = 0, park: str = "sgpr", bal
         return myers_body10(nw, groups)
     b = Body()
     for g in range(groups):
-        VP = lambda w: f"S{(g * nw + w) * 2}"
-        VN = lambda w: f"S{(g * nw + w) * 2 + 1}"
-        E = lambda w: f"E{g * nw + w}"
-        A = lambda w: f"a{g}_{w}"      # VP & E, then [v_in = 2]
-        M = lambda w: f"m{g}_{w}"      # the sum, then M2
-        blocks = [(0, nw)] if split <= 0 else [(lo, min(nw, lo + split)) for lo in range(0, nw, split)]
-        vg = park == "vgpr"
-        save = (lambda slot: b.SAVEV(f"cv{g}_{slot}")) if vg else b.SAVECC
-        load = (lambda slot: b.LOADV(f"cv{g}_{slot}")) if vg else b.LOADCC
-        for j, (lo, hi) in enumerate(blocks):
-            first, last = j == 0, j == len(blocks) - 1
-            for w in range(lo, hi):  # phase A: the addition's carry chain
-                b.AND(A(w), VP(w), E(w))
-                (b.ADD_CO if w == 0 else b.ADDC)(M(w), VP(w), A(w))
-                if w == hi - 1 and not last and not vg:
-                    save(0)
-                if w == hi - 1 and not vg and balanced and hi - lo > 1:
-                    b.SETC1() if first else load(1)      # balanced: only two instructions of this phase are left behind it
-                b.BITOP3(A(w), M(w), VP(w), A(w), lambda s_, vp, a: s_ ^ vp ^ a)
-                if w == hi - 1 and not vg and not (balanced and hi - lo > 1):
-                    # the other chain's carry, two instructions ahead of its reader; block 0: the row edge D[i][0] - D[i-1][0] = +1
-                    # enters HP at bit 0 of word 0
-                    b.SETC1() if first else load(1)
-                b.BITOP3(M(w), E(w), VN(w), A(w), lambda e, vn, hn: e | vn | hn)
-                if w == hi - 1 and not last and vg:
-                    save(0)          # a VALU read of VCC: two instructions behind the link that wrote it
-                if not balanced or w == lo:
-                    b.BITOP3(VP(w), M(w), VN(w), VP(w), lambda m, vn, vp: (m & vn) | ~(m | vp))
-                if w == hi - 1 and vg:
-                    b.SETC1() if first else load(1)     # (as written its reader follows at once: schedule_ilp, or the emitter's s_nop, spaces them)
-            for w in range(lo, hi):  # phase B: HP << 1 across words, then the new deltas
-                b.ADDC(VP(w), VP(w), VP(w))
-                if balanced and w + 1 < hi:
-                    b.BITOP3(VP(w + 1), M(w + 1), VN(w + 1), VP(w + 1), lambda m, vn, vp: (m & vn) | ~(m | vp))
-                if w == hi - 1 and not last and not vg:
-                    save(1)
-                b.AND(VN(w), M(w), VP(w))
-                if w == hi - 1 and not last and not vg:
-                    load(0)
-                b.BITOP3(VP(w), M(w), A(w), VP(w), lambda m, hn, hp: (m & hn) | ~(m | hp))
-                if w == hi - 1 and not last and vg:
-                    save(1)
-                    load(0)
+        # A scalar pair hands chain 1 its carry two instructions ahead of its reader (the defaults); a vector register is read two
+        # instructions behind the link that wrote it (a VALU read of VCC) and, as written, loaded right in front of its reader:
+        # schedule_ilp, or the emitter's s_nop, spaces them
+        vgpr = dict(park=(lambda c: b.SAVEV(f"cv{g}_{c}"), lambda c: b.LOADV(f"cv{g}_{c}")),
+                    place={"park0": "m2", "take1": "hp", "park1": "vp", "take0": "vp"}) if park == "vgpr" else {}
+        _myers_eight(b, nw, *_state(g * nw), lambda w: f"E{g * nw + w}", f"a{g}_{{w}}", f"m{g}_{{w}}", split, balanced, **vgpr)
     return b
 
 
@@ -766,65 +870,11 @@ def run_band_stream(nw: int, state: list, peq: np.ndarray, stream: bytes, band: 
 
 
 def myers_body10(nw: int, groups: int = 1) -> Body:
-    """State layout: S[(g*nw + w)*2 + 0] = VP word w of group g, +1 = VN.  E[g*nw + w] = match mask.
-
-    Per word (10 instructions, full 32-bit words, hardware carries instead of the reference's
-    software carry bit, align_core.c:79-83,91-96):
-        D0 = (((P & E) + P) ^ P) | E | M ; HP = ~(D0 | P) | M ; HN = D0 & P
-        HP, HN <<= 1 (row boundary feeds 1 into HP)  ; P' = ~(D0 | HP) | HN ; M' = D0 & HP
-    """
+    """The ten-instruction row (_myers_ten) in myers_body's layout: S[(g*nw + w)*2 + 0] = VP word w of group g, +1 = VN,
+    E[g*nw + w] = match mask; the row boundary feeds 1 into the HP shift."""
     b = Body()
     for g in range(groups):
-        P = lambda w: f"S{(g * nw + w) * 2}"
-        M = lambda w: f"S{(g * nw + w) * 2 + 1}"
-        E = lambda w: f"E{g * nw + w}"
-        D = lambda w: f"d{g}_{w}"
-        HP = lambda w: f"hp{g}_{w}"
-        HN = lambda w: f"hn{g}_{w}"
-        for w in range(nw):  # phase A: the addition's carry chain
-            b.AND(D(w), P(w), E(w))   # (P & (E|M)) == (P & E): P & M == 0 is an invariant
-            (b.ADD_CO if w == 0 else b.ADDC)(D(w), D(w), P(w))
-            b.BITOP3(D(w), D(w), P(w), M(w), lambda a, p, m: (a ^ p) | m)
-            b.OR(D(w), D(w), E(w))
-        b.SETC1()  # D[i][0] - D[i-1][0] = +1 enters HP at bit 0 of word 0
-        for w in range(nw):  # phase C: HP << 1 across words
-            b.BITOP3(HP(w), D(w), P(w), M(w), lambda d, p, m: ~(d | p) | m)
-            b.AND(HN(w), D(w), P(w))
-            b.ADDC(HP(w), HP(w), HP(w))
-        for w in range(nw):  # phase D: HN << 1 across words, then the new vertical deltas
-            (b.ADD_CO if w == 0 else b.ADDC)(HN(w), HN(w), HN(w))
-            b.AND(M(w), D(w), HP(w))
-            b.BITOP3(P(w), D(w), HP(w), HN(w), lambda d, hp, hn: ~(d | hp) | hn)
-    return b
-
-
-def myers_parked_body(nw: int) -> Body:
-    """myers_body for 26..28 words: HN is parked in the VP register between the phases (as myers_planes_body does), so
-    a word needs 9 registers instead of 10 — 5 Peq masks, VP, VN, D0, HP — and 28 words (896 bp) still fit 256 VGPRs
-    with two waves per SIMD.  Same 10 instructions per word; state and masks as myers_body (one group).
-    (Round 4's eight-instruction myers_body needs nine registers per word as it is — HP lives in the dead VP register — and replaces it.)"""
-    if MYERS_EIGHT:
-        return myers_body(nw, 1)
-    b = Body()
-    P = lambda w: f"S{w * 2}"
-    M = lambda w: f"S{w * 2 + 1}"
-    E = lambda w: f"E{w}"
-    D = lambda w: f"d{w}"
-    HP = lambda w: f"hp{w}"
-    for w in range(nw):  # phase A
-        b.AND(D(w), P(w), E(w))
-        (b.ADD_CO if w == 0 else b.ADDC)(D(w), D(w), P(w))
-        b.BITOP3(D(w), D(w), P(w), M(w), lambda a, p, m: (a ^ p) | m)
-        b.OR(D(w), D(w), E(w))
-    b.SETC1()
-    for w in range(nw):  # phase C: HP chain; HN parks in the VP register
-        b.BITOP3(HP(w), D(w), P(w), M(w), lambda d, p, m: ~(d | p) | m)
-        b.AND(P(w), D(w), P(w))
-        b.ADDC(HP(w), HP(w), HP(w))
-    for w in range(nw):  # phase D: HN chain in place, then the new VP
-        (b.ADD_CO if w == 0 else b.ADDC)(P(w), P(w), P(w))
-        b.AND(M(w), D(w), HP(w))
-        b.BITOP3(P(w), D(w), HP(w), P(w), lambda d, hp, hn: ~(d | hp) | hn)
+        _myers_ten(b, nw, *_state(g * nw), lambda w: f"E{g * nw + w}", f"d{g}_{{w}}", f"hp{g}_{{w}}", f"hn{g}_{{w}}")
     return b
 
 
@@ -841,88 +891,22 @@ def myers_semi_body(nw: int, split: int = 0) -> Body:
     State: myers_body's, then S[2nw] = D[i][n] (running), S[2nw+1] = its minimum so far.
     split = K > 0: the two chains in turns over blocks of K words, as myers_body(split=K) — 2K temporaries, which keeps the five Peq
     planes resident up to 32 words (round 5); the two carries that leave the chains are taken where the LAST block's phases end."""
-    if MYERS_EIGHT and split > 0:
-        b = Body()
-        VP = lambda w: f"S{w * 2}"
-        VN = lambda w: f"S{w * 2 + 1}"
-        RUN, BEST = f"S{2 * nw}", f"S{2 * nw + 1}"
-        blocks = [(lo, min(nw, lo + split)) for lo in range(0, nw, split)]
-        for j, (lo, hi) in enumerate(blocks):
-            first, last = j == 0, j == len(blocks) - 1
-            for w in range(lo, hi):      # phase A: the addition's chain
-                b.AND(f"a{w}", VP(w), f"E{w}")
-                (b.ADD_CO if w == 0 else b.ADDC)(f"m{w}", VP(w), f"a{w}")
-                if w == hi - 1 and not last:
-                    b.SAVECC(0)
-                b.BITOP3(f"a{w}", f"m{w}", VP(w), f"a{w}", lambda s_, vp, a_: s_ ^ vp ^ a_)
-                b.BITOP3(f"m{w}", f"E{w}", VN(w), f"a{w}", lambda e, vn, hn: e | vn | hn)
-                if w == hi - 1 and last:
-                    b.SUBBZ(RUN)             # - the HN bit that left the last column (two instructions behind the chain's last link)
-                if w == hi - 1 and not first:
-                    b.LOADCC(1)              # the HP shift's carry out of the block before (block 0 starts it with carry-in 0: ADD_CO)
-                b.BITOP3(VP(w), f"m{w}", VN(w), VP(w), lambda m, vn, vp: (m & vn) | ~(m | vp))
-            for w in range(lo, hi):      # phase B: HP << 1 across words
-                (b.ADD_CO if w == 0 else b.ADDC)(VP(w), VP(w), VP(w))
-                if w == hi - 1 and not last:
-                    b.SAVECC(1)
-                b.AND(VN(w), f"m{w}", VP(w))
-                if w == hi - 1 and last:
-                    b.ADDCZ(RUN)             # + the HP bit that left the last column (before anything else writes VCC)
-                if w == hi - 1 and not last:
-                    b.LOADCC(0)
-                b.BITOP3(VP(w), f"m{w}", f"a{w}", VP(w), lambda m, hn, hp: (m & hn) | ~(m | hp))
-        b.MINU(BEST, BEST, RUN)
-        return b
-    if MYERS_EIGHT:
-        # the eight-instruction row (myers_body): the carry that LEAVES the addition chain is [v = 2] of the last column = its HN bit,
-        # the one that leaves the HP shift its HP bit — the same two score updates, 8 VALU per word + 3 per row
-        b = Body()
-        VP = lambda w: f"S{w * 2}"
-        VN = lambda w: f"S{w * 2 + 1}"
-        RUN, BEST = f"S{2 * nw}", f"S{2 * nw + 1}"
-        for w in range(nw):
-            b.AND(f"a{w}", VP(w), f"E{w}")
-            (b.ADD_CO if w == 0 else b.ADDC)(f"m{w}", VP(w), f"a{w}")
-            b.BITOP3(f"a{w}", f"m{w}", VP(w), f"a{w}", lambda s_, vp, a_: s_ ^ vp ^ a_)
-            b.BITOP3(f"m{w}", f"E{w}", VN(w), f"a{w}", lambda e, vn, hn: e | vn | hn)
-            if w == nw - 1:
-                b.SUBBZ(RUN)                    # - the HN bit that left the last column (two instructions behind the chain's last link)
-            b.BITOP3(VP(w), f"m{w}", VN(w), VP(w), lambda m, vn, vp: (m & vn) | ~(m | vp))
-        for w in range(nw):  # HP << 1 across words, carry-in 0
-            (b.ADD_CO if w == 0 else b.ADDC)(VP(w), VP(w), VP(w))
-            b.AND(VN(w), f"m{w}", VP(w))
-            if w == nw - 1:
-                b.ADDCZ(RUN)                    # + the HP bit that left the last column (before anything else writes VCC)
-            b.BITOP3(VP(w), f"m{w}", f"a{w}", VP(w), lambda m, hn, hp: (m & hn) | ~(m | hp))
-        b.MINU(BEST, BEST, RUN)
-        return b
+    return _myers_semi_rows(nw, lambda b: (lambda w: f"E{w}"), "hn{w}", split)
+
+
+def _myers_semi_rows(nw: int, mask, hn: str | None, split: int = 0) -> Body:
+    """myers_semi_body and myers_semi_planes_body behind their match masks (mask(b) is the cell's `mask`; hn: _myers_ten's).
+    Eight instructions: the carry that LEAVES the addition chain is [v = 2] of the last column = its HN bit, the one that leaves
+    the HP shift its HP bit — 8 VALU per word + 3 per row; both are taken where the LAST block's phases end, the HN bit two
+    instructions behind the chain's last link (and in front of the other chain's LOADCC), the HP bit before anything else
+    writes VCC.  Ten instructions (never split): the HP bit behind phase C, the HN bit behind phase D."""
     b = Body()
-    P = lambda w: f"S{w * 2}"
-    M = lambda w: f"S{w * 2 + 1}"
-    E = lambda w: f"E{w}"
-    D = lambda w: f"d{w}"
-    HP = lambda w: f"hp{w}"
-    HN = lambda w: f"hn{w}"
     RUN, BEST = f"S{2 * nw}", f"S{2 * nw + 1}"
-    for w in range(nw):
-        b.AND(D(w), P(w), E(w))
-        (b.ADD_CO if w == 0 else b.ADDC)(D(w), D(w), P(w))
-        b.BITOP3(D(w), D(w), P(w), M(w), lambda a, p, m: (a ^ p) | m)
-        b.OR(D(w), D(w), E(w))
-    for w in range(nw):  # HP << 1 across words, carry-in 0
-        b.BITOP3(HP(w), D(w), P(w), M(w), lambda d, p, m: ~(d | p) | m)
-        b.AND(HN(w), D(w), P(w))
-        (b.ADD_CO if w == 0 else b.ADDC)(HP(w), HP(w), HP(w))
-    b.AND(M(0), D(0), HP(0))            # two instructions behind the chain's last link
-    if nw > 1:
-        b.AND(M(1), D(1), HP(1))
-    b.ADDCZ(RUN)                        # + the HP bit that left the last column
-    for w in range(nw):  # HN << 1 across words, then the new vertical deltas
-        (b.ADD_CO if w == 0 else b.ADDC)(HN(w), HN(w), HN(w))
-        if w >= 2:
-            b.AND(M(w), D(w), HP(w))
-        b.BITOP3(P(w), D(w), HP(w), HN(w), lambda d, hp, hn: ~(d | hp) | hn)
-    b.SUBBZ(RUN)                        # - the HN bit that left the last column
+    less, more = (lambda: b.SUBBZ(RUN)), (lambda: b.ADDCZ(RUN))      # - the HN bit, + the HP bit that left the last column
+    if MYERS_EIGHT:
+        _myers_eight(b, nw, *_state(), mask(b), split=split, edge=0, tap=(less, more), place={"take1": "m2"})
+    else:
+        _myers_ten(b, nw, *_state(), mask(b), hn=hn, edge=0, tap=(more, less), early=2)
     b.MINU(BEST, BEST, RUN)
     return b
 
@@ -930,39 +914,43 @@ def myers_semi_body(nw: int, split: int = 0) -> Body:
 def semi_align(peq: np.ndarray, slen: int, nw: int):
     """What the semi-global kernels do to a subject's match masks once per task: right-align the slen columns
     in nw words and make the unused low columns match everything.  Returns (aligned peq [5][nw][n], VP init
-    per word [nw] — 0 in the unused columns, 1 in the subject's)."""
+    per word [nw] — 0 in the unused columns, 1 in the subject's).  peq may be any stack [planes][words][n] of per-column
+    bits: the code planes are aligned the same way, all ones = code 7 in their unused columns."""
     s = 32 * nw - slen
     assert s >= 0
-    n = peq.shape[2]
-    out = np.zeros((5, nw, n), dtype=np.uint32)
+    planes, words, n = peq.shape
+    out = np.zeros((planes, nw, n), dtype=np.uint32)
     vp = []
     for w in range(nw):
         lo_col = 32 * w - s                    # source column of bit 0 of aligned word w
-        word = np.zeros((5, n), dtype=np.uint64)
+        word = np.zeros((planes, n), dtype=np.uint64)
         for src in (lo_col // 32, lo_col // 32 + 1):
-            if 0 <= src < peq.shape[1]:
+            if 0 <= src < words:
                 shift = 32 * src - lo_col      # where source word `src` starts within the aligned word
                 v = peq[:, src].astype(np.uint64)
                 word |= (v << np.uint64(shift)) if shift >= 0 else (v >> np.uint64(-shift))
-        dummy = 0xFFFFFFFF if 32 * (w + 1) <= s else ((1 << (s - 32 * w)) - 1 if 32 * w < s else 0)
+        dummy = _low_mask(s - 32 * w)
         out[:, w] = ((word & np.uint64(0xFFFFFFFF)) | np.uint64(dummy)).astype(np.uint32)
-        vp.append(np.uint32(~dummy & 0xFFFFFFFF))
+        vp.append(~dummy)
     return out, vp
+
+
+def _semi_state(vp0: list, n: int, slen: int) -> list:
+    """Row 0 of the semi-global bodies: VP as semi_align gives it, VN = 0, D[0][n] = n running and as the best so far."""
+    st = []
+    for vp in vp0:
+        st += [np.full(n, vp, np.uint32), np.zeros(n, np.uint32)]
+    return st + [np.full(n, slen, np.uint32), np.full(n, slen, np.uint32)]
 
 
 def myers_semi_simulate(subjects: np.ndarray, query: np.ndarray, nw: int, body: "Body | None" = None) -> np.ndarray:
     """One query against the subjects with myers_semi_body (or the given form of it), set up as myers_semi_asm_kernel<NW> does."""
     n, slen = subjects.shape
     peq, vp0 = semi_align(build_peq32(subjects, (slen + 31) // 32), slen, nw)
-    st = []
-    for w in range(nw):
-        st += [np.full(n, vp0[w], np.uint32), np.zeros(n, np.uint32)]
-    st += [np.full(n, slen, np.uint32), np.full(n, slen, np.uint32)]     # D[0][n] = n
+    st = _semi_state(vp0, n, slen)
     body = myers_semi_body(nw) if body is None else body
-    code = {ord("A"): 0, ord("C"): 1, ord("G"): 2, ord("T"): 3, ord("N"): 4}
     for ch in query:
-        c = code.get(int(ch), 0)
-        body.simulate(st, [peq[c, w] for w in range(nw)])
+        body.simulate(st, list(peq[class_code(ch)]))
     return (-st[2 * nw + 1].astype(np.int64)).astype(np.int16)
 
 
@@ -973,59 +961,19 @@ def myers_planes_body(nw: int, split: int = 0, balanced: bool = False) -> Body:
     7*nw+1 registers, which keeps 32 words (1024 bp) at two waves per SIMD.  State as myers_body.
     split = K > 0: the chains in turns over blocks of K words (see myers_body): 5*nw + 2K + 1 registers.
     """
-    if MYERS_EIGHT:      # myers_body's eight instructions + the match mask: 9 per word, the same 7*nw + 1 registers
-        b = Body()
-        VP = lambda w: f"S{w * 2}"
-        VN = lambda w: f"S{w * 2 + 1}"
-        blocks = [(0, nw)] if split <= 0 else [(lo, min(nw, lo + split)) for lo in range(0, nw, split)]
-        for j, (lo, hi) in enumerate(blocks):
-            first, last = j == 0, j == len(blocks) - 1
-            for w in range(lo, hi):
-                b.MATCH3(f"e{w}", f"B{w * 3}", f"B{w * 3 + 1}", f"B{w * 3 + 2}")   # a name per word: no false dependency between the words' masks (the slots are reused)
-                b.AND(f"a{w}", VP(w), f"e{w}")
-                (b.ADD_CO if w == 0 else b.ADDC)(f"m{w}", VP(w), f"a{w}")
-                if w == hi - 1 and not last:
-                    b.SAVECC(0)
-                if w == nw - 1 and not split:
-                    b.SETC1()
-                b.BITOP3(f"a{w}", f"m{w}", VP(w), f"a{w}", lambda s_, vp, a_: s_ ^ vp ^ a_)
-                if w == hi - 1 and split:
-                    b.SETC1() if first else b.LOADCC(1)
-                b.BITOP3(f"m{w}", f"e{w}", VN(w), f"a{w}", lambda e, vn, hn: e | vn | hn)
-                if not balanced or w == lo:
-                    b.BITOP3(VP(w), f"m{w}", VN(w), VP(w), lambda m, vn, vp: (m & vn) | ~(m | vp))
-            for w in range(lo, hi):
-                b.ADDC(VP(w), VP(w), VP(w))
-                if balanced and w + 1 < hi:   # HP of the next word between this word's shift and its new deltas (myers_body: balanced)
-                    b.BITOP3(VP(w + 1), f"m{w + 1}", VN(w + 1), VP(w + 1), lambda m, vn, vp: (m & vn) | ~(m | vp))
-                if w == hi - 1 and not last:
-                    b.SAVECC(1)
-                b.AND(VN(w), f"m{w}", VP(w))
-                if w == hi - 1 and not last:
-                    b.LOADCC(0)
-                b.BITOP3(VP(w), f"m{w}", f"a{w}", VP(w), lambda m, hn, hp: (m & hn) | ~(m | hp))
-        return b
+    # a mask name per word: no false dependency between the words' masks (the slots are reused)
+    return _myers_planes_rows(nw, "e{w}" if MYERS_EIGHT else "e", split, balanced)
+
+
+def _myers_planes_rows(nw: int, e: str, split: int = 0, balanced: bool = False) -> Body:
+    """myers_planes_body with its match mask in the temporary `e` ('{w}' = the word)."""
     b = Body()
-    P = lambda w: f"S{w * 2}"
-    M = lambda w: f"S{w * 2 + 1}"
-    D = lambda w: f"d{w}"
-    HP = lambda w: f"hp{w}"
-    for w in range(nw):  # phase A
-        b.MATCH3("e", f"B{w * 3}", f"B{w * 3 + 1}", f"B{w * 3 + 2}")
-        b.AND(D(w), P(w), "e")
-        (b.ADD_CO if w == 0 else b.ADDC)(D(w), D(w), P(w))
-        b.BITOP3(D(w), D(w), P(w), M(w), lambda a, p, m: (a ^ p) | m)
-        b.OR(D(w), D(w), "e")
-    b.SETC1()
-    for w in range(nw):  # phase C: HP chain; HN parks in the VP register
-        b.BITOP3(HP(w), D(w), P(w), M(w), lambda d, p, m: ~(d | p) | m)
-        b.AND(P(w), D(w), P(w))            # HN
-        b.ADDC(HP(w), HP(w), HP(w))
-    for w in range(nw):  # phase D: HN chain in place, then the new VP; the new VN (needs only D and the
-        #                  shifted HP) is computed here so that every link has two instructions behind it
-        (b.ADD_CO if w == 0 else b.ADDC)(P(w), P(w), P(w))
-        b.AND(M(w), D(w), HP(w))
-        b.BITOP3(P(w), D(w), HP(w), P(w), lambda d, hp, hn: ~(d | hp) | hn)
+    if MYERS_EIGHT:      # myers_body's eight instructions + the match mask: 9 per word, the same 7*nw + 1 registers
+        _myers_eight(b, nw, *_state(), _plane_mask(b, e), split=split, balanced=balanced,
+                     place={"take1": "hn" if split > 0 else "sum"})
+    else:                # HN parks in the VP register; the new VN (needs only D and the shifted HP) is computed in phase D so that
+        #                  every link has two instructions behind it
+        _myers_ten(b, nw, *_state(), _plane_mask(b, e))
     return b
 
 
@@ -1033,84 +981,21 @@ def myers_semi_planes_body(nw: int) -> Body:
     """Semi-global Myers for subjects of 769..1024 bp: myers_planes_body with myers_semi_body's changes — HP shift
     with carry-in 0, the subject right-aligned, the carries leaving the HP / HN chains accumulated into the running
     last-column score — and the unused low columns coded 7 in the planes, the code that matches every class (MATCH3
-    wild), so they cost no instruction.  11 VALU per word + 3 per row.
+    wild), so they cost no instruction.  9 VALU per word + 3 per row (11 + 3 under the ten-instruction row).
     State: S[2w] = VP, S[2w+1] = VN, S[2nw] = D[i][n], S[2nw+1] = its minimum so far."""
-    if MYERS_EIGHT:      # as myers_semi_body's eight-instruction form, the match mask from the code planes: 9 per word + 3 per row
-        b = Body()
-        VP = lambda w: f"S{w * 2}"
-        VN = lambda w: f"S{w * 2 + 1}"
-        RUN, BEST = f"S{2 * nw}", f"S{2 * nw + 1}"
-        for w in range(nw):
-            b.MATCH3("e", f"B{w * 3}", f"B{w * 3 + 1}", f"B{w * 3 + 2}", wild=True)
-            b.AND(f"a{w}", VP(w), "e")
-            (b.ADD_CO if w == 0 else b.ADDC)(f"m{w}", VP(w), f"a{w}")
-            b.BITOP3(f"a{w}", f"m{w}", VP(w), f"a{w}", lambda s_, vp, a_: s_ ^ vp ^ a_)
-            b.BITOP3(f"m{w}", "e", VN(w), f"a{w}", lambda e, vn, hn: e | vn | hn)
-            if w == nw - 1:
-                b.SUBBZ(RUN)
-            b.BITOP3(VP(w), f"m{w}", VN(w), VP(w), lambda m, vn, vp: (m & vn) | ~(m | vp))
-        for w in range(nw):
-            (b.ADD_CO if w == 0 else b.ADDC)(VP(w), VP(w), VP(w))
-            b.AND(VN(w), f"m{w}", VP(w))
-            if w == nw - 1:
-                b.ADDCZ(RUN)
-            b.BITOP3(VP(w), f"m{w}", f"a{w}", VP(w), lambda m, hn, hp: (m & hn) | ~(m | hp))
-        b.MINU(BEST, BEST, RUN)
-        return b
-    b = Body()
-    P = lambda w: f"S{w * 2}"
-    M = lambda w: f"S{w * 2 + 1}"
-    D = lambda w: f"d{w}"
-    HP = lambda w: f"hp{w}"
-    RUN, BEST = f"S{2 * nw}", f"S{2 * nw + 1}"
-    for w in range(nw):
-        b.MATCH3("e", f"B{w * 3}", f"B{w * 3 + 1}", f"B{w * 3 + 2}", wild=True)
-        b.AND(D(w), P(w), "e")
-        (b.ADD_CO if w == 0 else b.ADDC)(D(w), D(w), P(w))
-        b.BITOP3(D(w), D(w), P(w), M(w), lambda a, p, m: (a ^ p) | m)
-        b.OR(D(w), D(w), "e")
-    for w in range(nw):  # HP chain, carry-in 0; HN parks in the VP register
-        b.BITOP3(HP(w), D(w), P(w), M(w), lambda d, p, m: ~(d | p) | m)
-        b.AND(P(w), D(w), P(w))
-        (b.ADD_CO if w == 0 else b.ADDC)(HP(w), HP(w), HP(w))
-    b.AND(M(0), D(0), HP(0))            # two instructions behind the chain's last link
-    b.AND(M(1), D(1), HP(1))
-    b.ADDCZ(RUN)                        # + the HP bit that left the last column
-    for w in range(nw):  # HN chain in place, then the new vertical deltas
-        (b.ADD_CO if w == 0 else b.ADDC)(P(w), P(w), P(w))
-        if w >= 2:
-            b.AND(M(w), D(w), HP(w))
-        b.BITOP3(P(w), D(w), HP(w), P(w), lambda d, hp, hn: ~(d | hp) | hn)
-    b.SUBBZ(RUN)                        # - the HN bit that left the last column
-    b.MINU(BEST, BEST, RUN)
-    return b
+    return _myers_semi_rows(nw, lambda b: _plane_mask(b, "e", wild=True), None)
 
 
 def myers_semi_planes_simulate(subjects: np.ndarray, query: np.ndarray, nw: int) -> np.ndarray:
     """One query against the subjects with myers_semi_planes_body, set up as myers_semi_planes_kernel<NW> does."""
     n, slen = subjects.shape
-    wn = (slen + 31) // 32
-    peq = build_peq32(subjects, wn)
-    planes5 = [peq[1] | peq[3], peq[2] | peq[3], peq[4]]                 # [3][wn][n]
-    s = 32 * nw - slen
-    B, st = [], []
-    for w in range(nw):
-        lo_col = 32 * w - s
-        dummy = 0xFFFFFFFF if 32 * (w + 1) <= s else ((1 << (s - 32 * w)) - 1 if 32 * w < s else 0)
-        for i in range(3):
-            word = np.zeros(n, dtype=np.uint64)
-            for src in (lo_col // 32, lo_col // 32 + 1):
-                if 0 <= src < wn:
-                    shift = 32 * src - lo_col
-                    v = planes5[i][src].astype(np.uint64)
-                    word |= (v << np.uint64(shift)) if shift >= 0 else (v >> np.uint64(-shift))
-            B.append(((word & np.uint64(0xFFFFFFFF)) | np.uint64(dummy)).astype(np.uint32))
-        st += [np.full(n, ~dummy & 0xFFFFFFFF, np.uint32), np.zeros(n, np.uint32)]
-    st += [np.full(n, slen, np.uint32), np.full(n, slen, np.uint32)]
+    peq = build_peq32(subjects, (slen + 31) // 32)
+    planes, vp0 = semi_align(np.stack([peq[1] | peq[3], peq[2] | peq[3], peq[4]]), slen, nw)      # code_planes' three bits
+    B = [planes[i, w] for w in range(nw) for i in range(3)]
+    st = _semi_state(vp0, n, slen)
     body = myers_semi_planes_body(nw)
-    code = {ord("A"): 0, ord("C"): 1, ord("G"): 2, ord("T"): 3, ord("N"): 4}
     for ch in query:
-        body.simulate(st, [], cls=code.get(int(ch), 0), planes=B)
+        body.simulate(st, [], cls=class_code(ch), planes=B)
     return (-st[2 * nw + 1].astype(np.int64)).astype(np.int16)
 
 
@@ -1120,70 +1005,22 @@ def myers_block_body(nw: int) -> Body:
     first row in bit 31:  x + x  shifts the next row's carry-in into VCC,  x + x + vcc  appends
     the row's carry-out — six extra fast-class instructions per row, no bit extraction.
     State: S[2w] = VP, S[2w+1] = VN, then CIN_S, CIN_P, CIN_N, COUT_S, COUT_P, COUT_N."""
-    if MYERS_EIGHT:      # two chains: the addition (its carries are [v_in = 2]) and the HP shift; the third pair of carry words stays unused
-        b = Body()
-        VP = lambda w: f"S{w * 2}"
-        VN = lambda w: f"S{w * 2 + 1}"
-        CIN = [f"S{2 * nw + i}" for i in range(3)]
-        COUT = [f"S{2 * nw + 3 + i}" for i in range(3)]
-        b.ADD_CO(CIN[0], CIN[0], CIN[0])
-        for w in range(nw):
-            b.MATCH3("e", f"B{w * 3}", f"B{w * 3 + 1}", f"B{w * 3 + 2}")
-            b.AND(f"a{w}", VP(w), "e")
-            b.ADDC(f"m{w}", VP(w), f"a{w}")
-            if w == nw - 1:
-                b.ADDC(COUT[0], COUT[0], COUT[0])
-                b.ADD_CO(CIN[1], CIN[1], CIN[1])
-            b.BITOP3(f"a{w}", f"m{w}", VP(w), f"a{w}", lambda s_, vp, a_: s_ ^ vp ^ a_)
-            b.BITOP3(f"m{w}", "e", VN(w), f"a{w}", lambda e, vn, hn: e | vn | hn)
-            b.BITOP3(VP(w), f"m{w}", VN(w), VP(w), lambda m, vn, vp: (m & vn) | ~(m | vp))
-        for w in range(nw):
-            b.ADDC(VP(w), VP(w), VP(w))
-            b.AND(VN(w), f"m{w}", VP(w))
-            b.BITOP3(VP(w), f"m{w}", f"a{w}", VP(w), lambda m, hn, hp: (m & hn) | ~(m | hp))
-        b.ADDC(COUT[1], COUT[1], COUT[1])
-        return schedule(b, 16)
-    b = Body()
-    P = lambda w: f"S{w * 2}"
-    M = lambda w: f"S{w * 2 + 1}"
-    D = lambda w: f"d{w}"
-    HP = lambda w: f"hp{w}"
-    CIN = [f"S{2 * nw + i}" for i in range(3)]
-    COUT = [f"S{2 * nw + 3 + i}" for i in range(3)]
-    b.ADD_CO(CIN[0], CIN[0], CIN[0])
-    for w in range(nw):
-        b.MATCH3("e", f"B{w * 3}", f"B{w * 3 + 1}", f"B{w * 3 + 2}")
-        b.AND(D(w), P(w), "e")
-        b.ADDC(D(w), D(w), P(w))
-        b.BITOP3(D(w), D(w), P(w), M(w), lambda a, p, m: (a ^ p) | m)
-        b.OR(D(w), D(w), "e")
-    b.ADDC(COUT[0], COUT[0], COUT[0])
-    b.ADD_CO(CIN[1], CIN[1], CIN[1])
-    for w in range(nw):
-        b.BITOP3(HP(w), D(w), P(w), M(w), lambda d, p, m: ~(d | p) | m)
-        b.AND(P(w), D(w), P(w))            # HN parks in the VP register
-        b.ADDC(HP(w), HP(w), HP(w))
-    b.ADDC(COUT[1], COUT[1], COUT[1])
-    b.ADD_CO(CIN[2], CIN[2], CIN[2])
-    for w in range(nw):
-        b.ADDC(P(w), P(w), P(w))
-        b.AND(M(w), D(w), HP(w))
-        b.BITOP3(P(w), D(w), HP(w), P(w), lambda d, hp, hn: ~(d | hp) | hn)
-    b.ADDC(COUT[2], COUT[2], COUT[2])
-    return schedule(b, 16)   # fills the slots around the carry-word instructions
+    return _myers_blocked(_myers_planes_rows(nw, "e"), nw)      # one mask name for all words, as this body has always had
+
+
+def _myers_blocked(body: Body, nw: int) -> Body:
+    """make_blocked on the kernel's three carry-word pairs.  Chains: addition (carry-in 0), HP shift (carry-in 1 in the first
+    block: the row edge), and under the ten-instruction row the HN shift (0); the eight-instruction row's two chains — the
+    addition's carries are [v_in = 2] — leave the third pair unused."""
+    body, init = make_blocked(body, 2 * nw, n_slots=3)
+    assert init == ([0, 1] if MYERS_EIGHT else [0, 1, 0])
+    return schedule(body, 16)   # fills the slots around the carry-word instructions
 
 
 def myers_peq_block_body(nw: int) -> Body:
     """Column-block form of myers_body (Peq planes resident, 8 VALU per word + 4 for the carry words; 10 + 6 until round 4),
-    derived mechanically like the BitPAl block bodies.  Chains: addition (carry-in 0), HP shift (carry-in
-    1 in the first block: the row edge), HN shift (0)."""
-    if MYERS_EIGHT:      # two chains in the first two of the kernel's three carry-word pairs (the second starts with the row edge, as before)
-        body, init = make_blocked(myers_body(nw, 1), 2 * nw, n_slots=3)
-        assert init == [0, 1]
-        return schedule(body, 16)
-    body, init = make_blocked(myers_body10(nw, 1), 2 * nw)
-    assert init == [0, 1, 0]
-    return schedule(body, 16)
+    derived mechanically like the BitPAl block bodies."""
+    return _myers_blocked(myers_body(nw, 1), nw)
 
 
 def myers_blocked_simulate(subjects: np.ndarray, query: np.ndarray, nw_block: int, peq_resident: bool = False) -> np.ndarray:
@@ -1192,45 +1029,39 @@ def myers_blocked_simulate(subjects: np.ndarray, query: np.ndarray, nw_block: in
     peq_resident: the block body built on myers_body (match masks in registers) instead of the code planes."""
     n, slen = subjects.shape
     qlen = len(query)
-    nw_total = (slen + 31) // 32
-    n_blocks = (nw_total + nw_block - 1) // nw_block
+    n_blocks = -(-((slen + 31) // 32) // nw_block)
     peq = build_peq32(subjects, n_blocks * nw_block)      # zero masks beyond the subject
     planes_all = code_planes(peq)
-    code = {ord("A"): 0, ord("C"): 1, ord("G"): 2, ord("T"): 3, ord("N"): 4}
-    n_chunks = (qlen + 31) // 32
-    FULL = np.uint32(0xFFFFFFFF)
     # carry words per 32-row chunk: addition carry-in 0, HP carry-in 1 (row edge), HN carry-in 0
-    carry = [[np.zeros(n, np.uint32), np.full(n, FULL, np.uint32), np.zeros(n, np.uint32)] for _ in range(n_chunks)]
+    carry = [[np.zeros(n, np.uint32), np.full(n, 0xFFFFFFFF, np.uint32), np.zeros(n, np.uint32)] for _ in range((qlen + 31) // 32)]
     body = myers_peq_block_body(nw_block) if peq_resident else myers_block_body(nw_block)
     score = np.full(n, qlen, dtype=np.int64)
     for blk in range(n_blocks):
-        st = []
-        for _ in range(nw_block):
-            st += [np.full(n, FULL, np.uint32), np.zeros(n, np.uint32)]
-        st += [c.copy() for c in carry[0]] + [np.zeros(n, np.uint32) for _ in range(3)]
-        planes = planes_all[blk * nw_block * 3:(blk + 1) * nw_block * 3]
-        for r, ch in enumerate(query):
-            if r > 0 and r % 32 == 0:           # the stream's CARRY event
-                j = r // 32
-                carry[j - 1] = [st[2 * nw_block + 3 + i].copy() for i in range(3)]
-                for i in range(3):
-                    st[2 * nw_block + i] = carry[j][i].copy()
-            c = code.get(int(ch), 0)
-            if peq_resident:
-                body.simulate(st, [peq[c, blk * nw_block + w] for w in range(nw_block)])
-            else:
-                body.simulate(st, [], cls=c, planes=planes)
-        tail = qlen % 32
-        last = [st[2 * nw_block + 3 + i] for i in range(3)]
-        if tail:
-            last = [x << np.uint32(32 - tail) for x in last]   # left-align a partial chunk
-        carry[n_chunks - 1] = [x.copy() for x in last]
-        for w in range(nw_block):
-            rem = slen - 32 * (blk * nw_block + w)
-            mask = np.uint32(0xFFFFFFFF if rem >= 32 else (0 if rem <= 0 else (1 << rem) - 1))
-            score += np.bitwise_count(st[2 * w] & mask).astype(np.int64)
-            score -= np.bitwise_count(st[2 * w + 1] & mask).astype(np.int64)
+        st = myers_init_state(nw_block, 1, n)
+        lo, hi = blk * nw_block, (blk + 1) * nw_block
+        if peq_resident:
+            row = lambda c: body.simulate(st, list(peq[c, lo:hi]))
+        else:
+            row = lambda c: body.simulate(st, [], cls=c, planes=planes_all[3 * lo:3 * hi])
+        _run_block(row, st, carry, query)
+        score += _myers_columns(st, nw_block, slen - 32 * lo)
     return (-score).astype(np.int16)
+
+
+def _run_block(row, st: list, carry: list, query) -> None:
+    """The rows of one column block under the blocked kernels' carry scheme (myers_blocked_kernel, bitpal_blocked_kernel): the
+    block's carry-in words (chunk 0's) and as many carry-out words are appended to its state `st`; at every 32nd row — the
+    stream's CARRY event — the carry-out words are stored for the block to the right and the chunk's carry-in words taken; a
+    partial last chunk is left-aligned.  carry[chunk][chain] is read and replaced; row(c) runs one row of class c on st."""
+    base, n_ch = len(st), len(carry[0])
+    st += [x.copy() for x in carry[0]] + [np.zeros_like(x) for x in carry[0]]
+    for r, ch in enumerate(query):
+        if r > 0 and r % 32 == 0:
+            carry[r // 32 - 1] = [x.copy() for x in st[base + n_ch:]]
+            st[base:base + n_ch] = [x.copy() for x in carry[r // 32]]
+        row(class_code(ch))
+    tail = len(query) % 32
+    carry[-1] = [x << np.uint32(32 - tail) if tail else x.copy() for x in st[base + n_ch:]]     # left-align a partial chunk
 
 
 def code_planes(peq: np.ndarray) -> list:
@@ -1250,13 +1081,16 @@ def myers_init_state(nw: int, groups: int, lanes: int) -> list:
 
 
 def myers_score(state: list, nw: int, qlen: int, slen: int, group: int = 0) -> np.ndarray:
-    score = np.full(state[0].shape, qlen, dtype=np.int64)
+    return (-(qlen + _myers_columns(state[2 * group * nw:], nw, slen))).astype(np.int16)
+
+
+def _myers_columns(state: list, nw: int, cols: int) -> np.ndarray:
+    """D[m][cols] - D[m][0] read off the vertical deltas of the first `cols` columns of nw words (VP, VN pairs)."""
+    total = np.zeros(state[0].shape, dtype=np.int64)
     for w in range(nw):
-        rem = slen - 32 * w
-        mask = np.uint32(0xFFFFFFFF if rem >= 32 else (0 if rem <= 0 else (1 << rem) - 1))
-        score += np.bitwise_count(state[(group * nw + w) * 2] & mask).astype(np.int64)
-        score -= np.bitwise_count(state[(group * nw + w) * 2 + 1] & mask).astype(np.int64)
-    return (-score).astype(np.int16)
+        mask = _low_mask(cols - 32 * w)
+        total += np.bitwise_count(state[2 * w] & mask).astype(np.int64) - np.bitwise_count(state[2 * w + 1] & mask).astype(np.int64)
+    return total
 
 
 # =================================================================================================
@@ -1273,19 +1107,24 @@ def banded_body() -> Body:
     instructions remain (the funnel shift and D0 >> 1); everything else is fast class.
     """
     b = Body()
-    b.ALIGNBIT("w", "E1", "E0", "$sh")
-    b.BITOP3("x", "w", "$mask", "S1", lambda w, m, vn: (w & m) | vn)
-    b.AND("t", "x", "S0")
-    b.ADD("t", "t", "S0")
-    b.BITOP3("d0", "t", "S0", "x", lambda t, vp, x: (t ^ vp) | x)
-    b.BITOP3("hp", "d0", "S0", "S1", lambda d, vp, vn: ~(d | vp) | vn)
-    b.AND("hn", "d0", "S0")
-    b.LSHR1("x2", "d0")
-    b.AND("S1", "x2", "hp")
-    b.BITOP3("S0", "hp", "x2", "hn", lambda hp, x2, hn: ~(hp | x2) | hn)
-    b.BITOP3("e", "d0", "$one", "$one", lambda d, one, _o: ~d & one)
-    b.ADD("S2", "S2", "e")
+    _banded_row(b, b.ALIGNBIT("w", "E1", "E0", "$sh"), lambda i: f"S{i}", lambda name: name, "d0")
     return b
+
+
+def _banded_row(b: Body, w: str, S, t, d: str) -> None:
+    """The sliding 32-bit row behind its window register w (banded_body: a funnel shift, banded_cut_body: a plain one).
+    S(0..2) = VP, VN, errors; t(name): the temporaries' names; d: D0's."""
+    b.BITOP3(t("x"), w, "$mask", S(1), lambda w_, m, vn: (w_ & m) | vn)
+    b.AND(t("t"), t("x"), S(0))
+    b.ADD(t("t"), t("t"), S(0))
+    b.BITOP3(d, t("t"), S(0), t("x"), lambda t_, vp, x: (t_ ^ vp) | x)
+    b.BITOP3(t("hp"), d, S(0), S(1), lambda d_, vp, vn: ~(d_ | vp) | vn)
+    b.AND(t("hn"), d, S(0))
+    b.LSHR1(t("x2"), d)
+    b.AND(S(1), t("x2"), t("hp"))
+    b.BITOP3(S(0), t("hp"), t("x2"), t("hn"), lambda hp, x2, hn: ~(hp | x2) | hn)
+    b.BITOP3(t("e"), d, "$one", "$one", lambda d_, one, _o: ~d_ & one)
+    b.ADD(S(2), S(2), t("e"))
 
 
 def banded_body64_sh64(g: int = 0) -> Body:
@@ -1374,20 +1213,8 @@ def banded_cut_body(groups: int = 1) -> Body:
     per = []
     for g in range(groups):
         b = Body()
-        t = lambda n, g=g: f"{n}{g}"
-        S = lambda i, g=g: f"S{3 * g + i}"
-        b.LSHRS(t("w"), f"E{g}", "$sh")
-        b.BITOP3(t("x"), t("w"), "$mask", S(1), lambda w, m, vn: (w & m) | vn)
-        b.AND(t("t"), t("x"), S(0))
-        b.ADD(t("t"), t("t"), S(0))
-        b.BITOP3(t("d"), t("t"), S(0), t("x"), lambda t_, vp, x: (t_ ^ vp) | x)
-        b.BITOP3(t("hp"), t("d"), S(0), S(1), lambda d, vp, vn: ~(d | vp) | vn)
-        b.AND(t("hn"), t("d"), S(0))
-        b.LSHR1(t("x2"), t("d"))
-        b.AND(S(1), t("x2"), t("hp"))
-        b.BITOP3(S(0), t("hp"), t("x2"), t("hn"), lambda hp, x2, hn: ~(hp | x2) | hn)
-        b.BITOP3(t("e"), t("d"), "$one", "$one", lambda d, one, _o: ~d & one)
-        b.ADD(S(2), S(2), t("e"))
+        t = lambda name, g=g: f"{name}{g}"
+        _banded_row(b, b.LSHRS(t("w"), f"E{g}", "$sh"), lambda i, g=g: f"S{3 * g + i}", t, t("d"))
         per.append(b.ops)
     out = Body()
     for ops in zip(*per):
@@ -1557,257 +1384,105 @@ def banded_stream_bytes(length: int, k: int, codes, phase: int = 0, cut: int = 0
     return out
 
 
-def _banded_simulate_cut(subjects: np.ndarray, query: np.ndarray, k: int, cut: int, groups: int) -> np.ndarray:
-    """banded_cut_kernel<G> on the CPU: banded_cut_body(groups) — the subjects split into `groups` halves that share
-    the token stream —, the cut / advance events as the generated loop runs them on its two registers per class (advance:
-    A <- B, B <- the next word; cut: A <- {B >> bits cut so far, A} >> cut; the row shifts A by the rows since), the
-    final band walk."""
+def banded_simulate(subjects: np.ndarray, query: np.ndarray, k: int, wide: bool | None = None,
+                    phase: int = 0, cut: int = 0, groups: int = 1) -> np.ndarray:
+    """Whole banded pipeline on the CPU with the shipped row body: Mext preprocess, token stream, events, final band walk.
+    Returns int8 results like the kernel; 127 for a lane over the limit at the latching test, and for every lane once a test
+    finds all of them over (the kernels stop there).  Four forms share the loop; the first that applies runs:
+      wide (the default for k > 15): banded_body64 on register pairs, three match-string words per row;
+      phase = banded_phase_rows(k): banded_phase_body as banded_asm_kernel<false, true> runs it — the prologue's window is the
+        first match word with the mask at offset 0, a re-anchor event every `phase` rows, the epilogue shifts by the rows of
+        the last phase and folds the collected error bits;
+      cut = banded_cut_rows(k): banded_cut_body(groups) as banded_cut_kernel<G> runs it — the subjects split into `groups`
+        parts that share the token stream, and per class two registers: A, the window the row shifts by the rows since the
+        last cut, and B, the next word (advance: A <- B, B <- the next word; cut: A <- {B >> bits cut so far, A} >> cut);
+      otherwise banded_body, two match-string words per row."""
+    if wide is None:
+        wide = k > 15
+    phase = 0 if wide else phase
+    cut = 0 if wide or phase else cut
+    groups = groups if cut else 1
     n, length = subjects.shape
     assert n % groups == 0
-    code = np.zeros(256, dtype=np.uint8)
-    for ch, c in zip(b"ACGTN", range(5)):
-        code[ch] = c
-    mapped = code[subjects]
-    nwords = (length + 31) // 32 + 3
-    mext = np.zeros((5, nwords, n), dtype=np.uint32)
-    for p in range(length):
-        i = p + k + 1
-        for c in range(5):
-            mext[c, i // 32] |= (mapped[:, p] == c).astype(np.uint32) << np.uint32(i % 32)
-    h = k
-    band_mask = np.uint32((1 << (2 * k + 1)) - 1)
-    body = banded_cut_body(groups)
     per = n // groups
     sl = [slice(g * per, (g + 1) * per) for g in range(groups)]
-    st = [np.zeros(per, dtype=np.uint32) for _ in range(3 * groups)]
-    dead = np.zeros(n, dtype=bool)
-    wi, sh, off = 0, 0, 0
-    E = [[mext[c, 0, sl[g]].copy() for c in range(5)] for g in range(groups)]   # register A; row 0: the first word itself
-    Bw = [[mext[c, 1, sl[g]].copy() for c in range(5)] for g in range(groups)]  # register B
+    mext = build_peq32(subjects, (length + 31) // 32 + (3 if wide or cut else 2), offset=k + 1)
+    band = (1 << (2 * k + 1)) - 1
+    z = lambda: np.zeros(per, dtype=np.uint32)
+    body = banded_body64() if wide else banded_phase_body() if phase else banded_cut_body(groups) if cut else banded_body()
+    n_state = 5 if wide else 6 if phase else 3
+    st = [z() for _ in range(n_state * groups)]
+    if phase:
+        st[3], st[4] = np.full(n, band, np.uint32), np.ones(n, np.uint32)
+        win = [mext[c, 0].copy() for c in range(5)]
+    if cut:
+        A = [[mext[c, 0, s].copy() for c in range(5)] for s in sl]      # row 0: the first word itself
+        B = [[mext[c, 1, s].copy() for c in range(5)] for s in sl]
+    ERR = 4 if wide else 2
+
+    def errors(g):      # counted on the lowest diagonal since row k
+        return st[n_state * g + ERR] + (np.bitwise_count(st[5]).astype(np.uint32) if phase else np.uint32(0))
 
     def alignbit(hi, lo, s):
         return ((((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)) >> np.uint64(s)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
 
-    qcode = code[query]
-    stopped = False
-    for kind, val in banded_tokens(length, k, phase=0, cut=cut):
-        if kind == "event":
-            if val & 4:
-                over = np.concatenate([st[3 * g + 2] > np.uint32(h + 1) for g in range(groups)])
-                if val & 8:
-                    dead = over.copy()
-                if over.all():
-                    stopped = True
-                    break
-            if val & 1:
-                for g in range(groups):
-                    st[3 * g + 2] = np.zeros(per, dtype=np.uint32)
-            if val & 2:
-                wi, sh, off = wi + 1, 0, 0
-                for g in range(groups):
-                    for c in range(5):
-                        E[g][c] = Bw[g][c]
-                        Bw[g][c] = mext[c, wi + 1, sl[g]].copy()
-            if val & 32:
-                for g in range(groups):
-                    for c in range(5):
-                        E[g][c] = alignbit(Bw[g][c] >> np.uint32(off), E[g][c], cut)
-                off, sh = off + cut, 0
-                for g in range(groups):      # what the window must be: bits off.. of the 64-bit pair of this advance
-                    for c in range(5):
-                        assert np.array_equal(E[g][c], alignbit(mext[c, wi + 1, sl[g]], mext[c, wi, sl[g]], off))
-        else:
+    dead = np.zeros(n, dtype=bool)
+    wi = sh = off = in_phase = 0
+    qcode = CLASS_CODE[query]
+    for kind, val in banded_tokens(length, k, phase=phase, cut=cut):
+        if kind == "row":
             c = int(qcode[val])
-            assert sh < cut and sh + 2 * k + 1 <= 32
-            body.simulate(st, [E[g][c] for g in range(groups)], scalars={"$sh": sh, "$mask": band_mask, "$one": 1})
+            assert not cut or (sh < cut and sh + 2 * k + 1 <= 32)
+            eq = [win[c]] if phase else [A[g][c] for g in range(groups)] if cut else [mext[c, wi + i] for i in range(3 if wide else 2)]
+            body.simulate(st, eq, scalars={"$sh": sh, "$mask": band & 0xFFFFFFFF, "$mask_lo": band & 0xFFFFFFFF,
+                                           "$mask_hi": band >> 32, "$one": 1})
             sh += 1
-    if stopped:
-        return np.full(n, 127, dtype=np.int8)
+            in_phase += 1
+            continue
+        if val & 4:      # test err > limit on all lanes
+            over = np.concatenate([errors(g) > np.uint32(k + 1) for g in range(groups)])
+            if val & 8:  # the reference's last checkpoint: latch the reject mask
+                dead = over.copy()
+            if over.all():
+                return np.full(n, 127, dtype=np.int8)
+        if val & 1:      # row k: the count starts
+            for g in range(groups):
+                st[n_state * g + ERR] = z()
+            if phase:
+                st[5] = z()
+        if val & 2:      # advance the match-string words
+            wi, sh, off = wi + 1, 0, 0
+            for g in range(groups if cut else 0):
+                A[g], B[g] = B[g], [mext[c, wi + 1, sl[g]].copy() for c in range(5)]
+        if val & 16:     # re-anchor the band
+            assert in_phase == phase
+            st[0], st[1], st[2] = st[0] >> np.uint32(phase), st[1] >> np.uint32(phase), errors(0)
+            st[3], st[4], st[5] = np.full(n, band, np.uint32), np.ones(n, np.uint32), z()
+            win = [alignbit(mext[c, wi + 1], mext[c, wi], sh) for c in range(5)]
+            in_phase = 0
+        if val & 32:     # cut the next one-word window
+            for g in range(groups):
+                A[g] = [alignbit(B[g][c] >> np.uint32(off), A[g][c], cut) for c in range(5)]
+            off, sh = off + cut, 0
+            for g in range(groups):      # what the window must be: bits off.. of the 64-bit pair of this advance
+                for c in range(5):
+                    assert np.array_equal(A[g][c], alignbit(mext[c, wi + 1, sl[g]], mext[c, wi, sl[g]], off))
+    if phase:
+        assert in_phase == length - phase * ((length - 1) // phase)
     out = np.empty(n, dtype=np.int8)
     for g in range(groups):
-        err = st[3 * g + 2].astype(np.int64) + k
+        S = [x.astype(np.uint64) for x in st[n_state * g:n_state * (g + 1)]]
+        if wide:
+            vp, vn = S[0] | (S[1] << np.uint64(32)), S[2] | (S[3] << np.uint64(32))
+        else:            # the phase form's band sits in_phase bits up
+            vp, vn = S[0] >> np.uint64(in_phase if phase else 0), S[1] >> np.uint64(in_phase if phase else 0)
+        err = errors(g).astype(np.int64) + k
         best = err.copy()
-        for i in range(h + 1):
-            err = err + ((st[3 * g] >> np.uint32(i)) & 1) - ((st[3 * g + 1] >> np.uint32(i)) & 1)
+        for i in range(k + 1):
+            err = err + ((vp >> np.uint64(i)) & np.uint64(1)).astype(np.int64) - ((vn >> np.uint64(i)) & np.uint64(1)).astype(np.int64)
             best = np.minimum(best, err)
         out[sl[g]] = np.where(dead[sl[g]], 127, best).astype(np.int8)
     return out
-
-
-def banded_simulate(subjects: np.ndarray, query: np.ndarray, k: int, wide: bool | None = None,
-                    phase: int = 0, cut: int = 0, groups: int = 1) -> np.ndarray:
-    """Whole banded pipeline on the CPU with the shipped row body: Mext preprocess, token
-    stream, events, final band walk.  Returns int8 results like the kernel.  wide = the 64-bit
-    band body (register pairs), the default for k > 15."""
-    if wide is None:
-        wide = k > 15
-    if wide:
-        return _banded_simulate64(subjects, query, k)
-    if phase:
-        return _banded_simulate_phase(subjects, query, k, phase)
-    if cut:
-        return _banded_simulate_cut(subjects, query, k, cut, groups)
-    n, length = subjects.shape
-    code = np.zeros(256, dtype=np.uint8)
-    for ch, c in zip(b"ACGTN", range(5)):
-        code[ch] = c
-    mapped = code[subjects]
-    nwords = (length + 31) // 32 + 2
-    mext = np.zeros((5, nwords, n), dtype=np.uint32)
-    for p in range(length):
-        i = p + k + 1
-        for c in range(5):
-            mext[c, i // 32] |= (mapped[:, p] == c).astype(np.uint32) << np.uint32(i % 32)
-    h = k
-    band_mask = np.uint32((1 << (2 * k + 1)) - 1)
-    body = banded_body()
-    st = [np.zeros(n, dtype=np.uint32) for _ in range(3)]
-    dead = np.zeros(n, dtype=bool)
-    wi, sh = 0, 0
-    qcode = code[query]
-    for kind, val in banded_tokens(length, k, phase=0):
-        if kind == "event":
-            if val & 4:
-                over = st[2] > np.uint32(h + 1)
-                if val & 8:
-                    dead = over.copy()
-                if over.all():
-                    dead[:] = True
-                    break
-            if val & 1:
-                st[2] = np.zeros(n, dtype=np.uint32)
-            if val & 2:
-                wi, sh = wi + 1, 0
-        else:
-            c = int(qcode[val])
-            body.simulate(st, [mext[c, wi], mext[c, wi + 1]], scalars={"$sh": sh, "$mask": band_mask, "$one": 1})
-            sh += 1
-    err = st[2].astype(np.int64) + k
-    best = err.copy()
-    for i in range(h + 1):
-        err = err + ((st[0] >> np.uint32(i)) & 1) - ((st[1] >> np.uint32(i)) & 1)
-        best = np.minimum(best, err)
-    return np.where(dead, 127, best).astype(np.int8)
-
-
-def _popcount32(x: np.ndarray) -> np.ndarray:
-    x = x.astype(np.uint64)
-    return sum(((x >> np.uint64(i)) & np.uint64(1)) for i in range(32)).astype(np.uint32)
-
-
-def _banded_simulate_phase(subjects: np.ndarray, query: np.ndarray, k: int, phase: int) -> np.ndarray:
-    """banded_asm_kernel<false, true> on the CPU: banded_phase_body, the token stream with re-anchor events, the
-    kernel's prologue (window = first match word, mask at offset 0) and epilogue (shift by the rows of the last
-    phase, fold the collected error bits)."""
-    n, length = subjects.shape
-    code = np.zeros(256, dtype=np.uint8)
-    for ch, c in zip(b"ACGTN", range(5)):
-        code[ch] = c
-    mapped = code[subjects]
-    nwords = (length + 31) // 32 + 2
-    mext = np.zeros((5, nwords, n), dtype=np.uint32)
-    for p in range(length):
-        i = p + k + 1
-        for c in range(5):
-            mext[c, i // 32] |= (mapped[:, p] == c).astype(np.uint32) << np.uint32(i % 32)
-    h = k
-    band_mask = np.uint32((1 << (2 * k + 1)) - 1)
-    body = banded_phase_body()
-    z = lambda: np.zeros(n, dtype=np.uint32)
-    st = [z(), z(), z(), np.full(n, band_mask, np.uint32), np.ones(n, np.uint32), z()]
-    W = [mext[c, 0].copy() for c in range(5)]
-    dead = np.zeros(n, dtype=bool)
-    wi, sh, in_phase = 0, 0, 0
-    qcode = code[query]
-    stopped = False
-    for kind, val in banded_tokens(length, k, phase=phase):
-        if kind == "event":
-            if val & 4:
-                over = (st[2] + _popcount32(st[5])) > np.uint32(h + 1)
-                if val & 8:
-                    dead = over.copy()
-                if over.all():
-                    dead[:] = True
-                    stopped = True
-                    break
-            if val & 1:
-                st[2], st[5] = z(), z()
-            if val & 2:
-                wi, sh = wi + 1, 0
-            if val & 16:
-                assert in_phase == phase
-                st[0] = st[0] >> np.uint32(phase)
-                st[1] = st[1] >> np.uint32(phase)
-                st[2] = st[2] + _popcount32(st[5])
-                st[3], st[4], st[5] = np.full(n, band_mask, np.uint32), np.ones(n, np.uint32), z()
-                for c in range(5):
-                    pair = (mext[c, wi + 1].astype(np.uint64) << np.uint64(32)) | mext[c, wi].astype(np.uint64)
-                    W[c] = ((pair >> np.uint64(sh)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-                in_phase = 0
-        else:
-            c = int(qcode[val])
-            body.simulate(st, [W[c]])
-            sh += 1
-            in_phase += 1
-    if stopped:
-        return np.full(n, 127, dtype=np.int8)
-    final_shift = length - phase * ((length - 1) // phase)
-    assert final_shift == in_phase
-    vp = st[0] >> np.uint32(final_shift)
-    vn = st[1] >> np.uint32(final_shift)
-    err = (st[2] + _popcount32(st[5])).astype(np.int64) + k
-    best = err.copy()
-    for i in range(h + 1):
-        err = err + ((vp >> np.uint32(i)) & 1) - ((vn >> np.uint32(i)) & 1)
-        best = np.minimum(best, err)
-    return np.where(dead, 127, best).astype(np.int8)
-
-
-def _banded_simulate64(subjects: np.ndarray, query: np.ndarray, k: int) -> np.ndarray:
-    n, length = subjects.shape
-    code = np.zeros(256, dtype=np.uint8)
-    for ch, c in zip(b"ACGTN", range(5)):
-        code[ch] = c
-    mapped = code[subjects]
-    nwords = (length + 31) // 32 + 3
-    mext = np.zeros((5, nwords, n), dtype=np.uint32)
-    for p in range(length):
-        i = p + k + 1
-        for c in range(5):
-            mext[c, i // 32] |= (mapped[:, p] == c).astype(np.uint32) << np.uint32(i % 32)
-    h = k
-    band = (1 << (2 * k + 1)) - 1
-    body = banded_body64()
-    st = [np.zeros(n, dtype=np.uint32) for _ in range(5)]
-    dead = np.zeros(n, dtype=bool)
-    wi, sh = 0, 0
-    qcode = code[query]
-    for kind, val in banded_tokens(length, k, phase=0):
-        if kind == "event":
-            if val & 4:
-                over = st[4] > np.uint32(h + 1)
-                if val & 8:
-                    dead = over.copy()
-                if over.all():
-                    dead[:] = True
-                    break
-            if val & 1:
-                st[4] = np.zeros(n, dtype=np.uint32)
-            if val & 2:
-                wi, sh = wi + 1, 0
-        else:
-            c = int(qcode[val])
-            body.simulate(st, [mext[c, wi], mext[c, wi + 1], mext[c, wi + 2]],
-                          scalars={"$sh": sh, "$mask_lo": band & 0xFFFFFFFF, "$mask_hi": band >> 32, "$one": 1})
-            sh += 1
-    vp = st[0].astype(np.uint64) | (st[1].astype(np.uint64) << np.uint64(32))
-    vn = st[2].astype(np.uint64) | (st[3].astype(np.uint64) << np.uint64(32))
-    err = st[4].astype(np.int64) + k
-    best = err.copy()
-    for i in range(h + 1):
-        err = err + ((vp >> np.uint64(i)) & np.uint64(1)).astype(np.int64) - ((vn >> np.uint64(i)) & np.uint64(1)).astype(np.int64)
-        best = np.minimum(best, err)
-    return np.where(dead, 127, best).astype(np.int8)
 
 
 # =================================================================================================
@@ -1858,23 +1533,23 @@ class BitpalScores:
 
 
 BITPAL_DEFAULT = BitpalScores(2, -3, -5)
-BITPAL_SCHEDULE_WINDOW = int(__import__('os').environ.get('BGSA_GEN_BITPAL_WINDOW', '48'))   # 0 = program order (A/B)
-# build-time A/B switches of round 4's two rewrites of the row body (see bitpal_scores_body; scripts/r04_bitpal_ab.sh,
+BITPAL_SCHEDULE_WINDOW = int(_knob('BITPAL_WINDOW', '48'))   # 0 = program order (A/B)
+# build-time A/B switches of round 4's two rewrites of the row body (see _bitpal_scores_body; scripts/r04_bitpal_ab.sh,
 # profiles/r04_bitpal_ab.txt, 10k x 1M x 150 bp on one box): reading "u <= D" off its plane — one instruction fewer — measured
 # 6,893 -> 6,854 ms and is on; one addition chain per class instead of two — same count, 13 -> 9 chains — measured 6,893 -> 6,949 ms
 # (and the chip held a lower clock under it) and is OFF
-BITPAL_ONE_CHAIN = __import__('os').environ.get('BGSA_GEN_BITPAL_ONE_CHAIN', '0') != '0'
-BITPAL_INLINE_LE = __import__('os').environ.get('BGSA_GEN_BITPAL_INLINE_LE', '1') != '0'
-# round 4, second step: new u = max(w, u) - v_in needs no clamp (see bitpal_scores_body: "the cell identity"); '0' builds the
+BITPAL_ONE_CHAIN = _knob('BITPAL_ONE_CHAIN', '0') != '0'
+BITPAL_INLINE_LE = _knob('BITPAL_INLINE_LE', '1') != '0'
+# round 4, second step: new u = max(w, u) - v_in needs no clamp (see _bitpal_scores_body: "the cell identity"); '0' builds the
 # previous form, new u = max(0, max(W, u) - v_in), for A/B
-BITPAL_CELL_MAX = __import__('os').environ.get('BGSA_GEN_BITPAL_CELL_MAX', '1') != '0'
+BITPAL_CELL_MAX = _knob('BITPAL_CELL_MAX', '1') != '0'
 # the one-hot mask of u = K - 1 has ONE reader — the lowest class's seed term with the top class — so that product is formed from the
 # planes and the class mask directly: one instruction per word fewer ('0': the mask is built like the others, for A/B)
-BITPAL_FOLD_LAST_Z = __import__('os').environ.get('BGSA_GEN_BITPAL_FOLD_LAST_Z', '1') != '0'
+BITPAL_FOLD_LAST_Z = _knob('BITPAL_FOLD_LAST_Z', '1') != '0'
 # the run mask (u = 0 at a MISMATCH) is not needed: the classes may propagate through every u = 0 column — what runs through a u = 0
 # match column is covered, column by column, by the top class's own propagation from that very column, and the extraction masks
 # with the top class instead of the match mask.  One instruction per word fewer ('0': the run mask, for A/B).
-BITPAL_NO_RUN = __import__('os').environ.get('BGSA_GEN_BITPAL_NO_RUN', '1') != '0'
+BITPAL_NO_RUN = _knob('BITPAL_NO_RUN', '1') != '0'
 
 
 
@@ -1942,9 +1617,11 @@ class _Bool:
         return cur
 
 
-@__import__("functools").lru_cache(maxsize=256)
-def bitpal_scores_body(nw: int, sc: BitpalScores = BITPAL_DEFAULT) -> Body:
-    """(Memoised: callers treat the returned Body as read-only.)  The row body for `nw` words, with the single-use one-hot mask folded into
+@functools.lru_cache(maxsize=256)
+def bitpal_body(nw: int, sc: BitpalScores = BITPAL_DEFAULT) -> Body:
+    """For the default scores this computes what the packed kernel of original/BGSA_AVX2/align_core.c:
+    183-428 computes (194 ALU operations per word there), on four unsigned planes, in 69 fast-class VALU.
+    (Memoised: callers treat the returned Body as read-only.)  The row body for `nw` words, with the single-use one-hot mask folded into
     its seed product where that saves an instruction for this score set (it does when the mask shares no partial product with the others:
     2/-3/-5 64 -> 63; 10/-9/-15 would lose one)."""
     if BITPAL_FOLD_LAST_Z and _bitpal_scores_body(1, sc, True).valu_count() < _bitpal_scores_body(1, sc, False).valu_count():
@@ -2212,7 +1889,7 @@ def _bitpal_scores_body(nw: int, sc: BitpalScores, fold_last_z: bool) -> Body:
     return schedule(b, BITPAL_SCHEDULE_WINDOW) if BITPAL_SCHEDULE_WINDOW else b
 
 
-def bitpal_scores_init_state(nw: int, lanes: int, sc: BitpalScores = BITPAL_DEFAULT, semi: bool = False) -> list:
+def bitpal_init_state(nw: int, lanes: int, sc: BitpalScores = BITPAL_DEFAULT, semi: bool = False) -> list:
     """Row 0: every column at dH = G (global), or at dH = 0, i.e. u = -G (semi-global: the
     generator's writeBitInitStr, BitPAlGenerator.java:2201-2218)."""
     stored = -sc.gap if semi else 0                                   # u itself
@@ -2230,8 +1907,8 @@ def bitpal_column_values(state: list, w: int, sc: BitpalScores) -> np.ndarray:
     return u
 
 
-def bitpal_scores_score(state: list, nw: int, qlen: int, slen: int, sc: BitpalScores = BITPAL_DEFAULT,
-                        semi: bool = False) -> np.ndarray:
+def bitpal_score(state: list, nw: int, qlen: int, slen: int, sc: BitpalScores = BITPAL_DEFAULT,
+                 semi: bool = False) -> np.ndarray:
     """Global: S[m][n] = G*(m + n) + sum over subject columns of u.  Semi-global: the maximum of
     S[m][j] = G*m + sum_{c <= j} (u_c + G) over j = 0..n (genPackedScore, BitPAlGenerator.java:78-116)."""
     B = sc.planes
@@ -2242,10 +1919,8 @@ def bitpal_scores_score(state: list, nw: int, qlen: int, slen: int, sc: BitpalSc
         return best.astype(np.int16)
     score = np.full(state[0].shape, sc.gap * (qlen + slen), dtype=np.int64)
     for w in range(nw):
-        rem = slen - 32 * w
-        mask = np.uint32(0xFFFFFFFF if rem >= 32 else (0 if rem <= 0 else (1 << rem) - 1))
         for i, wt in enumerate(sc.weights()):
-            score += wt * np.bitwise_count(state[w * B + i] & mask).astype(np.int64)
+            score += wt * np.bitwise_count(state[w * B + i] & _low_mask(slen - 32 * w)).astype(np.int64)
     return score.astype(np.int16)
 
 
@@ -2255,7 +1930,7 @@ def make_blocked(body: Body, n_state: int, n_slots: int | None = None):
     register S[n_state + k] (VCC = next row's bit) and appends its carry-out with `x + x + vcc` on
     S[n_state + n_chains + k].  Returns (new body, initial carry-in bit per chain): a chain that
     started with SETC1 has carry-in 1 in the first block, the others 0.
-    (myers_block_body is this transformation of myers_planes_body, written out by hand.)"""
+    (myers_block_body and myers_peq_block_body are this transformation of myers_planes_body and myers_body.)"""
     chains = []          # (index of the chain's first op, initial carry)
     for i, op in enumerate(body.ops):
         if op.kind == "add_co":
@@ -2345,7 +2020,6 @@ def bitpal_packed_blocked_simulate(subjects: np.ndarray, query: np.ndarray, nw_b
     peq = build_peq32(subjects, n_blocks * nw_block)
     body, init, n_words = bitpal_packed_block_body(nw_block, sc)
     assert not any(init) and n_words == (sc.chains + 31) // 32
-    code = {ord("A"): 0, ord("C"): 1, ord("G"): 2, ord("T"): 3, ord("N"): 4}
     carry = [[np.zeros(n, np.uint32) for _ in range(n_words)] for _ in range(qlen)]   # [row][word]
     run = np.full(n, sc.gap * qlen, dtype=np.int64)
     best = run.copy()
@@ -2356,9 +2030,8 @@ def bitpal_packed_blocked_simulate(subjects: np.ndarray, query: np.ndarray, nw_b
         for r, ch in enumerate(query):
             for j in range(n_words):
                 st[base + j] = carry[r][j].copy()
-            c = code.get(int(ch), 0)
-            body.simulate(st, [peq[c, blk * nw_block + w] for w in range(nw_block)])
-            carry[r] = [st[base + n_words + j].copy() for j in range(n_words)]
+            body.simulate(st, list(peq[class_code(ch), blk * nw_block:(blk + 1) * nw_block]))
+            carry[r] =[st[base + n_words + j].copy() for j in range(n_words)]
         for w in range(nw_block):
             cols = min(32, max(0, slen - 32 * (blk * nw_block + w)))
             if cols == 0:
@@ -2377,56 +2050,22 @@ def bitpal_block_body(nw: int, sc: BitpalScores = BITPAL_DEFAULT):
     return schedule(body, 200), init
 
 
-def bitpal_body(nw: int, sc: BitpalScores = BITPAL_DEFAULT) -> Body:
-    """For the default scores this computes what the packed kernel of original/BGSA_AVX2/align_core.c:
-    183-428 computes (194 ALU operations per word there), on four unsigned planes, in 69 fast-class VALU."""
-    return bitpal_scores_body(nw, sc)
-
-
-def bitpal_init_state(nw: int, lanes: int, sc: BitpalScores = BITPAL_DEFAULT, semi: bool = False) -> list:
-    return bitpal_scores_init_state(nw, lanes, sc, semi)
-
-
-def bitpal_score(state: list, nw: int, qlen: int, slen: int, sc: BitpalScores = BITPAL_DEFAULT,
-                 semi: bool = False) -> np.ndarray:
-    return bitpal_scores_score(state, nw, qlen, slen, sc, semi)
-
-
 def bitpal_blocked_simulate(subjects: np.ndarray, query: np.ndarray, nw_block: int,
                             sc: BitpalScores = BITPAL_DEFAULT, semi: bool = False) -> np.ndarray:
     """BitPAl over column blocks of nw_block words with carry words between blocks — the scheme of
     bitpal_blocked_kernel at toy scale.  Returns int16."""
     n, slen = subjects.shape
     qlen = len(query)
-    B = sc.planes
-    nw_total = (slen + 31) // 32
-    n_blocks = (nw_total + nw_block - 1) // nw_block
+    n_blocks = -(-((slen + 31) // 32) // nw_block)
     peq = build_peq32(subjects, n_blocks * nw_block)
     body, init = bitpal_block_body(nw_block, sc)
-    n_ch = len(init)
-    assert n_ch == sc.chains and not any(init)
-    code = {ord("A"): 0, ord("C"): 1, ord("G"): 2, ord("T"): 3, ord("N"): 4}
-    n_chunks = (qlen + 31) // 32
-    carry = [[np.zeros(n, np.uint32) for k in range(n_ch)] for _ in range(n_chunks)]
+    assert len(init) == sc.chains and not any(init)
+    carry = [[np.zeros(n, np.uint32) for _ in init] for _ in range((qlen + 31) // 32)]
     run = np.full(n, sc.gap * qlen, dtype=np.int64)      # S[m][j] walking right along the last row
     best = run.copy()
-    base = B * nw_block
     for blk in range(n_blocks):
-        st = bitpal_init_state(nw_block, n, sc, semi) + [c.copy() for c in carry[0]] + \
-             [np.zeros(n, np.uint32) for _ in range(n_ch)]
-        for r, ch in enumerate(query):
-            if r > 0 and r % 32 == 0:
-                j = r // 32
-                carry[j - 1] = [st[base + n_ch + k].copy() for k in range(n_ch)]
-                for k in range(n_ch):
-                    st[base + k] = carry[j][k].copy()
-            c = code.get(int(ch), 0)
-            body.simulate(st, [peq[c, blk * nw_block + w] for w in range(nw_block)])
-        tail = qlen % 32
-        last = [st[base + n_ch + k] for k in range(n_ch)]
-        if tail:
-            last = [x << np.uint32(32 - tail) for x in last]
-        carry[n_chunks - 1] = [x.copy() for x in last]
+        st = bitpal_init_state(nw_block, n, sc, semi)
+        _run_block(lambda c: body.simulate(st, list(peq[c, blk * nw_block:(blk + 1) * nw_block])), st, carry, query)
         for w in range(nw_block):
             cols = min(32, max(0, slen - 32 * (blk * nw_block + w)))
             if cols == 0:
@@ -2441,25 +2080,21 @@ def bitpal_blocked_simulate(subjects: np.ndarray, query: np.ndarray, nw_block: i
 # Reference-style match masks for the simulator (32 data bits per word)
 # =================================================================================================
 
-def build_peq32(subjects: np.ndarray, nw: int) -> np.ndarray:
-    """[5][nw][n_subjects] uint32; alphabet map of original/BGSA_CPU/global.c:9-15."""
+def build_peq32(subjects: np.ndarray, nw: int, offset: int = 0) -> np.ndarray:
+    """[5][nw][n_subjects] uint32, column p at bit p + offset (the banded kernels' match strings: offset = k + 1); alphabet map
+    CLASS_CODE."""
     n, slen = subjects.shape
-    code = np.zeros(256, dtype=np.uint8)
-    for ch, c in zip(b"ACGTN", range(5)):
-        code[ch] = c
-    mapped = code[subjects]
+    mapped = CLASS_CODE[subjects]
     peq = np.zeros((5, nw, n), dtype=np.uint32)
     for p in range(slen):
+        i = p + offset
         for c in range(5):
-            peq[c, p // 32] |= ((mapped[:, p] == c).astype(np.uint32) << np.uint32(p % 32))
+            peq[c, i // 32] |= ((mapped[:, p] == c).astype(np.uint32) << np.uint32(i % 32))
     return peq
 
 
 def run_rows(body: Body, state: list, peq: np.ndarray, query: np.ndarray, groups: int = 1) -> None:
-    code = {ord("A"): 0, ord("C"): 1, ord("G"): 2, ord("T"): 3, ord("N"): 4}
-    nw = peq.shape[1]
     planes = code_planes(peq)
     for ch in query:
-        c = code.get(int(ch), 0)
-        eq = [peq[c, w] for _ in range(groups) for w in range(nw)]
-        body.simulate(state, eq, cls=c, planes=planes)
+        c = class_code(ch)
+        body.simulate(state, list(peq[c]) * groups, cls=c, planes=planes)

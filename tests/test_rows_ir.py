@@ -44,14 +44,15 @@ def test_myers_body_matches_oracle(oracle, qlen, slen):
 
 @pytest.mark.parametrize("qlen,slen,nw", [(300, 832, 26), (90, 896, 28), (1000, 801, 26), (64, 40, 2)])
 def test_myers_parked_body_matches_oracle(oracle, qlen, slen, nw):
-    """The 9-registers-per-word form of the Myers body (HN parked in the VP register): 26 and 28 words, 801..896 bp."""
+    """myers_body at the widths that once had a 9-registers-per-word form of their own (HN parked in the VP register; the
+    eight-instruction row needs nine as it is): 26 and 28 words, 801..896 bp."""
     q = oracle.gen_reads(5100 + qlen, 2, qlen)
     s = oracle.gen_reads(5200 + slen, 24, slen)
     m = min(qlen, slen)
     s[:8, :m] = oracle.mutate(q[np.arange(8) % 2][:, :m], np.arange(8) * 3, 5300)
     s[3, : slen // 3] = ord("N")
     want = oracle.myers64(q, s)
-    body = R.myers_parked_body(nw)
+    body = R.myers_body(nw)
     peq = R.build_peq32(s, nw)
     for i in range(q.shape[0]):
         st = R.myers_init_state(nw, 1, s.shape[0])
