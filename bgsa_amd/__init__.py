@@ -35,6 +35,18 @@ class Params(ctypes.Structure):
                 ("mismatch", ctypes.c_int), ("gap", ctypes.c_int), ("k", ctypes.c_int)]
 
 
+class SamBatch(ctypes.Structure):
+    """bgsa_hip_sam_batch_t of include/bgsa_hip.h "SAM records": what the two record passes read, device pointers and extents."""
+    _fields_ = [("d_reads", ctypes.c_void_p), ("d_quals", ctypes.c_void_p), ("read_stride", ctypes.c_int64), ("n_read_rows", ctypes.c_int64),
+                ("d_names", ctypes.c_void_p), ("d_name_offsets", ctypes.c_void_p), ("n_names", ctypes.c_int64), ("names_bytes", ctypes.c_int64),
+                ("d_rname", ctypes.c_void_p), ("rname_len", ctypes.c_int64), ("d_reference", ctypes.c_void_p), ("ref_len", ctypes.c_int64),
+                ("d_runs", ctypes.c_void_p), ("n_run_rows", ctypes.c_int64), ("cigar_cap", ctypes.c_int64),
+                ("d_read_row", ctypes.c_void_p), ("d_name_of", ctypes.c_void_p), ("d_runs_row", ctypes.c_void_p),
+                ("d_read_len", ctypes.c_void_p), ("d_strand", ctypes.c_void_p), ("d_ref_begin", ctypes.c_void_p), ("d_ref_end", ctypes.c_void_p),
+                ("d_distance", ctypes.c_void_p), ("d_n_ops", ctypes.c_void_p), ("d_flag", ctypes.c_void_p), ("d_mapq", ctypes.c_void_p),
+                ("d_rnext", ctypes.c_void_p), ("d_pnext", ctypes.c_void_p), ("d_tlen", ctypes.c_void_p)]
+
+
 class BgsaHipError(RuntimeError):
     pass
 
@@ -173,6 +185,13 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
+    # SAM records (the same: an older build lacks them)
+    for name, types in (("bgsa_hip_sam_mapq_dev", [vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+                        ("bgsa_hip_sam_measure_dev", [ctypes.POINTER(SamBatch), i64, vp, vp, vp]),
+                        ("bgsa_hip_sam_emit_dev", [ctypes.POINTER(SamBatch), i64, vp, vp, i64, vp, vp])):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = i32
     L.bgsa_hip_stream_faults.argtypes = [i32]
     L.bgsa_hip_debug_inject_stream_fault.argtypes = [i32]
     L.bgsa_hip_set_auto_resident.argtypes = [i32]
@@ -1177,5 +1196,5 @@ def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: 
 
 
 # reads mapped onto one reference: windows cut on the device, both strands, reference coordinates (bgsa_amd/reference.py)
-from .reference import (PairedHits, Placement, ReferenceHits, ReferenceMapper, blank_beyond, max_stride, rescue_region,  # noqa: E402
-                        rescue_slots, seed_plan, seed_plan_ragged, window_plan)
+from .reference import (PairedHits, Placement, ReferenceHits, ReferenceMapper, SamRecords, blank_beyond, check_sam_call,  # noqa: E402
+                        list_mapq, max_stride, rescue_region, rescue_slots, seed_plan, seed_plan_ragged, window_plan, write_sam)

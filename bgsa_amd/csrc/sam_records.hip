@@ -1,0 +1,460 @@
+// sam_records.hip — the last stage of read mapping: a mapping quality per hit list, and the SAM text of every record written
+// by the device into one byte buffer (include/bgsa_hip.h "SAM records").  Three kernels:
+//   sam_mapq_kernel     one wave per read, one lane per slot of its hit list: the primary slot (the first kept one), the kept
+//                       slots at its distance (a ballot), the smallest kept distance above it (a butterfly minimum), the MAPQ.
+//   sam_measure_kernel  pass 1: one wave per record, the byte length of its line; a malformed record gets 0 and is counted.
+//   sam_emit_kernel     pass 2: the same walk once more to check the record against the length the caller's scan was made
+//                       from, then the text.  QNAME, RNAME, SEQ and QUAL are written by all lanes in contiguous pieces; the
+//                       CIGAR one lane per run, a wave prefix sum of the runs' text widths giving the offsets, 64 runs at a time;
+//                       MD by the same scheme — the '=' bases in front of a run are a segmented sum: a prefix sum of the '='
+//                       lengths minus its value at the last X or D run (a prefix maximum) —, the letters of a run of more than
+//                       kSerialBases bases written by the whole wave.
+// Ids, coordinates, lengths and runs are values until checked (check_record): none forms an address before it has been compared
+// with the extent the caller states, and pass 2 writes a record only if its recomputed length is the one its offsets leave
+// room for and that room lies inside the text buffer.  No LDS, no scratch, vector stores only.
+#include "bgsa_common.h"
+
+#include <limits.h>
+
+namespace bgsa {
+
+namespace {
+
+using Batch = bgsa_hip_sam_batch_t;
+
+constexpr int kSerialBases = 4;      // an X or D run up to this long is written by its own lane
+constexpr int kOpRefOnly = 1, kOpReadOnly = 2, kOpEqual = 7, kOpDiff = 8;   // the project's run codes: 1 prints as SAM D, 2 as SAM I
+
+__device__ const unsigned long long kPow10[20] = {
+    1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull, 1000000000ull, 10000000000ull,
+    100000000000ull, 1000000000000ull, 10000000000000ull, 100000000000000ull, 1000000000000000ull, 10000000000000000ull,
+    100000000000000000ull, 1000000000000000000ull, 10000000000000000000ull};
+
+// Decimal digits of v, by comparison: no division.
+__device__ __forceinline__ int dec_width32(uint32_t v)
+{
+    return 1 + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) +
+           (v >= 100000000u) + (v >= 1000000000u);
+}
+__device__ __forceinline__ int dec_width(unsigned long long v)
+{
+    if (v <= 0xffffffffull) return dec_width32(static_cast<uint32_t>(v));
+    int w = 10;
+#pragma unroll
+    for (int i = 10; i < 20; i++) w += v >= kPow10[i];
+    return w;
+}
+
+// v in decimal at out, lane j writing digit j; returns the width.  All lanes call it with the same v.
+__device__ __forceinline__ int put_dec(uint8_t *out, unsigned long long v, int lane)
+{
+    const int w = dec_width(v);
+    if (lane < w) {
+        const unsigned long long p = kPow10[w - 1 - lane];
+        const unsigned digit = v <= 0xffffffffull ? (static_cast<uint32_t>(v) / static_cast<uint32_t>(p)) % 10u
+                                                  : static_cast<unsigned>((v / p) % 10ull);
+        out[lane] = static_cast<uint8_t>('0' + digit);
+    }
+    return w;
+}
+// ... by ONE lane, for a value of its own (a run length, a count of '=' bases).
+__device__ __forceinline__ void put_dec_serial(uint8_t *out, unsigned long long v, int w)
+{
+    for (int i = w - 1; i >= 0; i--) {
+        out[i] = static_cast<uint8_t>('0' + static_cast<unsigned>(v % 10ull));
+        v /= 10ull;
+    }
+}
+
+__device__ __forceinline__ long long wave_scan_add(long long v, int lane)      // inclusive
+{
+#pragma unroll
+    for (int off = 1; off < kLanes; off <<= 1) {
+        const long long up = __shfl_up(v, off);
+        if (lane >= off) v += up;
+    }
+    return v;
+}
+__device__ __forceinline__ long long wave_scan_max(long long v, int lane)      // inclusive
+{
+#pragma unroll
+    for (int off = 1; off < kLanes; off <<= 1) {
+        const long long up = __shfl_up(v, off);
+        if (lane >= off && up > v) v = up;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint8_t class_letter(uint8_t code)      // "ACGTN"[code], the four letters packed into one word
+{
+    return code < 4 ? static_cast<uint8_t>(0x54474341u >> (8 * code)) : 'N';
+}
+
+// The letters of one X run (letter, then "0" letter per further base) or D run ('^', then the letters) behind its count, bases
+// first, first + step, ...: the run's own lane with (0, 1), the whole wave with (lane, 64).
+__device__ __forceinline__ void put_md_letters(uint8_t *out, bool diff, long long len, const uint8_t *ref, long long first, int step)
+{
+    if (!diff && first == 0) out[0] = '^';
+    for (long long t = first; t < len; t += step) {
+        const uint8_t letter = class_letter(ref[t]);
+        if (diff) {
+            if (t > 0) out[2 * t - 1] = '0';
+            out[2 * t] = letter;
+        } else {
+            out[1 + t] = letter;
+        }
+    }
+}
+
+struct Walk {
+    long long cigar_bytes, md_bytes, ref_bases, read_bases;
+    bool ok;         // every run has a known op and a positive length
+};
+
+// The runs of one record, 64 at a time.  EMIT false: the widths and the sums, nothing read but the runs.  EMIT true (only after
+// a walk without has shown that the reference-consuming runs sum to the checked interval at `ref`): the CIGAR text at cigar_out
+// and the MD text at md_out.  n_ops is wave-uniform.
+template <bool EMIT>
+__device__ __forceinline__ Walk walk_runs(const uint32_t *runs, int n_ops, const uint8_t *ref, uint8_t *cigar_out, uint8_t *md_out, int lane)
+{
+    long long c_cigar = 0, c_md = 0, c_ref = 0, c_read = 0, c_eq = 0, c_break = 0;   // what the runs in front of this chunk add up to
+    bool ok = true;
+    for (int base = 0; base < n_ops; base += kLanes) {      // wave-uniform
+        const bool mine = base + lane < n_ops;
+        const uint32_t word = mine ? runs[base + lane] : 0u;
+        const int op = static_cast<int>(word & 15u);
+        const long long len = word >> 4;
+        const bool known = op == kOpRefOnly || op == kOpReadOnly || op == kOpEqual || op == kOpDiff;
+        if (__ballot(mine && !(known && len > 0)) != 0ull) ok = false;
+        const bool live = mine && known && len > 0;
+        const bool breaks = live && (op == kOpDiff || op == kOpRefOnly);      // a run MD writes: X bases, or a SAM D
+        const long long on_ref = live && op != kOpReadOnly ? len : 0, on_read = live && op != kOpRefOnly ? len : 0;
+        const long long equal = live && op == kOpEqual ? len : 0;
+        const int digits = dec_width32(static_cast<uint32_t>(len));
+        const long long cigar_w = live ? digits + 1 : 0;
+        const long long cigar_end = c_cigar + wave_scan_add(cigar_w, lane);
+        const long long ref_end = c_ref + wave_scan_add(on_ref, lane);
+        const long long read_end = c_read + wave_scan_add(on_read, lane);
+        const long long eq_end = c_eq + wave_scan_add(equal, lane);
+        const long long break_end = wave_scan_max(breaks ? eq_end : c_break, lane);      // the '=' total at the last X or D run so far
+        long long break_before = __shfl_up(break_end, 1);
+        if (lane == 0) break_before = c_break;
+        const unsigned long long pending = static_cast<unsigned long long>(eq_end - equal - break_before);   // '=' bases MD has not written yet
+        const int pending_w = dec_width(pending);
+        const long long md_w = breaks ? pending_w + (op == kOpDiff ? 2 * len - 1 : 1 + len) : 0;
+        const long long md_end = c_md + wave_scan_add(md_w, lane);
+        if (EMIT) {
+            if (live) {
+                uint8_t *at = cigar_out + (cigar_end - cigar_w);
+                put_dec_serial(at, static_cast<unsigned long long>(len), digits);
+                at[digits] = op == kOpEqual ? '=' : op == kOpDiff ? 'X' : op == kOpRefOnly ? 'D' : 'I';
+            }
+            uint8_t *letters = md_out + (md_end - md_w) + pending_w;
+            const uint8_t *bases = ref + (ref_end - on_ref);
+            if (breaks) {
+                put_dec_serial(md_out + (md_end - md_w), pending, pending_w);
+                if (len <= kSerialBases) put_md_letters(letters, op == kOpDiff, len, bases, 0, 1);
+            }
+            unsigned long long wide = __ballot(breaks && len > kSerialBases);
+            while (wide) {                               // wave-uniform: the long runs, one after the other, by all lanes
+                const int owner = __ffsll(wide) - 1;
+                wide &= wide - 1;
+                uint8_t *o_letters = reinterpret_cast<uint8_t *>(__shfl(reinterpret_cast<unsigned long long>(letters), owner));
+                const uint8_t *o_bases = reinterpret_cast<const uint8_t *>(__shfl(reinterpret_cast<unsigned long long>(bases), owner));
+                put_md_letters(o_letters, __shfl(op, owner) == kOpDiff, __shfl(len, owner), o_bases, lane, kLanes);
+            }
+        }
+        c_cigar = __shfl(cigar_end, kLanes - 1);
+        c_ref = __shfl(ref_end, kLanes - 1);
+        c_read = __shfl(read_end, kLanes - 1);
+        c_eq = __shfl(eq_end, kLanes - 1);
+        c_break = __shfl(break_end, kLanes - 1);
+        c_md = __shfl(md_end, kLanes - 1);
+    }
+    const unsigned long long last = static_cast<unsigned long long>(c_eq - c_break);      // the count MD ends with
+    if (EMIT) put_dec(md_out + c_md, last, lane);
+    return Walk{c_cigar, c_md + dec_width(last), c_ref, c_read, ok};
+}
+
+// One record's scalars, every one compared with the extent it will index.  All wave-uniform.
+struct Record {
+    bool ok, mapped, reverse, mate_named;
+    const uint8_t *name, *seq, *qual, *ref;
+    const uint32_t *runs;
+    int name_len, read_len, n_ops;
+    long long cigar_bytes, md_bytes;      // of a mapped record: what its runs print as
+    unsigned flag, mapq, distance;
+    unsigned long long pos, pnext, tlen_abs;
+    bool tlen_negative;
+};
+
+__device__ __forceinline__ long long uniform_i64(long long v) { return static_cast<long long>(uniform_u64(static_cast<unsigned long long>(v))); }
+
+__device__ __forceinline__ Record check_record(const Batch &b, int64_t i)
+{
+    Record r{};
+    const long long row = uniform_i64(b.d_read_row[i]), name = uniform_i64(b.d_name_of[i]);
+    const int read_len = __builtin_amdgcn_readfirstlane(b.d_read_len[i]);
+    const int strand = __builtin_amdgcn_readfirstlane(b.d_strand[i]);
+    const int flag = b.d_flag[i], mapq = b.d_mapq[i];      // the same in every lane, and left in vector registers: only digits come of them
+    const int rnext = __builtin_amdgcn_readfirstlane(b.d_rnext[i]);
+    const long long pnext = b.d_pnext[i], tlen = b.d_tlen[i];
+    if (row < 0 || row >= b.n_read_rows || read_len < 1 || read_len > b.read_stride) return r;
+    if (name < 0 || name >= b.n_names) return r;
+    const long long name_lo = uniform_i64(b.d_name_offsets[name]), name_hi = uniform_i64(b.d_name_offsets[name + 1]);
+    if (name_lo < 0 || name_hi <= name_lo || name_hi > b.names_bytes || name_hi - name_lo > INT_MAX) return r;
+    if (strand < -1 || strand > 1 || flag < 0 || flag > 0xffff || mapq < 0 || mapq > 255 || (rnext != 0 && rnext != 1) || pnext < 0 ||
+        tlen == LLONG_MIN)
+        return r;
+    r.mapped = strand >= 0;
+    r.reverse = strand == 1;
+    r.mate_named = rnext == 1;
+    r.name = b.d_names + name_lo;
+    r.name_len = static_cast<int>(name_hi - name_lo);
+    r.seq = b.d_reads + row * b.read_stride;
+    r.qual = b.d_quals ? b.d_quals + row * b.read_stride : nullptr;
+    r.read_len = read_len;
+    r.flag = static_cast<unsigned>(flag);
+    r.mapq = r.mapped ? static_cast<unsigned>(mapq) : 0u;
+    r.pnext = static_cast<unsigned long long>(pnext);
+    r.tlen_negative = tlen < 0;
+    r.tlen_abs = static_cast<unsigned long long>(tlen < 0 ? -tlen : tlen);
+    r.pos = r.mate_named ? r.pnext : 0ull;      // an unmapped end of a pair takes its mapped mate's RNAME and POS
+    if (r.mapped) {
+        const long long begin = uniform_i64(b.d_ref_begin[i]), end = uniform_i64(b.d_ref_end[i]);
+        const long long runs_row = uniform_i64(b.d_runs_row[i]);
+        const int n_ops = __builtin_amdgcn_readfirstlane(b.d_n_ops[i]), distance = b.d_distance[i];
+        if (n_ops < 0 || n_ops > b.cigar_cap || begin < 0 || end < begin || end > b.ref_len || distance < 0) return r;
+        if (runs_row < 0 || runs_row >= b.n_run_rows) return r;
+        r.runs = b.d_runs + runs_row * b.cigar_cap;
+        r.n_ops = n_ops;
+        r.ref = b.d_reference + begin;
+        r.distance = static_cast<unsigned>(distance);
+        r.pos = static_cast<unsigned long long>(begin) + 1ull;
+        const Walk w = walk_runs<false>(r.runs, n_ops, nullptr, nullptr, nullptr, threadIdx.x & (kLanes - 1));
+        if (!w.ok || w.ref_bases != end - begin || w.read_bases != read_len) return r;
+        r.cigar_bytes = w.cigar_bytes;
+        r.md_bytes = w.md_bytes;
+    }
+    r.ok = true;
+    return r;
+}
+
+// The line of a checked record: EMIT false returns its length, EMIT true writes it at out as well.
+template <bool EMIT>
+__device__ __forceinline__ long long record_line(const Batch &b, const Record &r, uint8_t *out, int lane)
+{
+    long long at = 0;
+    auto bytes = [&](const uint8_t *src, long long n) {      // n bytes of src, then a tab
+        if (EMIT) {
+            for (long long j = lane; j < n; j += kLanes) out[at + j] = src[j];
+            if (lane == 0) out[at + n] = '\t';
+        }
+        at += n + 1;
+    };
+    auto one = [&](char c, char close = '\t') {
+        if (EMIT && lane == 0) {
+            out[at] = static_cast<uint8_t>(c);
+            out[at + 1] = static_cast<uint8_t>(close);
+        }
+        at += 2;
+    };
+    auto number = [&](unsigned long long v, bool negative = false) {
+        if (negative) {
+            if (EMIT && lane == 0) out[at] = '-';
+            at += 1;
+        }
+        const int w = EMIT ? put_dec(out + at, v, lane) : dec_width(v);
+        if (EMIT && lane == 0) out[at + w] = '\t';
+        at += w + 1;
+    };
+    const bool named = r.mapped || r.mate_named;
+    bytes(r.name, r.name_len);
+    number(r.flag);
+    if (named) bytes(b.d_rname, b.rname_len); else one('*');
+    number(r.pos);
+    number(r.mapq);
+    const long long cigar_at = at;
+    if (r.mapped) {
+        if (EMIT && lane == 0) out[at + r.cigar_bytes] = '\t';
+        at += r.cigar_bytes + 1;
+    } else {
+        one('*');
+    }
+    one(r.mate_named ? '=' : '*');
+    number(r.pnext);
+    number(r.tlen_abs, r.tlen_negative && r.tlen_abs != 0);
+    if (EMIT) {
+        for (int j = lane; j < r.read_len; j += kLanes) {
+            uint8_t c = r.seq[r.reverse ? r.read_len - 1 - j : j];
+            if (r.reverse) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N';
+            out[at + j] = c;
+        }
+        if (lane == 0) out[at + r.read_len] = '\t';
+    }
+    at += r.read_len + 1;
+    if (r.qual) {
+        if (EMIT)
+            for (int j = lane; j < r.read_len; j += kLanes) out[at + j] = r.qual[r.reverse ? r.read_len - 1 - j : j];
+        at += r.read_len;
+    } else {
+        if (EMIT && lane == 0) out[at] = '*';
+        at += 1;
+    }
+    if (r.mapped) {
+        if (EMIT && lane < 6) out[at + lane] = static_cast<uint8_t>("\tNM:i:"[lane]);
+        at += 6;
+        at += EMIT ? put_dec(out + at, r.distance, lane) : dec_width32(r.distance);
+        if (EMIT && lane < 6) out[at + lane] = static_cast<uint8_t>("\tMD:Z:"[lane]);
+        at += 6;
+        if (EMIT) walk_runs<true>(r.runs, r.n_ops, r.ref, out + cigar_at, out + at, lane);
+        at += r.md_bytes;
+    }
+    if (EMIT && lane == 0) out[at] = '\n';
+    return at + 1;
+}
+
+__device__ __forceinline__ void count_malformed(int32_t *malformed, int lane)
+{
+    if (lane == 0) atomicAdd(malformed, 1);
+}
+
+__global__ __launch_bounds__(256) void sam_measure_kernel(Batch b, int64_t n, int64_t *__restrict__ lengths, int32_t *__restrict__ malformed)
+{
+    const int lane = threadIdx.x & (kLanes - 1);
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (i >= n) return;              // wave-uniform
+    const Record r = check_record(b, i);
+    long long bytes = 0;
+    if (r.ok) bytes = record_line<false>(b, r, nullptr, lane);
+    else count_malformed(malformed, lane);
+    if (lane == 0) lengths[i] = bytes;
+}
+
+__global__ __launch_bounds__(256) void sam_emit_kernel(Batch b, int64_t n, const int64_t *__restrict__ offsets, uint8_t *__restrict__ text,
+                                                       int64_t text_bytes, int32_t *__restrict__ malformed)
+{
+    const int lane = threadIdx.x & (kLanes - 1);
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (i >= n) return;              // wave-uniform
+    const Record r = check_record(b, i);
+    const long long lo = uniform_i64(offsets[i]), hi = uniform_i64(offsets[i + 1]);
+    // written only where the line is exactly what its offsets leave room for, inside the buffer
+    if (!r.ok || lo < 0 || hi < lo || hi > text_bytes || record_line<false>(b, r, nullptr, lane) != hi - lo) {
+        count_malformed(malformed, lane);
+        return;
+    }
+    record_line<true>(b, r, text + lo, lane);
+}
+
+// ---- MAPQ of a hit list ----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int mapq_of(long long d1, int n1, long long d2, bool has_d2, long long bound)
+{
+    if (n1 >= 2) return n1 == 2 ? 3 : n1 == 3 ? 2 : n1 <= 9 ? 1 : 0;
+    const long long gap = has_d2 ? d2 - d1 : bound >= 0 ? bound + 1 - d1 : 6;
+    return gap <= 0 ? 0 : gap >= 6 ? 60 : static_cast<int>(10 * gap);
+}
+
+__global__ __launch_bounds__(256) void sam_mapq_kernel(const int32_t *__restrict__ scores, const int32_t *__restrict__ keep, int64_t ns, int k,
+                                                       int bound, int32_t *__restrict__ primary_out, int32_t *__restrict__ mapq_out,
+                                                       int32_t *__restrict__ n1_out, int32_t *__restrict__ d2_out)
+{
+    const int lane = threadIdx.x & (kLanes - 1);
+    const int64_t read = static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (read >= ns) return;          // wave-uniform
+    const int64_t p = read * k + lane;
+    const bool kept = lane < k && keep[p] != 0;
+    const long long d = kept ? -static_cast<long long>(scores[p]) : 0;
+    const unsigned long long kept_mask = __ballot(kept);
+    int primary = -1, mapq = 0, n1 = 0;
+    long long d2 = -1;
+    if (kept_mask) {                 // wave-uniform
+        primary = __ffsll(kept_mask) - 1;
+        const long long d1 = __shfl(d, primary);
+        n1 = __popcll(__ballot(kept && d == d1));
+        long long above = kept && d > d1 ? d : LLONG_MAX;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const long long other = __shfl_xor(above, off);
+            above = other < above ? other : above;
+        }
+        const bool has_d2 = above != LLONG_MAX;
+        if (has_d2) d2 = above;
+        mapq = mapq_of(d1, n1, above, has_d2, bound);
+    }
+    if (lane == 0) {
+        primary_out[read] = primary;
+        mapq_out[read] = mapq;
+        n1_out[read] = n1;
+        d2_out[read] = static_cast<int32_t>(d2);
+    }
+}
+
+// ---- checks --------------------------------------------------------------------------------------------------------------------
+int check_batch(const char *who, const Batch *b, int64_t n)
+{
+    if (!b) return refuse(who, BGSA_HIP_EINVAL, "the batch is NULL");
+    if (n < 0 || n > static_cast<int64_t>(INT32_MAX) * kWavesPerBlock) return refuse(who, BGSA_HIP_EINVAL, "n is negative or beyond one launch");
+    if (!b->d_reads || !b->d_names || !b->d_name_offsets || !b->d_rname || !b->d_reference || !b->d_runs || !b->d_read_row || !b->d_name_of ||
+        !b->d_runs_row || !b->d_read_len || !b->d_strand || !b->d_ref_begin || !b->d_ref_end || !b->d_distance || !b->d_n_ops || !b->d_flag ||
+        !b->d_mapq || !b->d_rnext || !b->d_pnext || !b->d_tlen)
+        return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer in the batch (only d_quals may be NULL)");
+    if (b->read_stride < 1 || b->read_stride > static_cast<int64_t>(INT32_MAX) || b->n_read_rows < 1)
+        return refuse(who, BGSA_HIP_EINVAL, "read_stride must lie in [1, 2^31 - 1] and n_read_rows be positive");
+    if (b->n_names < 1 || b->names_bytes < 1) return refuse(who, BGSA_HIP_EINVAL, "n_names and names_bytes must be positive");
+    if (b->rname_len < 1) return refuse(who, BGSA_HIP_EINVAL, "rname_len is not positive");
+    if (b->ref_len < 1) return refuse(who, BGSA_HIP_EINVAL, "ref_len is not positive");
+    if (b->cigar_cap < 1 || b->n_run_rows < 1) return refuse(who, BGSA_HIP_EINVAL, "cigar_cap and n_run_rows must be positive");
+    return BGSA_HIP_OK;
+}
+
+}  // namespace
+
+}  // namespace bgsa
+
+using namespace bgsa;
+
+extern "C" {
+
+int bgsa_hip_sam_mapq_dev(const int32_t *d_scores, const int32_t *d_keep, int64_t ns, int k, int bound, int32_t *d_primary, int32_t *d_mapq,
+                          int32_t *d_n1, int32_t *d_d2, void *stream)
+{
+    const char *who = "sam_mapq_dev";
+    if (!d_scores || !d_keep || !d_primary || !d_mapq || !d_n1 || !d_d2) return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer (only the stream may be NULL)");
+    if (k < 1 || k > HIP_V_NUM) return refuse(who, BGSA_HIP_EINVAL, "k must lie in 1..64 (one wavefront holds a read's list, one slot per lane)");
+    if (bound < -1) return refuse(who, BGSA_HIP_EINVAL, "bound is below -1 (-1: the list is complete within no bound)");
+    if (ns < 0 || ns > static_cast<int64_t>(INT32_MAX) * kWavesPerBlock) return refuse(who, BGSA_HIP_EINVAL, "ns is negative or beyond one launch");
+    if (ns == 0) return BGSA_HIP_OK;
+    hipLaunchKernelGGL(sam_mapq_kernel, dim3(static_cast<unsigned>((ns + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kWavesPerBlock * kLanes), 0,
+                       static_cast<hipStream_t>(stream), d_scores, d_keep, ns, k, bound, d_primary, d_mapq, d_n1, d_d2);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+int bgsa_hip_sam_measure_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int64_t *d_lengths, int32_t *d_malformed, void *stream)
+{
+    const char *who = "sam_measure_dev";
+    if (int rc = check_batch(who, batch, n)) return rc;
+    if (!d_lengths || !d_malformed) return refuse(who, BGSA_HIP_EINVAL, "d_lengths or d_malformed is NULL");
+    if (n == 0) return BGSA_HIP_OK;
+    hipLaunchKernelGGL(sam_measure_kernel, dim3(static_cast<unsigned>((n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kWavesPerBlock * kLanes), 0,
+                       static_cast<hipStream_t>(stream), *batch, n, d_lengths, d_malformed);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+int bgsa_hip_sam_emit_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, const int64_t *d_offsets, uint8_t *d_text, int64_t text_bytes,
+                          int32_t *d_malformed, void *stream)
+{
+    const char *who = "sam_emit_dev";
+    if (int rc = check_batch(who, batch, n)) return rc;
+    if (!d_offsets || !d_text || !d_malformed) return refuse(who, BGSA_HIP_EINVAL, "d_offsets, d_text or d_malformed is NULL");
+    if (text_bytes < 0) return refuse(who, BGSA_HIP_EINVAL, "text_bytes is negative");
+    if (n == 0) return BGSA_HIP_OK;
+    hipLaunchKernelGGL(sam_emit_kernel, dim3(static_cast<unsigned>((n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kWavesPerBlock * kLanes), 0,
+                       static_cast<hipStream_t>(stream), *batch, n, d_offsets, d_text, text_bytes, d_malformed);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+}  // extern "C"

@@ -99,9 +99,10 @@ def seed_plan_ragged(lens, max_distance: int, seed_len=None) -> list:
 
 def blank_beyond(hits: "ReferenceHits", bound: int) -> "ReferenceHits":
     """map_reads' result with every slot whose distance exceeds `bound` (and every unused slot) blanked: scores INT32_MIN, windows,
-    strand, ref_begin and ref_end -1, keep 0, cigar None.  This is what map_reads_seeded returns, bit for bit."""
+    strand, ref_begin and ref_end -1, keep 0, cigar None.  This is what map_reads_seeded returns, bit for bit.  (A result without
+    strings — cigars None, the SAM path's — stays without.)"""
     gone = (hits.windows < 0) | (-hits.scores.astype(np.int64) > int(bound))
-    cigars = [[None if gone[c, r] else text for r, text in enumerate(row)] for c, row in enumerate(hits.cigars)]
+    cigars = None if hits.cigars is None else [[None if gone[c, r] else text for r, text in enumerate(row)] for c, row in enumerate(hits.cigars)]
     return ReferenceHits(np.where(gone, INT32_MIN, hits.scores).astype(np.int32), np.where(gone, -1, hits.strand).astype(np.int32),
                          np.where(gone, -1, hits.ref_begin).astype(np.int64), np.where(gone, -1, hits.ref_end).astype(np.int64),
                          np.where(gone, 0, hits.keep).astype(np.int32), cigars, np.where(gone, -1, hits.windows).astype(np.int32))
@@ -260,6 +261,13 @@ def hit_arrays(hits: ReferenceHits) -> tuple:
     return hits[:5] + (hits.windows,)
 
 
+def blank_hits(ns: int, k: int, cigars) -> ReferenceHits:
+    """A result of ns reads whose every slot is unused: scores INT32_MIN, windows, strand and the interval -1, keep 0."""
+    blank = np.full((ns, k), -1, dtype=np.int32)
+    return ReferenceHits(np.full((ns, k), INT32_MIN, dtype=np.int32), blank, np.full((ns, k), -1, dtype=np.int64),
+                         np.full((ns, k), -1, dtype=np.int64), np.zeros((ns, k), dtype=np.int32), cigars, blank.copy())
+
+
 def decode_cigars(who: str, keep, n_ops, runs, cap: int, idx, cigars: list) -> None:
     """The edit scripts of one bin into the caller's order: keep and n_ops [n, k_sel], runs [n, k_sel, cap] uint32 (length << 4 | op)
     are the host copies of what place_hits returns for the bin, idx[c] is where the bin's read c stands in the caller's order.
@@ -296,6 +304,112 @@ def seed_stats(flags, totals, seed_len, max_candidates: int, bins=None) -> dict:
     if bins is not None:
         stats["bins"] = bins
     return stats
+
+
+# ---- SAM records: include/bgsa_hip.h "SAM records" — the host side, no device, no library ---------------------------------------
+class SamRecords(NamedTuple):
+    """What ReferenceMapper.map_reads_sam and map_pairs_sam return: the records' text as the device wrote it, and four columns."""
+    text: np.ndarray        # uint8: the records, one line each, without a header
+    offsets: np.ndarray     # int64[n + 1]: record i is text[offsets[i] : offsets[i + 1]]
+    flag: np.ndarray        # int32[n]
+    pos: np.ndarray         # int64[n]: POS, 1-based; 0 for an unmapped record without a mapped mate
+    mapq: np.ndarray        # int32[n]
+    nm: np.ndarray          # int32[n]: the distance, -1 for an unmapped record
+
+
+def list_mapq(d1: int, n1: int, d2, bound: int) -> int:
+    """The MAPQ of a hit list whose primary slot has distance d1 and n1 kept slots at that distance, d2 the smallest kept distance
+    above d1 (None or -1: none), bound the distance the list is complete within (-1: none).  The header's heuristic, in integers."""
+    if n1 >= 2:
+        return 3 if n1 == 2 else 2 if n1 == 3 else 1 if n1 <= 9 else 0
+    gap = d2 - d1 if d2 is not None and d2 >= 0 else bound + 1 - d1 if bound >= 0 else 6
+    return max(0, min(60, 10 * gap))
+
+
+def pair_mapq(torch, proper, n_best, cost, next_cost, alone1, alone2) -> tuple:
+    """The two ends' MAPQ from pair_select's outputs and the ends' list MAPQs (alone_e), elementwise on tensors: a proper pair gets
+    the table value of n_best >= 2, else min(60, 10 * (next_cost - cost)), 60 without a next cost; an end of a pair that is not
+    proper keeps its own."""
+    table = 3 - (n_best >= 3).to(torch.int32) - (n_best >= 4).to(torch.int32) - (n_best >= 10).to(torch.int32)
+    gap = (10 * (next_cost - cost)).clamp(min=0, max=60).masked_fill(next_cost < 0, 60)
+    both = torch.where(n_best >= 2, table, gap.to(torch.int32))
+    return torch.where(proper != 0, both, alone1), torch.where(proper != 0, both, alone2)
+
+
+def _field_bytes(who: str, what: str, text) -> np.ndarray:
+    """A name as uint8, refused where it is empty or holds a byte outside '!'..'~'."""
+    if isinstance(text, str):
+        text = text.encode("ascii", "replace")
+    name = np.array(bytearray(text), dtype=np.uint8)
+    if name.size == 0:
+        raise B.BgsaHipError(f"{who}: rc=-1: {what} is empty")
+    if ((name < 33) | (name > 126)).any():
+        raise B.BgsaHipError(f"{who}: rc=-1: {what} holds a tab, a space, a newline or another byte outside '!'..'~'")
+    return name
+
+
+def check_sam_call(who: str, lens, names, quals, reference_name) -> tuple:
+    """Every refusal the SAM entry point `who` adds to the mapping call's own, before anything is launched: reference_name and every
+    name non-empty and of bytes '!'..'~' (no tab, space or newline), as many names as reads, as many QUAL strings as reads, each as
+    long as its read and of bytes '!'..'~'.  lens[c] is read c's length; names a sequence of str or bytes, None: r0, r1, ...; quals
+    a [ns, n] uint8 array or a sequence of byte strings, None: no QUAL.  Returns (reference_name uint8, the names as one flat uint8
+    array, its int64[ns + 1] offsets, the QUAL rows uint8[ns, max(lens)] or None).  Array operations only: no loop over the reads."""
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    ns = int(lens.size)
+    rname = _field_bytes(who, "reference_name", reference_name)
+    if names is None:
+        names = np.char.add("r", np.arange(ns).astype(str))
+    try:
+        texts = np.asarray(names)
+        if texts.dtype.kind == "U":
+            texts = np.char.encode(texts, "ascii")
+    except (UnicodeError, ValueError) as exc:
+        raise B.BgsaHipError(f"{who}: rc=-1: names must be ASCII strings or byte strings ({exc})") from None
+    if texts.dtype.kind != "S" or texts.ndim != 1:
+        raise B.BgsaHipError(f"{who}: rc=-1: names must be a sequence of ASCII strings or byte strings")
+    if texts.shape[0] != ns:
+        raise B.BgsaHipError(f"{who}: rc=-1: {texts.shape[0]} names for {ns} reads")
+    name_lens = np.char.str_len(texts).astype(np.int64)
+    if (name_lens == 0).any():
+        raise B.BgsaHipError(f"{who}: rc=-1: the name of read {int(np.flatnonzero(name_lens == 0)[0])} is empty")
+    letters = np.ascontiguousarray(texts).view(np.uint8).reshape(ns, -1)
+    flat = letters[np.arange(letters.shape[1]) < name_lens[:, None]]
+    bad = (flat < 33) | (flat > 126)
+    if bad.any():
+        at = int(np.repeat(np.arange(ns), name_lens)[bad][0])
+        raise B.BgsaHipError(f"{who}: rc=-1: the name of read {at} holds a tab, a space, a newline or another byte outside '!'..'~'")
+    offsets = np.zeros(ns + 1, dtype=np.int64)
+    np.cumsum(name_lens, out=offsets[1:])
+    rows = None
+    if quals is not None:
+        if isinstance(quals, np.ndarray) and quals.ndim == 2:
+            rows = np.ascontiguousarray(quals, dtype=np.uint8)
+            qual_lens = np.full(rows.shape[0], rows.shape[1], dtype=np.int64)
+        else:
+            if len(quals) != ns:
+                raise B.BgsaHipError(f"{who}: rc=-1: {len(quals)} QUAL strings for {ns} reads")
+            try:
+                rows, qual_lens = B.pad_ragged(quals)
+            except B.BgsaHipError as exc:
+                raise B.BgsaHipError(f"{who}: rc=-1: quals: {exc}") from None
+        if rows.shape[0] != ns:
+            raise B.BgsaHipError(f"{who}: rc=-1: {rows.shape[0]} QUAL strings for {ns} reads")
+        wrong = np.flatnonzero(np.asarray(qual_lens, dtype=np.int64) != lens)
+        if wrong.size:
+            c = int(wrong[0])
+            raise B.BgsaHipError(f"{who}: rc=-1: the QUAL of read {c} has {int(qual_lens[c])} bytes, the read {int(lens[c])}")
+        own = np.arange(rows.shape[1]) < lens[:, None]
+        bad = own & ((rows < 33) | (rows > 126))
+        if bad.any():
+            raise B.BgsaHipError(f"{who}: rc=-1: the QUAL of read {int(np.flatnonzero(bad.any(axis=1))[0])} holds a byte outside '!'..'~'")
+    return rname, flat, offsets, rows
+
+
+def write_sam(path, header: bytes, records: SamRecords) -> None:
+    """The header (ReferenceMapper.sam_header) and the records' text into the file `path`."""
+    with open(path, "wb") as out:
+        out.write(header)
+        out.write(memoryview(np.ascontiguousarray(records.text)))
 
 
 class SeedBucket(NamedTuple):
@@ -443,13 +557,14 @@ class ReferenceMapper:
             raise B.BgsaHipError(f"{who}: rc=-1: reads must be [ns, n] with ns, n >= 1 (one read length per call)")
         return reads
 
-    def _map_bucket(self, rows: np.ndarray, lens, k_sel: int, limit, cap: int, block_rows: int, seed=None) -> tuple:
+    def _map_bucket(self, rows: np.ndarray, lens, k_sel: int, limit, cap: int, block_rows: int, seed=None, on_device: bool = False) -> tuple:
         """One bucket through the pipeline: rows [n, width] ASCII and lens (the reads' own lengths, or None where all are width
         long) are uploaded (DeviceAligner._set_bucket), the k_sel best windows of every read selected — seed None: select_windows
         over every window; seed (q, max_candidates): select_seeded within min(limit, width) —, placed within limit (place_hits, per
         read where lens is given) and the stream checked for faults.  limit None (exhaustive only): no bound where lens is given,
         else the worst selected distance, one scalar read back.  Returns host arrays: (the six of hit_arrays, n_ops, runs as uint32,
-        the reads' seed flags, (emitted, unique, within the bound)); the last two None without a seed."""
+        the reads' seed flags, (emitted, unique, within the bound)); the last two None without a seed.  on_device (the SAM entry points):
+        the six, n_ops and the runs stay device tensors, the runs int32 [n, k_sel, cap]; only the flags and the totals are copied."""
         a = self.aligner
         torch = a.torch
         d_rows, d_lens = a._set_bucket(rows, lens, qlen=self.window_len, reads_ragged=lens is not None)
@@ -466,20 +581,21 @@ class ReferenceMapper:
         a.check_faults()
         if seed is not None:
             flags, totals = counts.cpu().numpy(), tuple(int(x.item()) for x in stats)
+        if on_device:
+            return (scores, strand, ref_begin, ref_end, keep, ids), n_ops, cigar, flags, totals
         arrays = tuple(x.cpu().numpy() for x in (scores, strand, ref_begin, ref_end, keep, ids))
         return arrays, n_ops.cpu().numpy(), cigar.cpu().numpy().view(np.uint32), flags, totals
 
     def _map_bins(self, who: str, rows: np.ndarray, lens: np.ndarray, plan, k_sel: int, limit, cap: int, block_rows: int,
-                  max_candidates=None) -> tuple:
+                  max_candidates=None, sink=None) -> tuple:
         """The bins of `plan` — [(indices into rows, seed length or None for the exhaustive path)] —, each as one bucket of its own
         width through _map_bucket, scattered into the caller's order.  A bin of one length goes without lengths and launches the
         equal-length kernels; a seeded one too short for its seed and the bound is flagged -3 here, without a call.  Returns
-        (hits, flags[ns], [emitted, unique, within], bins: one dict per bin for last_seed_stats)."""
+        (hits, flags[ns], [emitted, unique, within], bins: one dict per bin for last_seed_stats).
+        sink (the SAM entry points): every bucket's DEVICE tensors go to sink.add(idx, the six, n_ops, runs) instead — nothing but
+        the flags is copied, no string is made, and hits is None."""
         ns = rows.shape[0]
-        blank = np.full((ns, k_sel), -1, dtype=np.int32)
-        out = ReferenceHits(np.full((ns, k_sel), INT32_MIN, dtype=np.int32), blank, np.full((ns, k_sel), -1, dtype=np.int64),
-                            np.full((ns, k_sel), -1, dtype=np.int64), np.zeros((ns, k_sel), dtype=np.int32),
-                            [[None] * k_sel for _ in range(ns)], blank.copy())
+        out = None if sink is not None else blank_hits(ns, k_sel, [[None] * k_sel for _ in range(ns)])
         flags, totals, bins = np.zeros(ns, dtype=np.int32), [0, 0, 0], []
         for idx, q in plan:
             mine = lens[idx]
@@ -490,10 +606,13 @@ class ReferenceMapper:
                 continue
             bucket = rows[:, :width] if idx.size == ns else rows[idx, :width]      # one bin of all reads: no copy
             arrays, n_ops, runs, seen, stats = self._map_bucket(bucket, mine if mixed else None, k_sel, limit, cap, block_rows,
-                                                                None if q is None else (q, max_candidates))
-            for field, theirs in zip(hit_arrays(out), arrays):
-                field[idx] = theirs
-            decode_cigars(who, arrays[4], n_ops, runs, cap, idx, out.cigars)
+                                                                None if q is None else (q, max_candidates), on_device=sink is not None)
+            if sink is not None:
+                sink.add(idx, arrays, n_ops, runs)
+            else:
+                for field, theirs in zip(hit_arrays(out), arrays):
+                    field[idx] = theirs
+                decode_cigars(who, arrays[4], n_ops, runs, cap, idx, out.cigars)
             if q is not None:
                 flags[idx] = seen
                 bins[-1].update(emitted=stats[0], unique=stats[1])
@@ -771,6 +890,13 @@ class ReferenceMapper:
         n_anchors = (anchors[3] != 0).sum(dim=1).clamp(max=k_best).sum()
         return (scores, strand, ref_begin, ref_end, keep, ids, rescued), n_ops, cigar, (n_anchors, emitted, verified, rescued.sum())
 
+    def _rescue_checked(self, e: int, reads, single, call: dict, insert_max: int, block_rows: int):
+        """rescue_end for end e of map_pairs' call (check_pair_call's dict), and the stream checked for faults."""
+        out = self.rescue_end(reads[e], single[e], single[1 - e], call["k_best"], call["k_pair"], int(insert_max), call["bounds"][e],
+                              call["caps"][e], block_rows)
+        self.aligner.check_faults()
+        return out
+
     def pair_select(self, one, two, insert_min: int, insert_max: int, block_rows: int = 1000):
         """Stage C: the best proper combination of every pair.  one, two = (scores, strand, ref_begin, ref_end, keep) of the two
         ends' final lists, device tensors [ns, k].  Returns device tensors (proper, slot1, slot2, insert int64, cost, n_best,
@@ -820,9 +946,7 @@ class ReferenceMapper:
                 single.append(blank_beyond(self.map_reads(rows, k_best, limit, block_rows, cigar_cap), min(limit, rows.shape[1])))
         ends, lists, counts = [], [], []
         for e, rows in enumerate(reads):      # stage B: end e's bucket resident, its mate's lists as anchors
-            final, n_ops, cigar, seen = self.rescue_end(rows, single[e], single[1 - e], k_best, k_pair, int(insert_max), call["bounds"][e],
-                                                        call["caps"][e], block_rows)
-            a.check_faults()
+            final, n_ops, cigar, seen = self._rescue_checked(e, reads, single, call, insert_max, block_rows)
             arrays = tuple(x.cpu().numpy() for x in final)
             cigars = [[None] * k_pair for _ in range(rows.shape[0])]
             decode_cigars(who, arrays[4], n_ops.cpu().numpy(), cigar.cpu().numpy().view(np.uint32), call["caps"][e], np.arange(rows.shape[0]),
@@ -864,3 +988,280 @@ class ReferenceMapper:
             out.append([Placement(int(hits.strand[c, r]), int(hits.ref_begin[c, r]), int(hits.ref_end[c, r]), -int(hits.scores[c, r]),
                                   hits.cigars[c][r]) for r in rows])
         return out
+
+    # ---- SAM records: include/bgsa_hip.h "SAM records" ----------------------------------------------------------------------
+    # The mapping pipeline above with a sink in place of the host copies, then on device tensors only: sam_list_mapq, the primary
+    # slots gathered (PrimarySink / sam_primaries), sam_records (measure -> scan -> emit -> one copy of the text).
+    # scripts/measure_sam.py times these same methods.
+    def sam_header(self, reference_name="ref") -> bytes:
+        """The three header lines of this mapper's one reference: @HD (unsorted), @SQ with its name and length, @PG."""
+        name = _field_bytes("sam_header", "reference_name", reference_name).tobytes()
+        return b"@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:" + name + b"\tLN:" + str(self.ref_len).encode() + b"\n@PG\tID:bgsa-hip\n"
+
+    def sam_list_mapq(self, scores, keep, bound: int) -> tuple:
+        """bgsa_hip_sam_mapq_dev on device tensors scores, keep [ns, k]: (primary slot, mapq, n1, d2), int32[ns] each."""
+        a = self.aligner
+        torch = a.torch
+        scores, keep = scores.contiguous(), keep.contiguous()
+        ns, k = scores.shape
+        out = tuple(torch.empty(ns, dtype=torch.int32, device=a.device) for _ in range(4))
+        B.check(B.lib().bgsa_hip_sam_mapq_dev(scores.data_ptr(), keep.data_ptr(), ns, k, int(bound), *(x.data_ptr() for x in out), a._stream()),
+                "sam_mapq_dev")
+        return out
+
+    @staticmethod
+    def sam_primaries(torch, slot, arrays, n_ops, cigar) -> tuple:
+        """The fields of slot[c] of every read's list, gathered on the device: (strand, ref_begin, ref_end, distance, n_ops,
+        runs[ns, cap]); slot -1: strand -1, the rest of no meaning."""
+        scores, strand, ref_begin, ref_end = arrays[:4]
+        at = slot.clamp(min=0).to(torch.int64).unsqueeze(1)
+
+        def pick(x):
+            return x.gather(1, at).squeeze(1)
+        runs = cigar.gather(1, at.unsqueeze(2).expand(-1, 1, cigar.shape[2])).squeeze(1)
+        return pick(strand).masked_fill(slot < 0, -1), pick(ref_begin), pick(ref_end), -pick(scores), pick(n_ops), runs
+
+    def sam_records(self, who: str, reads: np.ndarray, quals, names, name_offsets, rname, fields: dict, runs, read_label=None) -> SamRecords:
+        """The two record passes.  reads [n_rows, stride] and quals (or None) are the host rows, names / name_offsets / rname what
+        check_sam_call returned; fields holds the per-record DEVICE tensors read_row, name_of (int64), read_len, strand, ref_begin,
+        ref_end, distance, n_ops, flag, mapq, rnext, pnext, tlen; runs [n, cap] int32 holds record i's runs in row i.  Measure, an
+        exclusive scan of the lengths with its one scalar read back — it sizes the text —, emit, the text copied once.  A malformed
+        record raises; read_label(i) names record i's read in the message."""
+        a, L = self.aligner, B.lib()
+        torch, dev = a.torch, a.device
+        n = int(fields["strand"].shape[0])
+
+        def up(x):
+            x = np.ascontiguousarray(x)
+            return torch.from_numpy(x if x.flags.writeable else x.copy()).to(dev)
+        d_reads, d_quals = up(reads), None if quals is None else up(quals)
+        d_names, d_name_offsets, d_rname = up(names), up(name_offsets), up(rname)
+        f = {key: value.contiguous() for key, value in fields.items()}
+        runs = runs.contiguous()
+        runs_row = torch.arange(n, dtype=torch.int64, device=dev)
+        batch = B.SamBatch(d_reads.data_ptr(), None if d_quals is None else d_quals.data_ptr(), reads.shape[1], reads.shape[0],
+                           d_names.data_ptr(), d_name_offsets.data_ptr(), name_offsets.size - 1, names.size, d_rname.data_ptr(), rname.size,
+                           self.d_reference.data_ptr(), self.ref_len, runs.data_ptr(), runs.shape[0], runs.shape[1],
+                           f["read_row"].data_ptr(), f["name_of"].data_ptr(), runs_row.data_ptr(), f["read_len"].data_ptr(),
+                           f["strand"].data_ptr(), f["ref_begin"].data_ptr(), f["ref_end"].data_ptr(), f["distance"].data_ptr(),
+                           f["n_ops"].data_ptr(), f["flag"].data_ptr(), f["mapq"].data_ptr(), f["rnext"].data_ptr(), f["pnext"].data_ptr(),
+                           f["tlen"].data_ptr())
+        malformed = torch.zeros(2, dtype=torch.int32, device=dev)
+        lengths = torch.empty(n, dtype=torch.int64, device=dev)
+        B.check(L.bgsa_hip_sam_measure_dev(batch, n, lengths.data_ptr(), malformed[0:].data_ptr(), a._stream()), "sam_measure_dev")
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        offsets[1:] = torch.cumsum(lengths, 0)
+        total = int(offsets[-1].item())                 # the one scalar read back: it sizes the text
+        if int(malformed[0].item()):
+            mapped = f["strand"] >= 0
+            over = torch.nonzero(mapped & (f["n_ops"] > runs.shape[1])).reshape(-1)
+            label = read_label if read_label is not None else (lambda i: f"read {i}")
+            if over.numel():
+                i = int(over[0].item())
+                raise B.BgsaHipError(f"{who}: the hit of {label(i)} has {int(f['n_ops'][i].item())} runs, its row holds {runs.shape[1]} "
+                                     f"(raise cigar_cap)")
+            i = int(torch.nonzero(lengths == 0).reshape(-1)[0].item())
+            raise B.BgsaHipError(f"{who}: {int(malformed[0].item())} malformed records, the first the one of {label(i)}: an interval outside "
+                                 f"the reference, or runs that do not add up to it and to the read")
+        text = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        B.check(L.bgsa_hip_sam_emit_dev(batch, n, offsets.data_ptr(), text.data_ptr(), total, malformed[1:].data_ptr(), a._stream()),
+                "sam_emit_dev")
+        if int(malformed[1].item()):
+            raise B.BgsaHipError(f"{who}: the emit pass refused {int(malformed[1].item())} records the measure pass accepted")
+        mapped = f["strand"] >= 0
+        pos = torch.where(mapped, f["ref_begin"] + 1, f["pnext"] * f["rnext"])
+        nm = f["distance"].masked_fill(~mapped, -1)
+        mapq = f["mapq"].masked_fill(~mapped, 0)
+        return SamRecords(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(), mapq.cpu().numpy(),
+                          nm.cpu().numpy())
+
+    def _sam_rows(self, who: str, reads) -> tuple:
+        """(rows, lens, ragged) of a SAM call's reads: a [ns, n] array as it is, anything else as a list of mixed lengths."""
+        if isinstance(reads, np.ndarray) and reads.ndim == 2:
+            rows = self._one_length(who, reads)
+            return rows, np.full(rows.shape[0], rows.shape[1], dtype=np.int32), False
+        return (*B.pad_ragged(reads), True)
+
+    def _map_to(self, sink, rows: np.ndarray, lens: np.ndarray, ragged: bool, k_best, max_distance, seeded: bool, seed_len, max_candidates,
+                block_rows: int, cigar_cap):
+        """The pipeline of the four map_reads entry points — the one `ragged` and `seeded` name, with its refusals, its bins and its
+        exhaustive pass over the reads the seed filter does not cover — with every bucket's device tensors handed to a sink and
+        nothing decoded.  sink(ns, k_sel, cap) makes it once the call is accepted; it is returned."""
+        who = "map_reads" + ("_seeded" if seeded else "") + ("_ragged" if ragged else "")
+        ns, n = rows.shape
+
+        def exhaustive(of_lens):
+            return [(idx, None) for idx in B.bin_by_words(of_lens)] if ragged else [(np.arange(of_lens.size), None)]
+        if seeded:
+            plan_of = (lambda limit: seed_plan_ragged(lens, limit, seed_len)) if ragged else \
+                (lambda limit: [(np.arange(ns), seed_plan(n, limit, seed_len)[2])])
+            k_best, bound, cap, max_candidates, plan = self._check(who, n, ragged, k_best, max_distance, cigar_cap, True, max_candidates, plan_of)
+            limit = int(max_distance) if ragged else bound
+        else:
+            k_best, bound, cap, _, _ = self._check(who, n, ragged, k_best, max_distance, cigar_cap)
+            limit, plan = None if max_distance is None else int(max_distance), exhaustive(lens)
+        k_sel = self.k_selected(k_best)
+        sink = sink(ns, k_sel, cap)
+        _, flags, totals, bins = self._map_bins(who, rows, lens, plan, k_sel, limit, cap, block_rows, max_candidates, sink=sink)
+        if seeded:
+            self.last_seed_stats = seed_stats(flags, totals, plan[0][1] if not ragged else None if seed_len is None else int(seed_len),
+                                              max_candidates, bins if ragged else None)
+            rest = np.flatnonzero(flags < 0)
+            if rest.size:       # what _map_uncovered does: the exhaustive pass of the same kind, blanked beyond the bound
+                self._map_bins(who.replace("_seeded", ""), rows[rest], lens[rest], exhaustive(lens[rest]), k_sel, int(max_distance), cap,
+                               block_rows, sink=BeyondSink(self.aligner.torch, sink, rest, limit))
+        return sink
+
+    def map_reads_sam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
+                      seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None) -> SamRecords:
+        """Single-end reads to SAM records, formatted on the device (include/bgsa_hip.h "SAM records").  reads: a [ns, n] uint8 array
+        or a list of byte strings of mixed lengths; the mapping is that of the matching entry point of the four — map_reads_seeded
+        (seeded=True: max_distance is required), map_reads, or their _ragged forms — with its refusals.  Every read gives ONE record,
+        its first kept hit (flag 0 or 16) or an unmapped record (flag 4): no secondary lines.  MAPQ is the list heuristic: at bound
+        max_distance for a seeded call, whose filter makes the list complete within it, at -1 (no bound) for an exhaustive one, whose
+        list is its best windows whatever their distance; a second locus is only sure to be listed with k_best >= 2, hence the default.  names=None: r0,
+        r1, ...; quals=None: '*'.  check_sam_call refuses before anything is launched.  Nothing but the text, its offsets and four
+        columns is copied back; no CIGAR string is made on the host."""
+        who = "map_reads_sam"
+        rows, lens, ragged = self._sam_rows(who, reads)
+        rname, flat, name_offsets, qual_rows = check_sam_call(who, lens, names, quals, reference_name)
+        bound = int(max_distance) if seeded and max_distance is not None else -1
+        sink = self._map_to(lambda ns, k_sel, cap: PrimarySink(self, ns, cap, bound), rows, lens, ragged, k_best, max_distance, seeded, seed_len,
+                            max_candidates, block_rows, cigar_cap)
+        self.aligner.check_faults()
+        return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname)
+
+    def sam_single_records(self, who: str, sink: "PrimarySink", rows: np.ndarray, lens, qual_rows, names, name_offsets, rname) -> SamRecords:
+        """The records of single-end reads from their primaries on the device: flag 0, 16 or 4, no mate fields."""
+        torch, dev = self.aligner.torch, self.aligner.device
+        ns = rows.shape[0]
+        index = torch.arange(ns, dtype=torch.int64, device=dev)
+        zero = torch.zeros(ns, dtype=torch.int64, device=dev)
+        flag = (4 * (sink.strand < 0) + 16 * (sink.strand == 1)).to(torch.int32)
+        fields = dict(read_row=index, name_of=index, read_len=torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev),
+                      strand=sink.strand, ref_begin=sink.ref_begin, ref_end=sink.ref_end, distance=sink.distance, n_ops=sink.n_ops,
+                      flag=flag, mapq=sink.mapq, rnext=torch.zeros(ns, dtype=torch.int32, device=dev), pnext=zero, tlen=zero)
+        return self.sam_records(who, rows, qual_rows, names, name_offsets, rname, fields, sink.runs)
+
+    def map_pairs_sam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
+                      reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
+                      max_candidates=None, block_rows: int = 1000, cigar_cap=None) -> SamRecords:
+        """map_pairs to SAM records, formatted on the device: two records per pair, end 1 then end 2, each the slot pair_select chose
+        (a proper pair: flag 2) or the end's first kept hit, else unmapped.  Flags 1, 2, 4, 8, 16, 32, 64 / 128; RNEXT '=' and PNEXT
+        where the mate is mapped; TLEN where both are; an unmapped end beside a mapped mate takes the mate's RNAME and POS.  MAPQ:
+        pair_mapq.  One name per pair.  The stages are map_pairs' own (stage A through the same pipeline, without its strings);
+        last_pair_stats is not touched.  check_sam_call and check_pair_call refuse before anything is launched."""
+        who = "map_pairs_sam"
+        reads = (self._one_length(who, reads1), self._one_length(who, reads2))
+        ns = reads[0].shape[0]
+        if (quals1 is None) != (quals2 is None):
+            raise B.BgsaHipError(f"{who}: rc=-1: quals1 and quals2 come together")
+        checked = [check_sam_call(who, np.full(ns, rows.shape[1]), names, quals, reference_name) for rows, quals in zip(reads, (quals1, quals2))]
+        call = check_pair_call(self.both_strands, reads[0].shape, reads[1].shape, insert_min, insert_max, k_best, max_distance,
+                               rescue_distance, seeded, seed_len, max_candidates, cigar_cap, self.window_len, self.stride, self.ref_len,
+                               self.n_ids)
+        a = self.aligner
+        single = []
+        for rows in reads:      # stage A, the lists copied as map_pairs' stage B takes them, no script decoded
+            sink = self._map_to(lambda n, k_sel, cap: ListSink(n, k_sel), rows, np.full(ns, rows.shape[1], dtype=np.int32), False, call["k_best"],
+                                int(max_distance), seeded, seed_len, max_candidates, block_rows, cigar_cap)
+            single.append(sink.hits if seeded else blank_beyond(sink.hits, min(int(max_distance), rows.shape[1])))
+        ends = [self._rescue_checked(e, reads, single, call, insert_max, block_rows) for e in range(2)]      # stage B
+        chosen = self.pair_select(ends[0][0][:5], ends[1][0][:5], insert_min, insert_max, block_rows)      # stage C
+        a.check_faults()
+        return self.sam_pair_records(who, reads, ends, chosen, call, checked)
+
+    def sam_pair_records(self, who: str, reads, ends, chosen, call: dict, checked) -> SamRecords:
+        """The records of pairs from the device results of map_pairs' stages: ends[e] = rescue_end's return for end e, chosen =
+        pair_select's, call = check_pair_call's dict, checked[e] = check_sam_call's return for end e."""
+        torch, dev = self.aligner.torch, self.aligner.device
+        ns = reads[0].shape[0]
+        lists = [final for final, _, _, _ in ends]
+        proper, slot1, slot2, _, cost, n_best, next_cost = chosen
+        alone = [self.sam_list_mapq(final[0], final[4], call["bounds"][e])[1] for e, final in enumerate(lists)]
+        mapq = pair_mapq(torch, proper, n_best, cost, next_cost, *alone)
+        cap = max(call["caps"])
+        picked = []
+        for (final, n_ops, cigar, _), slot in zip(ends, (slot1, slot2)):
+            strand, begin, end, distance, ops, runs = self.sam_primaries(torch, slot, final, n_ops, cigar)
+            picked.append((strand, begin, end, distance, ops, torch.nn.functional.pad(runs, (0, cap - runs.shape[1]))))
+        mapped = [x[0] >= 0 for x in picked]
+        pos = [torch.where(m, x[1] + 1, torch.zeros_like(x[1])) for m, x in zip(mapped, picked)]
+        both = mapped[0] & mapped[1]
+        span = torch.maximum(picked[0][2], picked[1][2]) - torch.minimum(picked[0][1], picked[1][1])
+        first_left = picked[0][1] <= picked[1][1]
+        tlen1 = torch.where(both, torch.where(first_left, span, -span), torch.zeros_like(span))
+
+        def interleave(one, two):
+            return torch.stack((one, two), dim=1).reshape(-1, *one.shape[1:]).contiguous()
+        flags = [(1 + 2 * (proper != 0) + 4 * ~mapped[e] + 8 * ~mapped[1 - e] + 16 * (picked[e][0] == 1) + 32 * (picked[1 - e][0] == 1) +
+                  (64, 128)[e]).to(torch.int32) for e in range(2)]
+        stride = max(reads[0].shape[1], reads[1].shape[1])
+        rows = np.full((ns, 2, stride), ord("N"), dtype=np.uint8)
+        qual_rows = None if checked[0][3] is None else np.full((ns, 2, stride), ord("!"), dtype=np.uint8)
+        for e in range(2):
+            rows[:, e, : reads[e].shape[1]] = reads[e]
+            if qual_rows is not None:
+                qual_rows[:, e, : reads[e].shape[1]] = checked[e][3]
+        index = torch.arange(2 * ns, dtype=torch.int64, device=dev)
+        read_len = torch.tensor([reads[0].shape[1], reads[1].shape[1]], dtype=torch.int32, device=dev).repeat(ns)
+        fields = dict(read_row=index, name_of=index // 2, read_len=read_len, flag=interleave(*flags), mapq=interleave(*mapq),
+                      rnext=interleave(mapped[1].to(torch.int32), mapped[0].to(torch.int32)), pnext=interleave(pos[1], pos[0]),
+                      tlen=interleave(tlen1, -tlen1),
+                      **{key: interleave(picked[0][i], picked[1][i]) for i, key in enumerate(("strand", "ref_begin", "ref_end", "distance", "n_ops"))})
+        rname, flat, name_offsets, _ = checked[0]
+        return self.sam_records(who, rows.reshape(2 * ns, stride), None if qual_rows is None else qual_rows.reshape(2 * ns, stride), flat,
+                                name_offsets, rname, fields, interleave(picked[0][5], picked[1][5]),
+                                read_label=lambda i: f"end {i % 2 + 1} of pair {i // 2}")
+
+
+# ---- the sinks of ReferenceMapper._map_bins: what the SAM entry points keep of a bucket's device tensors ---------------------------
+class ListSink:
+    """The six arrays of every bucket copied into one host result in the caller's order, cigars None: map_pairs' stage A lists."""
+
+    def __init__(self, ns: int, k_sel: int):
+        self.hits = blank_hits(ns, k_sel, None)
+
+    def add(self, idx, arrays, n_ops, cigar) -> None:
+        for field, theirs in zip(hit_arrays(self.hits), arrays):
+            field[idx] = theirs.cpu().numpy()
+
+
+class PrimarySink:
+    """Per read, on the device: the primary slot of its list (bgsa_hip_sam_mapq_dev at `bound`), its MAPQ, and that slot's strand,
+    interval, distance, n_ops and runs, gathered bucket by bucket into the caller's order.  Nothing is copied to the host."""
+
+    def __init__(self, mapper: "ReferenceMapper", ns: int, cap: int, bound: int):
+        torch, dev = mapper.aligner.torch, mapper.aligner.device
+        self.mapper, self.bound = mapper, int(bound)
+        self.mapq = torch.zeros(ns, dtype=torch.int32, device=dev)
+        self.strand = torch.full((ns,), -1, dtype=torch.int32, device=dev)
+        self.ref_begin = torch.full((ns,), -1, dtype=torch.int64, device=dev)
+        self.ref_end = torch.full((ns,), -1, dtype=torch.int64, device=dev)
+        self.distance = torch.zeros(ns, dtype=torch.int32, device=dev)
+        self.n_ops = torch.zeros(ns, dtype=torch.int32, device=dev)
+        self.runs = torch.zeros((ns, cap), dtype=torch.int32, device=dev)
+
+    def add(self, idx, arrays, n_ops, cigar) -> None:
+        torch = self.mapper.aligner.torch
+        slot, mapq, _, _ = self.mapper.sam_list_mapq(arrays[0], arrays[4], self.bound)
+        picked = self.mapper.sam_primaries(torch, slot, arrays, n_ops, cigar)
+        at = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(self.mapq.device)
+        self.mapq[at] = mapq
+        for mine, theirs in zip((self.strand, self.ref_begin, self.ref_end, self.distance, self.n_ops, self.runs), picked):
+            mine[at] = theirs
+
+
+class BeyondSink:
+    """A sink for the exhaustive pass over the reads `rest` of a seeded call: every slot beyond `bound` blanked on the device, as
+    blank_beyond does on the host, and the bucket's indices taken through rest."""
+
+    def __init__(self, torch, sink, rest, bound: int):
+        self.torch, self.sink, self.rest, self.bound = torch, sink, np.asarray(rest), int(bound)
+
+    def add(self, idx, arrays, n_ops, cigar) -> None:
+        scores, strand, ref_begin, ref_end, keep, ids = arrays
+        gone = (ids < 0) | (-scores.to(self.torch.int64) > self.bound)
+        blanked = (scores.masked_fill(gone, INT32_MIN), strand.masked_fill(gone, -1), ref_begin.masked_fill(gone, -1),
+                   ref_end.masked_fill(gone, -1), keep.masked_fill(gone, 0), ids.masked_fill(gone, -1))
+        self.sink.add(self.rest[idx], blanked, n_ops, cigar)

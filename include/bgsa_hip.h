@@ -849,6 +849,83 @@ int bgsa_hip_pair_select_dev(const int32_t *d_scores1, const int32_t *d_strand1,
                              int64_t insert_min, int64_t insert_max, int32_t *d_proper, int32_t *d_slot1, int32_t *d_slot2,
                              int64_t *d_insert, int32_t *d_cost, int32_t *d_n_best, int32_t *d_next_cost, void *stream);
 
+/* ---- SAM records: a mapping quality per hit list, and the text of every record written by the device into one byte buffer ----
+ * The last stage of read mapping.  The calls above leave hit lists and edit scripts as arrays; these three turn them into the lines
+ * a downstream tool reads, without a copy of the lists to the host: bgsa_hip_sam_mapq_dev chooses every read's primary slot and
+ * its MAPQ, bgsa_hip_sam_measure_dev (pass 1) returns the byte length of every record, the caller takes an exclusive scan of the
+ * lengths — one scalar read back sizes the buffer —, and bgsa_hip_sam_emit_dev (pass 2) writes the text.
+ * DEFINITIONS (normative; bgsa_amd/reference.py: list_mapq, pair_mapq, ReferenceMapper.map_reads_sam / map_pairs_sam and
+ * tests/sam_reference.py restate them).
+ *   MAPQ of a list   scores[ns][k] (minus the distance), keep[ns][k] and `bound`, the distance within which the list is complete,
+ *              -1 for none.  The PRIMARY slot is the first slot with keep != 0; none: primary -1, the read is unmapped, MAPQ 0, n1 0,
+ *              d2 -1.  Otherwise d1 is its distance, n1 the kept slots at distance d1, d2 the smallest kept distance above d1 (-1:
+ *              none).  n1 >= 2: MAPQ = 3, 2, 1, 0 for n1 = 2, 3, 4..9, >= 10.  n1 = 1: MAPQ = min(60, 10 * gap), never below 0, with
+ *              gap = d2 - d1 if d2 exists, else bound + 1 - d1 if bound >= 0, else 6.  A stated heuristic in integers, calibrated
+ *              against no other mapper; a second locus is only sure to be listed with k_best >= 2.
+ *   MAPQ of a pair   from bgsa_hip_pair_select_dev's outputs, elementwise.  Proper: both ends get the table value of n_best when
+ *              n_best >= 2, else min(60, 10 * (next_cost - cost)), 60 with next_cost == -1.  Not proper: each end gets the list MAPQ
+ *              of its own final list at its own rescue bound; its record is its first kept slot (slot_e).
+ *   a record   one entry per record in every per-record array of bgsa_hip_sam_batch_t.  strand -1: unmapped.
+ *     CIGAR    the runs (length << 4 | op, d_runs[d_runs_row[i]][0 .. n_ops)) run along the forward reference, as
+ *              bgsa_hip_reference_placements_dev leaves them.  In this library the window is the query, so op 1 'I' consumes a
+ *              reference base only and op 2 'D' a read base only; SAM says the opposite: op 1 prints as D, op 2 as I, 7 as = and
+ *              8 as X.
+ *     SEQ/QUAL a forward hit or an unmapped read: the caller's bytes.  A reverse hit: SEQ reverse-complemented (A<->T, C<->G,
+ *              anything else N), QUAL reversed.  d_quals NULL: '*'.
+ *     POS      ref_begin + 1.  NM:i: is the distance.
+ *     MD:Z:    read off the mapped reference (bgsa_hip_map_queries_dev's codes), class letters "ACGTN"[code] — a lower-case or
+ *              IUPAC base is of class A and prints so.  Along [ref_begin, ref_end): a count of '=' bases runs through SAM I runs;
+ *              before every X base and before every SAM D run the count is written, even when 0, and reset; an X base writes its
+ *              reference letter, a D run '^' and its reference letters; the count is written once more at the end.  Grammar:
+ *              [0-9]+(([ACGTN]|\^[ACGTN]+)[0-9]+)*.
+ *     unmapped RNAME '*', POS 0, MAPQ 0, CIGAR '*', no tags; with rnext 1 (the end of a pair whose mate is mapped) RNAME is the
+ *              reference's name and POS is pnext, the mate's.
+ *     pairs    flags 1, 2 (proper), 4, 8, 16, 32 and 64 (end 1) or 128 (end 2) are the caller's, as are rnext (1: '=', the mate is
+ *              mapped; 0: '*'), pnext (the mate's POS, or 0) and tlen (both ends mapped: the rightmost end minus the leftmost
+ *              begin, positive for the end with the smaller begin — end 1 on equal begins —, negative for the other; else 0).
+ *     line     QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL separated by tabs, a mapped record then tab NM:i:<d> tab
+ *              MD:Z:<md>, then '\n'.
+ *   malformed  a record is MALFORMED when n_ops > cigar_cap, ref_begin < 0, ref_end > ref_len (or below ref_begin), its
+ *              reference-consuming runs do not sum to ref_end - ref_begin, its read-consuming runs do not sum to its read length,
+ *              a run has length 0 or an op other than 1, 2, 7, 8 — these of a mapped record —, or when its read row, read length
+ *              (1..read_stride), name id, name offsets, runs row, strand (-1, 0, 1), flag (0..65535), mapq (0..255), rnext (0, 1),
+ *              pnext (>= 0), distance (>= 0) or n_ops (>= 0) lies outside its range.  Pass 1 gives it length 0, pass 2 writes nothing
+ *              for it, each call adds the malformed records it met to *d_malformed, and none of its values forms an address.
+ *              Pass 2 also treats as malformed a record whose line is not exactly d_offsets[i + 1] - d_offsets[i] bytes long or
+ *              whose bytes would leave [0, text_bytes).
+ * One wave per read (mapq) or per record; k in 1..64.  All three only launch on `stream`: no allocation, no synchronisation, no
+ * workspace; n == 0 (ns == 0) is BGSA_HIP_OK and launches nothing.  BGSA_HIP_EINVAL, checked before the first HIP call: a NULL
+ * pointer (the stream and d_quals excepted), k outside 1..64, bound below -1, a negative count, read_stride outside [1, 2^31 - 1],
+ * n_read_rows, n_names, names_bytes, rname_len, ref_len, cigar_cap or n_run_rows below 1, a negative text_bytes.
+ * The C loop: fill the batch; measure; lengths -> offsets[n + 1] by an exclusive scan; read offsets[n] back; allocate the text;
+ * emit; read *d_malformed. */
+typedef struct bgsa_hip_sam_batch {
+    const uint8_t *d_reads;            /* ASCII rows: row r is d_reads + r * read_stride */
+    const uint8_t *d_quals;            /* the same layout, or NULL: QUAL is '*' */
+    int64_t read_stride, n_read_rows;
+    const uint8_t *d_names;            /* QNAME bytes, flat: name j is [d_name_offsets[j], d_name_offsets[j + 1]) */
+    const int64_t *d_name_offsets;     /* n_names + 1 entries */
+    int64_t n_names, names_bytes;
+    const uint8_t *d_rname;            /* the reference's name, rname_len bytes */
+    int64_t rname_len;
+    const uint8_t *d_reference;        /* the mapped reference (codes 0..4), ref_len bytes */
+    int64_t ref_len;
+    const uint32_t *d_runs;            /* [n_run_rows][cigar_cap]: length << 4 | op */
+    int64_t n_run_rows;
+    int64_t cigar_cap;
+    /* one entry per record */
+    const int64_t *d_read_row, *d_name_of, *d_runs_row;
+    const int32_t *d_read_len, *d_strand;
+    const int64_t *d_ref_begin, *d_ref_end;
+    const int32_t *d_distance, *d_n_ops, *d_flag, *d_mapq, *d_rnext;
+    const int64_t *d_pnext, *d_tlen;
+} bgsa_hip_sam_batch_t;
+int bgsa_hip_sam_mapq_dev(const int32_t *d_scores, const int32_t *d_keep, int64_t ns, int k, int bound, int32_t *d_primary, int32_t *d_mapq,
+                          int32_t *d_n1, int32_t *d_d2, void *stream);
+int bgsa_hip_sam_measure_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int64_t *d_lengths, int32_t *d_malformed, void *stream);
+int bgsa_hip_sam_emit_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, const int64_t *d_offsets, uint8_t *d_text, int64_t text_bytes,
+                          int32_t *d_malformed, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
