@@ -96,6 +96,47 @@ def band_edge_pairs(q: np.ndarray, n: int, h: int, full: bool = True, near: int 
     return np.stack(rows), tags
 
 
+def band_edge_two_waves(q: np.ndarray, n: int, h: int, dist, mutate, gen_reads, seed: int, groups: int = 1, lane: int = 0,
+                        group: int = 0, near: int = 4):
+    """Two waves of `groups` x 64 subjects for one query (groups = 2: the waves of a kernel that carries two subject groups):
+      * one in which every lane is within B of q: the near-B rungs with D = B - 1 and D = B and the rungs on the band's
+        outermost diagonals dlo and dhi that lie within B, dealt over the groups at lanes 0, 5, 10, ..., among copies of q
+        carrying 0 .. 20 random edits (fewer where |n - m| leaves less room below B);
+      * one with exactly one lane above B — at `lane` of `group`, the rung with the smallest D > B the ladders hold — and a
+        rung with the largest D <= B beside it, among such copies.
+    dist / mutate / gen_reads as for band_edge_waves.  Returns (subjects [128 groups, n], distances of the rungs placed in the
+    first wave, distance of the one lane above B)."""
+    q = np.asarray(q, dtype=np.uint8)
+    m = len(q)
+    assert groups in (1, 2) and 0 <= lane < 64 and 0 <= group < groups
+    B, dlo, dhi = band_limits(m, n, h)
+    s, _ = band_edge_pairs(q, n, h, full=False, near=near)
+    outer = [r for kind, k in (("ins", dhi), ("del", -dlo)) for sub in (0, 1) if (r := _rung(q, n, kind, k, sub)) is not None]
+    have = {r.tobytes() for r in s}
+    fresh = [r for r in outer if r.tobytes() not in have]
+    if fresh:
+        s = np.concatenate([s, np.stack(fresh)])
+    D = dist(q[None], s)[0]
+    assert (D > B).any() and (D <= B).any(), "the ladders stay on one side of B"
+    on_edge = np.array([r.tobytes() in {o.tobytes() for o in outer} for r in s])
+    first = np.flatnonzero(((D >= B - 1) | on_edge) & (D <= B))
+    assert len(first) <= 13 * groups
+    above = s[np.flatnonzero(D == D[D > B].min())[0]]
+    below = s[np.flatnonzero(D == D[D <= B].max())[0]]
+    size = 64 * groups
+    k = min(m, n)
+    # 32 copies, cycled over the lanes; an indel of mutate() costs two edits, so the copies stay within B whatever n - m is
+    most = min(20, (B - abs(n - m)) // 2)
+    pool = gen_reads(seed, 32, n)
+    pool[:, :k] = mutate(np.repeat(q[None, :k], 32, axis=0), np.arange(32) % (most + 1), seed)
+    out = np.resize(pool, (2 * size, n))
+    for i, r in enumerate(first):
+        out[64 * (i % groups) + (5 * (i // groups)) % 64] = s[r]
+    out[size + 64 * group + (lane + 1) % 64] = below
+    out[size + 64 * group + lane] = above
+    return np.ascontiguousarray(out), D[first], int(D[D > B].min())
+
+
 def band_edge_waves(q: np.ndarray, n: int, h: int, dist, mutate, gen_reads, seed: int, inside_waves: int = 0):
     """Whole waves of 64 subjects for one query, so that a GPU run observes the banded result and not the redo:
       * waves in which every lane is within B of q: the full ladders and the near-B rungs with D <= B (one with D = B),
