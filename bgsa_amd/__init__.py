@@ -221,6 +221,10 @@ def lib() -> ctypes.CDLL:
     if hasattr(L, "bgsa_hip_myers_prefix_depths"):   # (the same)
         L.bgsa_hip_myers_prefix_depths.argtypes = [i32, i64, i32, i32, i32, i32, ip, i32]
         L.bgsa_hip_myers_band_segments.argtypes = [vp, i32, i32, ip, i32, vp, i32, ip]
+    if hasattr(L, "bgsa_hip_myers_band_early"):   # (the same)
+        L.bgsa_hip_myers_band_early.argtypes = [i32, i32, i32, i64, ip]
+        L.bgsa_hip_myers_band_early_cuts.argtypes = [i32, i32, ip, ip]
+        L.bgsa_hip_myers_band_early_segments.argtypes = [vp, i32, i32, ip, ip, i32, ip, i32, vp, i32, ip]
     L.bgsa_hip_kernel_name.argtypes = [i32, i32]
     L.bgsa_hip_kernel_name.restype = ctypes.c_char_p
     L.bgsa_hip_malloc.argtypes = [ctypes.POINTER(vp), sz]

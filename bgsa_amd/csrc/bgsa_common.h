@@ -112,6 +112,8 @@ int myers_band_groups(int word_num, int64_t read_count, int ref_len, int read_le
 int myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_len, int n_queries, int mixed_lengths, int *depths);
 // The half-width of a global Myers launch that rescues its uncertified lanes (myers_band.h), 0 where it does not (host only).
 int myers_band_rescue(int ref_len, int read_len, int n_queries, int64_t read_count);
+// The early-leave cuts such a launch runs with (myers_band.h): their number, rows[j] / words[j] filled (host only).
+int myers_band_early(int ref_len, int read_len, int n_queries, int64_t read_count, int *rows, int *words);
 
 // Packed query stream (one per query, 8-byte windows): codes 0..4 = A C G T N row, 5 = END,
 // 6 = REFILL.  Window i < n_windows-1 holds characters 7i..7i+6 and a REFILL; the last window

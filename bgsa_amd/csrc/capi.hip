@@ -657,6 +657,60 @@ int bgsa_hip_myers_band_segments(const char *mapped_row, int ref_len, int read_l
     return n;
 }
 
+int bgsa_hip_myers_band_early(int ref_len, int read_len, int n_queries, int64_t read_count, int *rows_out)
+{
+    return myers_band_early(ref_len, read_len, n_queries, read_count, rows_out, nullptr);
+}
+
+int bgsa_hip_myers_band_early_cuts(int len, int h, int *rows, int *words)
+{
+    if (len <= 0) return 0;
+    const BandCuts c = band_early_cuts(len, len, h);
+    for (int j = 0; j < c.n; j++) {
+        if (rows) rows[j] = c.row[j];
+        if (words) words[j] = c.word[j];
+    }
+    return c.n;
+}
+
+int bgsa_hip_myers_band_early_segments(const char *mapped_row, int len, int h, const int *cut_rows, const int *cut_words, int n_cuts,
+                                       const int *depths, int n_depths, unsigned char *dst, int cap, int *offsets)
+{
+    if (!mapped_row || len <= 0 || n_cuts < 1 || n_cuts > kBandMaxCuts || !cut_rows || !cut_words || n_depths < 0 ||
+        (n_depths && !depths) || n_depths > kPrefixMaxDepths)
+        return 0;
+    BandCuts c;
+    c.n = n_cuts;
+    for (int j = 0; j < n_cuts; j++) c.row[j] = cut_rows[j], c.word[j] = cut_words[j];
+    BandSchedule s;
+    if (!band_schedule_early(len, len, h, (len + 31) / 32, c, &s)) return 0;
+    if (n_depths == 0) {   // the band stream, whole: as bgsa_hip_myers_band_stream
+        const int n = band_stream_layout(len, s, mapped_row, nullptr);
+        if (offsets) offsets[0] = 0, offsets[1] = n;
+        if (dst && cap >= n)
+            for (int i = 0; 8 * i < n; i++) {
+                memset(dst + 8 * i, kCodeEnd, 8);
+                band_stream_layout(len, s, mapped_row, dst + 8 * i, 8 * i, 8);
+            }
+        return n;
+    }
+    PrefixPlan p;
+    for (int j = 0; j < n_depths; j++) p.depth[p.n++] = depths[j];
+    if (!prefix_plan_layout(len, (len + 31) / 32, s, &p)) return 0;
+    const int n = p.off[p.n + 1];
+    if (offsets)
+        for (int j = 0; j <= p.n + 1; j++) offsets[j] = p.off[j];
+    if (dst && cap >= n)   // window by window, as pack_band_segments_kernel writes it
+        for (int i = 0; i < n / 8; i++) {
+            int seg = 0;
+            while (seg < p.n && p.off[seg + 1] <= 8 * i) seg++;
+            for (int j = 0; j < 8; j++) dst[8 * i + j] = kCodeEnd;
+            band_rows_layout(s, seg ? p.depth[seg - 1] : 0, seg < p.n ? p.depth[seg] : len, seg == p.n, mapped_row, dst + 8 * i,
+                             8 * i - p.off[seg], 8);
+        }
+    return n;
+}
+
 int bgsa_hip_myers_band_stream(const char *mapped_row, int ref_len, int read_len, unsigned char *dst, int cap)
 {
     if (!mapped_row || ref_len <= 0 || read_len <= 0) return BGSA_HIP_EINVAL;

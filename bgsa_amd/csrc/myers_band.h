@@ -32,6 +32,13 @@ struct BandSchedule {
 };
 
 __host__ __device__ inline int band_window_index(int nw, int a, int b) { return a * nw - a * (a - 1) / 2 + (b - a); }
+// ... and back: the window [a, b] of slot group `win`.
+inline void band_window_of(int nw, int win, int *a, int *b)
+{
+    *a = 0;
+    while (*a + 1 < nw && band_window_index(nw, *a + 1, *a + 1) <= win) ++*a;
+    *b = *a + win - band_window_index(nw, *a, *a);
+}
 
 // Default half-width for a length: the mean edit distance of random uniform ACGT pairs + 4.5 standard deviations
 // (rows_ir.py: myers_band_half, LABNOTES §11): 150 bp -> h = 48, B = 97.
@@ -87,6 +94,119 @@ inline bool band_schedule(int m, int n, int h, int nw, BandSchedule *s)
         return false;
     }
     return true;
+}
+
+// ---- early leave (LABNOTES §37) --------------------------------------------------------------------------------
+// The static rule keeps a low word in the window until its last column j_r = 32 (w + 1) lies more than h diagonals below the
+// row: all it knows is D[i][j] >= i - j.  The state knows D'[r][j_r] itself.  D'[r][j] - j does not grow with j, so every
+// in-window cell (r, j), j <= j_r, has D'[r][j] + (r - j) >= M = D'[r][j_r] + (r - j_r), and a path that enters the rows
+// behind r in columns <= j_r costs at least M (n = m).  Word w may therefore leave behind ANY row r >= j_r: the banded score
+// stays exact for every lane with D' <= min(B, M) — a limit per lane.  A lane above it is what a lane above B is: a pool entry
+// (rescue, below).  A CUT {row, word}: behind `row` rows (1-based row r of the text) the window's low end is at least word + 1.
+// Behind the cut no row touches words 0 .. w again, so they still hold D'[r][j_r] - r when the query ends: the kernel forms M
+// there, beside the score, from the state it has — the cuts cost the row loop nothing, and the stream is the band stream of
+// the schedule with the cuts applied (whole, or in the segments of prefix sharing): no segment and no code of its own.
+constexpr int kBandMaxCuts = 2;
+struct BandCuts {
+    int n = 0;                      // cuts (0: the static schedule)
+    int row[kBandMaxCuts] = {};     // ascending
+    int word[kBandMaxCuts] = {};    // ascending
+};
+// The cut rows of the default rescue lengths (band_rescue_lengths, n = m, h = band_rescue_half): per leaving word the earliest
+// row at which the cut adds at most 5e-5 of random uniform pairs to the rescue, the two words that save most; lengths whose
+// cuts save under 2 % of the word-rows have none (scripts/band_early_cuts.py, profiles/r12_band_early_cuts.txt).
+// 150 bp keeps the rows of the first CPU check, (106, 130): four and five rows behind the script's (102, 125), which costs
+// word-rows and never a score — the script's pair there waits for an A/B on the GPU (LABNOTES §37).
+struct BandEarlyEntry {
+    int len, n, row[kBandMaxCuts], word[kBandMaxCuts];
+};
+constexpr BandEarlyEntry kBandEarlyCuts[] = {
+    {68, 1, {51, 0}, {0, 0}},
+    {96, 2, {60, 83}, {0, 1}},
+    {100, 2, {62, 85}, {0, 1}},
+    {107, 2, {64, 88}, {0, 1}},
+    {111, 2, {65, 89}, {0, 1}},
+    {114, 2, {66, 90}, {0, 1}},
+    {118, 2, {67, 92}, {0, 1}},
+    {121, 2, {68, 93}, {0, 1}},
+    {125, 2, {69, 94}, {0, 1}},
+    {128, 2, {70, 95}, {0, 1}},
+    {132, 2, {71, 96}, {0, 1}},
+    {139, 2, {99, 121}, {1, 2}},
+    {143, 2, {100, 122}, {1, 2}},
+    {146, 2, {101, 123}, {1, 2}},
+    {150, 2, {106, 130}, {1, 2}},
+    {153, 2, {104, 126}, {1, 2}},
+    {157, 2, {105, 128}, {1, 2}},
+    {160, 2, {106, 129}, {1, 2}},
+};
+// The cuts of an m x n launch at half-width h: none unless n = m, the length is in the table and h is the table's.
+inline BandCuts band_early_cuts(int m, int n, int h)
+{
+    BandCuts c;
+    if (m != n || h != band_rescue_half(n)) return c;
+    for (const BandEarlyEntry &e : kBandEarlyCuts)
+        if (e.len == n) {
+            c.n = e.n;
+            for (int j = 0; j < e.n; j++) c.row[j] = e.row[j], c.word[j] = e.word[j];
+        }
+    return c;
+}
+// What the kernel gets of the cuts, in the launch's band_limit above B: per cut 2 r - j_r (nine bits) and w (two).
+constexpr int kBandEarlyLimitBits = 10, kBandEarlyCutBits = 11;
+constexpr int kBandEarlyLimitMask = (1 << kBandEarlyLimitBits) - 1;
+inline int band_early_word(int band_limit, const BandCuts &c)
+{
+    unsigned v = static_cast<unsigned>(band_limit) & kBandEarlyLimitMask;
+    for (int j = 0; j < c.n; j++)
+        v |= (static_cast<unsigned>(2 * c.row[j] - 32 * (c.word[j] + 1)) | static_cast<unsigned>(c.word[j]) << 9)
+             << (kBandEarlyLimitBits + kBandEarlyCutBits * j);
+    return static_cast<int>(v);
+}
+// band_schedule with the cuts applied: rows behind cut j run on windows whose low end is at least word[j] + 1.  False (s->n = 0,
+// as band_schedule) also where a cut is out of order, lies above its word's last column (r < j_r: the bound needs r >= j_r),
+// or would empty a window.  rows_ir.py: myers_band_windows(cuts = ...).
+inline bool band_schedule_early(int m, int n, int h, int nw, const BandCuts &cuts, BandSchedule *s)
+{
+    if (cuts.n == 0) return band_schedule(m, n, h, nw, s);
+    BandSchedule base;
+    s->n = 0;
+    if (m != n || cuts.n < 0 || cuts.n > kBandMaxCuts || !band_schedule(m, n, h, nw, &base)) return false;
+    for (int j = 0; j < cuts.n; j++)
+        if (cuts.word[j] < 0 || cuts.word[j] >= nw - 1 || cuts.row[j] < 32 * (cuts.word[j] + 1) || cuts.row[j] >= m ||
+            (j && (cuts.row[j] <= cuts.row[j - 1] || cuts.word[j] <= cuts.word[j - 1])))
+            return false;
+    int pw = -1, sw = 0;
+    for (int r = 0; r < m; r++) {   // 0-based row r is behind cut j when r >= cuts.row[j]
+        while (sw + 1 < base.n && base.row[sw + 1] <= r) sw++;
+        int a, b;
+        band_window_of(nw, base.win[sw], &a, &b);
+        for (int j = 0; j < cuts.n; j++)
+            if (r >= cuts.row[j] && a < cuts.word[j] + 1) a = cuts.word[j] + 1;
+        if (a > b || s->n == kBandMaxSwitches) {
+            s->n = 0;
+            return false;
+        }
+        const int win = band_window_index(nw, a, b);
+        if (win != pw) {
+            s->row[s->n] = r;
+            s->win[s->n] = win;
+            s->n++;
+            pw = win;
+        }
+    }
+    return true;
+}
+// Word-rows of a schedule (per subject group).
+inline long long band_schedule_word_rows(int m, int nw, const BandSchedule &s)
+{
+    long long words = 0;
+    for (int i = 0; i < s.n; i++) {
+        int a, b;
+        band_window_of(nw, s.win[i], &a, &b);
+        words += static_cast<long long>((i + 1 < s.n ? s.row[i + 1] : m) - s.row[i]) * (b - a + 1);
+    }
+    return words;
 }
 
 // Bytes of one band stream, padded like the plain one: the codes, at most 3 bytes per window change (SETWIN, its byte, a

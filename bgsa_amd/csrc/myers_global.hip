@@ -235,6 +235,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
     static_assert(!(LENS && BAND), "the certified band is derived from one (m, n): a length-aware launch runs full rows");
     static_assert(!SHARE || BAND, "prefix sharing: the band kernels only");
     static_assert(!RESCUE || (BAND && G == 2), "rescue: the two-group band kernels only");
+    // EARLY LEAVE (myers_band.h) is part of the RESCUE instantiations, no flag of its own: it needs the pool, which only they
+    // have, and it costs them a few instructions per query behind the row loop — two scalar compares where the launch has no
+    // cuts.  Every other instantiation keeps its code.  band_limit carries the cuts' constants above B (band_early_word).
+    constexpr bool kEarly = RESCUE;
     // LENS: the lane's length is loaded once per task and kept across the row loops, one VGPR per group — except beyond 8 words,
     // where the widths sit at their occupancy steps (20 words 238, 28 and 32 words 255 VGPRs): there the epilogue loads it again
     // per query, one dword per lane against >= 10 words x ref_len rows.
@@ -328,6 +332,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                 // whoever wrote it.  The full-row pass starts at row 0 and stores nothing (a banded snapshot is no full-row state);
                 // a wave whose guard is off shares nothing.  Without SHARE: one segment, the band stream as ever.
                 const int n_depths = SHARE ? static_cast<int>(prefix_segments >> 56) : 0;   // wave-uniform: a kernel argument
+                // kEarly: a lane is certified by score <= limit, its own (formed behind the rows, below; B wherever there are no
+                // cuts).  over[gi] = the group's lanes above theirs, as a mask: a limit kept per lane beside the score up to the
+                // store is a vector register per group, and these kernels have none to give
+                [[maybe_unused]] unsigned long long over[G];
+                [[maybe_unused]] auto is_over = [&](int gi) { return ((over[gi] >> lane_now()) & 1ull) != 0; };
                 const bool sharing = SHARE && band_on;
                 // [depth][wave][group][lane].  RESCUE: formed again at either use, like reporting_lane() and for its reason
                 [[maybe_unused]] auto wave_slots = [&]() {
@@ -363,21 +372,53 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                                     make_uint4(st[2 * gi * NW], st[2 * gi * NW + 1], st[2 * gi * NW + 2], st[2 * gi * NW + 3]);
                         }
                     }
+                    // kEarly: behind cut (r, w) no row touched words 0 .. w, so they hold D'[r][j_r] - r, j_r = 32 (w + 1): the sum
+                    // that is the score behind word w, and the lane's limit is the least of B and the cuts' M = D'[r][j_r] + (r - j_r)
+                    // (myers_band.h).  The cuts are wave-uniform, a kernel argument; the full-row pass forms a limit nobody reads.
+                    if constexpr (kEarly) {
+                        // (decoded here, query by query: kept across the row loop the five fields are five scalar registers more,
+                        // which the counter kernels, at their limit, park in vector lanes)
+                        unsigned packed = static_cast<unsigned>(band_limit);
+                        asm volatile("" : "+s"(packed));
+                        int cut_word[kBandMaxCuts], cut_add[kBandMaxCuts];
 #pragma unroll
-                    for (int gi = 0; gi < G; gi++) {
-                        score[gi] = ref_len;
+                        for (int j = 0; j < kBandMaxCuts; j++) {
+                            const unsigned cut = (packed >> (kBandEarlyLimitBits + kBandEarlyCutBits * j)) & ((1u << kBandEarlyCutBits) - 1u);
+                            cut_word[j] = cut ? static_cast<int>(cut >> 9) : -1;       // w
+                            cut_add[j] = static_cast<int>(cut & 0x1ffu) - ref_len;     // 2 r - j_r, less the score's first term
+                        }
 #pragma unroll
-                        for (int w = 0; w < NW; w++) {
-                            const int rem = read_len - 32 * w;
-                            const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
-                            score[gi] += __popc(st[2 * (gi * NW + w)] & m) - __popc(st[2 * (gi * NW + w) + 1] & m);
+                        for (int gi = 0; gi < G; gi++) {
+                            score[gi] = ref_len;
+                            int limit = static_cast<int>(packed & kBandEarlyLimitMask);
+#pragma unroll
+                            for (int w = 0; w < NW; w++) {
+                                const int rem = read_len - 32 * w;
+                                const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+                                score[gi] += __popc(st[2 * (gi * NW + w)] & m) - __popc(st[2 * (gi * NW + w) + 1] & m);
+#pragma unroll
+                                for (int j = 0; j < kBandMaxCuts; j++)   // (a band launch has (read_len + 31) / 32 = NW: words below the last are whole)
+                                    if (w < NW - 1 && w == cut_word[j]) limit = score[gi] + cut_add[j] < limit ? score[gi] + cut_add[j] : limit;
+                            }
+                            over[gi] = __builtin_amdgcn_ballot_w64(score[gi] > limit);
+                        }
+                    } else {
+#pragma unroll
+                        for (int gi = 0; gi < G; gi++) {
+                            score[gi] = ref_len;
+#pragma unroll
+                            for (int w = 0; w < NW; w++) {
+                                const int rem = read_len - 32 * w;
+                                const uint32_t m = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+                                score[gi] += __popc(st[2 * (gi * NW + w)] & m) - __popc(st[2 * (gi * NW + w) + 1] & m);
+                            }
                         }
                     }
                     if (!band) break;
-                    int n_over = 0;   // live groups with a lane above B
+                    int n_over = 0;   // live groups with a lane above the limit (B; early leave: the lane's own)
 #pragma unroll
                     for (int gi = 0; gi < G; gi++)
-                        if (gi < n_live && __builtin_amdgcn_ballot_w64(score[gi] > band_limit) != 0) n_over++;
+                        if (gi < n_live && (kEarly ? over[gi] : __builtin_amdgcn_ballot_w64(score[gi] > band_limit)) != 0) n_over++;
                     if (n_over == 0) break;
                     if constexpr (G == 1) n_over = 1;   // (what it is: said so that the one-group kernels keep their code)
                     if constexpr (RESCUE) {
@@ -386,8 +427,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                         // banded scores: the store below leaves those lanes out.  A claim that does not fit the pool marks what it
                         // holds of it as void, so that every entry below the capacity is written, and the wave goes on as it does
                         // for a group over the limit: the redo, the guard's pair, and the count of either in band_launch[3].
-                        const unsigned c0 = __popcll(__builtin_amdgcn_ballot_w64(score[0] > band_limit)),
-                                       c1 = n_live > 1 ? __popcll(__builtin_amdgcn_ballot_w64(score[1] > band_limit)) : 0u;
+                        const unsigned c0 = __popcll(over[0]), c1 = n_live > 1 ? __popcll(over[1]) : 0u;
                         unsigned forced = (c0 > kRescueMaxLanes ? 1u : 0u) + (c1 > kRescueMaxLanes ? 1u : 0u);
                         if (forced == 0) {
                             unsigned *const words = reinterpret_cast<unsigned *>(band_launch) - 16;   // band_launch_words() of them
@@ -404,7 +444,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                             const unsigned column = lane_now() + static_cast<unsigned>(group0) * kLanes;
 #pragma unroll
                             for (int gi = 0; gi < G; gi++) {
-                                const bool up = gi < n_live && score[gi] > band_limit;
+                                const bool up = gi < n_live && is_over(gi);
                                 const unsigned long long over = __builtin_amdgcn_ballot_w64(up);
                                 const unsigned at = (gi ? c0 : 0u) + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(over >> 32),
                                                                                               __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(over), 0u));
@@ -437,7 +477,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(band_kernel
                 unreported += tried;
 #pragma unroll
                 for (int gi = 0; gi < G; gi++)
-                    if (gi < n_live && !(RESCUE && band && score[gi] > band_limit))   // (band still set: those lanes are in the pool)
+                    if (gi < n_live && !(RESCUE && band && is_over(gi)))   // (band still set: those lanes are in the pool)
                         dst[static_cast<size_t>(q) * ld + gi * kLanes] = static_cast<int16_t>(-score[gi]);
             } else {
                 int left;
@@ -1077,6 +1117,32 @@ int band_half_for(int ref_len, int read_len, int nw, int groups, int nq, int64_t
     return h;
 }
 
+// ---- early leave (myers_band.h) ----
+// On exactly where the launch rescues by the DEFAULT rule (no BGSA_MYERS_BAND_RESCUE: the tests that force rescue count the
+// lanes of the plain rescue band), n = m, and the length has cuts at the launch's half-width.  BGSA_MYERS_BAND_EARLY=0|1 (read
+// once) forces it off, or on for every rescuing launch with a table entry.
+constexpr bool kEarlyDefault = true;
+static int early_knob()
+{
+    static const int v = [] {
+        const char *e = getenv("BGSA_MYERS_BAND_EARLY");
+        return (e && (e[0] == '0' || e[0] == '1') && e[1] == 0) ? e[0] - '0' : -1;
+    }();
+    return v;
+}
+// The cuts of a two-group launch that rescues (`rescue` entries, half-width h): where it leaves early, *sched becomes the
+// schedule with the cuts applied.  Whether the launch shares prefixes makes no difference: the cuts lie behind every depth.
+BandCuts early_select(int ref_len, int read_len, int nw, int h, long long rescue, BandSchedule *sched)
+{
+    if (rescue <= 0 || early_knob() == 0) return BandCuts{};
+    if (early_knob() < 0 && (!kEarlyDefault || rescue_knob() >= 0)) return BandCuts{};
+    const BandCuts cuts = band_early_cuts(ref_len, read_len, h);
+    BandSchedule early;
+    if (cuts.n == 0 || !band_schedule_early(ref_len, read_len, h, nw, cuts, &early)) return BandCuts{};
+    *sched = early;
+    return cuts;
+}
+
 // The pool's pairs, one per lane, with full rows: exact by themselves, so no band, no certificate and no stream.  Persistent
 // waves read the number of entries on the device and take chunks of 64.  A lane behind the last entry, or on an entry that is
 // void or names no pair of the launch, runs pair (0, 0) and stores nothing.
@@ -1176,12 +1242,14 @@ int launch_asm(const ScoreArgs &a)
     int h = 0;
     bool band = false;
     long long rescue = 0;   // the pool's capacity of a launch that rescues (myers_band.h)
+    BandCuts cuts;          // ... and where its low words leave early
     if constexpr ((G == 1 || kBandPair) && NW >= kBandMinWords && NW <= kBandMaxWords) {   // the certified band (myers_band.h)
         if (!lens) h = band_half_for(a.ref_len, a.read_len, NW, G, nq, a.read_count, &sched, &rescue);
         band = !lens && sched.n > 0;
         if (band) {
             on_grid = myers_global_asm_kernel<NW, G, false, true>;
             on_counter = myers_global_asm_kernel<NW, G, true, true>;
+            if constexpr (kBandPair) cuts = early_select(a.ref_len, a.read_len, NW, h, rescue, &sched);
             prefix_select(a.ref_len, NW, sched, nq, plan.q_tile, a.read_count, &prefix);
             if (prefix.n) {
                 on_grid = myers_global_asm_kernel<NW, G, false, true, false, true>;
@@ -1196,6 +1264,10 @@ int launch_asm(const ScoreArgs &a)
                 }
             }
         }
+    }
+    if (band && 2 * h + 1 > kBandEarlyLimitMask) {   // (no schedule has such a band: band_early_word keeps ten bits of it)
+        set_error_text("myers band: half-width out of range");
+        return BGSA_HIP_EINVAL;
     }
     if (kBandPair && !band) {   // myers_band_groups answers 2 for banded launches only
         set_error_text("myers: two subject groups per wave selected for a launch without the certified band");
@@ -1231,7 +1303,7 @@ int launch_asm(const ScoreArgs &a)
     hipLaunchKernelGGL(kernel, lg.grid, dim3(256), lds, a.stream,
                        static_cast<const unsigned char *>(a.d_workspace), a.d_peq, a.results<int16_t>(), a.ref_len, a.read_len,
                        static_cast<long long>(a.read_count), static_cast<int>(a.n_groups()), a.word_num, nq, plan.q_tile, stride,
-                       fault, lg.counter, band ? 2 * h + 1 : 0, guard, a.d_read_lens, prefix_segments_word(prefix),
+                       fault, lg.counter, band ? band_early_word(2 * h + 1, cuts) : 0, guard, a.d_read_lens, prefix_segments_word(prefix),
                        static_cast<const PrefixEntry *>(prefix_entries(words)));
     BGSA_HIP_TRY(hipGetLastError());
     if constexpr (kBandPair) {
@@ -1476,6 +1548,25 @@ int myers_prefix_depths(int word_num, int64_t read_count, int ref_len, int read_
     prefix_select(ref_len, c.nw, sched, n_queries, plan.q_tile, read_count, &p);
     for (int j = 0; j < p.n; j++) depths[j] = p.depth[j];
     return p.n;
+}
+
+int myers_band_early(int ref_len, int read_len, int n_queries, int64_t read_count, int *rows, int *words)
+{
+    if (ref_len <= 0 || read_len <= 0 || n_queries < 1 || read_count < 1) return 0;
+    const int word_num = (read_len + 31) / 32;
+    if (word_num > kMaxWords) return 0;
+    const MyersChoice c = myers_select(word_num, 0, read_count, ref_len, read_len, false);
+    if (c.family != MyersFamily::kAsmBandPairs) return 0;
+    BandSchedule sched;
+    long long rescue = 0;
+    const int h = band_half_for(ref_len, read_len, c.nw, c.G, n_queries, read_count, &sched, &rescue);
+    if (sched.n == 0) return 0;
+    const BandCuts cuts = early_select(ref_len, read_len, c.nw, h, rescue, &sched);
+    for (int j = 0; j < cuts.n; j++) {
+        if (rows) rows[j] = cuts.row[j];
+        if (words) words[j] = cuts.word[j];
+    }
+    return cuts.n;
 }
 
 int myers_band_rescue(int ref_len, int read_len, int n_queries, int64_t read_count)

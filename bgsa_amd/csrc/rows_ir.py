@@ -747,10 +747,47 @@ def myers_band_rescue_half(length: int) -> int:
     return myers_band_half(length) - 3
 
 
-def myers_band_windows(m: int, n: int, h: int, nw: int):
+# Early leave (myers_band.h: kBandEarlyCuts): per length the cuts (row r, word w) — behind row r the window begins at word w + 1.
+MYERS_BAND_EARLY_CUTS = {
+    68: ((51, 0),),
+    96: ((60, 0), (83, 1)),
+    100: ((62, 0), (85, 1)),
+    107: ((64, 0), (88, 1)),
+    111: ((65, 0), (89, 1)),
+    114: ((66, 0), (90, 1)),
+    118: ((67, 0), (92, 1)),
+    121: ((68, 0), (93, 1)),
+    125: ((69, 0), (94, 1)),
+    128: ((70, 0), (95, 1)),
+    132: ((71, 0), (96, 1)),
+    139: ((99, 1), (121, 2)),
+    143: ((100, 1), (122, 2)),
+    146: ((101, 1), (123, 2)),
+    150: ((106, 1), (130, 2)),
+    153: ((104, 1), (126, 2)),
+    157: ((105, 1), (128, 2)),
+    160: ((106, 1), (129, 2)),
+}
+
+
+def myers_band_early_cuts(length: int, h: int):
+    """The table's cuts for length x length at half-width h (myers_band.h: band_early_cuts): only at the rescue half-width."""
+    return MYERS_BAND_EARLY_CUTS.get(length, ()) if h == myers_band_rescue_half(length) else ()
+
+
+def myers_band_windows(m: int, n: int, h: int, nw: int, cuts=()):
     """Per query row i = 1..m the window (a, b) of words that holds the band's columns, or None when the band is off for
     this shape (the row windows would not save a fifth of the word-rows, or |n - m| leaves no room).  Same rule as
-    myers_global.hip: band_schedule."""
+    myers_global.hip: band_schedule.  cuts = ((r, w), ...), n = m: rows i > r run on windows that begin at word w + 1 or later
+    (myers_band.h: band_schedule_early); None where a cut is out of order, has r < 32 (w + 1) or empties a window."""
+    if cuts:
+        base = myers_band_windows(m, n, h, nw)
+        cuts = list(cuts)
+        if base is None or m != n or len(cuts) > 2 or any(not (0 <= w < nw - 1 and 32 * (w + 1) <= r < m) for r, w in cuts) or \
+                any(x[0] >= y[0] or x[1] >= y[1] for x, y in zip(cuts, cuts[1:])):
+            return None
+        out = [(max([a] + [w + 1 for r, w in cuts if i > r]), b) for i, (a, b) in enumerate(base, start=1)]
+        return None if any(a > b for a, b in out) else out
     B = 2 * h + 1
     delta = n - m
     if h <= 0 or abs(delta) > B or nw > MYERS_BAND_MAX_WORDS or nw < 3:
@@ -765,11 +802,12 @@ def myers_band_windows(m: int, n: int, h: int, nw: int):
     return out
 
 
-def myers_band_stream(codes, m: int, n: int, h: int, nw: int) -> bytes | None:
+def myers_band_stream(codes, m: int, n: int, h: int, nw: int, cuts=()) -> bytes | None:
     """The band stream of one query (codes: m class codes 0..4): the plain stream's row codes, END and REFILL, plus
     SETWIN (7) and a window byte wherever the row's window changes; a SETWIN never straddles a REFILL (a REFILL at byte 6
-    ends the window early).  One spare all-END window follows.  Restates myers_global.hip: band_stream_layout."""
-    win = myers_band_windows(m, n, h, nw)
+    ends the window early).  One spare all-END window follows.  Restates myers_global.hip: band_stream_layout.
+    cuts (early leave): on the windows of myers_band_windows(cuts = cuts)."""
+    win = myers_band_windows(m, n, h, nw, cuts) if cuts else myers_band_windows(m, n, h, nw)
     if win is None:
         return None
     out = bytearray()
@@ -799,13 +837,14 @@ def myers_band_stream(codes, m: int, n: int, h: int, nw: int) -> bytes | None:
     return bytes(out)
 
 
-def myers_band_segments(codes, m: int, n: int, h: int, nw: int, depths) -> tuple[bytes, list] | None:
+def myers_band_segments(codes, m: int, n: int, h: int, nw: int, depths, cuts=()) -> tuple[bytes, list] | None:
     """The stream of one query cut behind rows depths[0] < depths[1] < ... (prefix sharing): one band stream per
     segment — it begins with the SETWIN of its first row's window whether or not the window changes there, ends with END
     padded to its 8-byte window, and only the last one carries the spare all-END window.  Returns the bytes and the offsets
     of the segments followed by the total length.  None where the band is off or a row up to the deepest depth leaves
-    words 0..1.  Restates myers_band.h: band_rows_layout / prefix_plan_layout."""
-    win = myers_band_windows(m, n, h, nw)
+    words 0..1.  Restates myers_band.h: band_rows_layout / prefix_plan_layout.
+    cuts (early leave): on the windows of myers_band_windows(cuts = cuts)."""
+    win = myers_band_windows(m, n, h, nw, cuts) if cuts else myers_band_windows(m, n, h, nw)
     depths = list(depths)
     if win is None or not depths or depths != sorted(set(depths)) or depths[0] < 1 or depths[-1] >= m:
         return None
@@ -867,6 +906,21 @@ def run_band_stream(nw: int, state: list, peq: np.ndarray, stream: bytes, band: 
         bodies[cur].simulate(state, [peq[c, w] for w in range(groups * nw)], cls=c)
         rows += cur[1] - cur[0] + 1
         pos += 1
+
+
+def run_band_early(nw: int, peq: np.ndarray, codes, m: int, h: int, cuts, groups: int = 1, **kw):
+    """One query over its early-leave stream the way the RESCUE kernels certify it (myers_global.hip): behind cut (r, w) no row
+    touches words 0 .. w, so behind the last row they still hold D'[r][j_r] - r, j_r = 32 (w + 1), and the lane's limit is the
+    least of B and every cut's M = D'[r][j_r] + (r - j_r).  Returns (scores D' [groups][lanes], limits [groups][lanes],
+    word-rows); a lane is certified by D' <= limit."""
+    lanes = peq.shape[2]
+    state = myers_init_state(nw, groups, lanes)
+    rows = run_band_stream(nw, state, peq, myers_band_stream(codes, m, m, h, nw, cuts), groups=groups, **kw)
+    limit = [np.full(lanes, 2 * h + 1, dtype=np.int64) for _ in range(groups)]
+    for r, w in cuts:
+        for g in range(groups):
+            limit[g] = np.minimum(limit[g], 2 * r - 32 * (w + 1) + _myers_columns(state[2 * g * nw:], w + 1, 32 * (w + 1)))
+    return [m + _myers_columns(state[2 * g * nw:], nw, m) for g in range(groups)], limit, rows
 
 
 def myers_body10(nw: int, groups: int = 1) -> Body:

@@ -1003,7 +1003,23 @@ int bgsa_hip_query_stream(int algo, const char *mapped_row, int ref_len, int k, 
  * group-queries a rescuing wave ran again with full rows because a group held more than eight uncertified lanes or the pool
  * was full (they are among out[0] of bgsa_hip_myers_band_stats too; call after synchronising).
  * bgsa_hip_myers_band_rescue_half: FOR TESTS — the half-width formula alone, whatever the launch (the library's side of
- * rows_ir.py: myers_band_rescue_half); a caller asks bgsa_hip_myers_band_rescue. */
+ * rows_ir.py: myers_band_rescue_half); a caller asks bgsa_hip_myers_band_rescue.
+ * Early leave: a launch that rescues by the default rule, n = m, lets low words of the window leave before the static band
+ * does — behind a CUT row r the window begins at word w + 1 — and certifies each lane against min(B, D'[r][j_r] + r - j_r),
+ * j_r = 32 (w + 1), instead of B; the lanes above it join the rescue's, and the scores do not change.  The cut rows are a table
+ * by length (150 bp: behind rows 106 and 130, words 1 and 2).  BGSA_MYERS_BAND_EARLY=0|1 (read once) forces it off, or on for
+ * every rescuing launch whose length has cuts (BGSA_MYERS_BAND_RESCUE=1 alone leaves it off).
+ * bgsa_hip_myers_band_early: the cuts such a launch would run with — their number (0: none), rows_out[0 .. n) = the cut rows
+ * (host only, no GPU).
+ * bgsa_hip_myers_band_early_cuts: the table's entry for subjects and queries of `len` at half-width h: rows[j], words[j], and
+ * their number.
+ * bgsa_hip_myers_band_early_segments: the stream of a len x len launch at half-width h with these cuts, as such a launch packs it:
+ * the windows are the schedule's with the cuts applied, everything else is bgsa_hip_myers_band_stream's (n_depths = 0, offsets[0 .. 1])
+ * or bgsa_hip_myers_band_segments' (n_depths >= 1 sharing depths, offsets[0 .. n_depths + 1]).  0 where the cuts are no schedule. */
+int bgsa_hip_myers_band_early(int ref_len, int read_len, int n_queries, int64_t read_count, int *rows_out);
+int bgsa_hip_myers_band_early_cuts(int len, int h, int *rows, int *words);
+int bgsa_hip_myers_band_early_segments(const char *mapped_row, int len, int h, const int *cut_rows, const int *cut_words, int n_cuts,
+                                       const int *depths, int n_depths, unsigned char *dst, int cap, int *offsets);
 int bgsa_hip_myers_band_rescue_half(int len);
 int bgsa_hip_myers_band_rescue(int ref_len, int read_len, int n_queries, int64_t read_count);
 int bgsa_hip_myers_band_rescue_stats(unsigned long long *out, int clear);
