@@ -47,6 +47,12 @@ class SamBatch(ctypes.Structure):
                 ("d_rnext", ctypes.c_void_p), ("d_pnext", ctypes.c_void_p), ("d_tlen", ctypes.c_void_p)]
 
 
+class SamContigs(ctypes.Structure):
+    """bgsa_hip_sam_contigs_t of include/bgsa_hip.h "a reference of several contigs": the name table and the layout, device pointers."""
+    _fields_ = [("d_names", ctypes.c_void_p), ("d_name_offsets", ctypes.c_void_p), ("names_bytes", ctypes.c_int64),
+                ("d_starts", ctypes.c_void_p), ("d_lens", ctypes.c_void_p), ("n_contigs", ctypes.c_int64)]
+
+
 class BgsaHipError(RuntimeError):
     pass
 
@@ -189,6 +195,14 @@ def lib() -> ctypes.CDLL:
     for name, types in (("bgsa_hip_sam_mapq_dev", [vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
                         ("bgsa_hip_sam_measure_dev", [ctypes.POINTER(SamBatch), i64, vp, vp, vp]),
                         ("bgsa_hip_sam_emit_dev", [ctypes.POINTER(SamBatch), i64, vp, vp, i64, vp, vp])):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = i32
+    # a reference of several contigs (the same: an older build lacks them)
+    for name, types in (("bgsa_hip_contig_layout", [vp, i64, i32, i64, vp, vp]),
+                        ("bgsa_hip_contig_clip_dev", [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+                        ("bgsa_hip_sam_measure_contigs_dev", [ctypes.POINTER(SamBatch), ctypes.POINTER(SamContigs), i64, vp, vp, vp]),
+                        ("bgsa_hip_sam_emit_contigs_dev", [ctypes.POINTER(SamBatch), ctypes.POINTER(SamContigs), i64, vp, vp, i64, vp, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = i32
@@ -1200,5 +1214,5 @@ def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: 
 
 
 # reads mapped onto one reference: windows cut on the device, both strands, reference coordinates (bgsa_amd/reference.py)
-from .reference import (PairedHits, Placement, ReferenceHits, ReferenceMapper, SamRecords, blank_beyond, check_sam_call,  # noqa: E402
-                        list_mapq, max_stride, rescue_region, rescue_slots, seed_plan, seed_plan_ragged, window_plan, write_sam)
+from .reference import (ContigHits, ContigMapper, ContigPlacement, PairedHits, Placement, ReferenceHits, ReferenceMapper, SamRecords, blank_beyond, check_sam_call,  # noqa: E402
+                        list_mapq, max_stride, rescue_region, rescue_slots, seed_plan, seed_plan_ragged, window_plan, write_sam, contig_layout, read_fasta)

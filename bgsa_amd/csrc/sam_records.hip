@@ -21,6 +21,7 @@ namespace bgsa {
 namespace {
 
 using Batch = bgsa_hip_sam_batch_t;
+using Contigs = bgsa_hip_sam_contigs_t;
 
 constexpr int kSerialBases = 4;      // an X or D run up to this long is written by its own lane
 constexpr int kOpRefOnly = 1, kOpReadOnly = 2, kOpEqual = 7, kOpDiff = 8;   // the project's run codes: 1 prints as SAM D, 2 as SAM I
@@ -180,6 +181,8 @@ __device__ __forceinline__ Walk walk_runs(const uint32_t *runs, int n_ops, const
 struct Record {
     bool ok, mapped, reverse, mate_named;
     const uint8_t *name, *seq, *qual, *ref;
+    const uint8_t *rname, *rnext;         // RNAME where the record is named; RNEXT where it is a name of its own (else '=' or '*')
+    long long rname_len, rnext_len;
     const uint32_t *runs;
     int name_len, read_len, n_ops;
     long long cigar_bytes, md_bytes;      // of a mapped record: what its runs print as
@@ -190,7 +193,35 @@ struct Record {
 
 __device__ __forceinline__ long long uniform_i64(long long v) { return static_cast<long long>(uniform_u64(static_cast<unsigned long long>(v))); }
 
-__device__ __forceinline__ Record check_record(const Batch &b, int64_t i)
+// The contig that holds the linear position `at` (include/bgsa_hip.h "a reference of several contigs"): a binary search on the
+// starts, every index inside [0, n_contigs).  False where `at` lies on padding or a table entry is outside the reference.
+struct Located {
+    int contig;
+    long long start, end;
+    const uint8_t *name;
+    long long name_len;
+};
+
+__device__ __forceinline__ bool locate(const Contigs &ct, long long ref_len, long long at, Located *out)
+{
+    int lo = 0, hi = static_cast<int>(ct.n_contigs);      // the contigs whose start is <= at are [0, lo)
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (uniform_i64(ct.d_starts[mid]) <= at) lo = mid + 1; else hi = mid;
+    }
+    if (lo < 1) return false;
+    const int c = lo - 1;
+    const long long start = uniform_i64(ct.d_starts[c]), n = uniform_i64(ct.d_lens[c]);
+    if (start < 0 || n < 1 || start > ref_len - n || at >= start + n) return false;
+    const long long name_lo = uniform_i64(ct.d_name_offsets[c]), name_hi = uniform_i64(ct.d_name_offsets[c + 1]);
+    if (name_lo < 0 || name_hi <= name_lo || name_hi > ct.names_bytes) return false;
+    *out = Located{c, start, start + n, ct.d_names + name_lo, name_hi - name_lo};
+    return true;
+}
+
+// CONTIGS: ref_begin, ref_end and pnext of the batch are linear; RNAME, POS, RNEXT and PNEXT are those of the contig form.
+template <bool CONTIGS>
+__device__ __forceinline__ Record check_record(const Batch &b, const Contigs &ct, int64_t i)
 {
     Record r{};
     const long long row = uniform_i64(b.d_read_row[i]), name = uniform_i64(b.d_name_of[i]);
@@ -219,6 +250,15 @@ __device__ __forceinline__ Record check_record(const Batch &b, int64_t i)
     r.pnext = static_cast<unsigned long long>(pnext);
     r.tlen_negative = tlen < 0;
     r.tlen_abs = static_cast<unsigned long long>(tlen < 0 ? -tlen : tlen);
+    r.rname = b.d_rname;
+    r.rname_len = b.rname_len;
+    Located mate{-1, 0, 0, nullptr, 0};
+    if (CONTIGS && r.mate_named) {              // pnext is the mate's linear begin + 1
+        if (pnext < 1 || !locate(ct, b.ref_len, pnext - 1, &mate)) return r;
+        r.pnext = static_cast<unsigned long long>(pnext - mate.start);
+        r.rname = mate.name;                    // of an unmapped end; a mapped one takes its own below
+        r.rname_len = mate.name_len;
+    }
     r.pos = r.mate_named ? r.pnext : 0ull;      // an unmapped end of a pair takes its mapped mate's RNAME and POS
     if (r.mapped) {
         const long long begin = uniform_i64(b.d_ref_begin[i]), end = uniform_i64(b.d_ref_end[i]);
@@ -231,6 +271,17 @@ __device__ __forceinline__ Record check_record(const Batch &b, int64_t i)
         r.ref = b.d_reference + begin;
         r.distance = static_cast<unsigned>(distance);
         r.pos = static_cast<unsigned long long>(begin) + 1ull;
+        if (CONTIGS) {                          // inside ONE contig, or malformed
+            Located own;
+            if (!locate(ct, b.ref_len, begin, &own) || end > own.end) return r;
+            r.pos = static_cast<unsigned long long>(begin - own.start) + 1ull;
+            r.rname = own.name;
+            r.rname_len = own.name_len;
+            if (r.mate_named && mate.contig != own.contig) {
+                r.rnext = mate.name;
+                r.rnext_len = mate.name_len;
+            }
+        }
         const Walk w = walk_runs<false>(r.runs, n_ops, nullptr, nullptr, nullptr, threadIdx.x & (kLanes - 1));
         if (!w.ok || w.ref_bases != end - begin || w.read_bases != read_len) return r;
         r.cigar_bytes = w.cigar_bytes;
@@ -271,7 +322,7 @@ __device__ __forceinline__ long long record_line(const Batch &b, const Record &r
     const bool named = r.mapped || r.mate_named;
     bytes(r.name, r.name_len);
     number(r.flag);
-    if (named) bytes(b.d_rname, b.rname_len); else one('*');
+    if (named) bytes(r.rname, r.rname_len); else one('*');
     number(r.pos);
     number(r.mapq);
     const long long cigar_at = at;
@@ -281,7 +332,7 @@ __device__ __forceinline__ long long record_line(const Batch &b, const Record &r
     } else {
         one('*');
     }
-    one(r.mate_named ? '=' : '*');
+    if (r.rnext) bytes(r.rnext, r.rnext_len); else one(r.mate_named ? '=' : '*');
     number(r.pnext);
     number(r.tlen_abs, r.tlen_negative && r.tlen_abs != 0);
     if (EMIT) {
@@ -319,25 +370,27 @@ __device__ __forceinline__ void count_malformed(int32_t *malformed, int lane)
     if (lane == 0) atomicAdd(malformed, 1);
 }
 
-__global__ __launch_bounds__(256) void sam_measure_kernel(Batch b, int64_t n, int64_t *__restrict__ lengths, int32_t *__restrict__ malformed)
+template <bool CONTIGS>
+__global__ __launch_bounds__(256) void sam_measure_kernel(Batch b, Contigs ct, int64_t n, int64_t *__restrict__ lengths, int32_t *__restrict__ malformed)
 {
     const int lane = threadIdx.x & (kLanes - 1);
     const int64_t i = static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= n) return;              // wave-uniform
-    const Record r = check_record(b, i);
+    const Record r = check_record<CONTIGS>(b, ct, i);
     long long bytes = 0;
     if (r.ok) bytes = record_line<false>(b, r, nullptr, lane);
     else count_malformed(malformed, lane);
     if (lane == 0) lengths[i] = bytes;
 }
 
-__global__ __launch_bounds__(256) void sam_emit_kernel(Batch b, int64_t n, const int64_t *__restrict__ offsets, uint8_t *__restrict__ text,
-                                                       int64_t text_bytes, int32_t *__restrict__ malformed)
+template <bool CONTIGS>
+__global__ __launch_bounds__(256) void sam_emit_kernel(Batch b, Contigs ct, int64_t n, const int64_t *__restrict__ offsets,
+                                                       uint8_t *__restrict__ text, int64_t text_bytes, int32_t *__restrict__ malformed)
 {
     const int lane = threadIdx.x & (kLanes - 1);
     const int64_t i = static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= n) return;              // wave-uniform
-    const Record r = check_record(b, i);
+    const Record r = check_record<CONTIGS>(b, ct, i);
     const long long lo = uniform_i64(offsets[i]), hi = uniform_i64(offsets[i + 1]);
     // written only where the line is exactly what its offsets leave room for, inside the buffer
     if (!r.ok || lo < 0 || hi < lo || hi > text_bytes || record_line<false>(b, r, nullptr, lane) != hi - lo) {
@@ -391,20 +444,52 @@ __global__ __launch_bounds__(256) void sam_mapq_kernel(const int32_t *__restrict
 }
 
 // ---- checks --------------------------------------------------------------------------------------------------------------------
-int check_batch(const char *who, const Batch *b, int64_t n)
+int check_batch(const char *who, const Batch *b, int64_t n, bool one_name = true)
 {
     if (!b) return refuse(who, BGSA_HIP_EINVAL, "the batch is NULL");
     if (n < 0 || n > static_cast<int64_t>(INT32_MAX) * kWavesPerBlock) return refuse(who, BGSA_HIP_EINVAL, "n is negative or beyond one launch");
-    if (!b->d_reads || !b->d_names || !b->d_name_offsets || !b->d_rname || !b->d_reference || !b->d_runs || !b->d_read_row || !b->d_name_of ||
+    if (!b->d_reads || !b->d_names || !b->d_name_offsets || (one_name && !b->d_rname) || !b->d_reference || !b->d_runs || !b->d_read_row || !b->d_name_of ||
         !b->d_runs_row || !b->d_read_len || !b->d_strand || !b->d_ref_begin || !b->d_ref_end || !b->d_distance || !b->d_n_ops || !b->d_flag ||
         !b->d_mapq || !b->d_rnext || !b->d_pnext || !b->d_tlen)
         return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer in the batch (only d_quals may be NULL)");
     if (b->read_stride < 1 || b->read_stride > static_cast<int64_t>(INT32_MAX) || b->n_read_rows < 1)
         return refuse(who, BGSA_HIP_EINVAL, "read_stride must lie in [1, 2^31 - 1] and n_read_rows be positive");
     if (b->n_names < 1 || b->names_bytes < 1) return refuse(who, BGSA_HIP_EINVAL, "n_names and names_bytes must be positive");
-    if (b->rname_len < 1) return refuse(who, BGSA_HIP_EINVAL, "rname_len is not positive");
+    if (one_name && b->rname_len < 1) return refuse(who, BGSA_HIP_EINVAL, "rname_len is not positive");
     if (b->ref_len < 1) return refuse(who, BGSA_HIP_EINVAL, "ref_len is not positive");
     if (b->cigar_cap < 1 || b->n_run_rows < 1) return refuse(who, BGSA_HIP_EINVAL, "cigar_cap and n_run_rows must be positive");
+    return BGSA_HIP_OK;
+}
+
+// The contig form's batch (d_rname and rname_len are not read: RNAME comes from the table) and its table.
+int check_contig_batch(const char *who, const Batch *b, const Contigs *ct, int64_t n)
+{
+    if (int rc = check_batch(who, b, n, false)) return rc;
+    if (!ct) return refuse(who, BGSA_HIP_EINVAL, "the contig table is NULL");
+    if (!ct->d_names || !ct->d_name_offsets || !ct->d_starts || !ct->d_lens) return refuse(who, BGSA_HIP_EINVAL, "a NULL pointer in the contig table");
+    if (ct->n_contigs < 1 || ct->n_contigs > static_cast<int64_t>(INT32_MAX) || ct->names_bytes < 1)
+        return refuse(who, BGSA_HIP_EINVAL, "n_contigs must lie in [1, 2^31 - 1] and the table's names_bytes be positive");
+    return BGSA_HIP_OK;
+}
+
+// The two launches, shared by the one-sequence calls (CONTIGS false, an empty table) and the contig ones.
+template <bool CONTIGS>
+int launch_measure(const Batch *batch, const Contigs &ct, int64_t n, int64_t *d_lengths, int32_t *d_malformed, void *stream)
+{
+    hipLaunchKernelGGL(sam_measure_kernel<CONTIGS>, dim3(static_cast<unsigned>((n + kWavesPerBlock - 1) / kWavesPerBlock)),
+                       dim3(kWavesPerBlock * kLanes), 0, static_cast<hipStream_t>(stream), *batch, ct, n, d_lengths, d_malformed);
+    BGSA_HIP_TRY(hipGetLastError());
+    return BGSA_HIP_OK;
+}
+
+template <bool CONTIGS>
+int launch_emit(const Batch *batch, const Contigs &ct, int64_t n, const int64_t *d_offsets, uint8_t *d_text, int64_t text_bytes,
+                int32_t *d_malformed, void *stream)
+{
+    hipLaunchKernelGGL(sam_emit_kernel<CONTIGS>, dim3(static_cast<unsigned>((n + kWavesPerBlock - 1) / kWavesPerBlock)),
+                       dim3(kWavesPerBlock * kLanes), 0, static_cast<hipStream_t>(stream), *batch, ct, n, d_offsets, d_text, text_bytes,
+                       d_malformed);
+    BGSA_HIP_TRY(hipGetLastError());
     return BGSA_HIP_OK;
 }
 
@@ -437,10 +522,7 @@ int bgsa_hip_sam_measure_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int64
     if (int rc = check_batch(who, batch, n)) return rc;
     if (!d_lengths || !d_malformed) return refuse(who, BGSA_HIP_EINVAL, "d_lengths or d_malformed is NULL");
     if (n == 0) return BGSA_HIP_OK;
-    hipLaunchKernelGGL(sam_measure_kernel, dim3(static_cast<unsigned>((n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kWavesPerBlock * kLanes), 0,
-                       static_cast<hipStream_t>(stream), *batch, n, d_lengths, d_malformed);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
+    return launch_measure<false>(batch, Contigs{}, n, d_lengths, d_malformed, stream);
 }
 
 int bgsa_hip_sam_emit_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, const int64_t *d_offsets, uint8_t *d_text, int64_t text_bytes,
@@ -451,10 +533,28 @@ int bgsa_hip_sam_emit_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, const in
     if (!d_offsets || !d_text || !d_malformed) return refuse(who, BGSA_HIP_EINVAL, "d_offsets, d_text or d_malformed is NULL");
     if (text_bytes < 0) return refuse(who, BGSA_HIP_EINVAL, "text_bytes is negative");
     if (n == 0) return BGSA_HIP_OK;
-    hipLaunchKernelGGL(sam_emit_kernel, dim3(static_cast<unsigned>((n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kWavesPerBlock * kLanes), 0,
-                       static_cast<hipStream_t>(stream), *batch, n, d_offsets, d_text, text_bytes, d_malformed);
-    BGSA_HIP_TRY(hipGetLastError());
-    return BGSA_HIP_OK;
+    return launch_emit<false>(batch, Contigs{}, n, d_offsets, d_text, text_bytes, d_malformed, stream);
+}
+
+int bgsa_hip_sam_measure_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_hip_sam_contigs_t *contigs, int64_t n, int64_t *d_lengths,
+                                     int32_t *d_malformed, void *stream)
+{
+    const char *who = "sam_measure_contigs_dev";
+    if (int rc = check_contig_batch(who, batch, contigs, n)) return rc;
+    if (!d_lengths || !d_malformed) return refuse(who, BGSA_HIP_EINVAL, "d_lengths or d_malformed is NULL");
+    if (n == 0) return BGSA_HIP_OK;
+    return launch_measure<true>(batch, *contigs, n, d_lengths, d_malformed, stream);
+}
+
+int bgsa_hip_sam_emit_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_hip_sam_contigs_t *contigs, int64_t n, const int64_t *d_offsets,
+                                  uint8_t *d_text, int64_t text_bytes, int32_t *d_malformed, void *stream)
+{
+    const char *who = "sam_emit_contigs_dev";
+    if (int rc = check_contig_batch(who, batch, contigs, n)) return rc;
+    if (!d_offsets || !d_text || !d_malformed) return refuse(who, BGSA_HIP_EINVAL, "d_offsets, d_text or d_malformed is NULL");
+    if (text_bytes < 0) return refuse(who, BGSA_HIP_EINVAL, "text_bytes is negative");
+    if (n == 0) return BGSA_HIP_OK;
+    return launch_emit<true>(batch, *contigs, n, d_offsets, d_text, text_bytes, d_malformed, stream);
 }
 
 }  // extern "C"

@@ -14,6 +14,11 @@ Paired reads (include/bgsa_hip.h "paired reads") are that p
 map_pairs maps each end through map_reads_seeded (or map_reads), then per end joins the windows its mate's hits point at
 (rescue_slots, rescue_region, pair_rescue_windows) to the end's own, runs the seeded steps and place_hits on the union at the
 rescue bound, and chooses the best proper pair on the device (pair_select); check_pair_call makes every refusal first.
+
+A reference of SEVERAL contigs (include/bgsa_hip.h "a reference of several contigs") is that one sequence with
+padding between the contigs (contig_layout): ContigMapper builds it, lets the pipeline above run unchanged, clips every placed hit
+to its contig on the device right after place_hits (the hook _after_place), and reports contig and local coordinates (ContigHits);
+its SAM records go through the contig form of the two record passes.
 """
 from __future__ import annotations
 
@@ -543,6 +548,14 @@ class ReferenceMapper:
                                                         keep[lo:hi].data_ptr(), a._stream()), "reference_placements_dev")
         return strand, ref_begin, ref_end, keep, n_ops, cigar
 
+    def _after_place(self, scores, ids, strand, ref_begin, ref_end, keep, n_ops, cigar) -> None:
+        """Called with the device tensors of every place_hits result (_map_bucket, stage B of map_pairs) before anything reads them.
+        One sequence: nothing to do.  ContigMapper clips the hits to their contigs here, in place."""
+
+    def _sam_passes(self) -> tuple:
+        """The two record passes as (measure, emit), each called with the batch and the rest of the C call's arguments."""
+        return B.lib().bgsa_hip_sam_measure_dev, B.lib().bgsa_hip_sam_emit_dev
+
     # ---- the one pipeline behind map_reads, map_reads_ragged, map_reads_seeded and map_reads_seeded_ragged ----------------------
     def _check(self, who: str, longest: int, ragged: bool, k_best, max_distance, cigar_cap, seeded: bool = False, max_candidates=None,
                plan=None) -> tuple:
@@ -578,6 +591,7 @@ class ReferenceMapper:
             scores, ids, counts, stats = self.select_seeded(d_rows, rows.shape[0], rows.shape[1], min(limit, rows.shape[1]), seed[0], k_sel,
                                                             seed[1], block_rows, d_lens=d_lens)
         strand, ref_begin, ref_end, keep, n_ops, cigar = self.place_hits(ids, limit, cap, block_rows, ragged=lens is not None)
+        self._after_place(scores, ids, strand, ref_begin, ref_end, keep, n_ops, cigar)
         a.check_faults()
         if seed is not None:
             flags, totals = counts.cpu().numpy(), tuple(int(x.item()) for x in stats)
@@ -887,6 +901,7 @@ class ReferenceMapper:
             emitted += (rescue >= 0).sum()
             verified += pair_read.numel()
         strand, ref_begin, ref_end, keep, n_ops, cigar = self.place_hits(ids, bound, cap, block_rows)
+        self._after_place(scores, ids, strand, ref_begin, ref_end, keep, n_ops, cigar)
         n_anchors = (anchors[3] != 0).sum(dim=1).clamp(max=k_best).sum()
         return (scores, strand, ref_begin, ref_end, keep, ids, rescued), n_ops, cigar, (n_anchors, emitted, verified, rescued.sum())
 
@@ -1027,8 +1042,9 @@ class ReferenceMapper:
         ref_end, distance, n_ops, flag, mapq, rnext, pnext, tlen; runs [n, cap] int32 holds record i's runs in row i.  Measure, an
         exclusive scan of the lengths with its one scalar read back — it sizes the text —, emit, the text copied once.  A malformed
         record raises; read_label(i) names record i's read in the message."""
-        a, L = self.aligner, B.lib()
+        a = self.aligner
         torch, dev = a.torch, a.device
+        measure, emit = self._sam_passes()
         n = int(fields["strand"].shape[0])
 
         def up(x):
@@ -1048,7 +1064,7 @@ class ReferenceMapper:
                            f["tlen"].data_ptr())
         malformed = torch.zeros(2, dtype=torch.int32, device=dev)
         lengths = torch.empty(n, dtype=torch.int64, device=dev)
-        B.check(L.bgsa_hip_sam_measure_dev(batch, n, lengths.data_ptr(), malformed[0:].data_ptr(), a._stream()), "sam_measure_dev")
+        B.check(measure(batch, n, lengths.data_ptr(), malformed[0:].data_ptr(), a._stream()), "sam_measure_dev")
         offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         offsets[1:] = torch.cumsum(lengths, 0)
         total = int(offsets[-1].item())                 # the one scalar read back: it sizes the text
@@ -1064,8 +1080,7 @@ class ReferenceMapper:
             raise B.BgsaHipError(f"{who}: {int(malformed[0].item())} malformed records, the first the one of {label(i)}: an interval outside "
                                  f"the reference, or runs that do not add up to it and to the read")
         text = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        B.check(L.bgsa_hip_sam_emit_dev(batch, n, offsets.data_ptr(), text.data_ptr(), total, malformed[1:].data_ptr(), a._stream()),
-                "sam_emit_dev")
+        B.check(emit(batch, n, offsets.data_ptr(), text.data_ptr(), total, malformed[1:].data_ptr(), a._stream()), "sam_emit_dev")
         if int(malformed[1].item()):
             raise B.BgsaHipError(f"{who}: the emit pass refused {int(malformed[1].item())} records the measure pass accepted")
         mapped = f["strand"] >= 0
@@ -1265,3 +1280,247 @@ class BeyondSink:
         blanked = (scores.masked_fill(gone, INT32_MIN), strand.masked_fill(gone, -1), ref_begin.masked_fill(gone, -1),
                    ref_end.masked_fill(gone, -1), keep.masked_fill(gone, 0), ids.masked_fill(gone, -1))
         self.sink.add(self.rest[idx], blanked, n_ops, cigar)
+
+
+# ---- a reference of several contigs: include/bgsa_hip.h "a reference of several contigs" -------------------------------------------
+def contig_layout(lens, window_len: int, padding=None) -> tuple[np.ndarray, int]:
+    """(starts int64[C], total) of contigs of the lengths `lens` laid out in one reference with `padding` bytes of 'N' between
+    neighbours (None: window_len): start_0 = 0, start_{i+1} = start_i + len_i + padding, total = start_{C-1} + len_{C-1}.  Refused:
+    no contig, a length below 1, padding < window_len, a total beyond int64.  Pure Python: no device, no library (it restates
+    bgsa_hip_contig_layout)."""
+    W = int(window_len)
+    P = W if padding is None else int(padding)
+    sizes = [int(n) for n in lens]
+    if len(sizes) < 1:
+        raise B.BgsaHipError("contig_layout: rc=-1: n_contigs is not positive")
+    if W < 1 or P < W:
+        raise B.BgsaHipError(f"contig_layout: rc=-1: contig_padding {P} is below window_len {W}: a window would hold bases of two contigs")
+    starts, at = [], 0
+    for i, n in enumerate(sizes):
+        if n < 1:
+            raise B.BgsaHipError(f"contig_layout: rc=-1: contig {i} is empty (a contig length is below 1)")
+        at += P if i else 0
+        starts.append(at)
+        at += n
+        if at > 2 ** 63 - 1:
+            raise B.BgsaHipError("contig_layout: rc=-1: the padded contigs do not fit int64")
+    return np.array(starts, dtype=np.int64), at
+
+
+def read_fasta(data) -> tuple[list, list]:
+    """(names, sequences) of FASTA text: `data` is the text as bytes, or a path.  A record's name is its header up to the first
+    blank; its sequence the lines below, joined, blanks dropped.  Refused: text in front of the first header, no record, an empty
+    name, an empty record, a name given twice."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        with open(data, "rb") as handle:
+            data = handle.read()
+    names, parts = [], []
+    for line in bytes(data).splitlines():
+        line = line.strip()
+        if line.startswith(b">"):
+            words = line[1:].split()
+            if not words:
+                raise B.BgsaHipError(f"read_fasta: rc=-1: record {len(names)} has no name")
+            names.append(words[0].decode("ascii", "replace"))
+            parts.append([])
+        elif line:
+            if not parts:
+                raise B.BgsaHipError("read_fasta: rc=-1: text in front of the first '>' header")
+            parts[-1].append(b"".join(line.split()))
+    if not names:
+        raise B.BgsaHipError("read_fasta: rc=-1: no record")
+    sequences = [b"".join(lines) for lines in parts]
+    for name, sequence in zip(names, sequences):
+        if not sequence:
+            raise B.BgsaHipError(f"read_fasta: rc=-1: record {name} is empty")
+    if len(set(names)) != len(names):
+        twice = next(name for i, name in enumerate(names) if name in names[:i])
+        raise B.BgsaHipError(f"read_fasta: rc=-1: the name {twice} is given twice")
+    return names, sequences
+
+
+class ContigHits(NamedTuple):
+    """What ContigMapper's map_reads entry points return: ReferenceHits with the contig of every slot, the interval LOCAL to it."""
+    scores: np.ndarray      # [ns, k_sel] int32: minus the distance AFTER the clip; INT32_MIN = unused slot
+    strand: np.ndarray
+    ref_begin: np.ndarray   # [ns, k_sel] int64: half-open interval on the forward contig, -1 where the hit is not placed
+    ref_end: np.ndarray
+    keep: np.ndarray
+    cigars: list
+    windows: np.ndarray     # window ids of the padded reference
+    contig: np.ndarray      # [ns, k_sel] int32: the contig's index, -1 where the hit is not placed
+
+
+class ContigPlacement(NamedTuple):
+    contig: int
+    strand: int
+    ref_begin: int
+    ref_end: int
+    distance: int
+    cigar: str
+
+
+class ContigMapper(ReferenceMapper):
+    """A reference of several contigs: names[i] and sequences[i] (bytes, str or 1-D uint8 arrays of ASCII bases) are laid out in ONE
+    padded reference (contig_layout; contig_padding=None: window_len bytes of 'N' between neighbours, and behind the last contig
+    where the whole is shorter than a window), on which ReferenceMapper's pipeline runs unchanged.  Right after every placement the
+    hits are clipped to their contigs on the device (bgsa_hip_contig_clip_dev), so every reported hit lies inside ONE contig: the
+    map_reads entry points return ContigHits, map_pairs PairedHits whose ends are ContigHits, the SAM entry points records with the
+    contig's name and local positions; sam_header writes one @SQ per contig.  contig_starts / contig_lens are the layout.
+
+    Limits: those of ReferenceMapper, and the clip's: the lists are not sorted again, so a hit whose 'N' bases stood on padding can
+    carry a distance above its neighbour's and above max_distance; windows and rescue regions on padding cost time, not correctness;
+    map_pairs refuses insert_max > contig_padding, so mates on different contigs are never proper."""
+
+    def __init__(self, names, sequences, window_len: int, stride: int, contig_padding=None, device: str = "cuda:0", both_strands: bool = True,
+                 segment_windows: int = 65536):
+        who = "ContigMapper"
+        names, sequences = list(names), list(sequences)
+        if len(names) != len(sequences):
+            raise B.BgsaHipError(f"{who}: rc=-1: {len(names)} names for {len(sequences)} sequences")
+        self.contig_names = [_field_bytes(who, f"the name of contig {i}", name).tobytes() for i, name in enumerate(names)]
+        if len(set(self.contig_names)) != len(self.contig_names):
+            twice = next(name for i, name in enumerate(self.contig_names) if name in self.contig_names[:i])
+            raise B.BgsaHipError(f"{who}: rc=-1: the contig name {twice.decode()} is given twice")
+        bases = []
+        for i, sequence in enumerate(sequences):
+            if isinstance(sequence, str):
+                sequence = sequence.encode("ascii")
+            one = np.frombuffer(sequence, dtype=np.uint8) if isinstance(sequence, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(sequence, dtype=np.uint8)
+            if one.ndim != 1 or (one == ord("\n")).any():
+                raise B.BgsaHipError(f"{who}: rc=-1: contig {i} is not the bases of one sequence (1-D, no newline: read_fasta reads a file)")
+            bases.append(one)
+        self.contig_padding = int(window_len) if contig_padding is None else int(contig_padding)
+        self.contig_starts, total = contig_layout([one.size for one in bases], window_len, self.contig_padding)
+        self.contig_lens = np.array([one.size for one in bases], dtype=np.int64)
+        padded = np.full(max(total, int(window_len)), ord("N"), dtype=np.uint8)
+        for at, one in zip(self.contig_starts.tolist(), bases):
+            padded[at: at + one.size] = one
+        super().__init__(padded, window_len, stride, device, both_strands, segment_windows)
+        torch, dev = self.aligner.torch, self.aligner.device
+        self.d_contig_starts = torch.from_numpy(self.contig_starts).to(dev)
+        self.d_contig_lens = torch.from_numpy(self.contig_lens).to(dev)
+        offsets = np.zeros(len(names) + 1, dtype=np.int64)
+        np.cumsum([len(name) for name in self.contig_names], out=offsets[1:])
+        self.d_contig_names = torch.from_numpy(np.frombuffer(b"".join(self.contig_names), dtype=np.uint8).copy()).to(dev)
+        self.d_contig_name_offsets = torch.from_numpy(offsets).to(dev)
+        self.contig_table = B.SamContigs(self.d_contig_names.data_ptr(), self.d_contig_name_offsets.data_ptr(), int(offsets[-1]),
+                                         self.d_contig_starts.data_ptr(), self.d_contig_lens.data_ptr(), len(names))
+
+    # ---- the clip, and the way back to the contigs' own coordinates -----------------------------------------------------------
+    def _after_place(self, scores, ids, strand, ref_begin, ref_end, keep, n_ops, cigar) -> None:
+        a = self.aligner
+        ns, k = ids.shape
+        if not all(x.is_contiguous() for x in (scores, strand, ref_begin, ref_end, keep, n_ops, cigar)):
+            raise B.BgsaHipError("contig_clip_dev: the lists of a placement are not contiguous")
+        contig = a.torch.empty((ns, k), dtype=a.torch.int32, device=a.device)
+        B.check(B.lib().bgsa_hip_contig_clip_dev(self.d_contig_starts.data_ptr(), self.d_contig_lens.data_ptr(), self.contig_lens.size,
+                                                 self.ref_len, ns, k, scores.data_ptr(), strand.data_ptr(), ref_begin.data_ptr(),
+                                                 ref_end.data_ptr(), keep.data_ptr(), n_ops.data_ptr(), cigar.data_ptr(), cigar.shape[2],
+                                                 contig.data_ptr(), a._stream()), "contig_clip_dev")
+
+    def contig_of(self, linear) -> np.ndarray:
+        """The contig whose start is the last one at or below every linear position (int32; -1 for a negative position)."""
+        linear = np.asarray(linear, dtype=np.int64)
+        return np.where(linear >= 0, np.searchsorted(self.contig_starts, linear, side="right") - 1, -1).astype(np.int32)
+
+    def localise(self, hits: ReferenceHits) -> ContigHits:
+        """A result in the padded reference's coordinates — clipped: every placed interval inside one contig — as ContigHits."""
+        contig = self.contig_of(hits.ref_begin)
+        shift = np.where(contig >= 0, self.contig_starts[np.maximum(contig, 0)], 0)
+        return ContigHits(hits.scores, hits.strand, hits.ref_begin - shift, hits.ref_end - shift, hits.keep, hits.cigars, hits.windows, contig)
+
+    def _linear(self, call, *args, **kwargs):
+        """A base-class entry point run with this class's overrides answering in LINEAR coordinates: the base pipeline calls the
+        entry points from one another (the exhaustive pass of a seeded call, stage A of map_pairs) and reads what they return."""
+        self._nested = getattr(self, "_nested", 0) + 1
+        try:
+            return call(*args, **kwargs)
+        finally:
+            self._nested -= 1
+
+    def _contig_hits(self, call, args, kwargs):
+        hits = self._linear(call, *args, **kwargs)
+        return hits if getattr(self, "_nested", 0) else self.localise(hits)
+
+    def map_reads(self, *args, **kwargs) -> ContigHits:
+        """ReferenceMapper.map_reads on the padded reference, clipped: ContigHits."""
+        return self._contig_hits(super().map_reads, args, kwargs)
+
+    def map_reads_ragged(self, *args, **kwargs) -> ContigHits:
+        """ReferenceMapper.map_reads_ragged on the padded reference, clipped: ContigHits."""
+        return self._contig_hits(super().map_reads_ragged, args, kwargs)
+
+    def map_reads_seeded(self, *args, **kwargs) -> ContigHits:
+        """ReferenceMapper.map_reads_seeded on the padded reference, clipped: ContigHits."""
+        return self._contig_hits(super().map_reads_seeded, args, kwargs)
+
+    def map_reads_seeded_ragged(self, *args, **kwargs) -> ContigHits:
+        """ReferenceMapper.map_reads_seeded_ragged on the padded reference, clipped: ContigHits."""
+        return self._contig_hits(super().map_reads_seeded_ragged, args, kwargs)
+
+    def _check_insert(self, who: str, insert_max) -> None:
+        if int(insert_max) > self.contig_padding:
+            raise B.BgsaHipError(f"{who}: rc=-1: insert_max {int(insert_max)} exceeds contig_padding {self.contig_padding}: mates on "
+                                 f"neighbouring contigs could pass for a proper pair (build the mapper with contig_padding >= insert_max)")
+
+    def map_pairs(self, reads1, reads2, insert_min: int, insert_max: int, *args, **kwargs) -> PairedHits:
+        """ReferenceMapper.map_pairs on the padded reference: the pair is chosen on the clipped linear coordinates, the ends come
+        back as ContigHits.  insert_max > contig_padding is refused first."""
+        self._check_insert("map_pairs", insert_max)
+        paired = self._linear(super().map_pairs, reads1, reads2, insert_min, insert_max, *args, **kwargs)
+        return paired._replace(end1=self.localise(paired.end1), end2=self.localise(paired.end2))
+
+    @staticmethod
+    def pairs_of(paired: PairedHits) -> list:
+        """ReferenceMapper.pairs_of with ContigPlacements."""
+        def chosen(hits: ContigHits, c: int, r: int):
+            if r < 0:
+                return None
+            return ContigPlacement(int(hits.contig[c, r]), int(hits.strand[c, r]), int(hits.ref_begin[c, r]), int(hits.ref_end[c, r]),
+                                   -int(hits.scores[c, r]), hits.cigars[c][r])
+        return [(chosen(paired.end1, c, int(paired.slot1[c])), chosen(paired.end2, c, int(paired.slot2[c])), bool(paired.proper[c]))
+                for c in range(paired.proper.shape[0])]
+
+    @staticmethod
+    def placements_of(hits: ContigHits, k_best: int = 1) -> list:
+        """ReferenceMapper.placements_of with ContigPlacements."""
+        out = []
+        for c in range(hits.keep.shape[0]):
+            rows = np.flatnonzero(hits.keep[c])[: int(k_best)]
+            out.append([ContigPlacement(int(hits.contig[c, r]), int(hits.strand[c, r]), int(hits.ref_begin[c, r]), int(hits.ref_end[c, r]),
+                                        -int(hits.scores[c, r]), hits.cigars[c][r]) for r in rows])
+        return out
+
+    # ---- SAM records: the contig form ------------------------------------------------------------------------------------------
+    def sam_header(self, reference_name=None) -> bytes:
+        """@HD (unsorted), one @SQ per contig in order — its name and its own length —, @PG.  reference_name is not used."""
+        lines = [b"@SQ\tSN:" + name + b"\tLN:" + str(int(n)).encode() + b"\n" for name, n in zip(self.contig_names, self.contig_lens)]
+        return b"@HD\tVN:1.6\tSO:unsorted\n" + b"".join(lines) + b"@PG\tID:bgsa-hip\n"
+
+    def _sam_passes(self) -> tuple:
+        L, table = B.lib(), self.contig_table
+        return (lambda batch, *rest: L.bgsa_hip_sam_measure_contigs_dev(batch, table, *rest),
+                lambda batch, *rest: L.bgsa_hip_sam_emit_contigs_dev(batch, table, *rest))
+
+    def sam_records(self, who: str, reads, quals, names, name_offsets, rname, fields: dict, runs, read_label=None) -> SamRecords:
+        """ReferenceMapper.sam_records through the contig passes: the fields are linear, the device localises them; TLEN is set to 0
+        where the mate lies on another contig; the pos column comes back local.  rname is not used."""
+        torch = self.aligner.torch
+        own = torch.searchsorted(self.d_contig_starts, fields["ref_begin"].contiguous(), right=True)
+        mate = torch.searchsorted(self.d_contig_starts, (fields["pnext"] - 1).contiguous(), right=True)
+        fields = dict(fields, tlen=torch.where(own == mate, fields["tlen"], torch.zeros_like(fields["tlen"])))
+        records = super().sam_records(who, reads, quals, names, name_offsets, rname, fields, runs, read_label)
+        at = np.maximum(self.contig_of(records.pos - 1), 0)
+        return records._replace(pos=np.where(records.pos > 0, records.pos - self.contig_starts[at], 0))
+
+    def map_reads_sam(self, reads, names=None, quals=None, reference_name="ref", **kwargs) -> SamRecords:
+        """ReferenceMapper.map_reads_sam with RNAME the contig's name and POS local to it.  reference_name is not used."""
+        return super().map_reads_sam(reads, names, quals, reference_name, **kwargs)
+
+    def map_pairs_sam(self, reads1, reads2, insert_min: int, insert_max: int, *args, **kwargs) -> SamRecords:
+        """ReferenceMapper.map_pairs_sam in the contig form: RNEXT '=' or the mate's contig, PNEXT local, TLEN 0 across contigs; an
+        unmapped end takes its mate's contig.  insert_max > contig_padding is refused first."""
+        self._check_insert("map_pairs_sam", insert_max)
+        return super().map_pairs_sam(reads1, reads2, insert_min, insert_max, *args, **kwargs)

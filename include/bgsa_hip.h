@@ -926,6 +926,73 @@ int bgsa_hip_sam_measure_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int64
 int bgsa_hip_sam_emit_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, const int64_t *d_offsets, uint8_t *d_text, int64_t text_bytes,
                           int32_t *d_malformed, void *stream);
 
+/* ---- a reference of several contigs: one padded layout, hits clipped to their contig, records named by a table ----
+ * The calls above map onto ONE sequence.  A reference of C contigs is laid out as one such sequence with padding between the
+ * contigs; geometry, window ids, the k-mer index, verification, selection, placement and bgsa_hip_reference_placements_dev run
+ * unchanged on it.  What is new sits behind them: the layout, a clip of every placed hit to its contig, and a contig form of the
+ * two record passes.
+ * DEFINITIONS (normative; bgsa_amd/reference.py: contig_layout, ContigMapper and tests/contig_reference.py restate them).
+ *   layout     contigs i = 0..C-1 of len_i >= 1 bases, P >= W bytes of 'N' (code 4) between neighbours: start_0 = 0, start_{i+1} =
+ *              start_i + len_i + P, L = start_{C-1} + len_{C-1}; a caller whose L is below W pads the end with 'N' up to W.  A
+ *              contig may be shorter than the window or than a read.  With P >= W no window holds bases of two contigs, so a
+ *              placement touches one contig and padding on either side; the stride rule gives completeness for every placement
+ *              inside a contig; padding never seeds (a k-mer that holds an 'N' is not indexed).
+ *   clip       of a placed hit (ref_begin >= 0) with interval [begin, end) and runs along the forward reference (ops 1 reference
+ *              only, 2 read only, 7 '=', 8 'X').  Its contig c is the one that holds the first non-padding base of [begin, end) —
+ *              of an empty interval, a hit of read-only bases alone: the one it lies in or at the edge of, and nothing is clipped;
+ *              lead = max(0, start_c - begin), trail = max(0, end - (start_c + len_c)).  The runs are walked from the front for
+ *              lead reference columns: a reference-only column is dropped (distance - 1), an X column becomes a read-only base
+ *              (distance unchanged), an '=' column becomes a read-only base (distance + 1: a read's 'N' on padding); read-only
+ *              runs met on the way, and one that follows directly where the last walked run was used up, stay read-only; all of
+ *              these merge into ONE leading read-only run, followed by the rest of the split run.  The tail likewise, mirrored,
+ *              on the front's result.  Then begin += lead, end -= trail, score = -(new distance), n_ops = the runs the script now
+ *              needs — at most 2 more; above cigar_cap the row is left as it was and n_ops says what is needed.  Entries of the
+ *              row at and behind the new n_ops are not written.  A hit with no contig (an interval outside [0, L] or with begin >
+ *              end, or padding only) becomes unplaced: begin and end -1, n_ops 0, contig -1; its score and strand stay.  A row
+ *              whose n_ops lay outside [0, cigar_cap] before the call is not clipped.  keep of the whole list is then walked again
+ *              on the clipped intervals by bgsa_hip_reference_placements_dev's rule.
+ *   limits     the list is not sorted again: a clipped hit whose 'N' bases stood on padding can carry a distance above its
+ *              neighbour's, and above the bound it was selected within.  For a read without 'N' the clipped distance of a best hit
+ *              is the semi-global distance of the read against its contig alone.
+ *   pairs      bgsa_hip_pair_select_dev runs unchanged on the CLIPPED linear coordinates.  Mates on different contigs are at
+ *              least P apart, so with insert_max <= P — a caller with a larger one is refused — they are never proper.  Rescue
+ *              regions may reach into padding: that costs windows, not correctness.
+ *   records    the contig form of "SAM records": the batch's ref_begin, ref_end and pnext (the mate's POS: its begin + 1) are
+ *              LINEAR; d_rname and rname_len are not read.  A mapped record's contig c holds ref_begin, and ref_end <= start_c +
+ *              len_c, else the record is malformed; RNAME is name c, POS = ref_begin - start_c + 1.  With rnext 1 the mate's contig
+ *              m holds pnext - 1 (on padding, or pnext < 1: malformed), PNEXT = pnext - start_m; RNEXT is '=' when m = c, else name
+ *              m; an unmapped record takes RNAME m, POS = PNEXT and '='.  TLEN is the caller's: 0 across contigs.  MD reads the
+ *              linear reference.  A table entry outside the reference (start < 0, len < 1, start + len > ref_len) or a name outside
+ *              its bytes makes the records that meet it malformed.  Everything else — the two-pass contract, the counting, values
+ *              that never form addresses — is that of the one-sequence calls, whose output does not change.
+ * bgsa_hip_contig_layout: host only, no device — starts_out[n_contigs] and *total_out = L.  BGSA_HIP_EINVAL: a NULL pointer,
+ * n_contigs < 1, a length below 1, padding < window_len (or window_len < 1), a total beyond int64.
+ * bgsa_hip_contig_clip_dev: the lists are d_scores / d_strand / d_ref_begin / d_ref_end / d_keep / d_n_ops [n_reads][k] and
+ * d_cigar [n_reads][k][cigar_cap] as bgsa_hip_reference_placements_dev leaves them; d_scores, d_ref_begin, d_ref_end, d_keep,
+ * d_n_ops and d_cigar are rewritten in place, d_contig (int32 [n_reads][k]) is written: the contig of every placed slot, -1
+ * elsewhere.  d_starts / d_lens: int64 [n_contigs] on the device.  One wave per read, one lane per slot, k in 1..64; the contig by
+ * binary search.  Only a launch on `stream`: no allocation, no synchronisation; n_reads == 0 is BGSA_HIP_OK and launches nothing.
+ * BGSA_HIP_EINVAL, checked before the first HIP call: a NULL pointer (the stream excepted), n_contigs outside [1, 2^31 - 1],
+ * ref_len < 1, k outside 1..64, cigar_cap < 1, a negative n_reads.
+ * bgsa_hip_sam_measure_contigs_dev / bgsa_hip_sam_emit_contigs_dev: bgsa_hip_sam_measure_dev / _emit_dev with the table; the
+ * same refusals (d_rname and rname_len excepted), and a NULL table, a NULL pointer in it, n_contigs outside [1, 2^31 - 1] or
+ * names_bytes < 1. */
+typedef struct bgsa_hip_sam_contigs {
+    const uint8_t *d_names;            /* the contigs' names, flat: name c is [d_name_offsets[c], d_name_offsets[c + 1]) */
+    const int64_t *d_name_offsets;     /* n_contigs + 1 entries */
+    int64_t names_bytes;
+    const int64_t *d_starts, *d_lens;  /* n_contigs entries each: the layout */
+    int64_t n_contigs;
+} bgsa_hip_sam_contigs_t;
+int bgsa_hip_contig_layout(const int64_t *lens, int64_t n_contigs, int window_len, int64_t padding, int64_t *starts_out, int64_t *total_out);
+int bgsa_hip_contig_clip_dev(const int64_t *d_starts, const int64_t *d_lens, int64_t n_contigs, int64_t ref_len, int64_t n_reads, int k,
+                             int32_t *d_scores, const int32_t *d_strand, int64_t *d_ref_begin, int64_t *d_ref_end, int32_t *d_keep,
+                             int32_t *d_n_ops, int32_t *d_cigar, int cigar_cap, int32_t *d_contig, void *stream);
+int bgsa_hip_sam_measure_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_hip_sam_contigs_t *contigs, int64_t n, int64_t *d_lengths,
+                                     int32_t *d_malformed, void *stream);
+int bgsa_hip_sam_emit_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_hip_sam_contigs_t *contigs, int64_t n, const int64_t *d_offsets,
+                                  uint8_t *d_text, int64_t text_bytes, int32_t *d_malformed, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
