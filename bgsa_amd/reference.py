@@ -19,9 +19,15 @@ A reference of SEVERAL contigs (include/bgsa_hip.h "a reference of several conti
 padding between the contigs (contig_layout): ContigMapper builds it, lets the pipeline above run unchanged, clips every placed hit
 to its contig on the device right after place_hits (the hook _after_place), and reports contig and local coordinates (ContigHits);
 its SAM records go through the contig form of the two record passes.
+
+BAM (include/bgsa_hip.h "BAM records") is the SAM stage with another encoding behind the same field assembly:
+map_reads_bam / map_pairs_bam run the SAM entry points' mapping with fmt="bam", and sam_records then measures, scans, emits and
+frames the records into BGZF blocks of stored deflate; bam_header, bgzf_blocks and write_bam make a file of them on the host.
 """
 from __future__ import annotations
 
+import struct
+import zlib
 from typing import NamedTuple
 
 import numpy as np
@@ -417,6 +423,72 @@ def write_sam(path, header: bytes, records: SamRecords) -> None:
         out.write(memoryview(np.ascontiguousarray(records.text)))
 
 
+# ---- BAM records: include/bgsa_hip.h "BAM records" — the host side, no device, no library ---------------------------------------
+class BamRecords(NamedTuple):
+    """What ReferenceMapper.map_reads_bam and map_pairs_bam return: the records in BAM's layout inside BGZF blocks of stored
+    deflate, as the device wrote them, and SamRecords' four columns."""
+    blocks: np.ndarray      # uint8: the framed BGZF blocks of this call's records, without the BAM header and without the EOF block
+    offsets: np.ndarray     # int64[n + 1]: record i, its block_size included, is payload[offsets[i] : offsets[i + 1]] of the inflated blocks
+    flag: np.ndarray        # int32[n]
+    pos: np.ndarray         # int64[n]: POS, 1-based; 0 for an unmapped record without a mapped mate
+    mapq: np.ndarray        # int32[n]
+    nm: np.ndarray          # int32[n]: the distance, -1 for an unmapped record
+
+
+BGZF_BLOCK_PAYLOAD = 0xff00       # 65,280: what every BGZF writer puts into a block; the format's own limit is 65,505
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")      # SAMv1 §4.1.2: the empty block that ends a file
+
+
+def bgzf_blocks(data, block_payload: int = BGZF_BLOCK_PAYLOAD) -> bytes:
+    """`data` in BGZF blocks of STORED deflate, block_payload bytes each (the last may be shorter; no data: no block), the framing
+    bgsa_hip_bgzf_frame_dev writes on the device — here for the BAM header.  Without the EOF block."""
+    if not 1 <= int(block_payload) <= BGZF_BLOCK_PAYLOAD:
+        raise B.BgsaHipError(f"bgzf_blocks: rc=-1: block_payload {block_payload} outside 1..{BGZF_BLOCK_PAYLOAD}")
+    data, out = bytes(data), []
+    for at in range(0, len(data), int(block_payload)):
+        piece = data[at: at + int(block_payload)]
+        out.append(b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<HBHH", len(piece) + 30, 1, len(piece),
+                                                                                               len(piece) ^ 0xffff))
+        out.append(piece)
+        out.append(struct.pack("<II", zlib.crc32(piece), len(piece)))
+    return b"".join(out)
+
+
+def bam_header_bytes(who: str, text: bytes, references) -> bytes:
+    """The uncompressed BAM header: the magic, l_text and the SAM header text, n_ref, and l_name, the name + NUL and l_ref of every
+    (name, length) of `references`.  A length beyond 2^31 - 1 is refused."""
+    out = [b"BAM\x01", struct.pack("<i", len(text)), text, struct.pack("<i", len(references))]
+    for name, n in references:
+        if int(n) > 2 ** 31 - 1:
+            raise B.BgsaHipError(f"{who}: rc=-1: {name.decode()} has {int(n)} bases, a BAM header holds 2^31 - 1 at the most")
+        out += [struct.pack("<i", len(name) + 1), name, b"\x00", struct.pack("<i", int(n))]
+    return b"".join(out)
+
+
+def check_bam_call(who: str, lens, names, quals, reference_name, block_payload=BGZF_BLOCK_PAYLOAD) -> tuple:
+    """check_sam_call's refusals and returns, then BAM's own, before anything is launched or allocated: a name longer than 254
+    bytes (l_read_name is one byte and counts the NUL), a block_payload outside 1..65,280."""
+    checked = check_sam_call(who, lens, names, quals, reference_name)
+    name_lens = np.diff(checked[2])
+    if (name_lens > 254).any():
+        c = int(np.flatnonzero(name_lens > 254)[0])
+        raise B.BgsaHipError(f"{who}: rc=-1: the name of read {c} has {int(name_lens[c])} bytes, a BAM record holds 254 at the most")
+    if isinstance(block_payload, bool) or not isinstance(block_payload, (int, np.integer)) or not 1 <= int(block_payload) <= BGZF_BLOCK_PAYLOAD:
+        raise B.BgsaHipError(f"{who}: rc=-1: block_payload {block_payload!r} outside 1..{BGZF_BLOCK_PAYLOAD}")
+    return checked
+
+
+def write_bam(path, header: bytes, records) -> None:
+    """A BAM file: the header (ReferenceMapper.bam_header, uncompressed) framed by bgzf_blocks, the blocks of `records` — one
+    BamRecords or a sequence of them, in order: batches of reads stream into one file —, then BGZF_EOF."""
+    batches = [records] if isinstance(records, BamRecords) else list(records)
+    with open(path, "wb") as out:
+        out.write(bgzf_blocks(header))
+        for batch in batches:
+            out.write(memoryview(np.ascontiguousarray(batch.blocks)))
+        out.write(BGZF_EOF)
+
+
 class SeedBucket(NamedTuple):
     """What the steps of select_seeded share for one resident bucket (ReferenceMapper.seed_bucket)."""
     d_rows: object          # the bucket's ASCII rows on the device, read_len + 1 bytes each
@@ -552,9 +624,9 @@ class ReferenceMapper:
         """Called with the device tensors of every place_hits result (_map_bucket, stage B of map_pairs) before anything reads them.
         One sequence: nothing to do.  ContigMapper clips the hits to their contigs here, in place."""
 
-    def _sam_passes(self) -> tuple:
+    def _sam_passes(self, fmt: str = "sam") -> tuple:
         """The two record passes as (measure, emit), each called with the batch and the rest of the C call's arguments."""
-        return B.lib().bgsa_hip_sam_measure_dev, B.lib().bgsa_hip_sam_emit_dev
+        return getattr(B.lib(), f"bgsa_hip_{fmt}_measure_dev"), getattr(B.lib(), f"bgsa_hip_{fmt}_emit_dev")
 
     # ---- the one pipeline behind map_reads, map_reads_ragged, map_reads_seeded and map_reads_seeded_ragged ----------------------
     def _check(self, who: str, longest: int, ragged: bool, k_best, max_distance, cigar_cap, seeded: bool = False, max_candidates=None,
@@ -1013,6 +1085,12 @@ class ReferenceMapper:
         name = _field_bytes("sam_header", "reference_name", reference_name).tobytes()
         return b"@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:" + name + b"\tLN:" + str(self.ref_len).encode() + b"\n@PG\tID:bgsa-hip\n"
 
+    def bam_header(self, reference_name="ref") -> bytes:
+        """The UNCOMPRESSED BAM header of this mapper's one reference: the magic, sam_header's text, one reference entry.  write_bam
+        frames it."""
+        name = _field_bytes("bam_header", "reference_name", reference_name).tobytes()
+        return bam_header_bytes("bam_header", self.sam_header(reference_name), [(name, self.ref_len)])
+
     def sam_list_mapq(self, scores, keep, bound: int) -> tuple:
         """bgsa_hip_sam_mapq_dev on device tensors scores, keep [ns, k]: (primary slot, mapq, n1, d2), int32[ns] each."""
         a = self.aligner
@@ -1036,15 +1114,18 @@ class ReferenceMapper:
         runs = cigar.gather(1, at.unsqueeze(2).expand(-1, 1, cigar.shape[2])).squeeze(1)
         return pick(strand).masked_fill(slot < 0, -1), pick(ref_begin), pick(ref_end), -pick(scores), pick(n_ops), runs
 
-    def sam_records(self, who: str, reads: np.ndarray, quals, names, name_offsets, rname, fields: dict, runs, read_label=None) -> SamRecords:
+    def sam_records(self, who: str, reads: np.ndarray, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, fmt: str = "sam",
+                    block_payload: int = BGZF_BLOCK_PAYLOAD):
         """The two record passes.  reads [n_rows, stride] and quals (or None) are the host rows, names / name_offsets / rname what
         check_sam_call returned; fields holds the per-record DEVICE tensors read_row, name_of (int64), read_len, strand, ref_begin,
         ref_end, distance, n_ops, flag, mapq, rnext, pnext, tlen; runs [n, cap] int32 holds record i's runs in row i.  Measure, an
         exclusive scan of the lengths with its one scalar read back — it sizes the text —, emit, the text copied once.  A malformed
-        record raises; read_label(i) names record i's read in the message."""
+        record raises; read_label(i) names record i's read in the message.  fmt "bam": the same passes of the BAM stage, then the
+        payload framed into BGZF blocks of block_payload bytes on the device (bgsa_hip_bgzf_frame_dev) and the blocks copied once:
+        BamRecords, its offsets in payload coordinates."""
         a = self.aligner
         torch, dev = a.torch, a.device
-        measure, emit = self._sam_passes()
+        measure, emit = self._sam_passes(fmt)
         n = int(fields["strand"].shape[0])
 
         def up(x):
@@ -1064,7 +1145,7 @@ class ReferenceMapper:
                            f["tlen"].data_ptr())
         malformed = torch.zeros(2, dtype=torch.int32, device=dev)
         lengths = torch.empty(n, dtype=torch.int64, device=dev)
-        B.check(measure(batch, n, lengths.data_ptr(), malformed[0:].data_ptr(), a._stream()), "sam_measure_dev")
+        B.check(measure(batch, n, lengths.data_ptr(), malformed[0:].data_ptr(), a._stream()), f"{fmt}_measure_dev")
         offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         offsets[1:] = torch.cumsum(lengths, 0)
         total = int(offsets[-1].item())                 # the one scalar read back: it sizes the text
@@ -1078,17 +1159,25 @@ class ReferenceMapper:
                                      f"(raise cigar_cap)")
             i = int(torch.nonzero(lengths == 0).reshape(-1)[0].item())
             raise B.BgsaHipError(f"{who}: {int(malformed[0].item())} malformed records, the first the one of {label(i)}: an interval outside "
-                                 f"the reference, or runs that do not add up to it and to the read")
+                                 f"the reference, or runs that do not add up to it and to the read" +
+                                 (", or a position, PNEXT or TLEN beyond int32, or more than 65,535 runs" if fmt == "bam" else ""))
         text = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        B.check(emit(batch, n, offsets.data_ptr(), text.data_ptr(), total, malformed[1:].data_ptr(), a._stream()), "sam_emit_dev")
+        B.check(emit(batch, n, offsets.data_ptr(), text.data_ptr(), total, malformed[1:].data_ptr(), a._stream()), f"{fmt}_emit_dev")
         if int(malformed[1].item()):
             raise B.BgsaHipError(f"{who}: the emit pass refused {int(malformed[1].item())} records the measure pass accepted")
         mapped = f["strand"] >= 0
         pos = torch.where(mapped, f["ref_begin"] + 1, f["pnext"] * f["rnext"])
         nm = f["distance"].masked_fill(~mapped, -1)
         mapq = f["mapq"].masked_fill(~mapped, 0)
-        return SamRecords(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(), mapq.cpu().numpy(),
-                          nm.cpu().numpy())
+        kind = SamRecords
+        if fmt == "bam":
+            framed = int(B.lib().bgsa_hip_bgzf_framed_bytes(total, int(block_payload)))
+            blocks = torch.empty(max(framed, 1), dtype=torch.uint8, device=dev)
+            B.check(B.lib().bgsa_hip_bgzf_frame_dev(text.data_ptr(), total, int(block_payload), blocks.data_ptr(), framed, a._stream()),
+                    "bgzf_frame_dev")
+            kind, text, total = BamRecords, blocks, framed
+        return kind(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(), mapq.cpu().numpy(),
+                    nm.cpu().numpy())
 
     def _sam_rows(self, who: str, reads) -> tuple:
         """(rows, lens, ragged) of a SAM call's reads: a [ns, n] array as it is, anything else as a list of mixed lengths."""
@@ -1137,17 +1226,40 @@ class ReferenceMapper:
         list is its best windows whatever their distance; a second locus is only sure to be listed with k_best >= 2, hence the default.  names=None: r0,
         r1, ...; quals=None: '*'.  check_sam_call refuses before anything is launched.  Nothing but the text, its offsets and four
         columns is copied back; no CIGAR string is made on the host."""
-        who = "map_reads_sam"
+        return self._map_reads_records("sam", None, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len, max_candidates,
+                                       block_rows, cigar_cap)
+
+    def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
+                      seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None,
+                      block_payload: int = BGZF_BLOCK_PAYLOAD) -> BamRecords:
+        """map_reads_sam — the same arguments, mapping and record selection — with the records in BAM's layout inside BGZF blocks of
+        stored deflate, block_payload bytes of records each (include/bgsa_hip.h "BAM records"): measure, scan, emit, frame, all on the
+        device, one copy of the blocks.  A record may straddle blocks.  check_bam_call refuses before anything is launched; with
+        bam_header and write_bam the blocks of one or more calls make a file."""
+        return self._map_reads_records("bam", block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
+                                       max_candidates, block_rows, cigar_cap)
+
+    @staticmethod
+    def _check_records_call(fmt: str, who: str, lens, names, quals, reference_name, block_payload) -> tuple:
+        if fmt == "bam":
+            return check_bam_call(who, lens, names, quals, reference_name, block_payload)
+        return check_sam_call(who, lens, names, quals, reference_name)
+
+    def _map_reads_records(self, fmt: str, block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
+                           max_candidates, block_rows, cigar_cap):
+        """What map_reads_sam and map_reads_bam share: everything but the format of the records."""
+        who = f"map_reads_{fmt}"
         rows, lens, ragged = self._sam_rows(who, reads)
-        rname, flat, name_offsets, qual_rows = check_sam_call(who, lens, names, quals, reference_name)
+        rname, flat, name_offsets, qual_rows = self._check_records_call(fmt, who, lens, names, quals, reference_name, block_payload)
         bound = int(max_distance) if seeded and max_distance is not None else -1
         sink = self._map_to(lambda ns, k_sel, cap: PrimarySink(self, ns, cap, bound), rows, lens, ragged, k_best, max_distance, seeded, seed_len,
                             max_candidates, block_rows, cigar_cap)
         self.aligner.check_faults()
-        return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname)
+        return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname, fmt=fmt, block_payload=block_payload)
 
-    def sam_single_records(self, who: str, sink: "PrimarySink", rows: np.ndarray, lens, qual_rows, names, name_offsets, rname) -> SamRecords:
-        """The records of single-end reads from their primaries on the device: flag 0, 16 or 4, no mate fields."""
+    def sam_single_records(self, who: str, sink: "PrimarySink", rows: np.ndarray, lens, qual_rows, names, name_offsets, rname, **form):
+        """The records of single-end reads from their primaries on the device: flag 0, 16 or 4, no mate fields.  form: sam_records'
+        fmt and block_payload."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = rows.shape[0]
         index = torch.arange(ns, dtype=torch.int64, device=dev)
@@ -1156,7 +1268,7 @@ class ReferenceMapper:
         fields = dict(read_row=index, name_of=index, read_len=torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev),
                       strand=sink.strand, ref_begin=sink.ref_begin, ref_end=sink.ref_end, distance=sink.distance, n_ops=sink.n_ops,
                       flag=flag, mapq=sink.mapq, rnext=torch.zeros(ns, dtype=torch.int32, device=dev), pnext=zero, tlen=zero)
-        return self.sam_records(who, rows, qual_rows, names, name_offsets, rname, fields, sink.runs)
+        return self.sam_records(who, rows, qual_rows, names, name_offsets, rname, fields, sink.runs, **form)
 
     def map_pairs_sam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
                       reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
@@ -1166,12 +1278,26 @@ class ReferenceMapper:
         where the mate is mapped; TLEN where both are; an unmapped end beside a mapped mate takes the mate's RNAME and POS.  MAPQ:
         pair_mapq.  One name per pair.  The stages are map_pairs' own (stage A through the same pipeline, without its strings);
         last_pair_stats is not touched.  check_sam_call and check_pair_call refuse before anything is launched."""
-        who = "map_pairs_sam"
+        return self._map_pairs_records("sam", None, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
+                                       max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap)
+
+    def map_pairs_bam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
+                      reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
+                      max_candidates=None, block_rows: int = 1000, cigar_cap=None, block_payload: int = BGZF_BLOCK_PAYLOAD) -> BamRecords:
+        """map_pairs_sam — the same arguments, stages and records — in BAM's layout inside BGZF blocks (map_reads_bam)."""
+        return self._map_pairs_records("bam", block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name,
+                                       k_best, max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap)
+
+    def _map_pairs_records(self, fmt: str, block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
+                           max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap):
+        """What map_pairs_sam and map_pairs_bam share: everything but the format of the records."""
+        who = f"map_pairs_{fmt}"
         reads = (self._one_length(who, reads1), self._one_length(who, reads2))
         ns = reads[0].shape[0]
         if (quals1 is None) != (quals2 is None):
             raise B.BgsaHipError(f"{who}: rc=-1: quals1 and quals2 come together")
-        checked = [check_sam_call(who, np.full(ns, rows.shape[1]), names, quals, reference_name) for rows, quals in zip(reads, (quals1, quals2))]
+        checked = [self._check_records_call(fmt, who, np.full(ns, rows.shape[1]), names, quals, reference_name, block_payload)
+                   for rows, quals in zip(reads, (quals1, quals2))]
         call = check_pair_call(self.both_strands, reads[0].shape, reads[1].shape, insert_min, insert_max, k_best, max_distance,
                                rescue_distance, seeded, seed_len, max_candidates, cigar_cap, self.window_len, self.stride, self.ref_len,
                                self.n_ids)
@@ -1184,11 +1310,12 @@ class ReferenceMapper:
         ends = [self._rescue_checked(e, reads, single, call, insert_max, block_rows) for e in range(2)]      # stage B
         chosen = self.pair_select(ends[0][0][:5], ends[1][0][:5], insert_min, insert_max, block_rows)      # stage C
         a.check_faults()
-        return self.sam_pair_records(who, reads, ends, chosen, call, checked)
+        return self.sam_pair_records(who, reads, ends, chosen, call, checked, fmt=fmt, block_payload=block_payload)
 
-    def sam_pair_records(self, who: str, reads, ends, chosen, call: dict, checked) -> SamRecords:
+    def sam_pair_records(self, who: str, reads, ends, chosen, call: dict, checked, **form):
         """The records of pairs from the device results of map_pairs' stages: ends[e] = rescue_end's return for end e, chosen =
-        pair_select's, call = check_pair_call's dict, checked[e] = check_sam_call's return for end e."""
+        pair_select's, call = check_pair_call's dict, checked[e] = check_sam_call's return for end e.  form: sam_records' fmt and
+        block_payload."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = reads[0].shape[0]
         lists = [final for final, _, _, _ in ends]
@@ -1227,7 +1354,7 @@ class ReferenceMapper:
         rname, flat, name_offsets, _ = checked[0]
         return self.sam_records(who, rows.reshape(2 * ns, stride), None if qual_rows is None else qual_rows.reshape(2 * ns, stride), flat,
                                 name_offsets, rname, fields, interleave(picked[0][5], picked[1][5]),
-                                read_label=lambda i: f"end {i % 2 + 1} of pair {i // 2}")
+                                read_label=lambda i: f"end {i % 2 + 1} of pair {i // 2}", **form)
 
 
 # ---- the sinks of ReferenceMapper._map_bins: what the SAM entry points keep of a bucket's device tensors ---------------------------
@@ -1499,19 +1626,24 @@ class ContigMapper(ReferenceMapper):
         lines = [b"@SQ\tSN:" + name + b"\tLN:" + str(int(n)).encode() + b"\n" for name, n in zip(self.contig_names, self.contig_lens)]
         return b"@HD\tVN:1.6\tSO:unsorted\n" + b"".join(lines) + b"@PG\tID:bgsa-hip\n"
 
-    def _sam_passes(self) -> tuple:
+    def _sam_passes(self, fmt: str = "sam") -> tuple:
         L, table = B.lib(), self.contig_table
-        return (lambda batch, *rest: L.bgsa_hip_sam_measure_contigs_dev(batch, table, *rest),
-                lambda batch, *rest: L.bgsa_hip_sam_emit_contigs_dev(batch, table, *rest))
+        measure, emit = getattr(L, f"bgsa_hip_{fmt}_measure_contigs_dev"), getattr(L, f"bgsa_hip_{fmt}_emit_contigs_dev")
+        return (lambda batch, *rest: measure(batch, table, *rest), lambda batch, *rest: emit(batch, table, *rest))
 
-    def sam_records(self, who: str, reads, quals, names, name_offsets, rname, fields: dict, runs, read_label=None) -> SamRecords:
+    def bam_header(self, reference_name=None) -> bytes:
+        """The UNCOMPRESSED BAM header: sam_header's text and one reference entry per contig, in the order refID counts them.
+        reference_name is not used."""
+        return bam_header_bytes("bam_header", self.sam_header(), list(zip(self.contig_names, self.contig_lens.tolist())))
+
+    def sam_records(self, who: str, reads, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, **form):
         """ReferenceMapper.sam_records through the contig passes: the fields are linear, the device localises them; TLEN is set to 0
-        where the mate lies on another contig; the pos column comes back local.  rname is not used."""
+        where the mate lies on another contig; the pos column comes back local.  rname is not used.  form: fmt and block_payload."""
         torch = self.aligner.torch
         own = torch.searchsorted(self.d_contig_starts, fields["ref_begin"].contiguous(), right=True)
         mate = torch.searchsorted(self.d_contig_starts, (fields["pnext"] - 1).contiguous(), right=True)
         fields = dict(fields, tlen=torch.where(own == mate, fields["tlen"], torch.zeros_like(fields["tlen"])))
-        records = super().sam_records(who, reads, quals, names, name_offsets, rname, fields, runs, read_label)
+        records = super().sam_records(who, reads, quals, names, name_offsets, rname, fields, runs, read_label, **form)
         at = np.maximum(self.contig_of(records.pos - 1), 0)
         return records._replace(pos=np.where(records.pos > 0, records.pos - self.contig_starts[at], 0))
 
@@ -1524,3 +1656,14 @@ class ContigMapper(ReferenceMapper):
         unmapped end takes its mate's contig.  insert_max > contig_padding is refused first."""
         self._check_insert("map_pairs_sam", insert_max)
         return super().map_pairs_sam(reads1, reads2, insert_min, insert_max, *args, **kwargs)
+
+    def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", **kwargs) -> BamRecords:
+        """ReferenceMapper.map_reads_bam with refID the contig's index in bam_header's order and pos local to it.  reference_name is not
+        used."""
+        return super().map_reads_bam(reads, names, quals, reference_name, **kwargs)
+
+    def map_pairs_bam(self, reads1, reads2, insert_min: int, insert_max: int, *args, **kwargs) -> BamRecords:
+        """ReferenceMapper.map_pairs_bam in the contig form: next_refID the mate's contig, next_pos local, tlen 0 across contigs.
+        insert_max > contig_padding is refused first."""
+        self._check_insert("map_pairs_bam", insert_max)
+        return super().map_pairs_bam(reads1, reads2, insert_min, insert_max, *args, **kwargs)

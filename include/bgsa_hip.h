@@ -993,6 +993,61 @@ int bgsa_hip_sam_measure_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bg
 int bgsa_hip_sam_emit_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_hip_sam_contigs_t *contigs, int64_t n, const int64_t *d_offsets,
                                   uint8_t *d_text, int64_t text_bytes, int32_t *d_malformed, void *stream);
 
+/* ---- BAM records: the records of "SAM records" in BAM's binary layout, and BGZF blocks around them, written by the device ----
+ * What downstream tools read is BAM, not text.  The same bgsa_hip_sam_batch_t (and bgsa_hip_sam_contigs_t) goes through two passes
+ * of the same contract as the SAM ones — bgsa_hip_bam_measure_dev returns every record's byte length, the caller scans the
+ * lengths and reads one scalar back, bgsa_hip_bam_emit_dev writes the records into one payload buffer —, and
+ * bgsa_hip_bgzf_frame_dev then wraps the payload into BGZF blocks of STORED deflate: a valid BAM stream once the caller puts the
+ * header in front and the EOF block behind (bgsa_amd/reference.py: bam_header, write_bam, BGZF_EOF).  No compressor.
+ * DEFINITIONS (normative; SAMv1 §4.1, §4.2, §5.3; tests/bam_reference.py restates them).
+ *   a record   every value is that of the record's SAM line; all integers little-endian; a record starts at any byte address.
+ *     block_size  int32: the record's length minus these 4 bytes.  d_lengths[i] and the offsets count the 4 bytes in.
+ *     refID, pos  int32: the contig's index (0 in the one-sequence calls) and POS - 1.  An unmapped end beside a mapped mate
+ *              (rnext 1) takes the mate's, as the line does; any other unmapped record -1 and -1.
+ *     l_read_name uint8: the name's length + 1.     mapq uint8: 0 when unmapped.
+ *     bin      uint16: reg2bin(pos, end) of SAMv1 §5.3, its low 16 bits; end = pos + the reference bases of the runs, pos + 1
+ *              where that is 0 or the record is unmapped; 4680 = reg2bin(-1, 0) where pos is -1.
+ *     n_cigar_op uint16 (0 when unmapped), flag uint16, l_seq uint32 (the read's length).
+ *     next_refID, next_pos, tlen   int32: RNEXT as an index ('=': the record's refID, '*': -1), PNEXT - 1, TLEN.
+ *     read_name  the name and a NUL.
+ *     cigar    uint32[n_cigar_op], length << 4 | op: the library's run op 1 (reference only) is BAM's D 2, op 2 (read only) I 1,
+ *              7 '=' stays 7, 8 'X' stays 8.
+ *     seq      uint8[(l_seq + 1) / 2]: SEQ as the line prints it (a reverse hit reverse-complemented, anything but ACGT then N), two
+ *              bases a byte, the first in the high nibble, each the letter's index in "=ACMGRSVTWYHKDBN" whatever its case, 15
+ *              for any other byte; a last odd nibble is 0.
+ *     qual     uint8[l_seq]: QUAL - 33, reversed on a reverse hit; 0xff in every byte where d_quals is NULL.
+ *     tags     of a mapped record only: 'N' 'M' 'i' and the distance as int32; 'M' 'D' 'Z', the MD text of "SAM records", a NUL.
+ *   malformed  what "SAM records" (and its contig form) calls malformed, and a name longer than 254 bytes, n_ops > 65535, a POS - 1,
+ *              PNEXT - 1 or TLEN outside int32 (the read's length is an int32 already).  Pass 1 gives such a record length 0, pass 2
+ *              writes nothing for it, each call adds the malformed records it met to *d_malformed, and none of its values forms an
+ *              address.  Pass 2 also treats as malformed a record that is not exactly d_offsets[i + 1] - d_offsets[i] bytes long
+ *              or whose bytes would leave [0, payload_bytes).
+ *   BGZF       block b of the framed output carries payload bytes [b * P, min((b + 1) * P, total)), P = block_payload, LEN of
+ *              them: 1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, the subfield 'B' 'C' 2 0 BSIZE with BSIZE = LEN + 30 (the block's
+ *              length - 1), one stored deflate block 01 LEN ~LEN (uint16 each), the bytes, their CRC-32 (IEEE, reflected: zlib's),
+ *              ISIZE = LEN: LEN + 31 bytes.  Blocks follow one another without gaps; the last may be shorter; an empty payload
+ *              gives no block.  The 28-byte EOF block is NOT written: it belongs to the file, not to a batch.  The framing knows
+ *              nothing about BAM; a record may straddle blocks.
+ * bgsa_hip_bgzf_framed_bytes: host only — payload_bytes + 31 * ceil(payload_bytes / block_payload); 0 for an empty payload; -1 for
+ * a negative payload_bytes, one beyond 2^58, or a block_payload outside 1..65280 (0xff00, what every BGZF writer uses; the
+ * format's own limit is 65505).
+ * One wave per record; one workgroup per BGZF block, its threads on contiguous slices whose CRC states are joined by the CRC's
+ * linearity (bgzf.hip).  All five device calls only launch on `stream`: no allocation, no synchronisation, no workspace; n == 0
+ * and payload_bytes == 0 are BGSA_HIP_OK and launch nothing.  BGSA_HIP_EINVAL, checked before the first HIP call: what the SAM
+ * passes refuse (payload_bytes for text_bytes); for the framing a NULL pointer (the stream excepted), a block_payload outside
+ * 1..65280, a negative payload_bytes, an out_bytes that is not bgsa_hip_bgzf_framed_bytes(payload_bytes, block_payload).
+ * The C loop: fill the batch; measure; lengths -> offsets[n + 1]; read offsets[n] back; allocate payload and framed output; emit;
+ * frame; read *d_malformed. */
+int bgsa_hip_bam_measure_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int64_t *d_lengths, int32_t *d_malformed, void *stream);
+int bgsa_hip_bam_emit_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, const int64_t *d_offsets, uint8_t *d_payload, int64_t payload_bytes,
+                          int32_t *d_malformed, void *stream);
+int bgsa_hip_bam_measure_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_hip_sam_contigs_t *contigs, int64_t n, int64_t *d_lengths,
+                                     int32_t *d_malformed, void *stream);
+int bgsa_hip_bam_emit_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_hip_sam_contigs_t *contigs, int64_t n, const int64_t *d_offsets,
+                                  uint8_t *d_payload, int64_t payload_bytes, int32_t *d_malformed, void *stream);
+int64_t bgsa_hip_bgzf_framed_bytes(int64_t payload_bytes, int block_payload);
+int bgsa_hip_bgzf_frame_dev(const uint8_t *d_payload, int64_t payload_bytes, int block_payload, uint8_t *d_out, int64_t out_bytes, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
