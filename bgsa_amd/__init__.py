@@ -205,7 +205,10 @@ def lib() -> ctypes.CDLL:
                                  ("bgsa_hip_bam_emit_contigs_dev", [ctypes.POINTER(SamBatch), ctypes.POINTER(SamContigs), i64, vp, vp, i64, vp, vp],
                                   i32),
                                  ("bgsa_hip_bgzf_framed_bytes", [i64, i32], i64),
-                                 ("bgsa_hip_bgzf_frame_dev", [vp, i64, i32, vp, i64, vp], i32)):
+                                 ("bgsa_hip_bgzf_frame_dev", [vp, i64, i32, vp, i64, vp], i32),
+                                 ("bgsa_hip_bgzf_deflate_workspace_bytes", [i64, i32], i64),
+                                 ("bgsa_hip_bgzf_deflate_dev", [vp, i64, i32, vp, i64, vp, vp, i64, vp], i32),
+                                 ("bgsa_hip_bgzf_pack_dev", [vp, i32, i64, vp, vp, i64, vp, vp], i32)):
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype

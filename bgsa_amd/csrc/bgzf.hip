@@ -9,6 +9,7 @@
 // join them.  Payload and output may start at any byte address: byte loads and byte stores.  No scratch, vector stores only.
 // The output's extent is the caller's out_bytes, which must equal bgsa_hip_bgzf_framed_bytes: every block lies inside it.
 #include "bgsa_common.h"
+#include "bgzf_crc.h"
 
 #include <limits.h>
 
@@ -19,32 +20,6 @@ namespace {
 constexpr int kFrameThreads = 256;
 constexpr int kBlockExtra = 31;               // 18 + 5 in front of the bytes, 8 behind them
 constexpr int kBlockPayloadMax = 0xff00;      // what every BGZF writer uses; the format's own limit is 65,505
-constexpr uint32_t kCrcPoly = 0xedb88320u;    // IEEE 802.3, reflected
-
-// a * b mod the polynomial, both reflected (bit 31 is x^0).
-__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b)
-{
-    uint32_t p = 0;
-#pragma unroll 4
-    for (int i = 0; i < 32; i++) {
-        p ^= b & (0u - (a >> 31));
-        a <<= 1;
-        b = (b >> 1) ^ (kCrcPoly & (0u - (b & 1u)));
-    }
-    return p;
-}
-
-// x^(8n) mod the polynomial.
-__device__ __forceinline__ uint32_t gf_x_pow_bytes(unsigned n)
-{
-    uint32_t result = 0x80000000u, power = 0x00800000u;      // x^0, x^8
-    while (n) {
-        if (n & 1u) result = gf_mul(result, power);
-        power = gf_mul(power, power);
-        n >>= 1;
-    }
-    return result;
-}
 
 __global__ __launch_bounds__(kFrameThreads) void bgzf_frame_kernel(const uint8_t *__restrict__ payload, int64_t payload_bytes, int block_payload,
                                                                    uint8_t *__restrict__ out)

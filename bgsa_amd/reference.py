@@ -22,7 +22,8 @@ its SAM records go through the contig form of the two record passes.
 
 BAM (include/bgsa_hip.h "BAM records") is the SAM stage with another encoding behind the same field assembly:
 map_reads_bam / map_pairs_bam run the SAM entry points' mapping with fmt="bam", and sam_records then measures, scans, emits and
-frames the records into BGZF blocks of stored deflate; bam_header, bgzf_blocks and write_bam make a file of them on the host.
+frames the records into BGZF blocks of stored deflate — or, with compress=True, deflates them on the device (LZ77 and dynamic
+Huffman codes) and packs the blocks —; bam_header, bgzf_blocks and write_bam make a file of them on the host.
 """
 from __future__ import annotations
 
@@ -425,8 +426,8 @@ def write_sam(path, header: bytes, records: SamRecords) -> None:
 
 # ---- BAM records: include/bgsa_hip.h "BAM records" — the host side, no device, no library ---------------------------------------
 class BamRecords(NamedTuple):
-    """What ReferenceMapper.map_reads_bam and map_pairs_bam return: the records in BAM's layout inside BGZF blocks of stored
-    deflate, as the device wrote them, and SamRecords' four columns."""
+    """What ReferenceMapper.map_reads_bam and map_pairs_bam return: the records in BAM's layout inside BGZF blocks — of stored
+    deflate, or deflated where the call said compress=True —, as the device wrote them, and SamRecords' four columns."""
     blocks: np.ndarray      # uint8: the framed BGZF blocks of this call's records, without the BAM header and without the EOF block
     offsets: np.ndarray     # int64[n + 1]: record i, its block_size included, is payload[offsets[i] : offsets[i + 1]] of the inflated blocks
     flag: np.ndarray        # int32[n]
@@ -465,9 +466,9 @@ def bam_header_bytes(who: str, text: bytes, references) -> bytes:
     return b"".join(out)
 
 
-def check_bam_call(who: str, lens, names, quals, reference_name, block_payload=BGZF_BLOCK_PAYLOAD) -> tuple:
+def check_bam_call(who: str, lens, names, quals, reference_name, block_payload=BGZF_BLOCK_PAYLOAD, compress=False) -> tuple:
     """check_sam_call's refusals and returns, then BAM's own, before anything is launched or allocated: a name longer than 254
-    bytes (l_read_name is one byte and counts the NUL), a block_payload outside 1..65,280."""
+    bytes (l_read_name is one byte and counts the NUL), a block_payload outside 1..65,280, a compress that is not a bool."""
     checked = check_sam_call(who, lens, names, quals, reference_name)
     name_lens = np.diff(checked[2])
     if (name_lens > 254).any():
@@ -475,6 +476,8 @@ def check_bam_call(who: str, lens, names, quals, reference_name, block_payload=B
         raise B.BgsaHipError(f"{who}: rc=-1: the name of read {c} has {int(name_lens[c])} bytes, a BAM record holds 254 at the most")
     if isinstance(block_payload, bool) or not isinstance(block_payload, (int, np.integer)) or not 1 <= int(block_payload) <= BGZF_BLOCK_PAYLOAD:
         raise B.BgsaHipError(f"{who}: rc=-1: block_payload {block_payload!r} outside 1..{BGZF_BLOCK_PAYLOAD}")
+    if not isinstance(compress, (bool, np.bool_)):
+        raise B.BgsaHipError(f"{who}: rc=-1: compress {compress!r} is not a bool")
     return checked
 
 
@@ -1115,14 +1118,16 @@ class ReferenceMapper:
         return pick(strand).masked_fill(slot < 0, -1), pick(ref_begin), pick(ref_end), -pick(scores), pick(n_ops), runs
 
     def sam_records(self, who: str, reads: np.ndarray, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, fmt: str = "sam",
-                    block_payload: int = BGZF_BLOCK_PAYLOAD):
+                    block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False):
         """The two record passes.  reads [n_rows, stride] and quals (or None) are the host rows, names / name_offsets / rname what
         check_sam_call returned; fields holds the per-record DEVICE tensors read_row, name_of (int64), read_len, strand, ref_begin,
         ref_end, distance, n_ops, flag, mapq, rnext, pnext, tlen; runs [n, cap] int32 holds record i's runs in row i.  Measure, an
         exclusive scan of the lengths with its one scalar read back — it sizes the text —, emit, the text copied once.  A malformed
         record raises; read_label(i) names record i's read in the message.  fmt "bam": the same passes of the BAM stage, then the
         payload framed into BGZF blocks of block_payload bytes on the device (bgsa_hip_bgzf_frame_dev) and the blocks copied once:
-        BamRecords, its offsets in payload coordinates."""
+        BamRecords, its offsets in payload coordinates.  compress (fmt "bam" only): the blocks deflated into slots
+        (bgsa_hip_bgzf_deflate_dev), their lengths scanned, one more scalar read back, the blocks packed (bgsa_hip_bgzf_pack_dev) and
+        copied once — fewer bytes than the payload."""
         a = self.aligner
         torch, dev = a.torch, a.device
         measure, emit = self._sam_passes(fmt)
@@ -1170,7 +1175,9 @@ class ReferenceMapper:
         nm = f["distance"].masked_fill(~mapped, -1)
         mapq = f["mapq"].masked_fill(~mapped, 0)
         kind = SamRecords
-        if fmt == "bam":
+        if fmt == "bam" and compress:
+            kind, text, total = BamRecords, *self.bgzf_deflated(who, text, total, int(block_payload))
+        elif fmt == "bam":
             framed = int(B.lib().bgsa_hip_bgzf_framed_bytes(total, int(block_payload)))
             blocks = torch.empty(max(framed, 1), dtype=torch.uint8, device=dev)
             B.check(B.lib().bgsa_hip_bgzf_frame_dev(text.data_ptr(), total, int(block_payload), blocks.data_ptr(), framed, a._stream()),
@@ -1178,6 +1185,29 @@ class ReferenceMapper:
             kind, text, total = BamRecords, blocks, framed
         return kind(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(), mapq.cpu().numpy(),
                     nm.cpu().numpy())
+
+    def bgzf_deflated(self, who: str, payload, total: int, block_payload: int) -> tuple:
+        """(blocks, their bytes) of the first `total` bytes of the device tensor `payload`, deflated block by block on the device:
+        deflate into slots, torch.cumsum of the block lengths, one scalar, pack.  A block that pack refuses raises."""
+        a = self.aligner
+        torch, dev, L = a.torch, a.device, B.lib()
+        n_blocks = (total + block_payload - 1) // block_payload
+        slots = torch.empty(max(n_blocks * (block_payload + 31), 1), dtype=torch.uint8, device=dev)
+        lengths = torch.empty(max(n_blocks, 1), dtype=torch.int64, device=dev)
+        room = int(L.bgsa_hip_bgzf_deflate_workspace_bytes(total, block_payload))
+        workspace = torch.empty(max(room // 4, 1), dtype=torch.int32, device=dev)
+        B.check(L.bgsa_hip_bgzf_deflate_dev(payload.data_ptr(), total, block_payload, slots.data_ptr(), n_blocks * (block_payload + 31),
+                                            lengths.data_ptr(), workspace.data_ptr(), room, a._stream()), "bgzf_deflate_dev")
+        offsets = torch.zeros(n_blocks + 1, dtype=torch.int64, device=dev)
+        offsets[1:] = torch.cumsum(lengths[:n_blocks], 0)
+        out_bytes = int(offsets[-1].item())              # the one scalar read back: it sizes the packed blocks
+        blocks = torch.empty(max(out_bytes, 1), dtype=torch.uint8, device=dev)
+        refused = torch.zeros(1, dtype=torch.int32, device=dev)
+        B.check(L.bgsa_hip_bgzf_pack_dev(slots.data_ptr(), block_payload, n_blocks, offsets.data_ptr(), blocks.data_ptr(), out_bytes,
+                                         refused.data_ptr(), a._stream()), "bgzf_pack_dev")
+        if int(refused.item()):
+            raise B.BgsaHipError(f"{who}: the pack pass refused {int(refused.item())} of {n_blocks} deflated blocks")
+        return blocks, out_bytes
 
     def _sam_rows(self, who: str, reads) -> tuple:
         """(rows, lens, ragged) of a SAM call's reads: a [ns, n] array as it is, anything else as a list of mixed lengths."""
@@ -1231,35 +1261,39 @@ class ReferenceMapper:
 
     def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
                       seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None,
-                      block_payload: int = BGZF_BLOCK_PAYLOAD) -> BamRecords:
+                      block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False) -> BamRecords:
         """map_reads_sam — the same arguments, mapping and record selection — with the records in BAM's layout inside BGZF blocks of
         stored deflate, block_payload bytes of records each (include/bgsa_hip.h "BAM records"): measure, scan, emit, frame, all on the
-        device, one copy of the blocks.  A record may straddle blocks.  check_bam_call refuses before anything is launched; with
-        bam_header and write_bam the blocks of one or more calls make a file."""
+        device, one copy of the blocks.  A record may straddle blocks.  compress=True: every block deflated on the device instead (LZ77
+        and dynamic Huffman codes, or stored where that is no shorter), the blocks packed and copied once — fewer bytes than the
+        payload; the same records inflate from them.  check_bam_call refuses before anything is launched; with bam_header and
+        write_bam the blocks of one or more calls, compressed or not, make a file."""
         return self._map_reads_records("bam", block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                                       max_candidates, block_rows, cigar_cap)
+                                       max_candidates, block_rows, cigar_cap, compress)
 
     @staticmethod
-    def _check_records_call(fmt: str, who: str, lens, names, quals, reference_name, block_payload) -> tuple:
+    def _check_records_call(fmt: str, who: str, lens, names, quals, reference_name, block_payload, compress=False) -> tuple:
         if fmt == "bam":
-            return check_bam_call(who, lens, names, quals, reference_name, block_payload)
+            return check_bam_call(who, lens, names, quals, reference_name, block_payload, compress)
         return check_sam_call(who, lens, names, quals, reference_name)
 
     def _map_reads_records(self, fmt: str, block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                           max_candidates, block_rows, cigar_cap):
+                           max_candidates, block_rows, cigar_cap, compress=False):
         """What map_reads_sam and map_reads_bam share: everything but the format of the records."""
         who = f"map_reads_{fmt}"
         rows, lens, ragged = self._sam_rows(who, reads)
-        rname, flat, name_offsets, qual_rows = self._check_records_call(fmt, who, lens, names, quals, reference_name, block_payload)
+        rname, flat, name_offsets, qual_rows = self._check_records_call(fmt, who, lens, names, quals, reference_name, block_payload,
+                                                                        compress)
         bound = int(max_distance) if seeded and max_distance is not None else -1
         sink = self._map_to(lambda ns, k_sel, cap: PrimarySink(self, ns, cap, bound), rows, lens, ragged, k_best, max_distance, seeded, seed_len,
                             max_candidates, block_rows, cigar_cap)
         self.aligner.check_faults()
-        return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname, fmt=fmt, block_payload=block_payload)
+        return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname, fmt=fmt, block_payload=block_payload,
+                                       compress=compress)
 
     def sam_single_records(self, who: str, sink: "PrimarySink", rows: np.ndarray, lens, qual_rows, names, name_offsets, rname, **form):
         """The records of single-end reads from their primaries on the device: flag 0, 16 or 4, no mate fields.  form: sam_records'
-        fmt and block_payload."""
+        fmt, block_payload and compress."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = rows.shape[0]
         index = torch.arange(ns, dtype=torch.int64, device=dev)
@@ -1283,20 +1317,23 @@ class ReferenceMapper:
 
     def map_pairs_bam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
                       reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
-                      max_candidates=None, block_rows: int = 1000, cigar_cap=None, block_payload: int = BGZF_BLOCK_PAYLOAD) -> BamRecords:
-        """map_pairs_sam — the same arguments, stages and records — in BAM's layout inside BGZF blocks (map_reads_bam)."""
+                      max_candidates=None, block_rows: int = 1000, cigar_cap=None, block_payload: int = BGZF_BLOCK_PAYLOAD,
+                      compress: bool = False) -> BamRecords:
+        """map_pairs_sam — the same arguments, stages and records — in BAM's layout inside BGZF blocks, stored or, with compress=True,
+        deflated on the device (map_reads_bam)."""
         return self._map_pairs_records("bam", block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name,
-                                       k_best, max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap)
+                                       k_best, max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap,
+                                       compress)
 
     def _map_pairs_records(self, fmt: str, block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
-                           max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap):
+                           max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap, compress=False):
         """What map_pairs_sam and map_pairs_bam share: everything but the format of the records."""
         who = f"map_pairs_{fmt}"
         reads = (self._one_length(who, reads1), self._one_length(who, reads2))
         ns = reads[0].shape[0]
         if (quals1 is None) != (quals2 is None):
             raise B.BgsaHipError(f"{who}: rc=-1: quals1 and quals2 come together")
-        checked = [self._check_records_call(fmt, who, np.full(ns, rows.shape[1]), names, quals, reference_name, block_payload)
+        checked = [self._check_records_call(fmt, who, np.full(ns, rows.shape[1]), names, quals, reference_name, block_payload, compress)
                    for rows, quals in zip(reads, (quals1, quals2))]
         call = check_pair_call(self.both_strands, reads[0].shape, reads[1].shape, insert_min, insert_max, k_best, max_distance,
                                rescue_distance, seeded, seed_len, max_candidates, cigar_cap, self.window_len, self.stride, self.ref_len,
@@ -1310,12 +1347,12 @@ class ReferenceMapper:
         ends = [self._rescue_checked(e, reads, single, call, insert_max, block_rows) for e in range(2)]      # stage B
         chosen = self.pair_select(ends[0][0][:5], ends[1][0][:5], insert_min, insert_max, block_rows)      # stage C
         a.check_faults()
-        return self.sam_pair_records(who, reads, ends, chosen, call, checked, fmt=fmt, block_payload=block_payload)
+        return self.sam_pair_records(who, reads, ends, chosen, call, checked, fmt=fmt, block_payload=block_payload, compress=compress)
 
     def sam_pair_records(self, who: str, reads, ends, chosen, call: dict, checked, **form):
         """The records of pairs from the device results of map_pairs' stages: ends[e] = rescue_end's return for end e, chosen =
-        pair_select's, call = check_pair_call's dict, checked[e] = check_sam_call's return for end e.  form: sam_records' fmt and
-        block_payload."""
+        pair_select's, call = check_pair_call's dict, checked[e] = check_sam_call's return for end e.  form: sam_records' fmt,
+        block_payload and compress."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = reads[0].shape[0]
         lists = [final for final, _, _, _ in ends]
@@ -1638,7 +1675,7 @@ class ContigMapper(ReferenceMapper):
 
     def sam_records(self, who: str, reads, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, **form):
         """ReferenceMapper.sam_records through the contig passes: the fields are linear, the device localises them; TLEN is set to 0
-        where the mate lies on another contig; the pos column comes back local.  rname is not used.  form: fmt and block_payload."""
+        where the mate lies on another contig; the pos column comes back local.  rname is not used.  form: fmt, block_payload, compress."""
         torch = self.aligner.torch
         own = torch.searchsorted(self.d_contig_starts, fields["ref_begin"].contiguous(), right=True)
         mate = torch.searchsorted(self.d_contig_starts, (fields["pnext"] - 1).contiguous(), right=True)

@@ -998,7 +998,8 @@ int bgsa_hip_sam_emit_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_
  * of the same contract as the SAM ones — bgsa_hip_bam_measure_dev returns every record's byte length, the caller scans the
  * lengths and reads one scalar back, bgsa_hip_bam_emit_dev writes the records into one payload buffer —, and
  * bgsa_hip_bgzf_frame_dev then wraps the payload into BGZF blocks of STORED deflate: a valid BAM stream once the caller puts the
- * header in front and the EOF block behind (bgsa_amd/reference.py: bam_header, write_bam, BGZF_EOF).  No compressor.
+ * header in front and the EOF block behind (bgsa_amd/reference.py: bam_header, write_bam, BGZF_EOF).  The compressing form of the
+ * framing is "deflate" below.
  * DEFINITIONS (normative; SAMv1 §4.1, §4.2, §5.3; tests/bam_reference.py restates them).
  *   a record   every value is that of the record's SAM line; all integers little-endian; a record starts at any byte address.
  *     block_size  int32: the record's length minus these 4 bytes.  d_lengths[i] and the offsets count the 4 bytes in.
@@ -1047,6 +1048,41 @@ int bgsa_hip_bam_emit_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_
                                   uint8_t *d_payload, int64_t payload_bytes, int32_t *d_malformed, void *stream);
 int64_t bgsa_hip_bgzf_framed_bytes(int64_t payload_bytes, int block_payload);
 int bgsa_hip_bgzf_frame_dev(const uint8_t *d_payload, int64_t payload_bytes, int block_payload, uint8_t *d_out, int64_t out_bytes, void *stream);
+
+/* BAM records: deflate — the same BGZF blocks with their payload DEFLATED on the device (RFC 1951; bgzf_deflate.hip).  Block b
+ * carries the same payload bytes as above; its 18 header bytes, CRC-32 and ISIZE are the framing's, BSIZE is the real length - 1,
+ * and the deflate data between them is ONE deflate block with BFINAL = 1 in one of two forms: STORED, byte for byte what
+ * bgsa_hip_bgzf_frame_dev writes, or DYNAMIC (BTYPE 10) — chosen if and only if its byte length is strictly smaller than the stored
+ * form's LEN + 5, from the exact bit count, before a bit is written.  So a block is never longer than LEN + 31, and blocks are
+ * independent: no match reaches into another block's bytes.  The output is a pure function of (payload, block_payload) — not of
+ * timing, not of the device — and tests/deflate_reference.py, the NORMATIVE model, reproduces it byte for byte:
+ *   matches  positions in tiles of 1,024; position i tries i - 1 and, if i + 4 <= LEN, the greatest position of any EARLIER tile
+ *            whose 4 bytes hash alike (little-endian word * 0x9E3779B1, top 15 bits) at a distance <= 32,768; lengths by comparison,
+ *            at most 258 and the block's end; the longer wins, a tie goes to distance 1; used from length 4, or 3 below 4,096
+ *   parse    greedy from position 0
+ *   codes    Huffman lengths of the 286 + 30 counts (EOB once): Moffat and Katajainen's in-place method on the used symbols sorted
+ *            by (count, symbol); limited to 15 by clamping and repairing the Kraft sum a unit at a time (miniz's rule); the
+ *            shortest lengths to the greatest counts; canonical codes.  One used distance symbol: length 1; none: all 30 lengths 0
+ *   header   HLIT 286, HDIST 30, HCLEN 19, the code-length code FIXED (symbols 0..15 at 4 bits, 16..18 unused): every one of the
+ *            316 lengths is its own 4-bit symbol, 1,338 bits in all; a block of up to 163 bytes is therefore always stored
+ * The stage's two-pass idiom: bgsa_hip_bgzf_deflate_dev writes block b complete at the start of slot b of d_slots (slots of
+ * block_payload + 31 bytes; the rest of a slot is not touched) and its length into d_block_bytes[b]; the caller makes
+ * d_block_offsets[n_blocks + 1], the exclusive scan of the lengths, reads ONE scalar back — out_bytes = d_block_offsets[n_blocks] —
+ * and bgsa_hip_bgzf_pack_dev copies block b to d_out + d_block_offsets[b].  pack does not copy a block whose offsets are not
+ * monotone or negative, whose length exceeds its slot or whose extent leaves [0, out_bytes): each such block adds 1 to *d_refused
+ * (the caller zeroes it), and no value read from device memory forms an address unchecked.
+ * bgsa_hip_bgzf_deflate_workspace_bytes: host only — 4 * payload_bytes (a word per payload byte: the parse); 0 for an empty payload;
+ * -1 where bgsa_hip_bgzf_framed_bytes gives -1.  d_workspace is aligned to 4 bytes; payload, slots and output start anywhere.
+ * One workgroup of 1,024 threads per block, 141 KiB of LDS: one workgroup per CU.  Both device calls only launch on `stream`: no
+ * allocation, no synchronisation; an empty payload (n_blocks == 0) is BGSA_HIP_OK and launches nothing.  BGSA_HIP_EINVAL, before
+ * the first HIP call: a NULL pointer (the stream excepted), a block_payload outside 1..65280, a negative or overflowing
+ * payload_bytes, a slots_bytes that is not n_blocks * (block_payload + 31), a workspace_bytes below the function's value, a
+ * misaligned d_workspace; for pack a negative n_blocks or out_bytes. */
+int64_t bgsa_hip_bgzf_deflate_workspace_bytes(int64_t payload_bytes, int block_payload);
+int bgsa_hip_bgzf_deflate_dev(const uint8_t *d_payload, int64_t payload_bytes, int block_payload, uint8_t *d_slots, int64_t slots_bytes,
+                              int64_t *d_block_bytes, void *d_workspace, int64_t workspace_bytes, void *stream);
+int bgsa_hip_bgzf_pack_dev(const uint8_t *d_slots, int block_payload, int64_t n_blocks, const int64_t *d_block_offsets, uint8_t *d_out,
+                           int64_t out_bytes, int32_t *d_refused, void *stream);
 
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
