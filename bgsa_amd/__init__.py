@@ -212,6 +212,16 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
+    # coordinate order and the BAI index (the same: an older build lacks them)
+    for name, types, restype in (("bgsa_hip_bam_coordinates_dev", [ctypes.POINTER(SamBatch), i64] + [vp] * 7, i32),
+                                 ("bgsa_hip_bam_coordinates_contigs_dev", [ctypes.POINTER(SamBatch), ctypes.POINTER(SamContigs), i64] + [vp] * 7,
+                                  i32),
+                                 ("bgsa_hip_bam_index_windows", [vp, i64, vp], i64),
+                                 ("bgsa_hip_bam_index_marks_dev", [vp] * 4 + [i64, vp, i64, i32, vp, i64, vp, i64] + [vp] * 6, i32),
+                                 ("bgsa_hip_bam_index_chunks_dev", [vp] * 6 + [i64, i64] + [vp] * 6, i32)):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = types
+            getattr(L, name).restype = restype
     # a reference of several contigs (the same: an older build lacks them)
     for name, types in (("bgsa_hip_contig_layout", [vp, i64, i32, i64, vp, vp]),
                         ("bgsa_hip_contig_clip_dev", [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
@@ -1230,4 +1240,4 @@ def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: 
 # reads mapped onto one reference: windows cut on the device, both strands, reference coordinates (bgsa_amd/reference.py)
 from .reference import (ContigHits, ContigMapper, ContigPlacement, PairedHits, Placement, ReferenceHits, ReferenceMapper, SamRecords, blank_beyond, check_sam_call,  # noqa: E402
                         list_mapq, max_stride, rescue_region, rescue_slots, seed_plan, seed_plan_ragged, window_plan, write_sam, contig_layout, read_fasta,
-                        BGZF_EOF, BamRecords, bgzf_blocks, check_bam_call, write_bam)
+                        BGZF_EOF, BamRecords, bgzf_blocks, check_bam_call, write_bam, BamIndex, SortedBamRecords, bai_bytes)

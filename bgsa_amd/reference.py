@@ -23,7 +23,10 @@ its SAM records go through the contig form of the two record passes.
 BAM (include/bgsa_hip.h "BAM records") is the SAM stage with another encoding behind the same field assembly:
 map_reads_bam / map_pairs_bam run the SAM entry points' mapping with fmt="bam", and sam_records then measures, scans, emits and
 frames the records into BGZF blocks of stored deflate — or, with compress=True, deflates them on the device (LZ77 and dynamic
-Huffman codes) and packs the blocks —; bam_header, bgzf_blocks and write_bam make a file of them on the host.
+Huffman codes) and packs the blocks —; bam_header, bgzf_blocks and write_bam make a file of them on the host.  With sort=True
+(include/bgsa_hip.h "BAM records: coordinate order and index") the records of one call are put in coordinate
+order before the passes — keys by a kernel, torch.sort, the per-record tensors gathered — and the arrays of a BAI index are built
+after them (SortedBamRecords, BamIndex); bai_bytes and write_bam(index=True) write x.bam.bai beside x.bam.
 """
 from __future__ import annotations
 
@@ -466,9 +469,11 @@ def bam_header_bytes(who: str, text: bytes, references) -> bytes:
     return b"".join(out)
 
 
-def check_bam_call(who: str, lens, names, quals, reference_name, block_payload=BGZF_BLOCK_PAYLOAD, compress=False) -> tuple:
+def check_bam_call(who: str, lens, names, quals, reference_name, block_payload=BGZF_BLOCK_PAYLOAD, compress=False, sort=False,
+                   ref_lens=()) -> tuple:
     """check_sam_call's refusals and returns, then BAM's own, before anything is launched or allocated: a name longer than 254
-    bytes (l_read_name is one byte and counts the NUL), a block_payload outside 1..65,280, a compress that is not a bool."""
+    bytes (l_read_name is one byte and counts the NUL), a block_payload outside 1..65,280, a compress or a sort that is not a
+    bool, and with sort=True a reference or contig (ref_lens) longer than 2^29 bases: a BAI index reaches no further."""
     checked = check_sam_call(who, lens, names, quals, reference_name)
     name_lens = np.diff(checked[2])
     if (name_lens > 254).any():
@@ -478,18 +483,111 @@ def check_bam_call(who: str, lens, names, quals, reference_name, block_payload=B
         raise B.BgsaHipError(f"{who}: rc=-1: block_payload {block_payload!r} outside 1..{BGZF_BLOCK_PAYLOAD}")
     if not isinstance(compress, (bool, np.bool_)):
         raise B.BgsaHipError(f"{who}: rc=-1: compress {compress!r} is not a bool")
+    if not isinstance(sort, (bool, np.bool_)):
+        raise B.BgsaHipError(f"{who}: rc=-1: sort {sort!r} is not a bool")
+    if sort:
+        for c, n in enumerate(np.asarray(ref_lens, dtype=np.int64).reshape(-1).tolist()):
+            if n > BAI_REACH:
+                raise B.BgsaHipError(f"{who}: rc=-1: sort=True: reference {c} has {n} bases, a BAI index reaches 2^29 = {BAI_REACH}")
     return checked
 
 
-def write_bam(path, header: bytes, records) -> None:
+def write_bam(path, header: bytes, records, index: bool = False) -> None:
     """A BAM file: the header (ReferenceMapper.bam_header, uncompressed) framed by bgzf_blocks, the blocks of `records` — one
-    BamRecords or a sequence of them, in order: batches of reads stream into one file —, then BGZF_EOF."""
-    batches = [records] if isinstance(records, BamRecords) else list(records)
+    BamRecords or a sequence of them, in order: batches of reads stream into one file —, then BGZF_EOF.  index=True: `records` is
+    ONE SortedBamRecords (a sorted file holds one call's records) and the header says SO:coordinate; the BAI index goes to
+    path + ".bai" (bai_bytes, its offsets moved behind the framed header)."""
+    framed = bgzf_blocks(header)
+    if index:
+        if not isinstance(records, SortedBamRecords):
+            raise B.BgsaHipError("write_bam: rc=-1: index=True takes ONE SortedBamRecords (map_reads_bam / map_pairs_bam with sort=True)")
+        text = bytes(header)[8: 8 + max(struct.unpack_from("<i", bytes(header), 4)[0], 0)] if len(header) >= 8 else b""
+        if b"SO:coordinate" not in text.split(b"\n")[0]:
+            raise B.BgsaHipError("write_bam: rc=-1: index=True, and the header's @HD line does not say SO:coordinate "
+                                 "(bam_header(sort_order=\"coordinate\"))")
+    batches = [records] if isinstance(records, (BamRecords, SortedBamRecords)) else list(records)
     with open(path, "wb") as out:
-        out.write(bgzf_blocks(header))
+        out.write(framed)
         for batch in batches:
             out.write(memoryview(np.ascontiguousarray(batch.blocks)))
         out.write(BGZF_EOF)
+    if index:
+        with open(str(path) + ".bai", "wb") as out:
+            out.write(bai_bytes(records.index, records.flag, records.ref_id, len(framed)))
+
+
+# ---- BAM records: coordinate order and index: include/bgsa_hip.h — the host side, no device, no library --------------------------
+BAI_REACH = 1 << 29               # what a BAI's bins and 16 Kbp windows cover
+BAI_WINDOW_SHIFT = 14
+BAI_META_BIN = 37450
+SORT_ORDERS = ("unsorted", "coordinate")
+
+
+class BamIndex(NamedTuple):
+    """The arrays of a BAI index as the device built them for ONE call's sorted records; offsets are virtual offsets relative to
+    the first byte of the call's blocks."""
+    ref_lens: np.ndarray      # int64[n_ref]
+    chunk_ref: np.ndarray     # int32[n_chunks]: the chunks in (ref, bin, beg) order
+    chunk_bin: np.ndarray     # int32[n_chunks]
+    chunk_beg: np.ndarray     # int64[n_chunks]
+    chunk_end: np.ndarray     # int64[n_chunks]
+    window_base: np.ndarray   # int64[n_ref + 1]: reference c owns linear[window_base[c] : window_base[c + 1]]
+    linear: np.ndarray        # int64: the suffix minimum of the windows' smallest offsets; INT64_MAX behind the last record
+    n_intv: np.ndarray        # int64[n_ref]: the windows of reference c a .bai writes
+
+
+class SortedBamRecords(NamedTuple):
+    """What map_reads_bam and map_pairs_bam return with sort=True: BamRecords' six fields in OUTPUT (coordinate) order, then the
+    refID column, the permutation and the index."""
+    blocks: np.ndarray
+    offsets: np.ndarray
+    flag: np.ndarray
+    pos: np.ndarray
+    mapq: np.ndarray
+    nm: np.ndarray
+    ref_id: np.ndarray        # int32[n]: -1 for a record without coordinates
+    order: np.ndarray         # int64[n]: output record i is input record order[i]
+    index: BamIndex
+
+
+def sort_order_line(who: str, sort_order) -> bytes:
+    """The @HD line for sort_order "unsorted" or "coordinate"; anything else is refused."""
+    if not isinstance(sort_order, str) or sort_order not in SORT_ORDERS:
+        raise B.BgsaHipError(f"{who}: rc=-1: sort_order {sort_order!r} is neither 'unsorted' nor 'coordinate'")
+    return b"@HD\tVN:1.6\tSO:" + sort_order.encode() + b"\n"
+
+
+def bai_bytes(index: BamIndex, flag, ref_id, base: int = 0) -> bytes:
+    """The .bai file (SAMv1 §5.2) of `index` and the sorted records' flag and ref_id columns, every offset moved by base << 16
+    (base: the bytes in front of the call's blocks in the file, the framed header).  Per reference its bins ascending — bin,
+    n_chunk, the chunks —, the metadata pseudo-bin 37450 last — (smallest begin, largest end), (mapped, unmapped) —, n_intv and the
+    linear offsets; n_no_coor at the end.  A reference without records: n_bin 0 and n_intv 0.  Host only."""
+    flag, ref_id = np.asarray(flag).reshape(-1), np.asarray(ref_id).reshape(-1)
+    shift = int(base) << 16
+    n_ref = int(np.asarray(index.ref_lens).size)
+    chunk_ref = np.asarray(index.chunk_ref)
+    first = np.searchsorted(chunk_ref, np.arange(n_ref + 1))       # the chunks are in (ref, bin, beg) order
+    out = [b"BAI\x01", struct.pack("<i", n_ref)]
+    for c in range(n_ref):
+        lo, hi = int(first[c]), int(first[c + 1])
+        if hi == lo:
+            out.append(struct.pack("<ii", 0, 0))
+            continue
+        bins = np.asarray(index.chunk_bin[lo:hi])
+        cuts = np.concatenate(([0], np.flatnonzero(np.diff(bins)) + 1, [hi - lo]))
+        out.append(struct.pack("<i", cuts.size))                  # the bins and the pseudo-bin
+        pairs = np.stack((index.chunk_beg[lo:hi], index.chunk_end[lo:hi]), axis=1).astype(np.uint64) + np.uint64(shift)
+        for a, b in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
+            out += [struct.pack("<Ii", int(bins[a]), b - a), pairs[a:b].astype("<u8").tobytes()]
+        own = ref_id == c
+        unmapped = int((own & ((flag & 4) != 0)).sum())
+        out.append(struct.pack("<Ii4Q", BAI_META_BIN, 2, int(index.chunk_beg[lo:hi].min()) + shift, int(index.chunk_end[lo:hi].max()) + shift,
+                               int(own.sum()) - unmapped, unmapped))
+        n_intv = int(index.n_intv[c])
+        at = int(index.window_base[c])
+        out += [struct.pack("<i", n_intv), (np.asarray(index.linear[at: at + n_intv]).astype(np.uint64) + np.uint64(shift)).astype("<u8").tobytes()]
+    out.append(struct.pack("<Q", int((ref_id < 0).sum())))
+    return b"".join(out)
 
 
 class SeedBucket(NamedTuple):
@@ -632,6 +730,14 @@ class ReferenceMapper:
         return getattr(B.lib(), f"bgsa_hip_{fmt}_measure_dev"), getattr(B.lib(), f"bgsa_hip_{fmt}_emit_dev")
 
     # ---- the one pipeline behind map_reads, map_reads_ragged, map_reads_seeded and map_reads_seeded_ragged ----------------------
+    def _coordinates_pass(self):
+        """The key pass of sam_records(sort=True): bgsa_hip_bam_coordinates_dev, the contig mapper's with its table."""
+        return B.lib().bgsa_hip_bam_coordinates_dev
+
+    def index_ref_lens(self) -> np.ndarray:
+        """The lengths of the references in refID's order: what a BAI index of this mapper's records covers."""
+        return np.array([self.ref_len], dtype=np.int64)
+
     def _check(self, who: str, longest: int, ragged: bool, k_best, max_distance, cigar_cap, seeded: bool = False, max_candidates=None,
                plan=None) -> tuple:
         """check_call with this mapper's geometry; map_reads alone takes reads beyond 1,024 bp."""
@@ -1083,16 +1189,17 @@ class ReferenceMapper:
     # The mapping pipeline above with a sink in place of the host copies, then on device tensors only: sam_list_mapq, the primary
     # slots gathered (PrimarySink / sam_primaries), sam_records (measure -> scan -> emit -> one copy of the text).
     # scripts/measure_sam.py times these same methods.
-    def sam_header(self, reference_name="ref") -> bytes:
-        """The three header lines of this mapper's one reference: @HD (unsorted), @SQ with its name and length, @PG."""
+    def sam_header(self, reference_name="ref", sort_order="unsorted") -> bytes:
+        """The three header lines of this mapper's one reference: @HD (SO: sort_order, "unsorted" or "coordinate"), @SQ with its
+        name and length, @PG."""
         name = _field_bytes("sam_header", "reference_name", reference_name).tobytes()
-        return b"@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:" + name + b"\tLN:" + str(self.ref_len).encode() + b"\n@PG\tID:bgsa-hip\n"
+        return sort_order_line("sam_header", sort_order) + b"@SQ\tSN:" + name + b"\tLN:" + str(self.ref_len).encode() + b"\n@PG\tID:bgsa-hip\n"
 
-    def bam_header(self, reference_name="ref") -> bytes:
+    def bam_header(self, reference_name="ref", sort_order="unsorted") -> bytes:
         """The UNCOMPRESSED BAM header of this mapper's one reference: the magic, sam_header's text, one reference entry.  write_bam
-        frames it."""
+        frames it.  sort_order="coordinate" is the header of a sort=True call's file."""
         name = _field_bytes("bam_header", "reference_name", reference_name).tobytes()
-        return bam_header_bytes("bam_header", self.sam_header(reference_name), [(name, self.ref_len)])
+        return bam_header_bytes("bam_header", self.sam_header(reference_name, sort_order), [(name, self.ref_len)])
 
     def sam_list_mapq(self, scores, keep, bound: int) -> tuple:
         """bgsa_hip_sam_mapq_dev on device tensors scores, keep [ns, k]: (primary slot, mapq, n1, d2), int32[ns] each."""
@@ -1118,7 +1225,7 @@ class ReferenceMapper:
         return pick(strand).masked_fill(slot < 0, -1), pick(ref_begin), pick(ref_end), -pick(scores), pick(n_ops), runs
 
     def sam_records(self, who: str, reads: np.ndarray, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, fmt: str = "sam",
-                    block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False):
+                    block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False):
         """The two record passes.  reads [n_rows, stride] and quals (or None) are the host rows, names / name_offsets / rname what
         check_sam_call returned; fields holds the per-record DEVICE tensors read_row, name_of (int64), read_len, strand, ref_begin,
         ref_end, distance, n_ops, flag, mapq, rnext, pnext, tlen; runs [n, cap] int32 holds record i's runs in row i.  Measure, an
@@ -1127,7 +1234,12 @@ class ReferenceMapper:
         payload framed into BGZF blocks of block_payload bytes on the device (bgsa_hip_bgzf_frame_dev) and the blocks copied once:
         BamRecords, its offsets in payload coordinates.  compress (fmt "bam" only): the blocks deflated into slots
         (bgsa_hip_bgzf_deflate_dev), their lengths scanned, one more scalar read back, the blocks packed (bgsa_hip_bgzf_pack_dev) and
-        copied once — fewer bytes than the payload."""
+        copied once — fewer bytes than the payload.  sort (fmt "bam" only; include/bgsa_hip.h "BAM records: coordinate order and
+        index"): the key pass on the batch as assembled, torch.sort(stable=True) of the keys, the per-record tensors gathered by the
+        permutation — the runs stay where they are, d_runs_row is the permutation —, then the passes above on the permuted batch and
+        the index (bam_index): SortedBamRecords, its columns in output order."""
+        if sort and fmt != "bam":
+            raise B.BgsaHipError(f"{who}: rc=-1: sort=True needs fmt 'bam'")
         a = self.aligner
         torch, dev = a.torch, a.device
         measure, emit = self._sam_passes(fmt)
@@ -1141,13 +1253,31 @@ class ReferenceMapper:
         f = {key: value.contiguous() for key, value in fields.items()}
         runs = runs.contiguous()
         runs_row = torch.arange(n, dtype=torch.int64, device=dev)
-        batch = B.SamBatch(d_reads.data_ptr(), None if d_quals is None else d_quals.data_ptr(), reads.shape[1], reads.shape[0],
-                           d_names.data_ptr(), d_name_offsets.data_ptr(), name_offsets.size - 1, names.size, d_rname.data_ptr(), rname.size,
-                           self.d_reference.data_ptr(), self.ref_len, runs.data_ptr(), runs.shape[0], runs.shape[1],
-                           f["read_row"].data_ptr(), f["name_of"].data_ptr(), runs_row.data_ptr(), f["read_len"].data_ptr(),
-                           f["strand"].data_ptr(), f["ref_begin"].data_ptr(), f["ref_end"].data_ptr(), f["distance"].data_ptr(),
-                           f["n_ops"].data_ptr(), f["flag"].data_ptr(), f["mapq"].data_ptr(), f["rnext"].data_ptr(), f["pnext"].data_ptr(),
-                           f["tlen"].data_ptr())
+        label = read_label if read_label is not None else (lambda i: f"read {i}")
+
+        def malformed_error(count: int, i: int):
+            return B.BgsaHipError(f"{who}: {count} malformed records, the first the one of {label(i)}: an interval outside "
+                                  f"the reference, or runs that do not add up to it and to the read" +
+                                  (", or a position, PNEXT or TLEN beyond int32, or more than 65,535 runs" if fmt == "bam" else ""))
+
+        def batch_of(f, runs_row):
+            return B.SamBatch(d_reads.data_ptr(), None if d_quals is None else d_quals.data_ptr(), reads.shape[1], reads.shape[0],
+                              d_names.data_ptr(), d_name_offsets.data_ptr(), name_offsets.size - 1, names.size, d_rname.data_ptr(), rname.size,
+                              self.d_reference.data_ptr(), self.ref_len, runs.data_ptr(), runs.shape[0], runs.shape[1],
+                              f["read_row"].data_ptr(), f["name_of"].data_ptr(), runs_row.data_ptr(), f["read_len"].data_ptr(),
+                              f["strand"].data_ptr(), f["ref_begin"].data_ptr(), f["ref_end"].data_ptr(), f["distance"].data_ptr(),
+                              f["n_ops"].data_ptr(), f["flag"].data_ptr(), f["mapq"].data_ptr(), f["rnext"].data_ptr(), f["pnext"].data_ptr(),
+                              f["tlen"].data_ptr())
+        coordinates = None
+        if sort:
+            key, *coordinates = self.bam_coordinates(batch_of(f, runs_row), n)
+            if int(coordinates[-1].item()):
+                raise malformed_error(int(coordinates[-1].item()), int(torch.nonzero(key == torch.iinfo(torch.int64).max).reshape(-1)[0].item()))
+            order = self.sort_permutation(key)
+            f, coordinates = self.gather_records(f, coordinates[:4], order)
+            runs_row, host_order, unsorted_label = order.contiguous(), order.cpu().numpy(), label
+            label = lambda i: unsorted_label(int(host_order[i]))      # noqa: E731
+        batch = batch_of(f, runs_row)
         malformed = torch.zeros(2, dtype=torch.int32, device=dev)
         lengths = torch.empty(n, dtype=torch.int64, device=dev)
         B.check(measure(batch, n, lengths.data_ptr(), malformed[0:].data_ptr(), a._stream()), f"{fmt}_measure_dev")
@@ -1157,15 +1287,11 @@ class ReferenceMapper:
         if int(malformed[0].item()):
             mapped = f["strand"] >= 0
             over = torch.nonzero(mapped & (f["n_ops"] > runs.shape[1])).reshape(-1)
-            label = read_label if read_label is not None else (lambda i: f"read {i}")
             if over.numel():
                 i = int(over[0].item())
                 raise B.BgsaHipError(f"{who}: the hit of {label(i)} has {int(f['n_ops'][i].item())} runs, its row holds {runs.shape[1]} "
                                      f"(raise cigar_cap)")
-            i = int(torch.nonzero(lengths == 0).reshape(-1)[0].item())
-            raise B.BgsaHipError(f"{who}: {int(malformed[0].item())} malformed records, the first the one of {label(i)}: an interval outside "
-                                 f"the reference, or runs that do not add up to it and to the read" +
-                                 (", or a position, PNEXT or TLEN beyond int32, or more than 65,535 runs" if fmt == "bam" else ""))
+            raise malformed_error(int(malformed[0].item()), int(torch.nonzero(lengths == 0).reshape(-1)[0].item()))
         text = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
         B.check(emit(batch, n, offsets.data_ptr(), text.data_ptr(), total, malformed[1:].data_ptr(), a._stream()), f"{fmt}_emit_dev")
         if int(malformed[1].item()):
@@ -1174,21 +1300,94 @@ class ReferenceMapper:
         pos = torch.where(mapped, f["ref_begin"] + 1, f["pnext"] * f["rnext"])
         nm = f["distance"].masked_fill(~mapped, -1)
         mapq = f["mapq"].masked_fill(~mapped, 0)
-        kind = SamRecords
+        kind, payload_bytes, block_offsets = SamRecords, total, None
         if fmt == "bam" and compress:
-            kind, text, total = BamRecords, *self.bgzf_deflated(who, text, total, int(block_payload))
+            kind, (text, total, block_offsets) = BamRecords, self.bgzf_deflated(who, text, total, int(block_payload), with_offsets=True)
         elif fmt == "bam":
             framed = int(B.lib().bgsa_hip_bgzf_framed_bytes(total, int(block_payload)))
             blocks = torch.empty(max(framed, 1), dtype=torch.uint8, device=dev)
             B.check(B.lib().bgsa_hip_bgzf_frame_dev(text.data_ptr(), total, int(block_payload), blocks.data_ptr(), framed, a._stream()),
                     "bgzf_frame_dev")
             kind, text, total = BamRecords, blocks, framed
+        if sort:
+            index = self.bam_index(who, *coordinates, offsets, payload_bytes, int(block_payload), block_offsets)
+            return SortedBamRecords(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(),
+                                    mapq.cpu().numpy(), nm.cpu().numpy(), coordinates[0].cpu().numpy(), host_order, index)
         return kind(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(), mapq.cpu().numpy(),
                     nm.cpu().numpy())
 
-    def bgzf_deflated(self, who: str, payload, total: int, block_payload: int) -> tuple:
+    def bam_coordinates(self, batch, n: int) -> tuple:
+        """The key pass on a bgsa_hip_sam_batch_t of n records: the device tensors (key int64, ref_id, pos, end, bin int32, the
+        malformed count int32[1])."""
+        a = self.aligner
+        torch, dev = a.torch, a.device
+        key = torch.empty(n, dtype=torch.int64, device=dev)
+        ref_id, pos, end, bin_ = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+        malformed = torch.zeros(1, dtype=torch.int32, device=dev)
+        B.check(self._coordinates_pass()(batch, n, key.data_ptr(), ref_id.data_ptr(), pos.data_ptr(), end.data_ptr(), bin_.data_ptr(),
+                                         malformed.data_ptr(), a._stream()), "bam_coordinates_dev")
+        return key, ref_id, pos, end, bin_, malformed
+
+    def sort_permutation(self, key):
+        """The permutation that puts the keys in order, ties in input order: torch.sort(stable=True), plumbing."""
+        return self.aligner.torch.sort(key, stable=True)[1]
+
+    @staticmethod
+    def gather_records(fields: dict, coordinates, order) -> tuple:
+        """The per-record field tensors and the coordinate tensors in the order of the permutation."""
+        return {name: value[order].contiguous() for name, value in fields.items()}, [x[order].contiguous() for x in coordinates]
+
+    def bam_index(self, who: str, ref_id, pos, end, bin_, offsets, payload_bytes: int, block_payload: int, block_offsets=None) -> BamIndex:
+        """The BAI arrays of SORTED records on the device — their coordinates (int32[n] each), offsets int64[n + 1] into a payload of
+        payload_bytes in blocks of block_payload, block_offsets the deflated blocks' scan or None for stored ones —: marks, one
+        cumsum and its scalar, chunks, a stable sort of the chunks by ref << 32 | bin, the suffix minimum over the windows, one copy
+        of each array."""
+        a = self.aligner
+        torch, dev, L = a.torch, a.device, B.lib()
+        n, ref_lens = int(ref_id.shape[0]), self.index_ref_lens()
+        n_refs = int(ref_lens.size)
+        window_base = np.zeros(n_refs + 1, dtype=np.int64)
+        windows = int(L.bgsa_hip_bam_index_windows(ref_lens.ctypes.data, n_refs, window_base.ctypes.data))
+        if windows < 0:
+            raise B.BgsaHipError(f"{who}: rc=-1: a reference shorter than 1 or longer than 2^29 bases has no BAI index")
+        top = torch.iinfo(torch.int64).max
+        d_base = torch.from_numpy(window_base).to(dev)
+        linear = torch.full((max(windows, 1),), top, dtype=torch.int64, device=dev)
+        voff_beg, voff_end = (torch.zeros(max(n, 1), dtype=torch.int64, device=dev) for _ in range(2))
+        starts = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        refused = torch.zeros(2, dtype=torch.int32, device=dev)
+        n_blocks = (payload_bytes + block_payload - 1) // block_payload
+        B.check(L.bgsa_hip_bam_index_marks_dev(ref_id.data_ptr(), pos.data_ptr(), end.data_ptr(), bin_.data_ptr(), n, offsets.data_ptr(),
+                                               payload_bytes, block_payload, None if block_offsets is None else block_offsets.data_ptr(),
+                                               n_blocks, d_base.data_ptr(), n_refs, voff_beg.data_ptr(), voff_end.data_ptr(),
+                                               starts.data_ptr(), linear.data_ptr(), refused[0:].data_ptr(), a._stream()), "bam_index_marks_dev")
+        chunk_of = torch.cumsum(starts, 0, dtype=torch.int64)
+        n_chunks = int(chunk_of[-1].item()) if n else 0          # the one scalar read back: it sizes the chunk list
+        chunk_ref, chunk_bin = (torch.empty(max(n_chunks, 1), dtype=torch.int32, device=dev) for _ in range(2))
+        chunk_beg, chunk_end = (torch.empty(max(n_chunks, 1), dtype=torch.int64, device=dev) for _ in range(2))
+        B.check(L.bgsa_hip_bam_index_chunks_dev(ref_id.data_ptr(), bin_.data_ptr(), voff_beg.data_ptr(), voff_end.data_ptr(), starts.data_ptr(),
+                                                chunk_of.data_ptr(), n, n_chunks, chunk_ref.data_ptr(), chunk_bin.data_ptr(),
+                                                chunk_beg.data_ptr(), chunk_end.data_ptr(), refused[1:].data_ptr(), a._stream()),
+                "bam_index_chunks_dev")
+        if int(refused.sum().item()):
+            raise B.BgsaHipError(f"{who}: the index passes refused {refused.tolist()} records (marks, chunks): coordinates out of order or "
+                                 f"beyond their reference, or offsets outside the payload")
+        by = torch.sort(chunk_ref[:n_chunks].to(torch.int64) << 32 | chunk_bin[:n_chunks].to(torch.int64), stable=True)[1]
+        linear = linear[:windows]
+        window = torch.arange(windows, dtype=torch.int64, device=dev)
+        of_ref = torch.searchsorted(d_base[1:].contiguous(), window, right=True).clamp(max=max(n_refs - 1, 0))
+        filled = linear != top
+        n_intv = torch.zeros(max(n_refs, 1), dtype=torch.int64, device=dev)
+        if windows:
+            n_intv.scatter_reduce_(0, of_ref[filled], (window - d_base[of_ref] + 1)[filled], "amax")
+            linear = torch.flip(torch.cummin(torch.flip(linear, (0,)), 0)[0], (0,))      # an empty window takes the next filled one's
+        return BamIndex(ref_lens, chunk_ref[:n_chunks][by].cpu().numpy(), chunk_bin[:n_chunks][by].cpu().numpy(), chunk_beg[:n_chunks][by].cpu().numpy(),
+                        chunk_end[:n_chunks][by].cpu().numpy(), window_base, linear.cpu().numpy(), n_intv[:n_refs].cpu().numpy())
+
+    def bgzf_deflated(self, who: str, payload, total: int, block_payload: int, with_offsets: bool = False) -> tuple:
         """(blocks, their bytes) of the first `total` bytes of the device tensor `payload`, deflated block by block on the device:
-        deflate into slots, torch.cumsum of the block lengths, one scalar, pack.  A block that pack refuses raises."""
+        deflate into slots, torch.cumsum of the block lengths, one scalar, pack.  A block that pack refuses raises.  with_offsets:
+        the blocks' int64[n_blocks + 1] offsets on the device as a third value."""
         a = self.aligner
         torch, dev, L = a.torch, a.device, B.lib()
         n_blocks = (total + block_payload - 1) // block_payload
@@ -1207,7 +1406,7 @@ class ReferenceMapper:
                                          refused.data_ptr(), a._stream()), "bgzf_pack_dev")
         if int(refused.item()):
             raise B.BgsaHipError(f"{who}: the pack pass refused {int(refused.item())} of {n_blocks} deflated blocks")
-        return blocks, out_bytes
+        return (blocks, out_bytes, offsets) if with_offsets else (blocks, out_bytes)
 
     def _sam_rows(self, who: str, reads) -> tuple:
         """(rows, lens, ragged) of a SAM call's reads: a [ns, n] array as it is, anything else as a list of mixed lengths."""
@@ -1261,39 +1460,41 @@ class ReferenceMapper:
 
     def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
                       seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None,
-                      block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False) -> BamRecords:
+                      block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False):
         """map_reads_sam — the same arguments, mapping and record selection — with the records in BAM's layout inside BGZF blocks of
         stored deflate, block_payload bytes of records each (include/bgsa_hip.h "BAM records"): measure, scan, emit, frame, all on the
         device, one copy of the blocks.  A record may straddle blocks.  compress=True: every block deflated on the device instead (LZ77
         and dynamic Huffman codes, or stored where that is no shorter), the blocks packed and copied once — fewer bytes than the
         payload; the same records inflate from them.  check_bam_call refuses before anything is launched; with bam_header and
-        write_bam the blocks of one or more calls, compressed or not, make a file."""
+        write_bam the blocks of one or more calls, compressed or not, make a file.  sort=True: the records of this call leave the
+        device in coordinate order (the `samtools sort` key, ties in input order, records without coordinates last) with the arrays
+        of a BAI index beside them — SortedBamRecords; bam_header(sort_order="coordinate") and write_bam(index=True) then write
+        x.bam and x.bam.bai (include/bgsa_hip.h "BAM records: coordinate order and index").  A sorted file holds ONE call's records."""
         return self._map_reads_records("bam", block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                                       max_candidates, block_rows, cigar_cap, compress)
+                                       max_candidates, block_rows, cigar_cap, compress, sort)
 
-    @staticmethod
-    def _check_records_call(fmt: str, who: str, lens, names, quals, reference_name, block_payload, compress=False) -> tuple:
+    def _check_records_call(self, fmt: str, who: str, lens, names, quals, reference_name, block_payload, compress=False, sort=False) -> tuple:
         if fmt == "bam":
-            return check_bam_call(who, lens, names, quals, reference_name, block_payload, compress)
+            return check_bam_call(who, lens, names, quals, reference_name, block_payload, compress, sort, self.index_ref_lens())
         return check_sam_call(who, lens, names, quals, reference_name)
 
     def _map_reads_records(self, fmt: str, block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                           max_candidates, block_rows, cigar_cap, compress=False):
+                           max_candidates, block_rows, cigar_cap, compress=False, sort=False):
         """What map_reads_sam and map_reads_bam share: everything but the format of the records."""
         who = f"map_reads_{fmt}"
         rows, lens, ragged = self._sam_rows(who, reads)
         rname, flat, name_offsets, qual_rows = self._check_records_call(fmt, who, lens, names, quals, reference_name, block_payload,
-                                                                        compress)
+                                                                        compress, sort)
         bound = int(max_distance) if seeded and max_distance is not None else -1
         sink = self._map_to(lambda ns, k_sel, cap: PrimarySink(self, ns, cap, bound), rows, lens, ragged, k_best, max_distance, seeded, seed_len,
                             max_candidates, block_rows, cigar_cap)
         self.aligner.check_faults()
         return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname, fmt=fmt, block_payload=block_payload,
-                                       compress=compress)
+                                       compress=compress, sort=sort)
 
     def sam_single_records(self, who: str, sink: "PrimarySink", rows: np.ndarray, lens, qual_rows, names, name_offsets, rname, **form):
         """The records of single-end reads from their primaries on the device: flag 0, 16 or 4, no mate fields.  form: sam_records'
-        fmt, block_payload and compress."""
+        fmt, block_payload, compress and sort."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = rows.shape[0]
         index = torch.arange(ns, dtype=torch.int64, device=dev)
@@ -1318,22 +1519,23 @@ class ReferenceMapper:
     def map_pairs_bam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
                       reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
                       max_candidates=None, block_rows: int = 1000, cigar_cap=None, block_payload: int = BGZF_BLOCK_PAYLOAD,
-                      compress: bool = False) -> BamRecords:
+                      compress: bool = False, sort: bool = False):
         """map_pairs_sam — the same arguments, stages and records — in BAM's layout inside BGZF blocks, stored or, with compress=True,
-        deflated on the device (map_reads_bam)."""
+        deflated on the device (map_reads_bam).  sort=True: coordinate order and a BAI index, as map_reads_bam's; of two ends at one
+        position end 1 stays in front, and an unmapped end stays right behind the mate whose position it takes."""
         return self._map_pairs_records("bam", block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name,
                                        k_best, max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap,
-                                       compress)
+                                       compress, sort)
 
     def _map_pairs_records(self, fmt: str, block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
-                           max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap, compress=False):
+                           max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap, compress=False, sort=False):
         """What map_pairs_sam and map_pairs_bam share: everything but the format of the records."""
         who = f"map_pairs_{fmt}"
         reads = (self._one_length(who, reads1), self._one_length(who, reads2))
         ns = reads[0].shape[0]
         if (quals1 is None) != (quals2 is None):
             raise B.BgsaHipError(f"{who}: rc=-1: quals1 and quals2 come together")
-        checked = [self._check_records_call(fmt, who, np.full(ns, rows.shape[1]), names, quals, reference_name, block_payload, compress)
+        checked = [self._check_records_call(fmt, who, np.full(ns, rows.shape[1]), names, quals, reference_name, block_payload, compress, sort)
                    for rows, quals in zip(reads, (quals1, quals2))]
         call = check_pair_call(self.both_strands, reads[0].shape, reads[1].shape, insert_min, insert_max, k_best, max_distance,
                                rescue_distance, seeded, seed_len, max_candidates, cigar_cap, self.window_len, self.stride, self.ref_len,
@@ -1347,12 +1549,13 @@ class ReferenceMapper:
         ends = [self._rescue_checked(e, reads, single, call, insert_max, block_rows) for e in range(2)]      # stage B
         chosen = self.pair_select(ends[0][0][:5], ends[1][0][:5], insert_min, insert_max, block_rows)      # stage C
         a.check_faults()
-        return self.sam_pair_records(who, reads, ends, chosen, call, checked, fmt=fmt, block_payload=block_payload, compress=compress)
+        return self.sam_pair_records(who, reads, ends, chosen, call, checked, fmt=fmt, block_payload=block_payload, compress=compress,
+                                     sort=sort)
 
     def sam_pair_records(self, who: str, reads, ends, chosen, call: dict, checked, **form):
         """The records of pairs from the device results of map_pairs' stages: ends[e] = rescue_end's return for end e, chosen =
         pair_select's, call = check_pair_call's dict, checked[e] = check_sam_call's return for end e.  form: sam_records' fmt,
-        block_payload and compress."""
+        block_payload, compress and sort."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = reads[0].shape[0]
         lists = [final for final, _, _, _ in ends]
@@ -1658,24 +1861,32 @@ class ContigMapper(ReferenceMapper):
         return out
 
     # ---- SAM records: the contig form ------------------------------------------------------------------------------------------
-    def sam_header(self, reference_name=None) -> bytes:
-        """@HD (unsorted), one @SQ per contig in order — its name and its own length —, @PG.  reference_name is not used."""
+    def sam_header(self, reference_name=None, sort_order="unsorted") -> bytes:
+        """@HD (SO: sort_order, "unsorted" or "coordinate"), one @SQ per contig in order — its name and its own length —, @PG.
+        reference_name is not used."""
         lines = [b"@SQ\tSN:" + name + b"\tLN:" + str(int(n)).encode() + b"\n" for name, n in zip(self.contig_names, self.contig_lens)]
-        return b"@HD\tVN:1.6\tSO:unsorted\n" + b"".join(lines) + b"@PG\tID:bgsa-hip\n"
+        return sort_order_line("sam_header", sort_order) + b"".join(lines) + b"@PG\tID:bgsa-hip\n"
 
     def _sam_passes(self, fmt: str = "sam") -> tuple:
         L, table = B.lib(), self.contig_table
         measure, emit = getattr(L, f"bgsa_hip_{fmt}_measure_contigs_dev"), getattr(L, f"bgsa_hip_{fmt}_emit_contigs_dev")
         return (lambda batch, *rest: measure(batch, table, *rest), lambda batch, *rest: emit(batch, table, *rest))
 
-    def bam_header(self, reference_name=None) -> bytes:
+    def bam_header(self, reference_name=None, sort_order="unsorted") -> bytes:
         """The UNCOMPRESSED BAM header: sam_header's text and one reference entry per contig, in the order refID counts them.
         reference_name is not used."""
-        return bam_header_bytes("bam_header", self.sam_header(), list(zip(self.contig_names, self.contig_lens.tolist())))
+        return bam_header_bytes("bam_header", self.sam_header(sort_order=sort_order), list(zip(self.contig_names, self.contig_lens.tolist())))
+
+    def _coordinates_pass(self):
+        call, table = B.lib().bgsa_hip_bam_coordinates_contigs_dev, self.contig_table
+        return lambda batch, *rest: call(batch, table, *rest)
+
+    def index_ref_lens(self) -> np.ndarray:
+        return np.asarray(self.contig_lens, dtype=np.int64)
 
     def sam_records(self, who: str, reads, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, **form):
         """ReferenceMapper.sam_records through the contig passes: the fields are linear, the device localises them; TLEN is set to 0
-        where the mate lies on another contig; the pos column comes back local.  rname is not used.  form: fmt, block_payload, compress."""
+        where the mate lies on another contig; the pos column comes back local.  rname is not used.  form: fmt, block_payload, compress, sort."""
         torch = self.aligner.torch
         own = torch.searchsorted(self.d_contig_starts, fields["ref_begin"].contiguous(), right=True)
         mate = torch.searchsorted(self.d_contig_starts, (fields["pnext"] - 1).contiguous(), right=True)
@@ -1694,12 +1905,12 @@ class ContigMapper(ReferenceMapper):
         self._check_insert("map_pairs_sam", insert_max)
         return super().map_pairs_sam(reads1, reads2, insert_min, insert_max, *args, **kwargs)
 
-    def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", **kwargs) -> BamRecords:
+    def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", **kwargs):
         """ReferenceMapper.map_reads_bam with refID the contig's index in bam_header's order and pos local to it.  reference_name is not
         used."""
         return super().map_reads_bam(reads, names, quals, reference_name, **kwargs)
 
-    def map_pairs_bam(self, reads1, reads2, insert_min: int, insert_max: int, *args, **kwargs) -> BamRecords:
+    def map_pairs_bam(self, reads1, reads2, insert_min: int, insert_max: int, *args, **kwargs):
         """ReferenceMapper.map_pairs_bam in the contig form: next_refID the mate's contig, next_pos local, tlen 0 across contigs.
         insert_max > contig_padding is refused first."""
         self._check_insert("map_pairs_bam", insert_max)

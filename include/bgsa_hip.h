@@ -1084,6 +1084,75 @@ int bgsa_hip_bgzf_deflate_dev(const uint8_t *d_payload, int64_t payload_bytes, i
 int bgsa_hip_bgzf_pack_dev(const uint8_t *d_slots, int block_payload, int64_t n_blocks, const int64_t *d_block_offsets, uint8_t *d_out,
                            int64_t out_bytes, int32_t *d_refused, void *stream);
 
+/* ---- BAM records: coordinate order and index — the keys a caller sorts a batch by, and the arrays of a BAI index (SAMv1 §5.2) ----
+ * Downstream tools take a coordinate-sorted, indexed BAM.  bgsa_hip_bam_coordinates_dev gives every record of a batch its sort key
+ * and coordinates; the caller sorts the keys (stable), gathers the per-record arrays of the batch by the permutation — d_runs_row
+ * becomes the permutation, no run moves — and runs measure, scan, emit and frame (or deflate and pack) as above.  From the SORTED
+ * coordinates, the record offsets and the block offsets, bgsa_hip_bam_index_marks_dev and bgsa_hip_bam_index_chunks_dev then build
+ * the index arrays (bam_index.hip; bgsa_amd/reference.py: sam_records(sort=True), bai_bytes, write_bam(index=True)).
+ * DEFINITIONS (normative; tests/bai_reference.py restates them).
+ *   coordinates  the values the record pass writes for the same record ("BAM records", the contig form included): refID and pos
+ *              of a mapped record its contig's index (0 on one sequence) and POS - 1; of an unmapped end with rnext 1 its mate's;
+ *              of any other unmapped record -1 and -1.  end = pos + (ref_end - ref_begin) of a mapped record (pos + 1 where that
+ *              is 0, as its bin counts it), pos + 1 of an unmapped but placed one, 0 with pos -1.  bin = reg2bin(pos, end) in
+ *              full (not cut to 16 bits), 4680 with pos -1.
+ *   key        a non-negative int64, the order of `samtools sort`: ref' << 32 | (pos + 1) << 1 | reverse; ref' = refID, or
+ *              0x7fffffff where refID is -1 (no coordinates: last); reverse = flag >> 4 & 1.  Ties keep input order (a STABLE
+ *              sort): of two ends at one position end 1 stays in front, and an unmapped end that ties with the mate it borrowed its
+ *              position from stays right behind it (a reverse mate's key is one greater: the unmapped end goes in front).
+ *   malformed  for the key kernel: strand outside -1..1; rnext outside 0..1, pnext < 0, rnext 1 with pnext < 1; a mapped
+ *              ref_begin < 0, ref_end < ref_begin or ref_end > ref_len; in the contig form what "records" there calls malformed
+ *              about the contig of ref_begin or of pnext - 1; pos + 1 or end beyond 2^29, a BAI's reach.  Such a record gets the key
+ *              INT64_MAX, refID -1, pos -1, end 0, bin 4680 and adds 1 to *d_malformed; no value of it forms an address.  The kernel
+ *              does not walk the runs: the measure pass that follows on the permuted batch still applies the full record check.
+ *   virtual offset  of a payload offset o, P = block_payload: block_start(o / P) << 16 | o % P; block_start(b) = b * (P + 31) for
+ *              stored blocks, d_block_offsets[b] (n_blocks + 1 entries, the scan bgsa_hip_bgzf_pack_dev takes) for deflated ones; so
+ *              o = payload_bytes on a block boundary gives out_bytes << 16.  Record i: voff_beg that of d_offsets[i], voff_end that
+ *              of d_offsets[i + 1].  All relative to the first byte of the call's blocks: a file adds base << 16, base the byte
+ *              length of the framed header in front.
+ *   chunks     over the sorted records with refID >= 0, every maximal run of consecutive records of equal (refID, bin) is one
+ *              chunk (refID, bin, voff_beg of its first record, voff_end of its last) — htslib's hts_idx_push rule, without its
+ *              later merge of small bins.  The list is ordered by (refID, bin, beg).
+ *   linear     reference c has ceil(len_c / 16384) windows; linear[c][w] = the smallest voff_beg of a record of c with
+ *              pos >> 14 <= w <= (end - 1) >> 14, unmapped-placed records included; n_intv[c] = 1 + the last non-empty window, 0
+ *              without one; an empty window below n_intv[c] takes the value of the next non-empty one (a suffix minimum).
+ *   metadata   pseudo-bin 37450 of every reference with a record: (smallest voff_beg, largest voff_end), then (records with flag 4
+ *              clear, records with flag 4 set); n_no_coor = the records with refID -1.
+ *   .bai       "BAI\1", n_ref; per reference n_bin, per bin ascending and 37450 last: bin, n_chunk, the chunks as uint64 pairs;
+ *              n_intv and the ioffsets; n_no_coor at the end.  All little-endian.  A reference without records: n_bin 0, n_intv 0.
+ * bgsa_hip_bam_coordinates_dev / _contigs_dev: one THREAD per record of the batch as assembled; d_key int64[n], the others int32[n].
+ * bgsa_hip_bam_index_windows: host only — window_base_out[n_refs + 1] = the exclusive scan of ceil(len / 16384); returns the
+ * total, -1 for a NULL pointer, a negative n_refs or a length < 1 or > 2^29.
+ * bgsa_hip_bam_index_marks_dev: SORTED coordinates in; per record d_voff_beg, d_voff_end and d_chunk_start — 1 where refID >= 0
+ * and (i == 0 or (refID, bin) differs from record i - 1's), else 0 —, and the linear minima by a 64-bit atomicMin on
+ * d_linear[d_window_base[refID] + w], which the caller filled with INT64_MAX (d_window_base[n_refs] entries); a window the
+ * record's predecessor on the same reference covers is skipped: that offset is smaller.  d_block_offsets NULL: stored blocks.  A
+ * record is REFUSED — it adds 1 to *d_refused (the caller zeroes it), gets flag 0 and touches nothing else — when refID is outside
+ * [-1, n_refs); refID >= 0 and pos < 0, end <= pos, or end beyond the reference's windows (or the window table is not monotone);
+ * its offsets are negative, not monotone or beyond payload_bytes; its block is beyond n_blocks; it stands before its predecessor
+ * in (ref', pos) order.
+ * bgsa_hip_bam_index_chunks_dev: d_chunk_of = the inclusive scan of d_chunk_start (the caller's; n_chunks its last entry, one
+ * scalar read back); chunk c = d_chunk_of[i] - 1.  A start writes ref, bin and beg of its chunk; a record with refID >= 0 whose
+ * successor is a start, has refID -1 or does not exist writes end.  A d_chunk_of[i] outside 1..n_chunks is refused and counted.
+ * The caller then sorts the chunks by ref << 32 | bin (stable) and takes the suffix minimum over d_linear.
+ * The four device calls only launch on `stream`: no allocation, no synchronisation; n == 0 is BGSA_HIP_OK and launches nothing.
+ * BGSA_HIP_EINVAL, before the first HIP call: a NULL pointer (the stream, d_quals and d_block_offsets excepted), a negative count,
+ * a block_payload outside 1..65280, what the SAM passes refuse about the batch and the table.
+ * LIMITS: one call, one sorted file (no merge of batches); BAI only (contigs up to 2^29 bases, no CSI); no merge of small bins. */
+int bgsa_hip_bam_coordinates_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int64_t *d_key, int32_t *d_ref_id, int32_t *d_pos,
+                                 int32_t *d_end, int32_t *d_bin, int32_t *d_malformed, void *stream);
+int bgsa_hip_bam_coordinates_contigs_dev(const bgsa_hip_sam_batch_t *batch, const bgsa_hip_sam_contigs_t *contigs, int64_t n, int64_t *d_key,
+                                         int32_t *d_ref_id, int32_t *d_pos, int32_t *d_end, int32_t *d_bin, int32_t *d_malformed, void *stream);
+int64_t bgsa_hip_bam_index_windows(const int64_t *ref_lens, int64_t n_refs, int64_t *window_base_out);
+int bgsa_hip_bam_index_marks_dev(const int32_t *d_ref_id, const int32_t *d_pos, const int32_t *d_end, const int32_t *d_bin, int64_t n,
+                                 const int64_t *d_offsets, int64_t payload_bytes, int block_payload, const int64_t *d_block_offsets,
+                                 int64_t n_blocks, const int64_t *d_window_base, int64_t n_refs, int64_t *d_voff_beg, int64_t *d_voff_end,
+                                 int32_t *d_chunk_start, int64_t *d_linear, int32_t *d_refused, void *stream);
+int bgsa_hip_bam_index_chunks_dev(const int32_t *d_ref_id, const int32_t *d_bin, const int64_t *d_voff_beg, const int64_t *d_voff_end,
+                                  const int32_t *d_chunk_start, const int64_t *d_chunk_of, int64_t n, int64_t n_chunks,
+                                  int32_t *d_chunk_ref, int32_t *d_chunk_bin, int64_t *d_chunk_beg, int64_t *d_chunk_end,
+                                  int32_t *d_refused, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
