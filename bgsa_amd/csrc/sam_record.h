@@ -327,8 +327,9 @@ int check_batch(const char *who, const Batch *b, int64_t n, bool one_name = true
     return BGSA_HIP_OK;
 }
 
-// The contig form's batch (d_rname and rname_len are not read: RNAME comes from the table) and its table.
-int check_contig_batch(const char *who, const Batch *b, const Contigs *ct, int64_t n)
+// The contig form's batch (d_rname and rname_len are not read: RNAME comes from the table) and its table.  mark_duplicates.hip
+// has no contig form, hence maybe_unused.
+[[maybe_unused]] int check_contig_batch(const char *who, const Batch *b, const Contigs *ct, int64_t n)
 {
     if (int rc = check_batch(who, b, n, false)) return rc;
     if (!ct) return refuse(who, BGSA_HIP_EINVAL, "the contig table is NULL");

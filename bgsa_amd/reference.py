@@ -523,6 +523,19 @@ BAI_META_BIN = 37450
 SORT_ORDERS = ("unsorted", "coordinate")
 
 
+# ---- duplicate marking: include/bgsa_hip.h "Duplicate marking" — the host side, no device, no library ---------------------------
+DUPLICATE_FLAG = 0x400
+DUPLICATE_MIN_QUALITY = 15        # Picard's SUM_OF_BASE_QUALITIES counts the bases of quality 15 and above
+DUPLICATE_STATS = ("pair_units", "fragment_units", "records_skipped", "duplicate_pair_units", "duplicate_fragment_units", "records_flagged")
+
+
+def check_mark_duplicates(who: str, mark_duplicates) -> bool:
+    """The refusal of a mark_duplicates that is not a bool, in sort's wording; before anything is launched."""
+    if not isinstance(mark_duplicates, (bool, np.bool_)):
+        raise B.BgsaHipError(f"{who}: rc=-1: mark_duplicates {mark_duplicates!r} is not a bool")
+    return bool(mark_duplicates)
+
+
 class BamIndex(NamedTuple):
     """The arrays of a BAI index as the device built them for ONE call's sorted records; offsets are virtual offsets relative to
     the first byte of the call's blocks."""
@@ -645,6 +658,7 @@ class ReferenceMapper:
         self.d_verify_work = None   # the carries of a verify beyond 16 words, grown on demand
         self.last_seed_stats = None
         self.last_pair_stats = None
+        self.last_duplicate_stats = None    # of the last SAM / BAM call with mark_duplicates=True
 
     def _rows_buffer(self, n_rows: int):
         need = n_rows * (self.window_len + 1) + 8
@@ -1225,7 +1239,8 @@ class ReferenceMapper:
         return pick(strand).masked_fill(slot < 0, -1), pick(ref_begin), pick(ref_end), -pick(scores), pick(n_ops), runs
 
     def sam_records(self, who: str, reads: np.ndarray, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, fmt: str = "sam",
-                    block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False):
+                    block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False, mark_duplicates: bool = False,
+                    ends: int = 1):
         """The two record passes.  reads [n_rows, stride] and quals (or None) are the host rows, names / name_offsets / rname what
         check_sam_call returned; fields holds the per-record DEVICE tensors read_row, name_of (int64), read_len, strand, ref_begin,
         ref_end, distance, n_ops, flag, mapq, rnext, pnext, tlen; runs [n, cap] int32 holds record i's runs in row i.  Measure, an
@@ -1237,7 +1252,10 @@ class ReferenceMapper:
         copied once — fewer bytes than the payload.  sort (fmt "bam" only; include/bgsa_hip.h "BAM records: coordinate order and
         index"): the key pass on the batch as assembled, torch.sort(stable=True) of the keys, the per-record tensors gathered by the
         permutation — the runs stay where they are, d_runs_row is the permutation —, then the passes above on the permuted batch and
-        the index (bam_index): SortedBamRecords, its columns in output order."""
+        the index (bam_index): SortedBamRecords, its columns in output order.  mark_duplicates (any fmt; include/bgsa_hip.h
+        "Duplicate marking"): on a COPY of fields["flag"], right after the batch is assembled and before the sort, the duplicate
+        records of this batch get bit 1024 (mark_duplicate_records; ends 2: records 2u and 2u + 1 are pair u) and
+        last_duplicate_stats is filled; everything downstream reads the changed flags."""
         if sort and fmt != "bam":
             raise B.BgsaHipError(f"{who}: rc=-1: sort=True needs fmt 'bam'")
         a = self.aligner
@@ -1268,6 +1286,9 @@ class ReferenceMapper:
                               f["strand"].data_ptr(), f["ref_begin"].data_ptr(), f["ref_end"].data_ptr(), f["distance"].data_ptr(),
                               f["n_ops"].data_ptr(), f["flag"].data_ptr(), f["mapq"].data_ptr(), f["rnext"].data_ptr(), f["pnext"].data_ptr(),
                               f["tlen"].data_ptr())
+        if mark_duplicates:
+            f = dict(f, flag=f["flag"].clone())
+            self.last_duplicate_stats = self.mark_duplicate_records(batch_of(f, runs_row), n, int(ends), f["flag"])
         coordinates = None
         if sort:
             key, *coordinates = self.bam_coordinates(batch_of(f, runs_row), n)
@@ -1315,6 +1336,49 @@ class ReferenceMapper:
                                     mapq.cpu().numpy(), nm.cpu().numpy(), coordinates[0].cpu().numpy(), host_order, index)
         return kind(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(), mapq.cpu().numpy(),
                     nm.cpu().numpy())
+
+    def duplicate_keys(self, batch, n: int, ends: int, counts) -> tuple:
+        """The key kernel on a bgsa_hip_sam_batch_t of n records: the device tensors (end key int64[n], score int32[n / ends], the
+        pair key's halves int64[n / ends] each); counts int32[3] += pair units, fragment units, skipped records."""
+        a = self.aligner
+        torch, dev = a.torch, a.device
+        units = n // ends if ends in (1, 2) else 0
+        end_key = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        score = torch.empty(max(units, 1), dtype=torch.int32, device=dev)
+        key_a, key_b = (torch.empty(max(units, 1), dtype=torch.int64, device=dev) for _ in range(2))
+        B.check(B.lib().bgsa_hip_dup_keys_dev(batch, n, ends, DUPLICATE_MIN_QUALITY, end_key.data_ptr(), score.data_ptr(), key_a.data_ptr(),
+                                              key_b.data_ptr(), counts.data_ptr(), a._stream()), "dup_keys_dev")
+        return end_key[:n], score[:units], key_a[:units], key_b[:units]
+
+    def duplicate_order(self, score, *keys) -> tuple:
+        """(the permutation, the keys gathered by it) that leaves the entries in (keys ascending, the first the most significant;
+        score descending; index ascending) order: stable torch.sort passes, least significant key first — plumbing."""
+        torch = self.aligner.torch
+        order = torch.sort(-score.to(torch.int64), stable=True)[1]
+        for key in reversed(keys):
+            order = order[torch.sort(key[order], stable=True)[1]]
+        return order.contiguous(), [key[order].contiguous() for key in keys]
+
+    def duplicate_marks(self, keys, order, n: int, ends: int, flag, counts) -> None:
+        """The mark kernel on sorted entries: ends 2 the pair pass (keys = the two halves), ends 1 the end pass (keys = the end
+        keys); flag int32[n] gets bit 1024; counts int32[3] += duplicate pair units, duplicate fragment units, records flagged."""
+        B.check(B.lib().bgsa_hip_dup_mark_dev(keys[0].data_ptr(), keys[1].data_ptr() if len(keys) > 1 else None, order.data_ptr(), n, ends,
+                                              flag.data_ptr(), counts.data_ptr(), self.aligner._stream()), "dup_mark_dev")
+
+    def mark_duplicate_records(self, batch, n: int, ends: int, flag) -> dict:
+        """Duplicate marking of the batch as assembled (include/bgsa_hip.h "Duplicate marking"): keys and scores, for a paired
+        batch the pair pass, then the end pass; the device tensor `flag` (the batch's d_flag) gets bit 1024 on the duplicates.  No
+        per-record array goes to the host: the six counters come back in one small copy, as the dict last_duplicate_stats holds."""
+        torch = self.aligner.torch
+        counts = torch.zeros(6, dtype=torch.int32, device=self.aligner.device)
+        end_key, score, key_a, key_b = self.duplicate_keys(batch, n, ends, counts[0:])
+        if n and ends == 2:
+            order, keys = self.duplicate_order(score, key_a, key_b)
+            self.duplicate_marks(keys, order, n, 2, flag, counts[3:])
+        if n:
+            order, keys = self.duplicate_order(score.repeat_interleave(ends), end_key)
+            self.duplicate_marks(keys, order, n, 1, flag, counts[3:])
+        return dict(zip(DUPLICATE_STATS, counts.tolist()))
 
     def bam_coordinates(self, batch, n: int) -> tuple:
         """The key pass on a bgsa_hip_sam_batch_t of n records: the device tensors (key int64, ref_id, pos, end, bin int32, the
@@ -1446,7 +1510,7 @@ class ReferenceMapper:
         return sink
 
     def map_reads_sam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
-                      seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None) -> SamRecords:
+                      seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None, mark_duplicates: bool = False) -> SamRecords:
         """Single-end reads to SAM records, formatted on the device (include/bgsa_hip.h "SAM records").  reads: a [ns, n] uint8 array
         or a list of byte strings of mixed lengths; the mapping is that of the matching entry point of the four — map_reads_seeded
         (seeded=True: max_distance is required), map_reads, or their _ragged forms — with its refusals.  Every read gives ONE record,
@@ -1454,13 +1518,16 @@ class ReferenceMapper:
         max_distance for a seeded call, whose filter makes the list complete within it, at -1 (no bound) for an exhaustive one, whose
         list is its best windows whatever their distance; a second locus is only sure to be listed with k_best >= 2, hence the default.  names=None: r0,
         r1, ...; quals=None: '*'.  check_sam_call refuses before anything is launched.  Nothing but the text, its offsets and four
-        columns is copied back; no CIGAR string is made on the host."""
+        columns is copied back; no CIGAR string is made on the host.  mark_duplicates=True: the duplicate reads among THIS call's
+        records carry flag bit 1024 (include/bgsa_hip.h "Duplicate marking": mapped reads of equal 5' coordinate — of the record
+        as written — and strand; the highest sum of base qualities >= 15 stays, ties the first read); nothing else changes, and
+        last_duplicate_stats holds the counts.  Duplicates are found within one call only."""
         return self._map_reads_records("sam", None, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len, max_candidates,
-                                       block_rows, cigar_cap)
+                                       block_rows, cigar_cap, mark_duplicates=mark_duplicates)
 
     def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
                       seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None,
-                      block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False):
+                      block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False, mark_duplicates: bool = False):
         """map_reads_sam — the same arguments, mapping and record selection — with the records in BAM's layout inside BGZF blocks of
         stored deflate, block_payload bytes of records each (include/bgsa_hip.h "BAM records"): measure, scan, emit, frame, all on the
         device, one copy of the blocks.  A record may straddle blocks.  compress=True: every block deflated on the device instead (LZ77
@@ -1469,9 +1536,11 @@ class ReferenceMapper:
         write_bam the blocks of one or more calls, compressed or not, make a file.  sort=True: the records of this call leave the
         device in coordinate order (the `samtools sort` key, ties in input order, records without coordinates last) with the arrays
         of a BAI index beside them — SortedBamRecords; bam_header(sort_order="coordinate") and write_bam(index=True) then write
-        x.bam and x.bam.bai (include/bgsa_hip.h "BAM records: coordinate order and index").  A sorted file holds ONE call's records."""
+        x.bam and x.bam.bai (include/bgsa_hip.h "BAM records: coordinate order and index").  A sorted file holds ONE call's records.
+        mark_duplicates=True: map_reads_sam's, independent of compress and sort — the flags change before the records are sorted and
+        written, so order and index are those of the unmarked call; duplicates are found within one call only."""
         return self._map_reads_records("bam", block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                                       max_candidates, block_rows, cigar_cap, compress, sort)
+                                       max_candidates, block_rows, cigar_cap, compress, sort, mark_duplicates)
 
     def _check_records_call(self, fmt: str, who: str, lens, names, quals, reference_name, block_payload, compress=False, sort=False) -> tuple:
         if fmt == "bam":
@@ -1479,9 +1548,10 @@ class ReferenceMapper:
         return check_sam_call(who, lens, names, quals, reference_name)
 
     def _map_reads_records(self, fmt: str, block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                           max_candidates, block_rows, cigar_cap, compress=False, sort=False):
+                           max_candidates, block_rows, cigar_cap, compress=False, sort=False, mark_duplicates=False):
         """What map_reads_sam and map_reads_bam share: everything but the format of the records."""
         who = f"map_reads_{fmt}"
+        mark_duplicates = check_mark_duplicates(who, mark_duplicates)
         rows, lens, ragged = self._sam_rows(who, reads)
         rname, flat, name_offsets, qual_rows = self._check_records_call(fmt, who, lens, names, quals, reference_name, block_payload,
                                                                         compress, sort)
@@ -1490,11 +1560,11 @@ class ReferenceMapper:
                             max_candidates, block_rows, cigar_cap)
         self.aligner.check_faults()
         return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname, fmt=fmt, block_payload=block_payload,
-                                       compress=compress, sort=sort)
+                                       compress=compress, sort=sort, mark_duplicates=mark_duplicates)
 
     def sam_single_records(self, who: str, sink: "PrimarySink", rows: np.ndarray, lens, qual_rows, names, name_offsets, rname, **form):
         """The records of single-end reads from their primaries on the device: flag 0, 16 or 4, no mate fields.  form: sam_records'
-        fmt, block_payload, compress and sort."""
+        fmt, block_payload, compress, sort and mark_duplicates (every mapped record a fragment unit: ends 1)."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = rows.shape[0]
         index = torch.arange(ns, dtype=torch.int64, device=dev)
@@ -1503,34 +1573,43 @@ class ReferenceMapper:
         fields = dict(read_row=index, name_of=index, read_len=torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev),
                       strand=sink.strand, ref_begin=sink.ref_begin, ref_end=sink.ref_end, distance=sink.distance, n_ops=sink.n_ops,
                       flag=flag, mapq=sink.mapq, rnext=torch.zeros(ns, dtype=torch.int32, device=dev), pnext=zero, tlen=zero)
-        return self.sam_records(who, rows, qual_rows, names, name_offsets, rname, fields, sink.runs, **form)
+        return self.sam_records(who, rows, qual_rows, names, name_offsets, rname, fields, sink.runs, ends=1, **form)
 
     def map_pairs_sam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
                       reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
-                      max_candidates=None, block_rows: int = 1000, cigar_cap=None) -> SamRecords:
+                      max_candidates=None, block_rows: int = 1000, cigar_cap=None, mark_duplicates: bool = False) -> SamRecords:
         """map_pairs to SAM records, formatted on the device: two records per pair, end 1 then end 2, each the slot pair_select chose
         (a proper pair: flag 2) or the end's first kept hit, else unmapped.  Flags 1, 2, 4, 8, 16, 32, 64 / 128; RNEXT '=' and PNEXT
         where the mate is mapped; TLEN where both are; an unmapped end beside a mapped mate takes the mate's RNAME and POS.  MAPQ:
         pair_mapq.  One name per pair.  The stages are map_pairs' own (stage A through the same pipeline, without its strings);
-        last_pair_stats is not touched.  check_sam_call and check_pair_call refuse before anything is launched."""
+        last_pair_stats is not touched.  check_sam_call and check_pair_call refuse before anything is launched.  mark_duplicates=True:
+        both records of every duplicate pair among THIS call's pairs carry flag bit 1024 (include/bgsa_hip.h "Duplicate marking":
+        pairs with both ends mapped, of equal 5' coordinates — of the records as written — and strands; the highest sum of base
+        qualities >= 15 over both ends stays, ties the first pair), and so does a mapped end whose mate is unmapped where it stands on
+        an end of such a pair or behind a better end of its kind; an unmapped mate is not flagged.  last_duplicate_stats holds the
+        counts.  Duplicates are found within one call only."""
         return self._map_pairs_records("sam", None, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
-                                       max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap)
+                                       max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap,
+                                       mark_duplicates=mark_duplicates)
 
     def map_pairs_bam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
                       reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
                       max_candidates=None, block_rows: int = 1000, cigar_cap=None, block_payload: int = BGZF_BLOCK_PAYLOAD,
-                      compress: bool = False, sort: bool = False):
+                      compress: bool = False, sort: bool = False, mark_duplicates: bool = False):
         """map_pairs_sam — the same arguments, stages and records — in BAM's layout inside BGZF blocks, stored or, with compress=True,
         deflated on the device (map_reads_bam).  sort=True: coordinate order and a BAI index, as map_reads_bam's; of two ends at one
-        position end 1 stays in front, and an unmapped end stays right behind the mate whose position it takes."""
+        position end 1 stays in front, and an unmapped end stays right behind the mate whose position it takes.
+        mark_duplicates=True: map_pairs_sam's, independent of compress and sort; duplicates are found within one call only."""
         return self._map_pairs_records("bam", block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name,
                                        k_best, max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap,
-                                       compress, sort)
+                                       compress, sort, mark_duplicates)
 
     def _map_pairs_records(self, fmt: str, block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
-                           max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap, compress=False, sort=False):
+                           max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap, compress=False, sort=False,
+                           mark_duplicates=False):
         """What map_pairs_sam and map_pairs_bam share: everything but the format of the records."""
         who = f"map_pairs_{fmt}"
+        mark_duplicates = check_mark_duplicates(who, mark_duplicates)
         reads = (self._one_length(who, reads1), self._one_length(who, reads2))
         ns = reads[0].shape[0]
         if (quals1 is None) != (quals2 is None):
@@ -1550,12 +1629,12 @@ class ReferenceMapper:
         chosen = self.pair_select(ends[0][0][:5], ends[1][0][:5], insert_min, insert_max, block_rows)      # stage C
         a.check_faults()
         return self.sam_pair_records(who, reads, ends, chosen, call, checked, fmt=fmt, block_payload=block_payload, compress=compress,
-                                     sort=sort)
+                                     sort=sort, mark_duplicates=mark_duplicates)
 
     def sam_pair_records(self, who: str, reads, ends, chosen, call: dict, checked, **form):
         """The records of pairs from the device results of map_pairs' stages: ends[e] = rescue_end's return for end e, chosen =
         pair_select's, call = check_pair_call's dict, checked[e] = check_sam_call's return for end e.  form: sam_records' fmt,
-        block_payload, compress and sort."""
+        block_payload, compress, sort and mark_duplicates (records 2u and 2u + 1 are pair u: ends 2)."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = reads[0].shape[0]
         lists = [final for final, _, _, _ in ends]
@@ -1594,7 +1673,7 @@ class ReferenceMapper:
         rname, flat, name_offsets, _ = checked[0]
         return self.sam_records(who, rows.reshape(2 * ns, stride), None if qual_rows is None else qual_rows.reshape(2 * ns, stride), flat,
                                 name_offsets, rname, fields, interleave(picked[0][5], picked[1][5]),
-                                read_label=lambda i: f"end {i % 2 + 1} of pair {i // 2}", **form)
+                                read_label=lambda i: f"end {i % 2 + 1} of pair {i // 2}", ends=2, **form)
 
 
 # ---- the sinks of ReferenceMapper._map_bins: what the SAM entry points keep of a bucket's device tensors ---------------------------
@@ -1886,7 +1965,8 @@ class ContigMapper(ReferenceMapper):
 
     def sam_records(self, who: str, reads, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, **form):
         """ReferenceMapper.sam_records through the contig passes: the fields are linear, the device localises them; TLEN is set to 0
-        where the mate lies on another contig; the pos column comes back local.  rname is not used.  form: fmt, block_payload, compress, sort."""
+        where the mate lies on another contig; the pos column comes back local.  rname is not used.  form: fmt, block_payload, compress, sort,
+        mark_duplicates and ends (the duplicate keys are linear coordinates: equal local positions on two contigs are two keys)."""
         torch = self.aligner.torch
         own = torch.searchsorted(self.d_contig_starts, fields["ref_begin"].contiguous(), right=True)
         mate = torch.searchsorted(self.d_contig_starts, (fields["pnext"] - 1).contiguous(), right=True)

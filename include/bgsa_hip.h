@@ -1153,6 +1153,48 @@ int bgsa_hip_bam_index_chunks_dev(const int32_t *d_ref_id, const int32_t *d_bin,
                                   int32_t *d_chunk_ref, int32_t *d_chunk_bin, int64_t *d_chunk_beg, int64_t *d_chunk_end,
                                   int32_t *d_refused, void *stream);
 
+/* ---- Duplicate marking: flag 0x400 on the PCR copies of ONE batch, before its records are written ----
+ * After `sort`, short-read workflows mark duplicates (Picard MarkDuplicates, samtools markdup).  Everything that needs is in the
+ * batch already, and the flag is a per-record scalar both record passes read: flags changed before the passes reach the SAM text,
+ * the BAM records, the sorted order and the index (the sort key reads bit 16 of the flag only).  bgsa_hip_dup_keys_dev writes the
+ * keys and scores of a batch as assembled, the caller orders them with stable sorts, bgsa_hip_dup_mark_dev ORs 1024 into the flags
+ * (mark_duplicates.hip; bgsa_amd/reference.py: sam_records(mark_duplicates=True), mark_duplicate_records).
+ * DEFINITIONS (normative; tests/markdup_reference.py restates them).  The Picard core: no optical duplicates, no UMIs, no libraries.
+ *   malformed  a record with strand outside -1..1, read_len < 0 or > read_stride, read_row outside [0, n_read_rows), or, mapped
+ *              (strand >= 0), ref_begin < 0, ref_end < ref_begin or ref_end > ref_len.  It takes its whole unit out of marking,
+ *              adds 1 to the skipped count and forms no address; the measure pass that follows refuses it as ever.
+ *   5' coordinate  of a mapped record: ref_begin on strand 0; ref_end - 1 on strand 1 (ref_begin where ref_end == ref_begin).
+ *              Linear, as in the batch — after the contig clip where there is one —: the coordinate of the record AS WRITTEN
+ *              (placement is end to end, no record carries a soft clip, so this is the unclipped 5' position).
+ *   units      ends 1: every mapped record is a fragment unit.  ends 2: records 2u and 2u + 1 are pair u; both mapped (proper or
+ *              not): one pair unit; exactly one mapped: that end is a fragment unit.  Unmapped records are in no unit.
+ *   score      of a unit: the sum of q - 33 over the QUAL bytes of its mapped records with q - 33 >= min_quality (Picard's
+ *              SUM_OF_BASE_QUALITIES at 15), at most 2^31 - 1; 0 without QUAL.
+ *   pair pass  half(e) = 5' << 1 | strand; the pair key is (the smaller half, the greater half).  Among pair units of equal key the
+ *              highest score stays, a tie goes to the lowest pair index; both records of every other one get 0x400.
+ *   end pass   every mapped record of a unit is an entry with key (5', strand), tagged paired or fragment.  A group of equal key
+ *              that holds a paired entry: every fragment of it is a duplicate.  Otherwise the fragment of the highest score stays,
+ *              a tie goes to the lowest record index.  Paired entries are never flagged here, nor is a fragment's unmapped mate.
+ * bgsa_hip_dup_keys_dev: one WAVE per unit.  d_end_key int64[n]: half << 1 | tag (tag 1: fragment, so paired entries sort first),
+ * INT64_MAX where the record is no entry.  Per unit (n / ends entries): d_score int32, d_pair_key_a / _b int64 — the two halves,
+ * INT64_MAX where the unit is no pair unit.  d_counts int32[3], zeroed by the caller: += pair units, fragment units, malformed records.
+ * bgsa_hip_dup_mark_dev: one THREAD per sorted entry.  ends 2, the pair pass: n / 2 entries, d_key_a / d_key_b the pair keys in
+ * SORTED order, d_order[j] the unit at place j.  ends 1, the end pass (of a single-end AND of a paired batch): n entries, d_key_a
+ * the end keys in sorted order, d_key_b not read (may be NULL), d_order[j] the record at place j.  The order the caller gives
+ * (stable sorts, least significant first): key ascending, score descending, index ascending.  An entry whose key equals its
+ * predecessor's — the tag left out — is a duplicate: with that order a fragment that does not head its group stands behind a paired
+ * entry or a better fragment, so this one comparison is the whole rule.  Only tagged entries are flagged in the end pass.  Entries
+ * of key INT64_MAX are none.  d_order[j] is compared with the entry count, the records with n, before d_flag is touched; every
+ * record is written by at most one thread.  d_counts int32[3]: += duplicate pair units, duplicate fragment units, records flagged.
+ * Both only launch on `stream`: no allocation, no synchronisation; n == 0 is BGSA_HIP_OK and launches nothing.  BGSA_HIP_EINVAL,
+ * before the first HIP call: a NULL pointer (the stream, d_quals and the end pass's d_key_b excepted), n < 0, ends outside 1..2, an
+ * odd n with ends 2, min_quality outside 0..93, ref_len beyond 2^60, what the SAM passes refuse about the batch.
+ * LIMITS: duplicates are found within ONE call's records; no optical duplicates, UMIs or read groups; an unmapped mate is not flagged. */
+int bgsa_hip_dup_keys_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int ends, int min_quality, int64_t *d_end_key, int32_t *d_score,
+                          int64_t *d_pair_key_a, int64_t *d_pair_key_b, int32_t *d_counts, void *stream);
+int bgsa_hip_dup_mark_dev(const int64_t *d_key_a, const int64_t *d_key_b, const int64_t *d_order, int64_t n, int ends, int32_t *d_flag,
+                          int32_t *d_counts, void *stream);
+
 /* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
