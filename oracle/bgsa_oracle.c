@@ -663,10 +663,12 @@ void bgsa_oracle_dp_semiglobal(const char *queries, int64_t nq, int qlen, const 
 }
 
 /*
- * Closed form of the banded kernel (validated there against the compiled
- * reference for qlen == slen): unit-cost DP with D[i][0] = i, D[0][j] = 0, cells restricted to
- * diagonals j - i in [-(k+1), h]; 127 if D[m-k][m-2k-1] > k+h+1; else min over j in [m-k-1, n]
- * of D[m][j].  Only meaningful for qlen == slen > 2k+1.
+ * Closed form of the banded kernel for qlen == slen: unit-cost DP with
+ * D[i][0] = i, D[0][j] = 0 for j <= h-1, cells restricted to diagonals j - i in [-(k+1), h-1]
+ * (the band's 2k+1 bits; bit 2k+1 of the reference's word only carries); with last = m if
+ * m <= 64, else max(n-h, 64) — the reference's last err > max_err test — 127 if
+ * D[last][last-k-1] > k+h+1; else min over j in [m-k-1, n] of D[m][j].  Equal to
+ * bgsa_oracle_banded64 at every qlen == slen > 2k+1 (tests/test_banded_census_cpu.py).
  */
 void bgsa_oracle_dp_banded(const char *queries, int64_t nq, int qlen, const char *subjects,
                            int64_t ns, int slen, int threshold, int8_t *out, int threads)
@@ -674,6 +676,7 @@ void bgsa_oracle_dp_banded(const char *queries, int64_t nq, int qlen, const char
     if (nq <= 0 || ns <= 0) return;
     const int k = threshold, m = qlen, n = slen, h = k + n - m;
     const int INF = 1 << 20;
+    const int last = m <= 64 ? m : (n - h > 64 ? n - h : 64);
     uint8_t *q = map_rows(queries, nq, qlen);
     uint8_t *s = map_rows(subjects, ns, slen);
 #pragma omp parallel num_threads(pick_threads(threads))
@@ -685,18 +688,18 @@ void bgsa_oracle_dp_banded(const char *queries, int64_t nq, int qlen, const char
             for (int64_t sj = 0; sj < ns; sj++) {
                 const uint8_t *a = q + qi * m, *b = s + sj * n;
                 int check = INF;
-                for (int j = 0; j <= n; j++) prev[j] = (j <= h) ? 0 : INF;
+                for (int j = 0; j <= n; j++) prev[j] = (j <= h - 1) ? 0 : INF;
                 for (int i = 1; i <= m; i++) {
                     for (int j = 0; j <= n; j++) {
                         int d = j - i;
-                        if (d < -(k + 1) || d > h) { cur[j] = INF; continue; }
+                        if (d < -(k + 1) || d > h - 1) { cur[j] = INF; continue; }
                         if (j == 0) { cur[j] = i; continue; }
                         int best = prev[j - 1] + (a[i - 1] != b[j - 1]);
                         if (prev[j] + 1 < best) best = prev[j] + 1;
                         if (cur[j - 1] + 1 < best) best = cur[j - 1] + 1;
                         cur[j] = best;
                     }
-                    if (i == m - k && m - 2 * k - 1 >= 0) check = cur[m - 2 * k - 1];
+                    if (i == last && last - k - 1 >= 0) check = cur[last - k - 1];
                     int *t = prev; prev = cur; cur = t;
                 }
                 int8_t r;

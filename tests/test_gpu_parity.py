@@ -1352,7 +1352,7 @@ print("knobs ok")
                                  {"BGSA_BANDED_PUSH_SOLID": "0", "BGSA_BANDED_SOLID_MARGIN": "0"},   # any lane within the limit counts as a solid survivor, from the first test
                                  {"BGSA_BANDED_PUSH_SOLID": "48", "BGSA_BANDED_GROUPS": "2"},
                                  {"BGSA_BANDED_PUSH_MAX": "0"},                               # no survivor queue
-                                 {"BGSA_BANDED_PUSH_MAX": "64", "BGSA_BANDED_PUSH_ROW": "0"},   # everything alive at the first test is queued
+                                 {"BGSA_BANDED_PUSH_MAX": "32", "BGSA_BANDED_PUSH_ROW": "0"},   # everything alive at the first test is queued (32: the most banded_push_max takes)
                                  {"BGSA_MYERS_MAX_PLAIN_WORDS": "8"},
                                  {"BGSA_MYERS_MAX_PLAIN_WORDS": "8", "BGSA_MYERS_BLOCK_FORM": "planes"},
                                  {"BGSA_MYERS_PEQ_MAX_WORDS": "8"},
