@@ -173,6 +173,7 @@ def lib() -> ctypes.CDLL:
                                  ("bgsa_hip_seed_count_candidates_dev", seed + [i64, vp, vp], i32),
                                  ("bgsa_hip_seed_emit_candidates_dev", seed + [vp, vp, i64, vp, vp, vp], i32),
                                  ("bgsa_hip_reference_verify_workspace_bytes", [i32, i32, i64], sz),
+                                 ("bgsa_hip_reference_verify_kernel_name", [i32, i32], ctypes.c_char_p),
                                  ("bgsa_hip_reference_verify_pairs_dev",
                                   [vp, i64, i32, i32, vp, i32, i64, i32, vp, vp, i64, i64, vp, vp, sz, vp], i32),
                                  ("bgsa_hip_seed_select_dev", [vp, vp, vp, i64, i32, i32, vp, vp, vp], i32),

@@ -441,20 +441,43 @@ int launch_verify(const VerifyArgs &a, dim3 grid, int64_t first, hipStream_t str
     return BGSA_HIP_OK;
 }
 
+// ---- which instance verifies a read of wn words: decided here, once; dispatch_verify launches the answer,
+// verify_kernel_name formats it ----
+template <int WB, bool Blocks>
+struct VerifyWidth {
+    static constexpr int words = WB;
+    static constexpr bool blocks = Blocks;
+};
+
 // The narrowest instance that holds the read in one block; column blocks of kVerifyWords beyond that.
+template <typename F>
+int verify_select(int wn, F &&f)
+{
+    if (wn > kVerifyWords) return f(VerifyWidth<kVerifyWords, true>{});
+    if (wn <= 1) return f(VerifyWidth<1, false>{});
+    if (wn <= 2) return f(VerifyWidth<2, false>{});
+    if (wn <= 3) return f(VerifyWidth<3, false>{});
+    if (wn <= 4) return f(VerifyWidth<4, false>{});
+    if (wn <= 5) return f(VerifyWidth<5, false>{});
+    if (wn <= 6) return f(VerifyWidth<6, false>{});
+    if (wn <= 8) return f(VerifyWidth<8, false>{});
+    if (wn <= 12) return f(VerifyWidth<12, false>{});
+    return f(VerifyWidth<16, false>{});
+}
+
 int dispatch_verify(const VerifyArgs &a, dim3 grid, int64_t first, hipStream_t stream)
 {
-    const int wn = a.word_num;
-    if (wn > kVerifyWords) return launch_verify<kVerifyWords, true>(a, grid, first, stream);
-    if (wn <= 1) return launch_verify<1, false>(a, grid, first, stream);
-    if (wn <= 2) return launch_verify<2, false>(a, grid, first, stream);
-    if (wn <= 3) return launch_verify<3, false>(a, grid, first, stream);
-    if (wn <= 4) return launch_verify<4, false>(a, grid, first, stream);
-    if (wn <= 5) return launch_verify<5, false>(a, grid, first, stream);
-    if (wn <= 6) return launch_verify<6, false>(a, grid, first, stream);
-    if (wn <= 8) return launch_verify<8, false>(a, grid, first, stream);
-    if (wn <= 12) return launch_verify<12, false>(a, grid, first, stream);
-    return launch_verify<16, false>(a, grid, first, stream);
+    return verify_select(a.word_num, [&](auto w) { return launch_verify<decltype(w)::words, decltype(w)::blocks>(a, grid, first, stream); });
+}
+
+const char *verify_kernel_name(int word_num, bool lens)
+{
+    static thread_local char name[64];
+    verify_select(word_num, [&](auto w) {
+        return snprintf(name, sizeof name, "reference_verify_pairs_kernel<%d, %s, %s>", decltype(w)::words,
+                        decltype(w)::blocks ? "true" : "false", lens ? "true" : "false");
+    });
+    return name;
 }
 
 // ---- select --------------------------------------------------------------------------------------------------------------------
@@ -684,6 +707,8 @@ size_t bgsa_hip_reference_verify_workspace_bytes(int window_len, int read_len, i
     const size_t per = verify_wave_bytes(window_len, (read_len + 31) / 32);
     return per ? pair_workspace_for(per, n_pairs) : 0;
 }
+
+const char *bgsa_hip_reference_verify_kernel_name(int word_num, int lens) { return verify_kernel_name(word_num, lens != 0); }
 
 // per_lane: the *_lens call — d_read_lens is required and every lane verifies at its own length.
 static int verify_pairs(const char *who, const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,

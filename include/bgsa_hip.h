@@ -754,7 +754,11 @@ int bgsa_hip_reference_placements_dev(int64_t ref_len, int window_len, int strid
  * bgsa_hip_myers_place_score_lens_dev writes for that (window, column); n == 0 gives 0.  What the columns above n hold never
  * enters a result.  Workspace, chunking, ownership and the "no window" rule are those of bgsa_hip_reference_verify_pairs_dev;
  * any lengths may share a bucket, at every width up to 32 words.  bgsa_hip_seed_select_dev needs no per-read form: a semi-global
- * distance never exceeds n_r. */
+ * distance never exceeds n_r.
+ * bgsa_hip_reference_verify_kernel_name(word_num, lens): host only.  The kernel instance the two verify calls launch for a bucket
+ * of word_num words — lens != 0: the *_lens_dev call —, e.g. "reference_verify_pairs_kernel<8, false, true>" (words per block,
+ * column blocks, per-lane lengths); the choice is the launch's own.  It knows no limit: beyond 32 words it names the column-block
+ * instance the calls refuse to launch.  The string is the calling thread's and lives until its next call. */
 int64_t bgsa_hip_seed_index_offsets(int seed_len);
 size_t bgsa_hip_seed_index_workspace_bytes(int64_t ref_len, int seed_len);
 int bgsa_hip_seed_index_build_dev(const char *d_reference, int64_t ref_len, int seed_len, int32_t *d_offsets, int32_t *d_positions,
@@ -767,6 +771,7 @@ int bgsa_hip_seed_emit_candidates_dev(int64_t ref_len, int window_len, int strid
                                       int max_distance, int both_strands, const int32_t *d_counts, const int64_t *d_prefix,
                                       int64_t read_base, int32_t *d_cand_read, int32_t *d_cand_window, void *stream);
 size_t bgsa_hip_reference_verify_workspace_bytes(int window_len, int read_len, int64_t n_pairs);
+const char *bgsa_hip_reference_verify_kernel_name(int word_num, int lens);
 int bgsa_hip_reference_verify_pairs_dev(const char *d_reference, int64_t ref_len, int window_len, int stride, const hip_read_t *d_peq,
                                         int read_len, int64_t read_count, int word_num, const int32_t *d_pair_window,
                                         const int64_t *d_pair_subject, int64_t n_pairs, int64_t subject_base, int32_t *d_distance,

@@ -247,6 +247,22 @@ def test_scores_with_a_common_factor_use_the_reduced_set(L):
     assert L.bgsa_hip_select_algorithm(B.ALGO_MYERS) == 0
 
 
+def test_reference_verify_kernel_name(L):
+    # the instance dispatch_verify launches: the narrowest one-block width that holds the read, column blocks of 16 words beyond
+    name = lambda wn, lens: L.bgsa_hip_reference_verify_kernel_name(wn, lens)
+    assert name(1, 0) == b"reference_verify_pairs_kernel<1, false, false>"
+    assert name(5, 0) == b"reference_verify_pairs_kernel<5, false, false>"
+    assert name(7, 0) == name(8, 0) == b"reference_verify_pairs_kernel<8, false, false>"
+    assert name(8, 1) == b"reference_verify_pairs_kernel<8, false, true>" == name(8, 7)      # lens: any nonzero value
+    assert name(13, 1) == name(16, 1) == b"reference_verify_pairs_kernel<16, false, true>"
+    assert name(17, 0) == name(32, 0) == name(130, 0) == b"reference_verify_pairs_kernel<16, true, false>"
+    assert name(17, 1) == b"reference_verify_pairs_kernel<16, true, true>"
+    # independent of the selected algorithm and scores
+    assert L.bgsa_hip_select_algorithm(B.ALGO_BITPAL) == 0
+    assert name(5, 0) == b"reference_verify_pairs_kernel<5, false, false>"
+    assert L.bgsa_hip_select_algorithm(B.ALGO_MYERS) == 0
+
+
 def test_myers_positive_weights_are_the_generators_m1(L):
     assert L.bgsa_hip_select_scores(0, 1, 1) == 0
     assert L.bgsa_hip_current_algorithm() == B.ALGO_MYERS
