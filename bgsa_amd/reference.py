@@ -492,6 +492,13 @@ def check_bam_call(who: str, lens, names, quals, reference_name, block_payload=B
     return checked
 
 
+def check_coordinate_header(who: str, header: bytes) -> None:
+    """The refusal of an uncompressed BAM header whose @HD line does not say SO:coordinate: an indexed file is a sorted one."""
+    text = bytes(header)[8: 8 + max(struct.unpack_from("<i", bytes(header), 4)[0], 0)] if len(header) >= 8 else b""
+    if b"SO:coordinate" not in text.split(b"\n")[0]:
+        raise B.BgsaHipError(f"{who} the header's @HD line does not say SO:coordinate (bam_header(sort_order=\"coordinate\"))")
+
+
 def write_bam(path, header: bytes, records, index: bool = False) -> None:
     """A BAM file: the header (ReferenceMapper.bam_header, uncompressed) framed by bgzf_blocks, the blocks of `records` — one
     BamRecords or a sequence of them, in order: batches of reads stream into one file —, then BGZF_EOF.  index=True: `records` is
@@ -501,10 +508,7 @@ def write_bam(path, header: bytes, records, index: bool = False) -> None:
     if index:
         if not isinstance(records, SortedBamRecords):
             raise B.BgsaHipError("write_bam: rc=-1: index=True takes ONE SortedBamRecords (map_reads_bam / map_pairs_bam with sort=True)")
-        text = bytes(header)[8: 8 + max(struct.unpack_from("<i", bytes(header), 4)[0], 0)] if len(header) >= 8 else b""
-        if b"SO:coordinate" not in text.split(b"\n")[0]:
-            raise B.BgsaHipError("write_bam: rc=-1: index=True, and the header's @HD line does not say SO:coordinate "
-                                 "(bam_header(sort_order=\"coordinate\"))")
+        check_coordinate_header("write_bam: rc=-1: index=True, and", header)
     batches = [records] if isinstance(records, (BamRecords, SortedBamRecords)) else list(records)
     with open(path, "wb") as out:
         out.write(framed)
@@ -601,6 +605,185 @@ def bai_bytes(index: BamIndex, flag, ref_id, base: int = 0) -> bytes:
         out += [struct.pack("<i", n_intv), (np.asarray(index.linear[at: at + n_intv]).astype(np.uint64) + np.uint64(shift)).astype("<u8").tobytes()]
     out.append(struct.pack("<Q", int((ref_id < 0).sum())))
     return b"".join(out)
+
+
+# ---- BAM records: merge: include/bgsa_hip.h "BAM records: merge" ------------------------------------------------------------------
+MERGE_COLUMNS = ("lengths", "key", "ref_id", "pos", "end", "bin", "flag", "POS", "mapq", "nm")      # per record, in input order
+MERGE_DUPLICATE_COLUMNS = ("end_key", "score", "key_a", "key_b")                                    # per record, per unit x 3
+
+
+def check_bam_merge(who: str, block_payload=BGZF_BLOCK_PAYLOAD, compress=False, mark_duplicates=False, segment_blocks=4096, reserve_bytes=None,
+                    ref_lens=()) -> None:
+    """What a merge refuses before anything is launched or allocated, pure host: a compress or mark_duplicates that is not a bool,
+    a block_payload outside 1..65,280, a segment_blocks that is not an int >= 1, a reserve_bytes that is not None or an int >= 0,
+    a reference or contig (ref_lens) beyond 2^29 bases."""
+    def is_int(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+    if not isinstance(compress, (bool, np.bool_)):
+        raise B.BgsaHipError(f"{who}: rc=-1: compress {compress!r} is not a bool")
+    check_mark_duplicates(who, mark_duplicates)
+    if not is_int(block_payload) or not 1 <= int(block_payload) <= BGZF_BLOCK_PAYLOAD:
+        raise B.BgsaHipError(f"{who}: rc=-1: block_payload {block_payload!r} outside 1..{BGZF_BLOCK_PAYLOAD}")
+    if not is_int(segment_blocks) or int(segment_blocks) < 1:
+        raise B.BgsaHipError(f"{who}: rc=-1: segment_blocks {segment_blocks!r} is not an int >= 1")
+    if reserve_bytes is not None and (not is_int(reserve_bytes) or int(reserve_bytes) < 0):
+        raise B.BgsaHipError(f"{who}: rc=-1: reserve_bytes {reserve_bytes!r} is neither None nor an int >= 0")
+    for c, n in enumerate(np.asarray(ref_lens, dtype=np.int64).reshape(-1).tolist()):
+        if n > BAI_REACH:
+            raise B.BgsaHipError(f"{who}: rc=-1: reference {c} has {n} bases, a BAI index reaches 2^29 = {BAI_REACH}")
+
+
+def check_bam_merge_add(who: str, merge, mapper, ends: int, block_payload=BGZF_BLOCK_PAYLOAD, compress=False, sort=False,
+                        mark_duplicates=False) -> None:
+    """What a call with merge= refuses before anything is launched, pure host: a merge that is no BamMerge, or another mapper's, or
+    finished; a batch of the other kind (a merge has one `ends`: 1 single-end, 2 paired); a sort, compress, block_payload or
+    mark_duplicates beside the merge — they belong to the merge and stay at their defaults in the call."""
+    if not isinstance(merge, BamMerge):
+        raise B.BgsaHipError(f"{who}: rc=-1: merge {merge!r} is not a BamMerge (mapper.bam_merge())")
+    given = [name for name, value, default in (("sort", sort, False), ("compress", compress, False), ("block_payload", block_payload, BGZF_BLOCK_PAYLOAD),
+                                               ("mark_duplicates", mark_duplicates, False)) if value is not default and value != default]
+    if given:
+        raise B.BgsaHipError(f"{who}: rc=-1: {', '.join(given)} beside merge=: they belong to the merge (mapper.bam_merge(...))")
+    if merge.mapper is not mapper:
+        raise B.BgsaHipError(f"{who}: rc=-1: the merge belongs to another mapper")
+    if merge.finished:
+        raise B.BgsaHipError(f"{who}: rc=-1: the merge is finished")
+    if merge.ends not in (None, ends):
+        kinds = {1: "single-end", 2: "paired"}
+        raise B.BgsaHipError(f"{who}: rc=-1: a {kinds[ends]} batch into a merge of {kinds[merge.ends]} ones: a merge has one `ends`")
+
+
+class BamMerge:
+    """The BAM records of any number of map_reads_bam / map_pairs_bam calls (merge=this), kept on the device as every call emitted
+    them — in input order, batch after batch —, and finished into ONE coordinate-sorted, indexed result: finish() returns the
+    SortedBamRecords of one sort=True call on the concatenated reads, write() streams the same bytes to a .bam and its .bai
+    (include/bgsa_hip.h "BAM records: merge").  Made by mapper.bam_merge(); nothing is allocated before the
+    first batch."""
+
+    def __init__(self, mapper, block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, mark_duplicates: bool = False,
+                 segment_blocks: int = 4096, reserve_bytes=None):
+        check_bam_merge("bam_merge", block_payload, compress, mark_duplicates, segment_blocks, reserve_bytes, mapper.index_ref_lens())
+        self.mapper, self.block_payload, self.compress = mapper, int(block_payload), bool(compress)
+        self.mark_duplicates, self.segment_blocks = bool(mark_duplicates), int(segment_blocks)
+        self.reserve_bytes = None if reserve_bytes is None else int(reserve_bytes)
+        self.ends, self.finished = None, False
+        self.n, self.payload_bytes, self.payload = 0, 0, None      # records, their bytes, the device buffer that holds them
+        self.columns = {name: [] for name in MERGE_COLUMNS + MERGE_DUPLICATE_COLUMNS}
+        self.key_counts = [0, 0, 0]                                # pair units, fragment units, skipped records: the key kernel's
+
+    def _append(self, ends: int, payload, payload_bytes: int, columns: dict, key_counts=None) -> int:
+        """One accepted batch: its emitted payload (a device tensor, payload_bytes of it) behind the others', its per-record device
+        tensors (MERGE_COLUMNS, and MERGE_DUPLICATE_COLUMNS with the key kernel's three counters where the merge marks
+        duplicates) kept as they are.  Called after the batch's last check; the number of records added."""
+        torch = self.mapper.aligner.torch
+        need = self.payload_bytes + payload_bytes
+        if self.payload is None or need > self.payload.numel():
+            room = max(need, 1, self.reserve_bytes or 0) if self.payload is None else max(need, 2 * self.payload.numel())
+            grown = torch.empty(room, dtype=torch.uint8, device=self.mapper.aligner.device)
+            if self.payload_bytes:
+                grown[: self.payload_bytes] = self.payload[: self.payload_bytes]
+            self.payload = grown
+        self.payload[self.payload_bytes: need] = payload[:payload_bytes]
+        n = int(columns["lengths"].shape[0])
+        for name, value in columns.items():
+            self.columns[name].append(value)
+        if key_counts is not None:
+            self.key_counts = [a + b for a, b in zip(self.key_counts, key_counts)]
+        self.ends, self.n, self.payload_bytes = ends, self.n + n, need
+        return n
+
+    def _column(self, name: str, dtype):
+        """A column of all batches, batch after batch."""
+        torch, dev = self.mapper.aligner.torch, self.mapper.aligner.device
+        parts = self.columns[name]
+        return torch.cat(parts).contiguous() if parts else torch.empty(0, dtype=dtype, device=dev)
+
+    def _empty_index(self) -> BamIndex:
+        """The index of no record: no chunk, no window filled (the index calls take no empty array)."""
+        ref_lens = self.mapper.index_ref_lens()
+        window_base = np.zeros(ref_lens.size + 1, dtype=np.int64)
+        windows = int(B.lib().bgsa_hip_bam_index_windows(ref_lens.ctypes.data, ref_lens.size, window_base.ctypes.data))
+        none = [np.zeros(0, dtype=dtype) for dtype in (np.int32, np.int32, np.int64, np.int64)]
+        return BamIndex(ref_lens, *none, window_base, np.full(windows, np.iinfo(np.int64).max, dtype=np.int64), np.zeros(ref_lens.size, dtype=np.int64))
+
+    def _finish(self, who: str, on_blocks) -> tuple:
+        """The steps of finish and write: one stable sort of all keys, duplicate marking over all records, the scan of the sorted
+        lengths, then per segment of segment_blocks blocks gather -> frame or deflate and pack -> one copy, handed to
+        on_blocks(numpy bytes); the index at the end.  Everything of SortedBamRecords but the blocks."""
+        m, L = self.mapper, B.lib()
+        a = m.aligner
+        torch, dev, n, total, P = a.torch, a.device, self.n, self.payload_bytes, self.block_payload
+        self.finished = True
+        order = m.sort_permutation(self._column("key", torch.int64)).contiguous()
+        flag = self._column("flag", torch.int32).clone()
+        if self.mark_duplicates:
+            counts = torch.zeros(6, dtype=torch.int32, device=dev)
+            score = self._column("score", torch.int32)
+            if n and self.ends == 2:
+                by, keys = m.duplicate_order(score, self._column("key_a", torch.int64), self._column("key_b", torch.int64))
+                m.duplicate_marks(keys, by, n, 2, flag, counts[3:])
+            if n:
+                by, keys = m.duplicate_order(score.repeat_interleave(self.ends), self._column("end_key", torch.int64))
+                m.duplicate_marks(keys, by, n, 1, flag, counts[3:])
+            m.last_duplicate_stats = dict(zip(DUPLICATE_STATS, self.key_counts + counts[3:].tolist()))
+        src_offsets, dst_offsets = (torch.zeros(n + 1, dtype=torch.int64, device=dev) for _ in range(2))
+        lengths = self._column("lengths", torch.int64)
+        src_offsets[1:] = torch.cumsum(lengths, 0)
+        dst_offsets[1:] = torch.cumsum(lengths[order], 0)
+        span = self.segment_blocks * P
+        lo = torch.arange(0, total, span, dtype=torch.int64, device=dev)
+        first = torch.searchsorted(dst_offsets[1:].contiguous(), lo, right=True)                  # the first record that ends behind lo
+        behind = torch.searchsorted(dst_offsets[:-1].contiguous(), (lo + span).clamp(max=total))      # the records that start before hi
+        plan = torch.stack((lo, first, behind - first), dim=1).cpu().tolist()                    # one copy: every segment's records
+        segment = torch.empty(max(min(span, total), 1), dtype=torch.uint8, device=dev)
+        refused = torch.zeros(1, dtype=torch.int32, device=dev)
+        block_offsets, base = [], 0
+        for at, head, count in plan:
+            size = min(span, total - at)
+            B.check(L.bgsa_hip_bam_gather_dev(self.payload.data_ptr(), total, src_offsets.data_ptr(), n, order.data_ptr(), dst_offsets.data_ptr(),
+                                              n, head, count, at, at + size, flag.data_ptr(), segment.data_ptr(), refused.data_ptr(),
+                                              a._stream()), "bam_gather_dev")
+            if self.compress:
+                blocks, framed, offsets = m.bgzf_deflated(who, segment, size, P, with_offsets=True)
+                block_offsets.append(offsets[:-1] + base)
+            else:
+                framed = int(L.bgsa_hip_bgzf_framed_bytes(size, P))
+                blocks = torch.empty(framed, dtype=torch.uint8, device=dev)
+                B.check(L.bgsa_hip_bgzf_frame_dev(segment.data_ptr(), size, P, blocks.data_ptr(), framed, a._stream()), "bgzf_frame_dev")
+            host = blocks[:framed].cpu().numpy()
+            if int(refused.item()):
+                raise B.BgsaHipError(f"{who}: the gather pass refused {int(refused.item())} records: an order, offsets or lengths that do "
+                                     f"not describe the merged payload")
+            on_blocks(host)
+            base += framed
+        if self.compress:
+            block_offsets = torch.cat(block_offsets + [torch.full((1,), base, dtype=torch.int64, device=dev)]).contiguous()
+        coordinates = [self._column(name, torch.int32) for name in ("ref_id", "pos", "end", "bin")]
+        coordinates = [x[order].contiguous() for x in coordinates]
+        index = m.bam_index(who, *coordinates, dst_offsets, total, P, block_offsets if self.compress else None) if n else self._empty_index()
+        column = lambda name, dtype: self._column(name, dtype)[order].cpu().numpy()      # noqa: E731
+        return (dst_offsets.cpu().numpy(), flag[order].cpu().numpy(), m.local_pos(column("POS", torch.int64)), column("mapq", torch.int32),
+                column("nm", torch.int32), coordinates[0].cpu().numpy(), order.cpu().numpy(), index)
+
+    def finish(self) -> SortedBamRecords:
+        """All records in coordinate order with their index: what ONE map_reads_bam / map_pairs_bam call with sort=True (and this
+        merge's compress, block_payload and mark_duplicates) returns for the concatenated reads; `order` holds global input
+        indices, batch after batch.  With mark_duplicates the mapper's last_duplicate_stats is filled.  No batch can follow."""
+        pieces = []
+        rest = self._finish("bam_merge.finish", pieces.append)
+        return SortedBamRecords(np.concatenate(pieces) if pieces else np.zeros(0, dtype=np.uint8), *rest)
+
+    def write(self, path, header: bytes) -> None:
+        """The file write_bam(path, header, self.finish(), index=True) writes, every segment's blocks streamed as they arrive: the
+        framed header, the blocks, BGZF_EOF, then path + ".bai".  A header without SO:coordinate is refused first."""
+        check_coordinate_header("bam_merge.write: rc=-1:", header)
+        framed = bgzf_blocks(header)
+        with open(path, "wb") as out:
+            out.write(framed)
+            _, flag, _, _, _, ref_id, _, index = self._finish("bam_merge.write", lambda blocks: out.write(memoryview(blocks)))
+            out.write(BGZF_EOF)
+        with open(str(path) + ".bai", "wb") as out:
+            out.write(bai_bytes(index, flag, ref_id, len(framed)))
 
 
 class SeedBucket(NamedTuple):
@@ -1240,7 +1423,7 @@ class ReferenceMapper:
 
     def sam_records(self, who: str, reads: np.ndarray, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, fmt: str = "sam",
                     block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False, mark_duplicates: bool = False,
-                    ends: int = 1):
+                    ends: int = 1, merge=None):
         """The two record passes.  reads [n_rows, stride] and quals (or None) are the host rows, names / name_offsets / rname what
         check_sam_call returned; fields holds the per-record DEVICE tensors read_row, name_of (int64), read_len, strand, ref_begin,
         ref_end, distance, n_ops, flag, mapq, rnext, pnext, tlen; runs [n, cap] int32 holds record i's runs in row i.  Measure, an
@@ -1255,7 +1438,15 @@ class ReferenceMapper:
         the index (bam_index): SortedBamRecords, its columns in output order.  mark_duplicates (any fmt; include/bgsa_hip.h
         "Duplicate marking"): on a COPY of fields["flag"], right after the batch is assembled and before the sort, the duplicate
         records of this batch get bit 1024 (mark_duplicate_records; ends 2: records 2u and 2u + 1 are pair u) and
-        last_duplicate_stats is filled; everything downstream reads the changed flags."""
+        last_duplicate_stats is filled; everything downstream reads the changed flags.  merge (fmt "bam" only; include/bgsa_hip.h
+        "BAM records: merge"): the batch as assembled goes through the duplicate KEY kernel where the merge marks duplicates — no
+        mark —, the key pass, then measure, scan and emit in INPUT order, and the device tensors are handed to the BamMerge;
+        nothing is framed, no per-record array is copied, the number of records added is returned.  block_payload, compress, sort
+        and mark_duplicates are the merge's then."""
+        if merge is not None and fmt != "bam":
+            raise B.BgsaHipError(f"{who}: rc=-1: merge= needs fmt 'bam'")
+        if merge is not None and (sort or compress or mark_duplicates):
+            raise B.BgsaHipError(f"{who}: rc=-1: sort, compress and mark_duplicates belong to the merge")
         if sort and fmt != "bam":
             raise B.BgsaHipError(f"{who}: rc=-1: sort=True needs fmt 'bam'")
         a = self.aligner
@@ -1289,11 +1480,15 @@ class ReferenceMapper:
         if mark_duplicates:
             f = dict(f, flag=f["flag"].clone())
             self.last_duplicate_stats = self.mark_duplicate_records(batch_of(f, runs_row), n, int(ends), f["flag"])
-        coordinates = None
-        if sort:
+        coordinates, duplicate_keys = None, None
+        if merge is not None and merge.mark_duplicates:
+            key_counts = torch.zeros(3, dtype=torch.int32, device=dev)
+            duplicate_keys = self.duplicate_keys(batch_of(f, runs_row), n, int(ends), key_counts)
+        if sort or merge is not None:
             key, *coordinates = self.bam_coordinates(batch_of(f, runs_row), n)
             if int(coordinates[-1].item()):
                 raise malformed_error(int(coordinates[-1].item()), int(torch.nonzero(key == torch.iinfo(torch.int64).max).reshape(-1)[0].item()))
+        if sort:
             order = self.sort_permutation(key)
             f, coordinates = self.gather_records(f, coordinates[:4], order)
             runs_row, host_order, unsorted_label = order.contiguous(), order.cpu().numpy(), label
@@ -1321,6 +1516,11 @@ class ReferenceMapper:
         pos = torch.where(mapped, f["ref_begin"] + 1, f["pnext"] * f["rnext"])
         nm = f["distance"].masked_fill(~mapped, -1)
         mapq = f["mapq"].masked_fill(~mapped, 0)
+        if merge is not None:       # the last check is behind us: only now does the merge change
+            columns = dict(zip(MERGE_COLUMNS, (lengths, key, *coordinates[:4], f["flag"], pos, mapq, nm)))
+            if duplicate_keys is not None:
+                columns.update(zip(MERGE_DUPLICATE_COLUMNS, duplicate_keys))
+            return merge._append(int(ends), text, total, columns, None if duplicate_keys is None else key_counts.tolist())
         kind, payload_bytes, block_offsets = SamRecords, total, None
         if fmt == "bam" and compress:
             kind, (text, total, block_offsets) = BamRecords, self.bgzf_deflated(who, text, total, int(block_payload), with_offsets=True)
@@ -1391,6 +1591,19 @@ class ReferenceMapper:
         B.check(self._coordinates_pass()(batch, n, key.data_ptr(), ref_id.data_ptr(), pos.data_ptr(), end.data_ptr(), bin_.data_ptr(),
                                          malformed.data_ptr(), a._stream()), "bam_coordinates_dev")
         return key, ref_id, pos, end, bin_, malformed
+
+    def local_pos(self, pos: np.ndarray) -> np.ndarray:
+        """The POS column as the caller sees it: on one sequence the linear positions are it."""
+        return pos
+
+    def bam_merge(self, block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, mark_duplicates: bool = False, segment_blocks: int = 4096,
+                  reserve_bytes=None) -> BamMerge:
+        """A merge of this mapper's BAM records over many calls (BamMerge; include/bgsa_hip.h "BAM records: merge"): pass it as
+        merge= to map_reads_bam or map_pairs_bam, batch after batch, then finish() or write().  block_payload, compress and
+        mark_duplicates are those of a sort=True call and hold for every batch; segment_blocks blocks are gathered, framed or
+        deflated and copied at a time; reserve_bytes sizes the payload buffer once (it doubles otherwise).  check_bam_merge
+        refuses before anything is allocated."""
+        return BamMerge(self, block_payload, compress, mark_duplicates, segment_blocks, reserve_bytes)
 
     def sort_permutation(self, key):
         """The permutation that puts the keys in order, ties in input order: torch.sort(stable=True), plumbing."""
@@ -1527,7 +1740,8 @@ class ReferenceMapper:
 
     def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
                       seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None,
-                      block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False, mark_duplicates: bool = False):
+                      block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False, mark_duplicates: bool = False,
+                      merge=None):
         """map_reads_sam — the same arguments, mapping and record selection — with the records in BAM's layout inside BGZF blocks of
         stored deflate, block_payload bytes of records each (include/bgsa_hip.h "BAM records"): measure, scan, emit, frame, all on the
         device, one copy of the blocks.  A record may straddle blocks.  compress=True: every block deflated on the device instead (LZ77
@@ -1536,11 +1750,16 @@ class ReferenceMapper:
         write_bam the blocks of one or more calls, compressed or not, make a file.  sort=True: the records of this call leave the
         device in coordinate order (the `samtools sort` key, ties in input order, records without coordinates last) with the arrays
         of a BAI index beside them — SortedBamRecords; bam_header(sort_order="coordinate") and write_bam(index=True) then write
-        x.bam and x.bam.bai (include/bgsa_hip.h "BAM records: coordinate order and index").  A sorted file holds ONE call's records.
+        x.bam and x.bam.bai (include/bgsa_hip.h "BAM records: coordinate order and index").  A sorted call holds ONE call's records;
+        many calls go into one sorted file through a merge.
         mark_duplicates=True: map_reads_sam's, independent of compress and sort — the flags change before the records are sorted and
-        written, so order and index are those of the unmarked call; duplicates are found within one call only."""
+        written, so order and index are those of the unmarked call; duplicates are found within one call only — across calls by a
+        merge.  merge=a BamMerge (self.bam_merge(...); include/bgsa_hip.h "BAM records: merge"): the records of this call stay on the
+        device behind those of the merge's earlier calls and the number of records added is returned; block_payload, compress, sort
+        and mark_duplicates are the merge's and stay at their defaults here; merge.finish() or merge.write() then give the sorted,
+        indexed records of all calls as ONE sort=True call on all reads would."""
         return self._map_reads_records("bam", block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                                       max_candidates, block_rows, cigar_cap, compress, sort, mark_duplicates)
+                                       max_candidates, block_rows, cigar_cap, compress, sort, mark_duplicates, merge)
 
     def _check_records_call(self, fmt: str, who: str, lens, names, quals, reference_name, block_payload, compress=False, sort=False) -> tuple:
         if fmt == "bam":
@@ -1548,10 +1767,12 @@ class ReferenceMapper:
         return check_sam_call(who, lens, names, quals, reference_name)
 
     def _map_reads_records(self, fmt: str, block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                           max_candidates, block_rows, cigar_cap, compress=False, sort=False, mark_duplicates=False):
+                           max_candidates, block_rows, cigar_cap, compress=False, sort=False, mark_duplicates=False, merge=None):
         """What map_reads_sam and map_reads_bam share: everything but the format of the records."""
         who = f"map_reads_{fmt}"
         mark_duplicates = check_mark_duplicates(who, mark_duplicates)
+        if merge is not None:
+            check_bam_merge_add(who, merge, self, 1, block_payload, compress, sort, mark_duplicates)
         rows, lens, ragged = self._sam_rows(who, reads)
         rname, flat, name_offsets, qual_rows = self._check_records_call(fmt, who, lens, names, quals, reference_name, block_payload,
                                                                         compress, sort)
@@ -1560,7 +1781,7 @@ class ReferenceMapper:
                             max_candidates, block_rows, cigar_cap)
         self.aligner.check_faults()
         return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname, fmt=fmt, block_payload=block_payload,
-                                       compress=compress, sort=sort, mark_duplicates=mark_duplicates)
+                                       compress=compress, sort=sort, mark_duplicates=mark_duplicates, merge=merge)
 
     def sam_single_records(self, who: str, sink: "PrimarySink", rows: np.ndarray, lens, qual_rows, names, name_offsets, rname, **form):
         """The records of single-end reads from their primaries on the device: flag 0, 16 or 4, no mate fields.  form: sam_records'
@@ -1595,21 +1816,25 @@ class ReferenceMapper:
     def map_pairs_bam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
                       reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
                       max_candidates=None, block_rows: int = 1000, cigar_cap=None, block_payload: int = BGZF_BLOCK_PAYLOAD,
-                      compress: bool = False, sort: bool = False, mark_duplicates: bool = False):
+                      compress: bool = False, sort: bool = False, mark_duplicates: bool = False, merge=None):
         """map_pairs_sam — the same arguments, stages and records — in BAM's layout inside BGZF blocks, stored or, with compress=True,
         deflated on the device (map_reads_bam).  sort=True: coordinate order and a BAI index, as map_reads_bam's; of two ends at one
         position end 1 stays in front, and an unmapped end stays right behind the mate whose position it takes.
-        mark_duplicates=True: map_pairs_sam's, independent of compress and sort; duplicates are found within one call only."""
+        mark_duplicates=True: map_pairs_sam's, independent of compress and sort; duplicates are found within one call only — across
+        calls by a merge.  merge=a BamMerge: map_reads_bam's, two records per pair; a merge takes paired batches or single-end
+        ones, not both."""
         return self._map_pairs_records("bam", block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name,
                                        k_best, max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap,
-                                       compress, sort, mark_duplicates)
+                                       compress, sort, mark_duplicates, merge)
 
     def _map_pairs_records(self, fmt: str, block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
                            max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap, compress=False, sort=False,
-                           mark_duplicates=False):
+                           mark_duplicates=False, merge=None):
         """What map_pairs_sam and map_pairs_bam share: everything but the format of the records."""
         who = f"map_pairs_{fmt}"
         mark_duplicates = check_mark_duplicates(who, mark_duplicates)
+        if merge is not None:
+            check_bam_merge_add(who, merge, self, 2, block_payload, compress, sort, mark_duplicates)
         reads = (self._one_length(who, reads1), self._one_length(who, reads2))
         ns = reads[0].shape[0]
         if (quals1 is None) != (quals2 is None):
@@ -1629,7 +1854,7 @@ class ReferenceMapper:
         chosen = self.pair_select(ends[0][0][:5], ends[1][0][:5], insert_min, insert_max, block_rows)      # stage C
         a.check_faults()
         return self.sam_pair_records(who, reads, ends, chosen, call, checked, fmt=fmt, block_payload=block_payload, compress=compress,
-                                     sort=sort, mark_duplicates=mark_duplicates)
+                                     sort=sort, mark_duplicates=mark_duplicates, merge=merge)
 
     def sam_pair_records(self, who: str, reads, ends, chosen, call: dict, checked, **form):
         """The records of pairs from the device results of map_pairs' stages: ends[e] = rescue_end's return for end e, chosen =
@@ -1972,8 +2197,13 @@ class ContigMapper(ReferenceMapper):
         mate = torch.searchsorted(self.d_contig_starts, (fields["pnext"] - 1).contiguous(), right=True)
         fields = dict(fields, tlen=torch.where(own == mate, fields["tlen"], torch.zeros_like(fields["tlen"])))
         records = super().sam_records(who, reads, quals, names, name_offsets, rname, fields, runs, read_label, **form)
-        at = np.maximum(self.contig_of(records.pos - 1), 0)
-        return records._replace(pos=np.where(records.pos > 0, records.pos - self.contig_starts[at], 0))
+        if form.get("merge") is not None:
+            return records                       # the number of records added: the merge localises at finish
+        return records._replace(pos=self.local_pos(records.pos))
+
+    def local_pos(self, pos: np.ndarray) -> np.ndarray:
+        at = np.maximum(self.contig_of(pos - 1), 0)
+        return np.where(pos > 0, pos - self.contig_starts[at], 0)
 
     def map_reads_sam(self, reads, names=None, quals=None, reference_name="ref", **kwargs) -> SamRecords:
         """ReferenceMapper.map_reads_sam with RNAME the contig's name and POS local to it.  reference_name is not used."""

@@ -1200,7 +1200,42 @@ int bgsa_hip_dup_keys_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int ends
 int bgsa_hip_dup_mark_dev(const int64_t *d_key_a, const int64_t *d_key_b, const int64_t *d_order, int64_t n, int ends, int32_t *d_flag,
                           int32_t *d_counts, void *stream);
 
-/* Stream faults.  The kernels walk each query as a packed code stream (below) under a window budget; a
+/* ---- BAM records: merge — the records of MANY calls in one coordinate-sorted, indexed file ----
+ * A call holds one working set of reads; a sequencing run is a thousand of them.  A merge keeps what every call emitted — the
+ * record bytes in input order and the per-record arrays of "coordinate order and index" and "Duplicate marking" — on the device,
+ * and when it is finished sorts ALL keys once, marks duplicates over ALL records once and moves the record bytes into coordinate
+ * order with the one kernel below, segment by segment through the framing or deflate calls and then the index calls above
+ * (bam_merge.hip; bgsa_amd/reference.py: BamMerge, sam_records(merge=...)).  The result is DEFINED as the one-call result: the
+ * blocks, columns, index arrays and .bai bytes of one sort=True call on the concatenated reads (tests/bam_merge_reference.py).
+ * That rests on five facts of the stages above:
+ *   tie order    the sort is stable and the merge's input order is batch-major, so equal keys fall as in one call.
+ *   keys         the sort key reads bit 16 of the flag only: keys computed before duplicate marking are the final keys.
+ *   the flag     a BAM record holds its flag in exactly two bytes, offsets 18 and 19 from the start of its block_size field,
+ *                little-endian; marking after the records were emitted changes those two bytes and nothing else (bin does not
+ *                depend on the flag).
+ *   deflate      a deflated block is a function of (its payload, block_payload) alone: segments of whole blocks give the bytes of
+ *                one pass.
+ *   duplicates   the duplicate rule's ties go to the lowest index; the global record or pair index is (batch order, index in batch).
+ * bgsa_hip_bam_gather_dev: one WAVE per output record.  Output record i (0 <= i < n) is source record s = d_order[i], the bytes
+ * d_src[d_src_offsets[s] .. d_src_offsets[s + 1]); in the sorted payload it occupies [d_dst_offsets[i], d_dst_offsets[i + 1])
+ * (both offset arrays have one entry more than records: n_src + 1 and n + 1).  The call handles output records first ..
+ * first + count - 1 and writes of each exactly the bytes whose sorted-payload position p lies in [window_lo, window_hi), to
+ * d_out[p - window_lo]: d_out holds window_hi - window_lo bytes, and a record that straddles a window edge is finished by the call
+ * of the next window.  d_flag not NULL (int32[n_src], indexed by s): the record's bytes 18 and 19 are d_flag[s] & 0xffff,
+ * little-endian, instead of the source's; each of the two is written or not by the window rule on its own.
+ * A record is REFUSED — it adds 1 to *d_refused (the caller zeroes it), not a byte of it is written and none of its values forms
+ * an address — when s is outside [0, n_src); a source or destination offset pair is negative or not monotone; the source extent
+ * leaves src_bytes; the two lengths differ; d_flag is given and the length is below 20.
+ * The call only launches on `stream`: no allocation, no synchronisation; count == 0 or an empty window is BGSA_HIP_OK and launches
+ * nothing.  BGSA_HIP_EINVAL, before the first HIP call: a NULL pointer (d_flag and the stream excepted), a negative count or size,
+ * first + count > n, window_hi < window_lo, count beyond one launch (2^33).
+ * LIMITS: the payload of all calls stays on the device (no host spill, no merge of files); BAM only; BAI only; no optical
+ * duplicates or UMIs; one source buffer (no table of source pointers). */
+int bgsa_hip_bam_gather_dev(const uint8_t *d_src, int64_t src_bytes, const int64_t *d_src_offsets, int64_t n_src, const int64_t *d_order,
+                            const int64_t *d_dst_offsets, int64_t n, int64_t first, int64_t count, int64_t window_lo, int64_t window_hi,
+                            const int32_t *d_flag, uint8_t *d_out, int32_t *d_refused, void *stream);
+
+/* Stream faults. The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
  * either: a set bit means the stream bytes were damaged between the packer and the row loop, and the
