@@ -224,7 +224,12 @@ def lib() -> ctypes.CDLL:
                                  ("bgsa_hip_dup_keys_dev", [ctypes.POINTER(SamBatch), i64, i32, i32] + [vp] * 6, i32),
                                  ("bgsa_hip_dup_mark_dev", [vp, vp, vp, i64, i32, vp, vp, vp], i32),
                                  # the merge of many calls' records
-                                 ("bgsa_hip_bam_gather_dev", [vp, i64, vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp], i32)):
+                                 ("bgsa_hip_bam_gather_dev", [vp, i64, vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp], i32),
+                                 # the pileup of the records and its candidate sites
+                                 ("bgsa_hip_pileup_dev", [ctypes.POINTER(SamBatch), i64, i32, i32, i32, vp, vp, vp], i32),
+                                 ("bgsa_hip_pileup_site_blocks", [i64], i64),
+                                 ("bgsa_hip_pileup_sites_count_dev", [vp, vp, i64, i32, i32, i32, vp, i64, vp], i32),
+                                 ("bgsa_hip_pileup_sites_emit_dev", [vp, vp, i64, i32, i32, i32, vp, i64, i64] + [vp] * 8, i32)):
         if hasattr(L, name):
             getattr(L, name).argtypes = types
             getattr(L, name).restype = restype
@@ -1247,4 +1252,5 @@ def place_top_queries_banded(queries: np.ndarray, subjects: np.ndarray, k_best: 
 from .reference import (ContigHits, ContigMapper, ContigPlacement, PairedHits, Placement, ReferenceHits, ReferenceMapper, SamRecords, blank_beyond, check_sam_call,  # noqa: E402
                         list_mapq, max_stride, rescue_region, rescue_slots, seed_plan, seed_plan_ragged, window_plan, write_sam, contig_layout, read_fasta,
                         BGZF_EOF, BamRecords, bgzf_blocks, check_bam_call, write_bam, BamIndex, SortedBamRecords, bai_bytes, check_mark_duplicates,
-                        DUPLICATE_FLAG, DUPLICATE_MIN_QUALITY, DUPLICATE_STATS, BamMerge, check_bam_merge, check_bam_merge_add)
+                        DUPLICATE_FLAG, DUPLICATE_MIN_QUALITY, DUPLICATE_STATS, BamMerge, check_bam_merge, check_bam_merge_add,
+                        PILEUP_COLUMNS, PILEUP_EXCLUDE_FLAGS, PILEUP_STATS, Pileup, PileupSites, check_pileup, check_pileup_add, check_pileup_sites)

@@ -786,6 +786,129 @@ class BamMerge:
             out.write(bai_bytes(index, flag, ref_id, len(framed)))
 
 
+# ---- Pileup: include/bgsa_hip.h "Pileup" ---------------------------------------------------------------------------------------------
+PILEUP_COLUMNS = ("A", "C", "G", "T", "other", "deleted", "inserted", "reverse")      # the count matrix's eight columns, fixed
+PILEUP_STATS = ("records_used", "records_filtered", "records_malformed", "bases_counted", "bases_low_quality")
+PILEUP_EXCLUDE_FLAGS = 0x704      # unmapped, secondary, QC fail, duplicate
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def check_pileup(who: str, min_mapq=0, min_base_quality=13, exclude_flags=PILEUP_EXCLUDE_FLAGS) -> tuple:
+    """What mapper.pileup refuses before anything is allocated, pure host: a min_mapq that is no int in 0..255, a min_base_quality
+    outside 0..93, exclude_flags outside 0..65535.  Returns the three as ints."""
+    for name, value, top in (("min_mapq", min_mapq, 255), ("min_base_quality", min_base_quality, 93), ("exclude_flags", exclude_flags, 65535)):
+        if not _is_int(value) or not 0 <= int(value) <= top:
+            raise B.BgsaHipError(f"{who}: rc=-1: {name} {value!r} is not an int in 0..{top}")
+    return int(min_mapq), int(min_base_quality), int(exclude_flags)
+
+
+def check_pileup_sites(who: str, min_cover=8, min_alt=3, min_percent=20) -> tuple:
+    """What Pileup.sites refuses before anything is launched: a min_cover or min_alt that is no int >= 1 (and below 2^31), a
+    min_percent that is no int in 0..100.  Returns the three as ints."""
+    for name, value, low, top in (("min_cover", min_cover, 1, 2 ** 31 - 1), ("min_alt", min_alt, 1, 2 ** 31 - 1), ("min_percent", min_percent, 0, 100)):
+        if not _is_int(value) or not low <= int(value) <= top:
+            raise B.BgsaHipError(f"{who}: rc=-1: {name} {value!r} is not an int in {low}..{top}")
+    return int(min_cover), int(min_alt), int(min_percent)
+
+
+def check_pileup_add(who: str, pileup, mapper, merge=None) -> None:
+    """What a call with pileup= refuses before anything is launched, pure host: a pileup that is no Pileup, or another mapper's;
+    a merge= beside it that marks duplicates — that merge learns its duplicate flags only at finish(), the pileup could not
+    honour them."""
+    if not isinstance(pileup, Pileup):
+        raise B.BgsaHipError(f"{who}: rc=-1: pileup {pileup!r} is not a Pileup (mapper.pileup())")
+    if pileup.mapper is not mapper:
+        raise B.BgsaHipError(f"{who}: rc=-1: the pileup belongs to another mapper")
+    if merge is not None and getattr(merge, "mark_duplicates", False):
+        raise B.BgsaHipError(f"{who}: rc=-1: pileup= beside a merge with mark_duplicates=True: the merge flags its duplicates at finish(), "
+                             f"after this call's records were counted")
+
+
+class PileupSites(NamedTuple):
+    """The candidate sites of a Pileup, in ascending (linear) position: numpy arrays of one length.  ref is the reference's code
+    0..3, alt the qualifying column of the highest count (0..3 a base, 5 a deletion, 6 an insertion behind pos), alts_mask bit a
+    for every qualifying column a.  On a ContigMapper pos is local to contig; elsewhere contig is None."""
+    pos: np.ndarray         # int64
+    ref: np.ndarray         # uint8
+    alt: np.ndarray         # uint8
+    alt_count: np.ndarray   # int32
+    cover: np.ndarray       # int32: columns 0..5 summed
+    alts_mask: np.ndarray   # uint8
+    contig: object = None   # int32 on a ContigMapper
+
+
+class Pileup:
+    """Per-position base counts of the records of any number of map_reads_* / map_pairs_* calls (pileup=this), on the device:
+    counts [ref_len, 8] int32 in LINEAR coordinates, the columns PILEUP_COLUMNS, and the five counters of PILEUP_STATS
+    (include/bgsa_hip.h "Pileup").  A record contributes when it is mapped, carries none of exclude_flags —
+    the default leaves out secondary, QC-fail and duplicate records — and has mapq >= min_mapq; a base with QUAL below
+    min_base_quality is not counted (no QUAL: every base is).  Made by mapper.pileup().
+    LIMITS: the mates of an overlapping pair are both counted; duplicates are only those marked within the call
+    (mark_duplicates=True), never across calls; no base-alignment quality, no genotype likelihoods, no VCF; insertions are counted
+    per run, not per inserted sequence."""
+
+    def __init__(self, mapper, min_mapq: int = 0, min_base_quality: int = 13, exclude_flags: int = PILEUP_EXCLUDE_FLAGS):
+        self.min_mapq, self.min_base_quality, self.exclude_flags = check_pileup("pileup", min_mapq, min_base_quality, exclude_flags)
+        a = mapper.aligner
+        self.mapper = mapper
+        self.counts = a.torch.zeros((mapper.ref_len, len(PILEUP_COLUMNS)), dtype=a.torch.int32, device=a.device)
+        self._stats = a.torch.zeros(len(PILEUP_STATS), dtype=a.torch.int64, device=a.device)
+
+    def _add(self, batch, n: int) -> None:
+        """The counts kernel on a bgsa_hip_sam_batch_t of n records.  Called after the call's last check."""
+        B.check(B.lib().bgsa_hip_pileup_dev(batch, n, self.min_mapq, self.min_base_quality, self.exclude_flags, self.counts.data_ptr(),
+                                            self._stats.data_ptr(), self.mapper.aligner._stream()), "pileup_dev")
+
+    def stats(self) -> dict:
+        """The five counters, in one small copy."""
+        return dict(zip(PILEUP_STATS, self._stats.tolist()))
+
+    def depth(self):
+        """Columns 0..5 summed: the device tensor int32[ref_len] of the records that cover every position."""
+        torch = self.mapper.aligner.torch
+        return self.counts[:, :6].sum(dim=1, dtype=torch.int32)
+
+    def counts_host(self, begin: int = 0, end=None) -> np.ndarray:
+        """Rows [begin, end) of counts (linear positions) on the host."""
+        return self.counts[int(begin): self.mapper.ref_len if end is None else int(end)].cpu().numpy()
+
+    def reset(self) -> None:
+        self.counts.zero_()
+        self._stats.zero_()
+
+    def sites(self, min_cover: int = 8, min_alt: int = 3, min_percent: int = 20) -> PileupSites:
+        """The candidate sites, reduced on the device: a position whose reference base is A, C, G or T, whose cover (columns 0..5)
+        is >= min_cover and where a column other than the reference's — a base, the deletions, the insertions — holds >= min_alt
+        and >= min_percent % of the cover (integers).  The count pass, a scan of the workgroups' counts, ONE scalar read back, the
+        emit pass, one copy per array; the count matrix stays on the device."""
+        min_cover, min_alt, min_percent = check_pileup_sites("pileup.sites", min_cover, min_alt, min_percent)
+        m, L = self.mapper, B.lib()
+        a = m.aligner
+        torch, dev = a.torch, a.device
+        n_blocks = int(L.bgsa_hip_pileup_site_blocks(m.ref_len))
+        block_sites = torch.empty(n_blocks, dtype=torch.int32, device=dev)
+        test = (self.counts.data_ptr(), m.d_reference.data_ptr(), m.ref_len, min_cover, min_alt, min_percent)
+        B.check(L.bgsa_hip_pileup_sites_count_dev(*test, block_sites.data_ptr(), n_blocks, a._stream()), "pileup_sites_count_dev")
+        ends = torch.cumsum(block_sites, 0, dtype=torch.int64)
+        total = int(ends[-1].item())                    # the one scalar read back: it sizes the outputs
+        block_offsets = (ends - block_sites).contiguous()
+        pos = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+        ref, alt, mask = (torch.empty(max(total, 1), dtype=torch.uint8, device=dev) for _ in range(3))
+        alt_count, cover = (torch.empty(max(total, 1), dtype=torch.int32, device=dev) for _ in range(2))
+        overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        B.check(L.bgsa_hip_pileup_sites_emit_dev(*test, block_offsets.data_ptr(), n_blocks, total, pos.data_ptr(), ref.data_ptr(), alt.data_ptr(),
+                                                 mask.data_ptr(), alt_count.data_ptr(), cover.data_ptr(), overflow.data_ptr(), a._stream()),
+                "pileup_sites_emit_dev")
+        if int(overflow.item()):
+            raise B.BgsaHipError(f"pileup.sites: the emit pass found {int(overflow.item())} sites beyond the {total} the count pass found")
+        local, contig = m.local_sites(pos[:total].cpu().numpy())
+        return PileupSites(local, ref[:total].cpu().numpy(), alt[:total].cpu().numpy(), alt_count[:total].cpu().numpy(),
+                           cover[:total].cpu().numpy(), mask[:total].cpu().numpy(), contig)
+
+
 class SeedBucket(NamedTuple):
     """What the steps of select_seeded share for one resident bucket (ReferenceMapper.seed_bucket)."""
     d_rows: object          # the bucket's ASCII rows on the device, read_len + 1 bytes each
@@ -1423,7 +1546,7 @@ class ReferenceMapper:
 
     def sam_records(self, who: str, reads: np.ndarray, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, fmt: str = "sam",
                     block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False, mark_duplicates: bool = False,
-                    ends: int = 1, merge=None):
+                    ends: int = 1, merge=None, pileup=None):
         """The two record passes.  reads [n_rows, stride] and quals (or None) are the host rows, names / name_offsets / rname what
         check_sam_call returned; fields holds the per-record DEVICE tensors read_row, name_of (int64), read_len, strand, ref_begin,
         ref_end, distance, n_ops, flag, mapq, rnext, pnext, tlen; runs [n, cap] int32 holds record i's runs in row i.  Measure, an
@@ -1442,13 +1565,17 @@ class ReferenceMapper:
         "BAM records: merge"): the batch as assembled goes through the duplicate KEY kernel where the merge marks duplicates — no
         mark —, the key pass, then measure, scan and emit in INPUT order, and the device tensors are handed to the BamMerge;
         nothing is framed, no per-record array is copied, the number of records added is returned.  block_payload, compress, sort
-        and mark_duplicates are the merge's then."""
+        and mark_duplicates are the merge's then.  pileup (any fmt; include/bgsa_hip.h "Pileup"): the batch as assembled — its flags
+        those duplicate marking left, before any sort — is counted into the Pileup once the call's last check has passed, so a
+        call that raises leaves the pileup as it was; check_pileup_add refuses first."""
         if merge is not None and fmt != "bam":
             raise B.BgsaHipError(f"{who}: rc=-1: merge= needs fmt 'bam'")
         if merge is not None and (sort or compress or mark_duplicates):
             raise B.BgsaHipError(f"{who}: rc=-1: sort, compress and mark_duplicates belong to the merge")
         if sort and fmt != "bam":
             raise B.BgsaHipError(f"{who}: rc=-1: sort=True needs fmt 'bam'")
+        if pileup is not None:
+            check_pileup_add(who, pileup, self, merge)
         a = self.aligner
         torch, dev = a.torch, a.device
         measure, emit = self._sam_passes(fmt)
@@ -1480,6 +1607,7 @@ class ReferenceMapper:
         if mark_duplicates:
             f = dict(f, flag=f["flag"].clone())
             self.last_duplicate_stats = self.mark_duplicate_records(batch_of(f, runs_row), n, int(ends), f["flag"])
+        assembled = (f, runs_row)                       # what the pileup counts: the flags as marked, the order as given
         coordinates, duplicate_keys = None, None
         if merge is not None and merge.mark_duplicates:
             key_counts = torch.zeros(3, dtype=torch.int32, device=dev)
@@ -1516,7 +1644,9 @@ class ReferenceMapper:
         pos = torch.where(mapped, f["ref_begin"] + 1, f["pnext"] * f["rnext"])
         nm = f["distance"].masked_fill(~mapped, -1)
         mapq = f["mapq"].masked_fill(~mapped, 0)
-        if merge is not None:       # the last check is behind us: only now does the merge change
+        if merge is not None:       # the last check is behind us: only now do the merge and the pileup change
+            if pileup is not None:
+                pileup._add(batch_of(*assembled), n)
             columns = dict(zip(MERGE_COLUMNS, (lengths, key, *coordinates[:4], f["flag"], pos, mapq, nm)))
             if duplicate_keys is not None:
                 columns.update(zip(MERGE_DUPLICATE_COLUMNS, duplicate_keys))
@@ -1530,8 +1660,10 @@ class ReferenceMapper:
             B.check(B.lib().bgsa_hip_bgzf_frame_dev(text.data_ptr(), total, int(block_payload), blocks.data_ptr(), framed, a._stream()),
                     "bgzf_frame_dev")
             kind, text, total = BamRecords, blocks, framed
+        index = self.bam_index(who, *coordinates, offsets, payload_bytes, int(block_payload), block_offsets) if sort else None
+        if pileup is not None:      # the last check is behind us
+            pileup._add(batch_of(*assembled), n)
         if sort:
-            index = self.bam_index(who, *coordinates, offsets, payload_bytes, int(block_payload), block_offsets)
             return SortedBamRecords(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(),
                                     mapq.cpu().numpy(), nm.cpu().numpy(), coordinates[0].cpu().numpy(), host_order, index)
         return kind(text[:total].cpu().numpy(), offsets.cpu().numpy(), f["flag"].cpu().numpy(), pos.cpu().numpy(), mapq.cpu().numpy(),
@@ -1595,6 +1727,16 @@ class ReferenceMapper:
     def local_pos(self, pos: np.ndarray) -> np.ndarray:
         """The POS column as the caller sees it: on one sequence the linear positions are it."""
         return pos
+
+    def local_sites(self, pos: np.ndarray) -> tuple:
+        """(pos, contig) of a pileup's sites as the caller sees them: on one sequence the linear positions and no contig."""
+        return pos, None
+
+    def pileup(self, min_mapq: int = 0, min_base_quality: int = 13, exclude_flags: int = PILEUP_EXCLUDE_FLAGS) -> Pileup:
+        """A pileup over this mapper's reference (Pileup; include/bgsa_hip.h "Pileup"): pass it as pileup= to map_reads_sam,
+        map_reads_bam, map_pairs_sam or map_pairs_bam, call after call, then read stats(), depth(), counts_host() or sites().
+        The count matrix [ref_len, 8] int32 is allocated and zeroed here; check_pileup refuses before that."""
+        return Pileup(self, min_mapq, min_base_quality, exclude_flags)
 
     def bam_merge(self, block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, mark_duplicates: bool = False, segment_blocks: int = 4096,
                   reserve_bytes=None) -> BamMerge:
@@ -1723,7 +1865,8 @@ class ReferenceMapper:
         return sink
 
     def map_reads_sam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
-                      seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None, mark_duplicates: bool = False) -> SamRecords:
+                      seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None, mark_duplicates: bool = False,
+                      pileup=None) -> SamRecords:
         """Single-end reads to SAM records, formatted on the device (include/bgsa_hip.h "SAM records").  reads: a [ns, n] uint8 array
         or a list of byte strings of mixed lengths; the mapping is that of the matching entry point of the four — map_reads_seeded
         (seeded=True: max_distance is required), map_reads, or their _ragged forms — with its refusals.  Every read gives ONE record,
@@ -1734,14 +1877,16 @@ class ReferenceMapper:
         columns is copied back; no CIGAR string is made on the host.  mark_duplicates=True: the duplicate reads among THIS call's
         records carry flag bit 1024 (include/bgsa_hip.h "Duplicate marking": mapped reads of equal 5' coordinate — of the record
         as written — and strand; the highest sum of base qualities >= 15 stays, ties the first read); nothing else changes, and
-        last_duplicate_stats holds the counts.  Duplicates are found within one call only."""
+        last_duplicate_stats holds the counts.  Duplicates are found within one call only.  pileup=a Pileup (self.pileup(...);
+        include/bgsa_hip.h "Pileup"): the records of this call — the duplicates just marked left out under the default
+        exclude_flags — are added to its counts on the device; the call returns what it returns without it."""
         return self._map_reads_records("sam", None, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len, max_candidates,
-                                       block_rows, cigar_cap, mark_duplicates=mark_duplicates)
+                                       block_rows, cigar_cap, mark_duplicates=mark_duplicates, pileup=pileup)
 
     def map_reads_bam(self, reads, names=None, quals=None, reference_name="ref", k_best: int = 2, max_distance=None, seeded: bool = True,
                       seed_len=None, max_candidates=None, block_rows: int = 1000, cigar_cap=None,
                       block_payload: int = BGZF_BLOCK_PAYLOAD, compress: bool = False, sort: bool = False, mark_duplicates: bool = False,
-                      merge=None):
+                      merge=None, pileup=None):
         """map_reads_sam — the same arguments, mapping and record selection — with the records in BAM's layout inside BGZF blocks of
         stored deflate, block_payload bytes of records each (include/bgsa_hip.h "BAM records"): measure, scan, emit, frame, all on the
         device, one copy of the blocks.  A record may straddle blocks.  compress=True: every block deflated on the device instead (LZ77
@@ -1757,9 +1902,10 @@ class ReferenceMapper:
         merge.  merge=a BamMerge (self.bam_merge(...); include/bgsa_hip.h "BAM records: merge"): the records of this call stay on the
         device behind those of the merge's earlier calls and the number of records added is returned; block_payload, compress, sort
         and mark_duplicates are the merge's and stay at their defaults here; merge.finish() or merge.write() then give the sorted,
-        indexed records of all calls as ONE sort=True call on all reads would."""
+        indexed records of all calls as ONE sort=True call on all reads would.  pileup=a Pileup: map_reads_sam's, independent of
+        compress and sort; beside a merge that marks duplicates it is refused (the merge flags them at finish())."""
         return self._map_reads_records("bam", block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                                       max_candidates, block_rows, cigar_cap, compress, sort, mark_duplicates, merge)
+                                       max_candidates, block_rows, cigar_cap, compress, sort, mark_duplicates, merge, pileup)
 
     def _check_records_call(self, fmt: str, who: str, lens, names, quals, reference_name, block_payload, compress=False, sort=False) -> tuple:
         if fmt == "bam":
@@ -1767,12 +1913,14 @@ class ReferenceMapper:
         return check_sam_call(who, lens, names, quals, reference_name)
 
     def _map_reads_records(self, fmt: str, block_payload, reads, names, quals, reference_name, k_best, max_distance, seeded, seed_len,
-                           max_candidates, block_rows, cigar_cap, compress=False, sort=False, mark_duplicates=False, merge=None):
+                           max_candidates, block_rows, cigar_cap, compress=False, sort=False, mark_duplicates=False, merge=None, pileup=None):
         """What map_reads_sam and map_reads_bam share: everything but the format of the records."""
         who = f"map_reads_{fmt}"
         mark_duplicates = check_mark_duplicates(who, mark_duplicates)
         if merge is not None:
             check_bam_merge_add(who, merge, self, 1, block_payload, compress, sort, mark_duplicates)
+        if pileup is not None:
+            check_pileup_add(who, pileup, self, merge)
         rows, lens, ragged = self._sam_rows(who, reads)
         rname, flat, name_offsets, qual_rows = self._check_records_call(fmt, who, lens, names, quals, reference_name, block_payload,
                                                                         compress, sort)
@@ -1781,11 +1929,11 @@ class ReferenceMapper:
                             max_candidates, block_rows, cigar_cap)
         self.aligner.check_faults()
         return self.sam_single_records(who, sink, rows, lens, qual_rows, flat, name_offsets, rname, fmt=fmt, block_payload=block_payload,
-                                       compress=compress, sort=sort, mark_duplicates=mark_duplicates, merge=merge)
+                                       compress=compress, sort=sort, mark_duplicates=mark_duplicates, merge=merge, pileup=pileup)
 
     def sam_single_records(self, who: str, sink: "PrimarySink", rows: np.ndarray, lens, qual_rows, names, name_offsets, rname, **form):
         """The records of single-end reads from their primaries on the device: flag 0, 16 or 4, no mate fields.  form: sam_records'
-        fmt, block_payload, compress, sort and mark_duplicates (every mapped record a fragment unit: ends 1)."""
+        fmt, block_payload, compress, sort, mark_duplicates, merge and pileup (every mapped record a fragment unit: ends 1)."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = rows.shape[0]
         index = torch.arange(ns, dtype=torch.int64, device=dev)
@@ -1798,7 +1946,8 @@ class ReferenceMapper:
 
     def map_pairs_sam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
                       reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
-                      max_candidates=None, block_rows: int = 1000, cigar_cap=None, mark_duplicates: bool = False) -> SamRecords:
+                      max_candidates=None, block_rows: int = 1000, cigar_cap=None, mark_duplicates: bool = False,
+                      pileup=None) -> SamRecords:
         """map_pairs to SAM records, formatted on the device: two records per pair, end 1 then end 2, each the slot pair_select chose
         (a proper pair: flag 2) or the end's first kept hit, else unmapped.  Flags 1, 2, 4, 8, 16, 32, 64 / 128; RNEXT '=' and PNEXT
         where the mate is mapped; TLEN where both are; an unmapped end beside a mapped mate takes the mate's RNAME and POS.  MAPQ:
@@ -1808,33 +1957,36 @@ class ReferenceMapper:
         pairs with both ends mapped, of equal 5' coordinates — of the records as written — and strands; the highest sum of base
         qualities >= 15 over both ends stays, ties the first pair), and so does a mapped end whose mate is unmapped where it stands on
         an end of such a pair or behind a better end of its kind; an unmapped mate is not flagged.  last_duplicate_stats holds the
-        counts.  Duplicates are found within one call only."""
+        counts.  Duplicates are found within one call only.  pileup=a Pileup: map_reads_sam's; both records of a pair are counted,
+        where the mates overlap both of them."""
         return self._map_pairs_records("sam", None, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
                                        max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap,
-                                       mark_duplicates=mark_duplicates)
+                                       mark_duplicates=mark_duplicates, pileup=pileup)
 
     def map_pairs_bam(self, reads1: np.ndarray, reads2: np.ndarray, insert_min: int, insert_max: int, names=None, quals1=None, quals2=None,
                       reference_name="ref", k_best: int = 1, max_distance=None, rescue_distance=None, seeded: bool = True, seed_len=None,
                       max_candidates=None, block_rows: int = 1000, cigar_cap=None, block_payload: int = BGZF_BLOCK_PAYLOAD,
-                      compress: bool = False, sort: bool = False, mark_duplicates: bool = False, merge=None):
+                      compress: bool = False, sort: bool = False, mark_duplicates: bool = False, merge=None, pileup=None):
         """map_pairs_sam — the same arguments, stages and records — in BAM's layout inside BGZF blocks, stored or, with compress=True,
         deflated on the device (map_reads_bam).  sort=True: coordinate order and a BAI index, as map_reads_bam's; of two ends at one
         position end 1 stays in front, and an unmapped end stays right behind the mate whose position it takes.
         mark_duplicates=True: map_pairs_sam's, independent of compress and sort; duplicates are found within one call only — across
         calls by a merge.  merge=a BamMerge: map_reads_bam's, two records per pair; a merge takes paired batches or single-end
-        ones, not both."""
+        ones, not both.  pileup=a Pileup: map_pairs_sam's."""
         return self._map_pairs_records("bam", block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name,
                                        k_best, max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap,
-                                       compress, sort, mark_duplicates, merge)
+                                       compress, sort, mark_duplicates, merge, pileup)
 
     def _map_pairs_records(self, fmt: str, block_payload, reads1, reads2, insert_min, insert_max, names, quals1, quals2, reference_name, k_best,
                            max_distance, rescue_distance, seeded, seed_len, max_candidates, block_rows, cigar_cap, compress=False, sort=False,
-                           mark_duplicates=False, merge=None):
+                           mark_duplicates=False, merge=None, pileup=None):
         """What map_pairs_sam and map_pairs_bam share: everything but the format of the records."""
         who = f"map_pairs_{fmt}"
         mark_duplicates = check_mark_duplicates(who, mark_duplicates)
         if merge is not None:
             check_bam_merge_add(who, merge, self, 2, block_payload, compress, sort, mark_duplicates)
+        if pileup is not None:
+            check_pileup_add(who, pileup, self, merge)
         reads = (self._one_length(who, reads1), self._one_length(who, reads2))
         ns = reads[0].shape[0]
         if (quals1 is None) != (quals2 is None):
@@ -1854,12 +2006,12 @@ class ReferenceMapper:
         chosen = self.pair_select(ends[0][0][:5], ends[1][0][:5], insert_min, insert_max, block_rows)      # stage C
         a.check_faults()
         return self.sam_pair_records(who, reads, ends, chosen, call, checked, fmt=fmt, block_payload=block_payload, compress=compress,
-                                     sort=sort, mark_duplicates=mark_duplicates, merge=merge)
+                                     sort=sort, mark_duplicates=mark_duplicates, merge=merge, pileup=pileup)
 
     def sam_pair_records(self, who: str, reads, ends, chosen, call: dict, checked, **form):
         """The records of pairs from the device results of map_pairs' stages: ends[e] = rescue_end's return for end e, chosen =
         pair_select's, call = check_pair_call's dict, checked[e] = check_sam_call's return for end e.  form: sam_records' fmt,
-        block_payload, compress, sort and mark_duplicates (records 2u and 2u + 1 are pair u: ends 2)."""
+        block_payload, compress, sort, mark_duplicates, merge and pileup (records 2u and 2u + 1 are pair u: ends 2)."""
         torch, dev = self.aligner.torch, self.aligner.device
         ns = reads[0].shape[0]
         lists = [final for final, _, _, _ in ends]
@@ -2191,7 +2343,8 @@ class ContigMapper(ReferenceMapper):
     def sam_records(self, who: str, reads, quals, names, name_offsets, rname, fields: dict, runs, read_label=None, **form):
         """ReferenceMapper.sam_records through the contig passes: the fields are linear, the device localises them; TLEN is set to 0
         where the mate lies on another contig; the pos column comes back local.  rname is not used.  form: fmt, block_payload, compress, sort,
-        mark_duplicates and ends (the duplicate keys are linear coordinates: equal local positions on two contigs are two keys)."""
+        mark_duplicates, ends, merge and pileup (the duplicate keys and the pileup's rows are linear coordinates: equal local
+        positions on two contigs are two keys, two rows)."""
         torch = self.aligner.torch
         own = torch.searchsorted(self.d_contig_starts, fields["ref_begin"].contiguous(), right=True)
         mate = torch.searchsorted(self.d_contig_starts, (fields["pnext"] - 1).contiguous(), right=True)
@@ -2204,6 +2357,11 @@ class ContigMapper(ReferenceMapper):
     def local_pos(self, pos: np.ndarray) -> np.ndarray:
         at = np.maximum(self.contig_of(pos - 1), 0)
         return np.where(pos > 0, pos - self.contig_starts[at], 0)
+
+    def local_sites(self, pos: np.ndarray) -> tuple:
+        """(pos local to its contig, contig) of a pileup's sites: the device side stays linear."""
+        contig = self.contig_of(pos)
+        return pos - self.contig_starts[np.maximum(contig, 0)], contig
 
     def map_reads_sam(self, reads, names=None, quals=None, reference_name="ref", **kwargs) -> SamRecords:
         """ReferenceMapper.map_reads_sam with RNAME the contig's name and POS local to it.  reference_name is not used."""

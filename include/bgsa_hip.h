@@ -1235,6 +1235,69 @@ int bgsa_hip_bam_gather_dev(const uint8_t *d_src, int64_t src_bytes, const int64
                             const int64_t *d_dst_offsets, int64_t n, int64_t first, int64_t count, int64_t window_lo, int64_t window_hi,
                             const int32_t *d_flag, uint8_t *d_out, int32_t *d_refused, void *stream);
 
+/* ---- Pileup: per-position base counts of the records, and the candidate sites of a count matrix ----
+ * Coverage, a consensus and variant candidates all start from a pileup, and a pileup walks the CIGAR runs that already lie on the
+ * device beside the reads, the qualities and the reference (bgsa_hip_sam_batch_t).  It is also the consumer that honours flag 1024
+ * of "Duplicate marking".  bgsa_hip_pileup_dev adds one batch to a count matrix; the two site passes reduce the matrix on the
+ * device to a list, as top_hits does for the score matrix, so the matrix (32 bytes per position) need not be copied
+ * (pileup.hip; bgsa_amd/reference.py: Pileup, sam_records(pileup=...)).
+ * THE COUNT MATRIX (public, fixed): d_counts is int32[ref_len][8], row p for LINEAR reference position p — the batch's ref_len, in
+ * the one-sequence and in the contig form alike.  The caller zeroes it once; every call adds to it.
+ *   columns 0..3   read base A, C, G, T              column 5   a SAM D run covers p
+ *   column  4      any other read byte               column 6   a SAM I run lies between p and p + 1
+ *   column  7      the share of columns 0..5 that comes from reverse-strand records
+ * Depth beyond 2^31 - 1 is not supported.
+ * DEFINITIONS (normative; tests/pileup_reference.py restates them).
+ *   contributes  a record contributes iff it is well formed by the rules of "SAM records" (malformed, there), it is mapped,
+ *              (flag & exclude_flags) == 0 and mapq >= min_mapq.  Coordinates are linear in both forms of the batch: one call
+ *              serves both, d_rname and rname_len are not read.
+ *   malformed  adds 1 to d_stats[2] and touches nothing else; none of its values forms an address.
+ *   as written seq[j] and qual[j], j in [0, read_len), are the record as the SAM stage writes it: the caller's bytes for a forward
+ *              hit; for a reverse hit the read reverse-complemented (A<->T, C<->G, anything else N) and QUAL reversed.
+ *   the walk   from p = ref_begin, j = 0 over the runs:
+ *              op 7 or 8, length len: for t in 0..len-1: if d_quals is not NULL and qual[j+t] - 33 < min_base_quality the base adds
+ *                to d_stats[4] and to nothing else; otherwise counts[p+t][class(seq[j+t])] += 1 with class 0..3 for upper-case A, C,
+ *                G, T and 4 for anything else, d_stats[3] += 1, and a reverse record also adds 1 to counts[p+t][7].  The column
+ *                comes from the read byte, never from the op.  Then p and j advance by len.
+ *              op 1 (reference only, SAM D): counts[p+t][5] += 1, a reverse record also counts[p+t][7] += 1; qualities are not
+ *                consulted.  Then p advances by len.
+ *              op 2 (read only, SAM I): if ref_begin < p < ref_end, counts[p-1][6] += 1, once per run whatever its length; a
+ *                leading or trailing run is counted nowhere.  Then j advances by len.
+ *   d_stats    int64[5], each call adds: [0] records used, [1] records filtered (unmapped, flag or MAPQ), [2] malformed records,
+ *              [3] bases counted, [4] bases below the quality bound.
+ * bgsa_hip_pileup_dev: one WAVE per record on a resident grid striding over the records, 64 runs at a time, a run of up to four
+ * bases by its own lane and a longer one by the whole wave; integer atomics on d_counts, so the result is exact whatever the order;
+ * the stats reduced per wave, then one atomic per counter and workgroup.  BGSA_HIP_EINVAL, before the first HIP call: a NULL
+ * pointer (d_quals and the stream excepted), a negative n, min_mapq outside 0..255, min_base_quality outside 0..93, exclude_flags
+ * outside 0..65535, what the SAM passes refuse about the batch (rname excepted).  n == 0 is BGSA_HIP_OK and launches nothing.
+ * CANDIDATE SITES.  For position p: r = d_reference[p] (codes 0..4); cover = the sum of columns 0..5; the allele columns are
+ * {0, 1, 2, 3, 5, 6} minus r; column a QUALIFIES when counts[p][a] >= min_alt and 100 * counts[p][a] >= min_percent * cover, in
+ * 64-bit integers; p is a SITE when r < 4, cover >= min_cover and at least one allele qualifies.  Its alt is the qualifying column
+ * of the highest count, ties going to the lowest column; alts_mask has bit a set for every qualifying column.
+ * bgsa_hip_pileup_sites_count_dev: one THREAD per position, one workgroup per 256; d_block_sites int32[n_blocks] gets every
+ * workgroup's number of sites, n_blocks = bgsa_hip_pileup_site_blocks(ref_len) (host only; 0 for ref_len < 1).  The caller takes an
+ * exclusive scan of them into d_block_offsets int64[n_blocks], reads ONE scalar back — the total — and sizes the outputs.
+ * bgsa_hip_pileup_sites_emit_dev repeats the test and writes the sites in ascending position, site k of workgroup b at
+ * d_block_offsets[b] + k: d_pos int64, d_ref / d_alt / d_alts_mask uint8, d_alt_count / d_cover int32, n_sites entries each.  A
+ * site whose slot lies outside [0, n_sites) is not written and adds 1 to *d_overflow (int32, zeroed by the caller).
+ * Both only launch on `stream`.  BGSA_HIP_EINVAL, before the first HIP call: a NULL pointer (the stream excepted), ref_len < 1 or
+ * beyond 2^39 - 256 (one launch), min_cover < 1, min_alt < 1, min_percent outside 0..100, an n_blocks that is not the one for
+ * ref_len, a negative n_sites.
+ * The C loop: zero d_counts and d_stats; bgsa_hip_pileup_dev per batch; count; scan; read the total; allocate; emit; read *d_overflow.
+ * LIMITS: the mates of an overlapping pair are both counted; duplicates are only those marked within the call; no base-alignment
+ * quality, no genotype likelihoods, no VCF; insertions are counted per run, not per inserted sequence. */
+#define BGSA_HIP_PILEUP_COLUMNS 8
+#define BGSA_HIP_PILEUP_STATS 5
+int bgsa_hip_pileup_dev(const bgsa_hip_sam_batch_t *batch, int64_t n, int min_mapq, int min_base_quality, int exclude_flags, int32_t *d_counts,
+                        int64_t *d_stats, void *stream);
+int64_t bgsa_hip_pileup_site_blocks(int64_t ref_len);
+int bgsa_hip_pileup_sites_count_dev(const int32_t *d_counts, const uint8_t *d_reference, int64_t ref_len, int min_cover, int min_alt,
+                                    int min_percent, int32_t *d_block_sites, int64_t n_blocks, void *stream);
+int bgsa_hip_pileup_sites_emit_dev(const int32_t *d_counts, const uint8_t *d_reference, int64_t ref_len, int min_cover, int min_alt,
+                                   int min_percent, const int64_t *d_block_offsets, int64_t n_blocks, int64_t n_sites, int64_t *d_pos,
+                                   uint8_t *d_ref, uint8_t *d_alt, uint8_t *d_alts_mask, int32_t *d_alt_count, int32_t *d_cover,
+                                   int32_t *d_overflow, void *stream);
+
 /* Stream faults. The kernels walk each query as a packed code stream (below) under a window budget; a
  * wave whose stream ends without an END token, or holds a byte that is no token, leaves its loop and
  * raises a bit in a sticky per-device word instead of storing a score.  A well-formed stream cannot do
